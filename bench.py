@@ -1,8 +1,16 @@
 """RIFT policy-update benchmark on MI355X (contract: see the task brief / DESIGN.md section "Measurement").
 
     python bench.py                         # 1 GPU, 200 timed steps
-    python bench.py --gpus N ...            # N > 1 from a plain shell: re-executes itself under torch.distributed.run (one rank per GPU, RCCL)
+    python bench.py --gpus N ...            # N > 1 from a plain shell: runs itself under torch.distributed.run (one rank per GPU, RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py --full ...              # + every companion figure (see below); the --no-* switches drop single companions of a --full run
+    python bench.py --dump-outputs DIR ...  # + what the last timed step computed, as DIR/<name>.npy (loss, probability, pi_head and its gradients)
+
+A plain run builds the headline leg, brings the device's clocks up with a throwaway leg of 200 update steps (what the companion legs used
+to do in front of the headline), runs W warm-up and K timed steps and prints the JSON line: nothing else.  `--full` adds the companion
+figures: the same steps with every output computed (all_outputs) and 200 of them in one region (steady_state), the full 16-epoch update, the
+roofline leg (per-kernel times + rocprofv3 counter child runs), the fp16 / fp32 legs and the precision contract, the end-to-end update, the
+CARLA-shaped step, the rollout tick, the CPU baseline and, with N > 1, the other scaling mode.
 
 One *step* = one policy-update step of the reference's RIFT trainer on a 256-scene minibatch per GPU:
 device-side collation of 256 scenes from the HBM-resident replay arena -> train-mode PlanningModel
@@ -28,6 +36,8 @@ import os
 import socket
 import sys
 import time
+
+import numpy as np
 
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # before the HIP runtime initialises (rift_amd/__init__.py explains; an explicit setting wins)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # the host driver supports dmabuf IPC only: RCCL needs it for any N > 1
@@ -197,7 +207,7 @@ def collect_counters(label, precision):
         for i, ctrs in enumerate(passes):
             out = os.path.join(root, f"p{i}")
             cmd = [rp, "--kernel-trace", "--pmc"] + ctrs + ["-d", out, "-o", "pmc", "--", sys.executable, os.path.abspath(__file__), "--steps", "4", "--warmup", "2",
-                   "--replay", "512", "--precision", precision, "--no-cpu-baseline", "--no-roofline", "--no-full-update", "--no-precisions", "--no-carla",
+                   "--replay", "512", "--precision", precision, "--full", "--no-cpu-baseline", "--no-roofline", "--no-full-update", "--no-precisions", "--no-carla",
                    "--no-tick", "--no-e2e"]
             r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=600)
             dbs = [os.path.join(d, f) for d, _, fs in os.walk(out) for f in fs if f.endswith(".db")]
@@ -267,7 +277,8 @@ def contract_device_losses(dev, sd, batch, precision):
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` from a plain shell: re-execute under torch.distributed.run, one rank per GPU of this node."""
+    """`python bench.py --gpus N` from a plain shell: run this command under torch.distributed.run in a child process, one rank per GPU of
+    this node, and exit with its status."""
     have = torch.cuda.device_count()
     if have < args.gpus:
         sys.stderr.write(f"bench.py: --gpus {args.gpus} needs {args.gpus} GPUs on this node, torch sees {have}; nothing was measured.\n"
@@ -281,7 +292,8 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stderr.write("bench.py: launching " + " ".join(cmd) + "\n")
-    os.execvpe(sys.executable, cmd, env)
+    import subprocess
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 def main():
@@ -303,9 +315,15 @@ def main():
     ap.add_argument("--no-carla", action="store_true", help="skip the CARLA-shaped companion step (49 agents, 60 polygons: the shapes train_cbv really produces)")
     ap.add_argument("--no-e2e", action="store_true", help="skip full_update_e2e (RIFTPluto.train() from a full CBVRolloutBuffer to the reloaded inference model)")
     ap.add_argument("--batch", type=int, default=256, help="scenes per minibatch (diagnostic: 32 = what one of 8 ranks runs under strong scaling)")
+    ap.add_argument("--full", action="store_true", help="also measure every companion figure (module docstring); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, probability, pi_head parameters and gradients) as DIR/<name>.npy")
     args = ap.parse_args()
     global BATCH
     BATCH = args.batch
+    if not args.full:       # a plain run: the headline leg only
+        args.no_cpu_baseline = args.no_roofline = args.no_precisions = args.no_full_update = True
+        args.no_tick = args.no_carla = args.no_e2e = True
 
     if args.gpus > 1 and "RANK" not in os.environ:
         self_launch(args)
@@ -377,7 +395,7 @@ def main():
     sd_cpu = syn.perturbed_state_dict({k: list(v.shape) for k, v in model.state_dict().items()})
     nsteps = args.warmup + args.steps + 8
 
-    def leg(scaling, precision, steps, want_all_outputs=False, want_full_update=False, want_roofline=False, want_steady=False):
+    def leg(scaling, precision, steps, want_all_outputs=False, want_full_update=False, want_roofline=False, want_steady=False, want_dump=False):
         """Time `steps` update steps in one (scaling, precision) configuration on fresh parameters / optimizer state.
         A generator: the first next() builds the leg (its own model, engine context, trainer, index tensors -- host work, tens of ms), the
         second one runs it and yields the result.  main() builds the headline leg BEFORE it runs the companion legs, so that the headline
@@ -434,6 +452,14 @@ def main():
         res = {"ms_per_step": dt / steps * 1e3, "value": steps / dt * global_bs, "steps_per_sec": steps / dt, "steps": steps,
                "per_gpu_batch": local_bs, "global_batch": global_bs, "replay_scenes_per_gpu": per_rank, "final_loss": float(loss.item())}
         eng.check_finite()
+        if want_dump:
+            # what the caller of the last timed step holds behind wait_update(): its loss, the policy logits of its minibatch (this rank's
+            # shard) and pi_head after its AdamW update, with the gradients that update used -- copied before any companion runs more steps
+            torch.cuda.synchronize()
+            res["outputs"] = {"loss": loss.detach().double().cpu().numpy().reshape(-1), "probability": trainer._prob.float().cpu().numpy()}
+            for k, p in trainer.params.items():
+                res["outputs"]["pi_head." + k] = p.detach().float().cpu().numpy()
+                res["outputs"]["pi_head." + k + ".grad"] = p.grad.detach().float().cpu().numpy()
 
         if (want_all_outputs or want_steady) and steps < 200:
             # companion figure: 200 steps behind the same barriers.  The step pipeline is four steps deep (gather / preparation / history and
@@ -598,10 +624,10 @@ def main():
         next(g)
         return g
 
-    head_leg = built(head_scaling, args.precision, args.steps, want_all_outputs=True, want_full_update=not args.no_full_update,
-                     want_roofline=not args.no_roofline)
+    head_leg = built(head_scaling, args.precision, args.steps, want_all_outputs=args.full, want_full_update=not args.no_full_update,
+                     want_roofline=not args.no_roofline, want_dump=args.dump_outputs is not None)
     other = None
-    if world > 1:
+    if world > 1 and args.full:
         other_scaling = "strong" if head_scaling == "weak" else "weak"
         other = (other_scaling, next(built(other_scaling, args.precision, args.steps)))
     precisions = None
@@ -617,7 +643,20 @@ def main():
             precisions[p] = {k: r[k] for k in keep}
             if "steady_state" in r:
                 precisions[p]["steady_ms_per_step"] = r["steady_state"]["ms_per_step"]
+    if precisions is None and other is None:
+        # without companion legs in front, the headline's warm-up would start on an idle device, whose clocks put its K = 20 region ~6 %
+        # above the same steps behind the companions (profiles/NOTES_r06.md): a throwaway leg of 200 update steps takes their place (its own
+        # model and trainer -- the headline's steps, and what they compute, are the same as behind the companions)
+        next(built(head_scaling, args.precision, 200))
     head = next(head_leg)
+    if args.dump_outputs is not None and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        outs = head.pop("outputs")
+        if sum(a.nbytes for a in outs.values()) > 64 << 20:      # (a large --batch: a fixed, seeded sample of the minibatch's rows)
+            rows = torch.randperm(outs["probability"].shape[0], generator=torch.Generator().manual_seed(0))[:4096].sort().values.numpy()
+            outs["probability"] = outs["probability"][rows]
+        for name, a in outs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     contract = None
     if world == 1 and rank == 0 and not args.no_cpu_baseline and BATCH == 256:
         # north_star's precision contract, machine-readable: the four objectives of the parity test's 256-scene batch per compute precision
@@ -676,15 +715,16 @@ def main():
                                   "all_outputs = the same steps with every output of PlanningModel.forward computed)"},
             # whole-step fraction of the dense bf16 MFMA peak, priced at the algorithmic FLOPs of what each variant executes
             "whole_step_mfma_frac": head["value"] / world * FLOPS_PER_SCENE_LOSS / (PEAK_BF16_TFLOPS * 1e12),
-            "all_outputs": head["all_outputs"],
+            **({"all_outputs": head["all_outputs"]} if "all_outputs" in head else {}),
             **({"steady_state": head["steady_state"]} if "steady_state" in head else {}),
             "final_loss": head["final_loss"], "replay_gen_s": round(t_gen, 2), "replay_hbm_mb": round(replays["weak"].nbytes() / 1e6, 1),
         }
         if world > 1:
-            for name, r in ((head_scaling, head), other):
+            notes = {"strong": "SURVEY.md 8(e): the reference's 256-scene minibatch split contiguously over the ranks (15 optimizer steps per epoch of the 4096-scene replay, as the reference); steps/s is the reference's optimizer-step rate",
+                     "weak": "256 scenes per GPU per step: the reference's update with train_batch_size = 256 N (fewer, larger optimizer steps per epoch)"}
+            for name, r in [(head_scaling, head)] + ([other] if other is not None else []):
                 line[name] = {k: r[k] for k in ("ms_per_step", "value", "steps_per_sec", "per_gpu_batch", "global_batch", "replay_scenes_per_gpu")}
-            line["strong"]["note"] = "SURVEY.md 8(e): the reference's 256-scene minibatch split contiguously over the ranks (15 optimizer steps per epoch of the 4096-scene replay, as the reference); steps/s is the reference's optimizer-step rate"
-            line["weak"]["note"] = "256 scenes per GPU per step: the reference's update with train_batch_size = 256 N (fewer, larger optimizer steps per epoch)"
+                line[name]["note"] = notes[name]
         if "full_update" in head:
             line["full_update"] = head["full_update"]
         if e2e is not None:
@@ -704,8 +744,9 @@ def main():
         # the companions the review reads, as flat scalars inside `config` (the driver's record keeps `config` and `roofline` whole and drops
         # other top-level keys): the reference-equivalent step (every output of PlanningModel.forward: pluto_model.py:173-199) and the
         # steady state (200 steps in one region)
-        line["config"]["all_outputs_ms_per_step"] = head["all_outputs"]["ms_per_step"]
-        line["config"]["all_outputs_value"] = head["all_outputs"]["value"]
+        if "all_outputs" in head:
+            line["config"]["all_outputs_ms_per_step"] = head["all_outputs"]["ms_per_step"]
+            line["config"]["all_outputs_value"] = head["all_outputs"]["value"]
         if "steady_state" in head:
             line["config"]["steady_state_ms_per_step"] = head["steady_state"]["ms_per_step"]
             line["config"]["steady_state_value"] = head["steady_state"]["value"]

@@ -250,7 +250,8 @@ def test_bench_two_ranks_sharing_one_gpu():
     completes and reports both legs.  (The numbers of such a run mean nothing: the all-reduces go through the host.)"""
     import json
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-                          "--master-port", "29657", os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--replay", "1024"],
+                          "--master-port", "29657", os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--replay", "1024",
+                          "--full"],
                          capture_output=True, text=True, timeout=1200, env=dict(os.environ, RIFT_BENCH_SAME_GPU="1"))
     assert out.returncode == 0, out.stdout[-1000:] + out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])

@@ -18,7 +18,7 @@ LABELS = ["collate_kernel", "prep_kernel", "nat_rank_kernel", "nat_l0w_kernel", 
 
 
 def step_ms(env, steps, batch):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--batch", str(batch), "--no-cpu-baseline", "--no-precisions",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--batch", str(batch), "--full", "--no-cpu-baseline", "--no-precisions",
            "--no-roofline", "--no-full-update", "--no-e2e", "--no-carla", "--no-tick"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600).stdout
     line = [ln for ln in out.splitlines() if ln.startswith("{")][-1]

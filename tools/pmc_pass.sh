@@ -8,6 +8,6 @@ mkdir -p $OUT
 TAG=$1; shift
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pmc_$TAG
-timeout 600 rocprofv3 --kernel-trace --pmc $1 -d /tmp/pmc_$TAG -o pmc -- python $REPO/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-roofline --no-full-update > $OUT/pmc_$TAG.json 2> $OUT/pmc_$TAG.err
+timeout 600 rocprofv3 --kernel-trace --pmc $1 -d /tmp/pmc_$TAG -o pmc -- python $REPO/bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-roofline --no-full-update > $OUT/pmc_$TAG.json 2> $OUT/pmc_$TAG.err
 DB=$(find /tmp/pmc_$TAG -name '*.db' | head -1)
 python $REPO/tools/rocpd_pmc.py "$DB" > $OUT/pmc_$TAG.txt 2>&1

@@ -21,7 +21,6 @@
 #include "nat_l0w.h"
 #include "nat_l1w.h"
 #include "enc_fused.h"
-#include "enc_fused.h"
 #include "dec_w.h"
 #include "dec_kv.h"
 #include "nat_l2w.h"
@@ -32,8 +31,8 @@
 #include "fourier_fused.h"
 #include "critic.h"
 #include "fpn_fused.h"
+#include "fwd_plan.h"
 #include "ego_fused.h"
-#include "front.h"
 #include "heads_fused.h"
 #include "pi_fused.h"
 #include "rollout.h"
@@ -113,9 +112,9 @@ struct RiftCtx {
   struct { std::string delay_label; long long delay_ticks = 0; int pe_ts = -1, pew_dbg = 0, pew_ts = 0, nat_ts = 0, enc_ts = 0, dec_ts = 0, dec_dbg = 0, poison_arena = -1; } dg;
   hipEvent_t param_event = nullptr;      // rift_set_param_event: the trainable parameters are valid once this event has passed
   bool dec_fused = true;
-  bool two_streams = true; bool nat_on_main = true; bool nat_compact = true; bool pe_live = true; bool pe_pack = true; bool tok_fused = false; bool keep_tokens = false; bool front_fused = false; bool front_ego = false; bool ego_nofit = false;
+  bool two_streams = true; bool nat_compact = true; bool pe_live = true; bool pe_pack = true;
   hipStream_t prep_stream = nullptr; bool prep_set = false; hipEvent_t ev_prep = nullptr; int side_gate = 0;      // rift_set_prepare_stream
-  hipEvent_t ev_join2 = nullptr; bool nat_aside = true; int join_once = -1;      // (the history chain behind the preparation on the prepare stream: its join event)
+  hipEvent_t ev_join2 = nullptr; bool nat_aside = true;      // (the history chain behind the preparation on the prepare stream: its join event)
   hipStream_t side = nullptr; bool side_owned = false; hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // (RIFT_TWO_STREAMS=0 switches it off) the agent-history chain (NAT levels + FPN tail) on a second stream beside the map / reference-line chain
   bool fo_w = true; unsigned short* fow_img[3] = {nullptr, nullptr, nullptr}; float* fow_par[3] = {nullptr, nullptr, nullptr};   // wave-private Fourier embeddings (fo_w.h): tokens, speed limits, reference-line positions
   bool pe_w = true; unsigned short* pew_img[2] = {nullptr, nullptr};   // wave-private PointsEncoder pass B (pe_w.h): weight streams of the map / reference-line encoders
@@ -125,6 +124,8 @@ struct RiftCtx {
   int* nonfinite = nullptr;              // device flag set by the policy-head kernels when the decoder output is not finite
   // the in-launch ranking's published per-scene counts (kernels.h: rank_scene_body), one array per arena; they persist between launches
   // (a word is valid when it carries the launch's epoch; zero at allocation, epochs start at 1)
+  // The look-back over these words relies on ONE preparation launch in flight per arena slot and on an epoch fixed on the host for each
+  // launch (prepare_inputs): a captured graph that replays the launch would replay a stale epoch, so that launch is never graph-replayed.
   unsigned long long* rk_pub[RIFT_DEFER_SLOTS] = {}; int rk_cap[RIFT_DEFER_SLOTS] = {}; unsigned int rk_epoch[RIFT_DEFER_SLOTS] = {};
   bool rank_fault = false;               // RIFT_RANK_FAULT=1 (diagnostic): the first scene block of the in-launch ranking never publishes its counts
   bool enc112 = true;                    // RIFT_ENC112=0: scenes of 97 .. 112 token slots on enc_w_kernel (rounds 3 - 5) instead of the fused kernel's 112-row layout
@@ -195,28 +196,7 @@ inline void delay_behind(RiftCtx* c, const char* label) {
   if (c->dg.delay_ticks > 0 && c->dg.delay_label == label) hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(1), 0, c->stream, c->dg.delay_ticks);
 }
 
-template <class... KArgs, class... Args>
-void launch(RiftCtx* c, const char* label, void (*kern)(KArgs...), dim3 grid, dim3 block, size_t shmem, Args... args) {
-  if (c->dry || grid.x == 0 || grid.y == 0) return;
-  if (c->poison_lds >= 0) {
-    const unsigned int b = (unsigned int)c->poison_lds & 0xffu;
-    hipLaunchKernelGGL(lds_poison_kernel, dim3(2048), dim3(256), 160 * 1024, c->stream, b | (b << 8) | (b << 16) | (b << 24));
-  }
-  if (c->prof_on) {
-    hipEvent_t e0, e1;
-    prof_events(c, &e0, &e1);
-    (void)hipEventRecord(e0, c->stream);
-    hipLaunchKernelGGL(kern, grid, block, shmem, c->stream, static_cast<KArgs>(args)...);
-    (void)hipEventRecord(e1, c->stream);
-    prof_push(c, label, e0, e1, c->prof_flops);
-    c->prof_flops = 0.0;
-    return;
-  }
-  hipLaunchKernelGGL(kern, grid, block, shmem, c->stream, static_cast<KArgs>(args)...);
-  delay_behind(c, label);
-}
-
-// same bookkeeping for a kernel that lives in another translation unit (its launch is the callable)
+// the bookkeeping around one launch (the callable): LDS poison ahead of it, profiling events around it, the diagnostic delay behind it
 template <class F>
 void launch_call(RiftCtx* c, const char* label, F&& f) {
   if (c->dry) return;
@@ -236,6 +216,12 @@ void launch_call(RiftCtx* c, const char* label, F&& f) {
   }
   f();
   delay_behind(c, label);
+}
+
+template <class... KArgs, class... Args>
+void launch(RiftCtx* c, const char* label, void (*kern)(KArgs...), dim3 grid, dim3 block, size_t shmem, Args... args) {
+  if (grid.x == 0 || grid.y == 0) return;
+  launch_call(c, label, [&] { hipLaunchKernelGGL(kern, grid, block, shmem, c->stream, static_cast<KArgs>(args)...); });
 }
 
 template <class... KArgs>
@@ -482,12 +468,35 @@ int set_lds_attrs(RiftCtx* c) {
   return RIFT_OK;
 }
 
-struct Fwd {   // per-forward context
+const std::string HE = "agent_encoder.history_encoder", PD = "planning_decoder";
+
+// per-forward context: the flags, the stream plan, the batch dimensions, and what one stage of forward_impl hands to the next
+struct Fwd {
   RiftCtx* c; bool train, drop, fp32, need_traj, bn_update; uint32_t seed; uint32_t stream_id = 1;
   uint32_t next_stream() { return stream_id++; }
   // data parallel (rift_set_dp): xchg[0, kb) = quirk-mask slots of the global minibatch, xchg[kb, ...) = BatchNorm sums of the current point
   bool dp = false, kpm_pending = false; int kb = 0; uint8_t* g_rkpm = nullptr;
   uint8_t* r_tiles = nullptr;                        // tiles of every reference line up to its last valid point (prep_kernel), for pe_w_kernel's packed rounds
+  const RiftFeatureBatch* B = nullptr; const RiftOutputs* out = nullptr; int flags = 0;
+  StreamPlan plan; hipStream_t on[3] = {nullptr, nullptr, nullptr};      // (indexed by PlanStream)
+  int bs = 0, A = 0, Mp = 0, R = 0, S = 0, T = 0, N = 0, M = 12, nA = 0, nP = 0, nL = 0, nQ = 0, nT = 0;
+  DropStats ds = {};                                 // diagnostic build (dropstats.h): this forward's counters; all zero in the product library
+  // prepare_inputs
+  float *F9 = nullptr, *F10 = nullptr, *F6 = nullptr, *pos = nullptr, *r_pos = nullptr;
+  uint8_t *valid_agent = nullptr, *kpm = nullptr, *r_kpm = nullptr;
+  bool nat_compact = false; int *nat_aidx = nullptr, *nat_cnt = nullptr;      // the history encoder on the compacted sequences (nat_l0w.h ranks them)
+  const uint8_t* q_kpm = nullptr; int q_bs = 0, q_off = 0;                    // the r2r mask quirk's rows: this shard's, or the gathered global minibatch's
+  // history_encoder, ego_token, map_and_embeddings, assemble_tokens
+  float *nat_out = nullptr, *x_ego = nullptr, *poly = nullptr, *r_emb = nullptr, *speed_emb = nullptr, *PEtok = nullptr, *Q = nullptr, *X = nullptr;
+  bool pe_pair = false, fo3 = false, rpe_done = false;
+  // scene_encoder
+  float* ENC = nullptr;
+  unsigned short* enc_KT = nullptr;   // the decoder's cross-attention K | V^T operand fragments, written by the encoder kernel's tail
+  uint8_t* kpm_c = nullptr;           // (RIFT_ENC_COMPACT) the key padding of the compacted encoder rows (bs, 96): what the decoder masks those fragments with
+  float* enc_x0p = nullptr;           // cat_x_proj's ego-token half, written by the encoder kernel's tail
+  bool enc_wide = false;
+  // planning_decoder
+  bool dec_deferred = false; DecWP dec_later;
 };
 
 // RCCL through dlopen (rift_comm_*): the library has no link-time dependency on a communication library; an RCCL that is already in the
@@ -888,7 +897,6 @@ __global__ void interleave_traj_kernel(const float* __restrict__ loc, const floa
 // The policy head of a forward: cat_x_proj -> pi_head (read LIVE: the only trainable parameters) -> masked logits, then the trajectory
 // heads on its q_final.  Launched on c->stream; leaves what rift_loss_backward consumes.
 int head_impl(RiftCtx* c, const RiftCtx::Head& h) {
-  const std::string PD = "planning_decoder";
   const int nQ = h.nQ, R = h.R, M = 12;
   Fwd f; f.c = c; f.fp32 = h.fp32; f.need_traj = h.need_traj; f.train = f.drop = f.bn_update = false; f.seed = 0;
   // Everything before reads frozen, load-time-packed weights only; pi_head.* is read LIVE from here on.  A host that updates pi_head on
@@ -941,183 +949,110 @@ int head_impl(RiftCtx* c, const RiftCtx::Head& h) {
   return RIFT_OK;
 }
 
-int forward_impl(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, int flags, uint32_t seed) {
-  Fwd f;
-  f.c = c; f.train = (flags & RIFT_F_TRAIN) != 0; f.drop = f.train && !(flags & RIFT_F_NO_DROP);
-  f.fp32 = (flags & RIFT_F_FP32) != 0; f.need_traj = (flags & RIFT_F_NEED_TRAJ) != 0;
-  f.bn_update = f.train && !(flags & RIFT_F_NO_BN_UPDATE); f.seed = seed;
-  const int bs = B->bs, A = B->A, Mp = B->Mp, R = B->R, S = B->S, T = B->T;
-  const int N = A + Mp + S, M = 12;
-  const int nA = bs * A, nP = bs * Mp, nL = bs * R, nQ = nL * M, nT = bs * N;
-  const std::string HE = "agent_encoder.history_encoder";
-
-  // ================= agent encoder (agent_encoder.py:54-96, embedding.py:62-87) =================
-  // ---- input-only preparation: one launch (prep_kernel) for the seven feature / mask / position builders
+// ================= agent encoder (agent_encoder.py:54-96, embedding.py:62-87) =================
+// ---- input-only preparation: one launch (prep_kernel) for the seven feature / mask / position builders
+// (on the plan's stream: the caller's prepare stream if there is one, rift_set_prepare_stream)
+int prepare_inputs(Fwd& f) {
+  RiftCtx* c = f.c;
+  const RiftFeatureBatch* B = f.B;
+  const int bs = f.bs, A = f.A, Mp = f.Mp, S = f.S, T = f.T, nA = f.nA, nP = f.nP, nL = f.nL, nT = f.nT;
   (void)A_alloc<float>(c, 64);          // front padding: the level-0 NAT kernel's window loads start up to 9 floats before a sequence's first row
-  float* F9 = A_alloc<float>(c, (size_t)nA * 20 * 9 + 64);
-  uint8_t* valid_agent = A_alloc<uint8_t>(c, nA);
+  f.F9 = A_alloc<float>(c, (size_t)nA * 20 * 9 + 64);
+  f.valid_agent = A_alloc<uint8_t>(c, nA);
   // the fused history encoder runs on the sequences its output is read of -- valid agents other than the ego (agent_encoder.py:77-87) -- in
   // compacted order (nat_l0w.h ranks them); the layer-wise / fp32 path keeps all nA sequences
-  const bool nat_compact = c->nat_compact && c->nat_fused && !f.fp32 && c->fpn_fused;
-  uint8_t* hist_agent = nat_compact ? A_alloc<uint8_t>(c, nA) : nullptr;
-  int* nat_aidx = nat_compact ? A_alloc<int>(c, nA) : nullptr;
-  int* nat_cnt = nat_compact ? A_alloc<int>(c, 4) : nullptr;
-  float* F10 = A_alloc<float>(c, (size_t)nP * 20 * 10);
-  float* F6 = A_alloc<float>(c, (size_t)nL * 120 * 6);
-  uint8_t* kpm = A_alloc<uint8_t>(c, nT);
-  float* pos = A_alloc<float>(c, (size_t)nT * 3);
-  float* r_pos = A_alloc<float>(c, (size_t)nL * 3);
-  uint8_t* r_kpm = A_alloc<uint8_t>(c, nL);
-  bool prefetched = false;
-  bool front_fused = false; float* x_ego_front = nullptr; EgoP ego_front; memset(&ego_front, 0, sizeof(ego_front));
+  f.nat_compact = c->nat_compact && c->nat_fused && !f.fp32 && c->fpn_fused;
+  uint8_t* hist_agent = f.nat_compact ? A_alloc<uint8_t>(c, nA) : nullptr;
+  f.nat_aidx = f.nat_compact ? A_alloc<int>(c, nA) : nullptr;
+  f.nat_cnt = f.nat_compact ? A_alloc<int>(c, 4) : nullptr;
+  f.F10 = A_alloc<float>(c, (size_t)nP * 20 * 10);
+  f.F6 = A_alloc<float>(c, (size_t)nL * 120 * 6);
+  f.kpm = A_alloc<uint8_t>(c, nT);
+  f.pos = A_alloc<float>(c, (size_t)nT * 3);
+  f.r_pos = A_alloc<float>(c, (size_t)nL * 3);
+  f.r_kpm = A_alloc<uint8_t>(c, nL);
   f.r_tiles = A_alloc<uint8_t>(c, (size_t)std::max(nL, 1));
-  {
-    PrepP q; memset(&q, 0, sizeof(q));
-    q.agent_pos = B->agent_position; q.agent_head = B->agent_heading; q.agent_vel = B->agent_velocity; q.agent_shape = B->agent_shape;
-    q.agent_valid = B->agent_valid_mask; q.nA = nA; q.Tfull = T; q.F9 = F9; q.valid_agent = valid_agent; q.hist_agent = hist_agent;
-    q.map_pp = B->map_point_position; q.map_pv = B->map_point_vector; q.map_po = B->map_point_orientation; q.map_center = B->map_polygon_center;
-    q.nPoly = nP; q.F10 = F10;
-    q.ref_pos = B->ref_position; q.ref_vec = B->ref_vector; q.ref_ori = B->ref_orientation; q.ref_valid = B->ref_valid_mask; q.nLine = nL;
-    q.F6 = F6; q.r_pos = r_pos; q.r_kpm = r_kpm; q.r_tiles = f.r_tiles;
-    q.map_valid = B->map_valid_mask; q.static_valid = B->static_valid_mask; q.st_pos = B->static_position; q.st_head = B->static_heading;
-    q.bs = bs; q.A = A; q.Mp = Mp; q.S = S; q.kpm = kpm; q.pos = pos;
-    q.nb[0] = cdiv((long long)nA * 20, 256); q.nb[1] = cdiv((long long)nP * 20, 256); q.nb[2] = cdiv((long long)nL * 120, 256);
-    q.nb[3] = cdiv(nL, 256); q.nb[4] = cdiv(nL, 256); q.nb[5] = cdiv(nT, 256); q.nb[6] = cdiv(nT, 256);
-    int tot = 0;
-    for (int i = 0; i < 7; ++i) tot += q.nb[i];
-    // (round 6) the ranking as the first bs blocks of this launch (kernels.h: rank_scene_body): no launch of its own on the history chain
-    const bool rank_in_prep = nat_compact && c->rank_in_prep && A <= 256 && !(c->front_fused && !f.fp32 && c->ego_fused);
-    if (rank_in_prep) {
-      const int sl = c->parity;
-      if (c->rk_cap[sl] < bs) {                          // (a batch beyond the arrays of rift_ctx_create: a fresh zeroed array, epochs start over)
-        HIPCHK(c, hipDeviceSynchronize());               // nothing in flight reads the old array; and the zeros below are in place before ANY stream's launch
-        if (c->rk_pub[sl]) { HIPCHK(c, hipFree(c->rk_pub[sl])); c->rk_pub[sl] = nullptr; c->rk_cap[sl] = 0; }
-        const int cap = std::max(2 * bs, 4096);
-        HIPCHK(c, hipMalloc((void**)&c->rk_pub[sl], (size_t)cap * sizeof(unsigned long long)));
-        HIPCHK(c, hipMemset(c->rk_pub[sl], 0, (size_t)cap * sizeof(unsigned long long)));
-        HIPCHK(c, hipDeviceSynchronize());               // (hipMemset of device memory may return before the fill has run, and the preparation is launched on a non-blocking stream)
-        c->rk_cap[sl] = cap; c->rk_epoch[sl] = 0;
-      }
-      q.nrk = bs; q.rk_pub = c->rk_pub[sl]; q.aidx = nat_aidx; q.cnt = nat_cnt; q.fail = c->nonfinite; q.rk_fault = c->rank_fault ? 1 : 0;
-      if (!c->dry) { if (++c->rk_epoch[sl] == 0u) c->rk_epoch[sl] = 1u; }      // (epoch 0 = "never written")
-      q.rk_epoch = c->rk_epoch[sl];
-      q.hist_agent = nullptr;                            // (the scene blocks derive the marks themselves)
-      tot += bs;
+  PrepP q; memset(&q, 0, sizeof(q));
+  q.agent_pos = B->agent_position; q.agent_head = B->agent_heading; q.agent_vel = B->agent_velocity; q.agent_shape = B->agent_shape;
+  q.agent_valid = B->agent_valid_mask; q.nA = nA; q.Tfull = T; q.F9 = f.F9; q.valid_agent = f.valid_agent; q.hist_agent = hist_agent;
+  q.map_pp = B->map_point_position; q.map_pv = B->map_point_vector; q.map_po = B->map_point_orientation; q.map_center = B->map_polygon_center;
+  q.nPoly = nP; q.F10 = f.F10;
+  q.ref_pos = B->ref_position; q.ref_vec = B->ref_vector; q.ref_ori = B->ref_orientation; q.ref_valid = B->ref_valid_mask; q.nLine = nL;
+  q.F6 = f.F6; q.r_pos = f.r_pos; q.r_kpm = f.r_kpm; q.r_tiles = f.r_tiles;
+  q.map_valid = B->map_valid_mask; q.static_valid = B->static_valid_mask; q.st_pos = B->static_position; q.st_head = B->static_heading;
+  q.bs = bs; q.A = A; q.Mp = Mp; q.S = S; q.kpm = f.kpm; q.pos = f.pos;
+  q.nb[0] = cdiv((long long)nA * 20, 256); q.nb[1] = cdiv((long long)nP * 20, 256); q.nb[2] = cdiv((long long)nL * 120, 256);
+  q.nb[3] = cdiv(nL, 256); q.nb[4] = cdiv(nL, 256); q.nb[5] = cdiv(nT, 256); q.nb[6] = cdiv(nT, 256);
+  int tot = 0;
+  for (int i = 0; i < 7; ++i) tot += q.nb[i];
+  // (round 6) the ranking as the first bs blocks of this launch (kernels.h: rank_scene_body): no launch of its own on the history chain
+  const bool rank_in_prep = f.nat_compact && c->rank_in_prep && A <= 256;
+  if (rank_in_prep) {
+    const int sl = c->parity;
+    if (c->rk_cap[sl] < bs) {                          // (a batch beyond the arrays of rift_ctx_create: a fresh zeroed array, epochs start over)
+      HIPCHK(c, hipDeviceSynchronize());               // nothing in flight reads the old array; and the zeros below are in place before ANY stream's launch
+      if (c->rk_pub[sl]) { HIPCHK(c, hipFree(c->rk_pub[sl])); c->rk_pub[sl] = nullptr; c->rk_cap[sl] = 0; }
+      const int cap = std::max(2 * bs, 4096);
+      HIPCHK(c, hipMalloc((void**)&c->rk_pub[sl], (size_t)cap * sizeof(unsigned long long)));
+      HIPCHK(c, hipMemset(c->rk_pub[sl], 0, (size_t)cap * sizeof(unsigned long long)));
+      HIPCHK(c, hipDeviceSynchronize());               // (hipMemset of device memory may return before the fill has run, and the preparation is launched on a non-blocking stream)
+      c->rk_cap[sl] = cap; c->rk_epoch[sl] = 0;
     }
-    // (round 4) the ranking and the ego token as blocks of the preparation's own launch (front.h): neither reads anything the preparation writes
-    front_fused = c->front_fused && !f.fp32 && c->ego_fused && !RIFT_DROP_STATS;      // (the diagnostic twin sets its counters up behind the preparation: it keeps the three launches)
-    FrontP fq; memset(&fq, 0, sizeof(fq));
-    if (front_fused) {
-      const std::string EG = "agent_encoder.ego_state_emb";
-      bool fill_eq;
-      float* eq = wconst_get(c, "ego_q", 128, f.fp32, &fill_eq);
-      if (fill_eq) gemm(c, mk(fptr(c, EG + ".query"), 128, 1, c->pw[EG + ".attn.q"], eq, 128), c->pw[EG + ".attn.q"], f.fp32);
-      x_ego_front = A_alloc<float>(c, (size_t)bs * 128);
-      EgoP& e = fq.ego;
-      e.cs = B->current_state; e.cs_ld = B->cs_ld; e.lw = c->ego_w; e.lb = c->ego_b; e.pos = fptr(c, EG + ".pos_embed");
-      e.wkv = (const unsigned short*)c->pw[EG + ".attn.kv"].bf; e.bkv = c->pw[EG + ".attn.kv"].bias; e.q = eq;
-      e.wo = (const unsigned short*)c->pw[EG + ".attn.out_proj"].bf; e.bo = c->pw[EG + ".attn.out_proj"].bias;
-      e.out = x_ego_front; e.bs = bs; e.drop_p = f.drop ? 0.75f : 0.f; e.seed = f.seed; e.stream = 0x45474Fu;      // (a stream id of its own: every other kernel keeps the id it had)
-      ego_front = e;
-      fq.n_ego = c->front_ego ? bs : 0;
-      fq.rank_on = nat_compact ? 1 : 0; fq.aidx = nat_aidx; fq.cnt = nat_cnt;
-      if (nat_compact) q.hist_agent = nullptr;          // (the ranking block derives the marks itself)
-      fq.prep = q;
-    }
-    auto launch_front = [&]() {
-      if (front_fused) {
-        c->prof_flops = 2.0 * bs * (6.0 * 128 * 256 + 128.0 * 128);
-        if (fq.n_ego) launch(c, "front_kernel", front_kernel<true>, dim3(tot + fq.n_ego + fq.rank_on), dim3(256), 0, fq);
-        else launch(c, "front_kernel", front_kernel<false>, dim3(tot + fq.rank_on), dim3(256), 0, fq);
-      } else {
-        launch(c, "prep_kernel", prep_kernel, dim3(tot), dim3(256), 0, q);
-        if (nat_compact && !rank_in_prep) launch(c, "nat_rank_kernel", nat_rank_kernel, dim3(1), dim3(NAT_RANK_THREADS), 0, (const uint8_t*)hist_agent, nA, nat_aidx, nat_cnt);
-      }
-    };
-    // on the caller's prepare stream if there is one (rift_set_prepare_stream): behind the gather of the batch, beside the previous step
-    prefetched = c->prep_set && !c->prof_on && !c->dry;
-    if (prefetched) {
-      if (!c->ev_prep) HIPCHK(c, hipEventCreateWithFlags(&c->ev_prep, hipEventDisableTiming));
-      hipStream_t own = c->stream;
-      c->stream = c->prep_stream;
-      launch_front();
-      c->stream = own;
-      HIPCHK(c, hipEventRecord(c->ev_prep, c->prep_stream));
-      // (round 6) when the history chain stays on the prepare stream and the map chain forks onto the side stream (the update loop's case),
-      // the caller's queue gets nothing before the join, and both joined chains are behind the preparation already: its own wait for the
-      // preparation would be a third one on the same fact (one event operation costs the host what a launch does)
-      const bool join_covers = c->two_streams && c->nat_fused && !f.fp32 && c->nat_aside && c->side_gate <= 0 && !c->dp.on;
-      if (!join_covers) HIPCHK(c, hipStreamWaitEvent(own, c->ev_prep, 0));
-    } else {
-      launch_front();
-    }
+    q.nrk = bs; q.rk_pub = c->rk_pub[sl]; q.aidx = f.nat_aidx; q.cnt = f.nat_cnt; q.fail = c->nonfinite; q.rk_fault = c->rank_fault ? 1 : 0;
+    if (!c->dry) { if (++c->rk_epoch[sl] == 0u) c->rk_epoch[sl] = 1u; }      // (epoch 0 = "never written")
+    q.rk_epoch = c->rk_epoch[sl];
+    q.hist_agent = nullptr;                            // (the scene blocks derive the marks themselves)
+    tot += bs;
   }
+  launch(c, "prep_kernel", prep_kernel, dim3(tot), dim3(256), 0, q);
+  if (f.nat_compact && !rank_in_prep) launch(c, "nat_rank_kernel", nat_rank_kernel, dim3(1), dim3(NAT_RANK_THREADS), 0, (const uint8_t*)hist_agent, nA, f.nat_aidx, f.nat_cnt);
+  return RIFT_OK;
+}
+
+void dp_kpm_fill(Fwd& f) {
+  RiftCtx* c = f.c;
+  launch(c, "dp_kpm_fill_kernel", dp_kpm_fill_kernel, dim3(cdiv(f.kb, 256)), dim3(256), 0, (const uint8_t*)f.r_kpm, f.nL, c->dp.off * f.R, f.kb, c->dp.xchg);
+}
+
+int dp_mask_and_drop_counters(Fwd& f) {
+  RiftCtx* c = f.c;
+  const int bs = f.bs, R = f.R, nA = f.nA;
   // data parallel: the r2r mask quirk indexes padding rows of the GLOBAL minibatch -> gather them (slots in the exchange buffer; the
   // first BatchNorm exchange carries them, an eval forward exchanges them on their own before the decoder)
-  const uint8_t* q_kpm = r_kpm; int q_bs = bs, q_off = 0;
+  f.q_kpm = f.r_kpm; f.q_bs = bs; f.q_off = 0;
   if (c->dp.on) {
     f.dp = true; f.kb = c->dp.gbs * R; f.kpm_pending = true;
     f.g_rkpm = A_alloc<uint8_t>(c, (size_t)f.kb);
     if ((long long)f.kb + 2 * 513 > c->dp.len || c->dp.off < 0 || c->dp.off + bs > c->dp.gbs) { c->err = "rift_set_dp: exchange buffer too small or shard outside the global minibatch"; return RIFT_ERR_ARG; }
-    // (with the preparation prefetched the fill waits for the head of the map chain: the exchange buffer is the one the previous forward's
-    // map chain exchanged through, and that chain's stream is what orders the two)
-    if (!prefetched) launch(c, "dp_kpm_fill_kernel", dp_kpm_fill_kernel, dim3(cdiv(f.kb, 256)), dim3(256), 0, (const uint8_t*)r_kpm, nL, c->dp.off * R, f.kb, c->dp.xchg);
-    q_kpm = f.g_rkpm; q_bs = c->dp.gbs; q_off = c->dp.off;
+    if (!f.plan.dp_fill_late) dp_kpm_fill(f);      // (late: behind the history chain's hand-back, forward_impl)
+    f.q_kpm = f.g_rkpm; f.q_bs = c->dp.gbs; f.q_off = c->dp.off;
   }
-  const bool dp_fill_late = c->dp.on && prefetched;
 #if RIFT_DROP_STATS      // diagnostic build (dropstats.h): the counters of this forward's stochastic decisions, readable as taps afterwards
-  DropStats ds; memset(&ds, 0, sizeof(ds));
   if (f.drop) {
-    ds.nmax = std::max(nA, bs * 6);
-    const size_t n = (size_t)RIFT_DS_SITES * ds.nmax;
-    ds.cnt = A_alloc<unsigned int>(c, n); ds.any = A_alloc<unsigned int>(c, n); ds.all = A_alloc<unsigned int>(c, n);
-    ds.scale = A_alloc<float>(c, RIFT_DS_SITES + RIFT_DS_DEC_SITES); ds.elem = A_alloc<unsigned long long>(c, 2 * RIFT_DS_DEC_SITES);
+    f.ds.nmax = std::max(nA, bs * 6);
+    const size_t n = (size_t)RIFT_DS_SITES * f.ds.nmax;
+    f.ds.cnt = A_alloc<unsigned int>(c, n); f.ds.any = A_alloc<unsigned int>(c, n); f.ds.all = A_alloc<unsigned int>(c, n);
+    f.ds.scale = A_alloc<float>(c, RIFT_DS_SITES + RIFT_DS_DEC_SITES); f.ds.elem = A_alloc<unsigned long long>(c, 2 * RIFT_DS_DEC_SITES);
     if (!c->dry) {
-      HIPCHK(c, hipMemsetAsync(ds.cnt, 0, n * 4, c->stream)); HIPCHK(c, hipMemsetAsync(ds.any, 0, n * 4, c->stream));
-      HIPCHK(c, hipMemsetAsync(ds.all, 0xff, n * 4, c->stream));
-      HIPCHK(c, hipMemsetAsync(ds.scale, 0, (RIFT_DS_SITES + RIFT_DS_DEC_SITES) * 4, c->stream));
-      HIPCHK(c, hipMemsetAsync(ds.elem, 0, 2 * RIFT_DS_DEC_SITES * 8, c->stream));
+      HIPCHK(c, hipMemsetAsync(f.ds.cnt, 0, n * 4, c->stream)); HIPCHK(c, hipMemsetAsync(f.ds.any, 0, n * 4, c->stream));
+      HIPCHK(c, hipMemsetAsync(f.ds.all, 0xff, n * 4, c->stream));
+      HIPCHK(c, hipMemsetAsync(f.ds.scale, 0, (RIFT_DS_SITES + RIFT_DS_DEC_SITES) * 4, c->stream));
+      HIPCHK(c, hipMemsetAsync(f.ds.elem, 0, 2 * RIFT_DS_DEC_SITES * 8, c->stream));
     }
-    tap(c, "drop_cnt", (float*)ds.cnt, (int64_t)n); tap(c, "drop_any", (float*)ds.any, (int64_t)n); tap(c, "drop_all", (float*)ds.all, (int64_t)n);
-    tap(c, "drop_scale", ds.scale, RIFT_DS_SITES + RIFT_DS_DEC_SITES); tap(c, "drop_elem", (float*)ds.elem, 4 * RIFT_DS_DEC_SITES);
+    tap(c, "drop_cnt", (float*)f.ds.cnt, (int64_t)n); tap(c, "drop_any", (float*)f.ds.any, (int64_t)n); tap(c, "drop_all", (float*)f.ds.all, (int64_t)n);
+    tap(c, "drop_scale", f.ds.scale, RIFT_DS_SITES + RIFT_DS_DEC_SITES); tap(c, "drop_elem", (float*)f.ds.elem, 4 * RIFT_DS_DEC_SITES);
   }
-#define RIFT_SET_DS(x) (x).ds = ds
-#else
-#define RIFT_SET_DS(x)
 #endif
-  if (nat_compact) { tap(c, "nat_aidx", (float*)nat_aidx, nA); tap(c, "nat_cnt", (float*)nat_cnt, 3); }      // (int32 words read back through the float tap)
+  if (f.nat_compact) { tap(c, "nat_aidx", (float*)f.nat_aidx, nA); tap(c, "nat_cnt", (float*)f.nat_cnt, 3); }      // (int32 words read back through the float tap)
+  return RIFT_OK;
+}
+
+// ---- agent-history chain: the three NAT levels (one launch each, or layer-wise) and the FPN tail
+void history_encoder(Fwd& f) {
+  RiftCtx* c = f.c;
+  const int nA = f.nA;
   static const float dpr[6] = {0.f, 0.04f, 0.08f, 0.12f, 0.16f, 0.2f};   // linspace(0, 0.2, 6), embedding.py:30
   const bool fused = c->nat_fused && !f.fp32;
-  // fork: the agent-history chain depends on prep_kernel only and joins at the token assembly; on its own stream it fills the CUs the
-  // map / reference-line chain leaves idle (partial last rounds, 238-workgroup launches) and vice versa.  Off while profiling per kernel.
-  hipStream_t main_stream = c->stream;
-  const bool forked = c->two_streams && fused && !c->prof_on && !c->dry;
-  bool nat_aside = false;
-  if (forked) {
-    if (!c->side) { HIPCHK(c, hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking)); c->side_owned = true; }
-    if (!c->ev_fork) { HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming)); HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming)); }
-    // With the preparation prefetched, neither front chain of step k + 1 needs anything of step k: the map chain (side stream) waits for
-    // the preparation only, the agent-history chain follows it on the prepare stream, and the caller's queue holds token assembly ->
-    // encoder -> decoder of step k, then of step k + 1 -- the fronts run beside the previous step's one-workgroup-per-scene encoder /
-    // decoder (which leave most of the chip idle below 256 scenes; at 256 they hold every CU whole, and what is gained is that the fronts
-    // start the moment CUs come free, with gather and preparation long done -- profiles/r03_timeline_256.txt).  ms per step, fronts behind the caller's queue
-    // / beside it: 32 scenes 0.372 / 0.237, 64 0.394 / 0.245, 128 0.462 / 0.389, 192 0.597 / 0.524, 256 0.701 / 0.678.  What it took:
-    // RIFT_DEFER_SLOTS = 4 arenas (with two, tail k - 1 -> front k + 1 -> encoder / decoder k + 1 -> tail k + 1 is a cycle two steps long)
-    // and no further hardware queue for the history chain (on a stream of its own every cross-queue wait of the step got slower: 0.372).
-    // RIFT_SIDE_GATE=1 keeps the fronts behind the caller's queue (the event record costs that queue ~5 us), RIFT_NAT_ASIDE=0 the history
-    // chain on it.
-    const bool gate = c->side_gate > 0;
-    if (prefetched) HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_prep, 0));
-    if (!prefetched || gate) {
-      HIPCHK(c, hipEventRecord(c->ev_fork, main_stream));
-      HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
-    }
-    nat_aside = prefetched && !gate && c->nat_aside;
-    if (nat_aside) {
-      if (!c->ev_join2) HIPCHK(c, hipEventCreateWithFlags(&c->ev_join2, hipEventDisableTiming));
-      c->stream = c->prep_stream;
-    } else if (!c->nat_on_main) c->stream = c->side;
-  }
   static const int Ll[3] = {20, 10, 5}, Cl[3] = {32, 64, 128}, Hl[3] = {2, 4, 8}, Kl[3] = {3, 3, 5};
   float* Oc[3];   // LayerNorm(norm_i) of the last 3 steps of level i: all that out[:, :, -1] of the FPN depends on
   for (int i = 0; i < 3; ++i) Oc[i] = A_alloc<float>(c, (size_t)nA * 3 * Cl[i]);
@@ -1132,31 +1067,31 @@ int forward_impl(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
       const int C = Cl[lv], H = Hl[lv], ksz = Kl[lv], L = Ll[lv], rows = nA * L;
       if (lv == 0) {   // level 0 as wave-private, register-resident tiles (no workgroup barriers): nat_l0w.h
         NatL0WP q; memset(&q, 0, sizeof(q));
-        q.aidx = nat_aidx; q.cnt = nat_cnt;
-        q.F9 = F9; q.nseq = nA; q.img = c->l0w_img; q.par = c->l0w_par; q.Oc = Oc[0]; q.Ocb = Ocb[0]; q.Xnext = Xin[1];
+        q.aidx = f.nat_aidx; q.cnt = f.nat_cnt;
+        q.F9 = f.F9; q.nseq = nA; q.img = c->l0w_img; q.par = c->l0w_par; q.Oc = Oc[0]; q.Ocb = Ocb[0]; q.Xnext = Xin[1];
         { if (c->dg.nat_ts == 1) { q.ts = A_alloc<long long>(c, 64); tap(c, "nat_ts", (float*)q.ts, 128); } }
         q.droppath[0] = f.drop ? dpr[0] : 0.f; q.droppath[1] = f.drop ? dpr[1] : 0.f; q.seed = f.seed; q.stream = f.next_stream(); f.stream_id += 4;
-        RIFT_SET_DS(q);
+        q.ds = f.ds;
         c->prof_flops = 2.0 * rows * (20.0 * C * C + 4.0 * ksz * C) + 2.0 * rows * 27 * 32 + (rows / 2) * 2.0 * 3 * C * 2 * C;
         { const int g0 = std::min(cdiv(cdiv(nA, 4), L0W_NWV), c->nat_grid); launch_call(c, "nat_l0w_kernel", [&] { l0w_launch(q, g0, c->stream); }); }
         continue;
       }
       if (lv == 1) {   // level 1 likewise (weights swapped through LDS between the two layers): nat_l1w.h
         NatL1WP q; memset(&q, 0, sizeof(q));
-        q.cnt = nat_cnt;
+        q.cnt = f.nat_cnt;
         q.X = Xin[1]; q.nseq = nA; q.img = c->l1w_img; q.par = c->l1w_par; q.Oc = Oc[1]; q.Ocb = Ocb[1]; q.Xnext = Xin[2];
         q.droppath[0] = f.drop ? dpr[2] : 0.f; q.droppath[1] = f.drop ? dpr[3] : 0.f; q.seed = f.seed; q.stream = f.next_stream(); f.stream_id += 4;
-        RIFT_SET_DS(q);
+        q.ds = f.ds;
         c->prof_flops = 2.0 * rows * (20.0 * C * C + 4.0 * ksz * C) + (rows / 2) * 2.0 * 3 * C * 2 * C;
         { const int g1 = std::min(cdiv(cdiv(nA, 4), L1W_NWV), c->nat_grid); launch_call(c, "nat_l1w_kernel", [&] { l1w_launch(q, g1, c->stream); }); }
         continue;
       }
       {   // level 2: wave-private tiles of 3 agents, the two layers' weights streamed through LDS (nat_l2w.h)
         NatL2WP q; memset(&q, 0, sizeof(q));
-        q.cnt = nat_cnt;
+        q.cnt = f.nat_cnt;
         q.X = Xin[2]; q.nseq = nA; q.img = c->l2w_img; q.par = c->l2w_par; q.Oc = Oc[2]; q.Ocb = Ocb[2];
         q.droppath[0] = f.drop ? dpr[4] : 0.f; q.droppath[1] = f.drop ? dpr[5] : 0.f; q.seed = f.seed; q.stream = f.next_stream(); f.stream_id += 4;
-        RIFT_SET_DS(q);
+        q.ds = f.ds;
         { if (c->dg.nat_ts == 3) { q.ts = A_alloc<long long>(c, 64); tap(c, "nat_ts", (float*)q.ts, 128); } }
         c->prof_flops = 2.0 * rows * (20.0 * C * C + 4.0 * ksz * C);
         // (round 6: up to one tile per workgroup -- a launch that does not fill the chip deals its tiles wave-major and waves without a tile skip
@@ -1169,7 +1104,7 @@ int forward_impl(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
   } else {
     float* X0 = A_alloc<float>(c, (size_t)nA * 20 * 32);
     {
-      GemmP g = mk(F9, 9, nA * 20, c->pw[HE + ".embed.proj"], X0, 32);
+      GemmP g = mk(f.F9, 9, nA * 20, c->pw[HE + ".embed.proj"], X0, 32);
       g.amode = AMODE_CONV3; g.cv_C = 9; g.cv_Lin = 20; g.cv_nout = 20; g.cv_t0 = 0; g.cv_stride = 1;
       gemm(c, g, c->pw[HE + ".embed.proj"], f.fp32);
     }
@@ -1206,7 +1141,7 @@ int forward_impl(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
                1e-5f, 0);
   }
   // FPN restricted to what out[:, :, -1] depends on
-  float* nat_out = A_alloc<float>(c, (size_t)nA * 128);
+  f.nat_out = A_alloc<float>(c, (size_t)nA * 128);
   if (fused && c->fpn_fused) {
     FpnP q; memset(&q, 0, sizeof(q));
     for (int i = 0; i < 3; ++i) {
@@ -1214,7 +1149,7 @@ int forward_impl(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
       q.oc[i] = Oc[i]; q.ocb[i] = Ocb[i]; q.wl[i] = (const unsigned short*)w.bf; q.bl[i] = w.bias;
     }
     q.wf = (const unsigned short*)c->pw[HE + ".fpn_conv.last"].bf; q.bf_ = c->pw[HE + ".fpn_conv.last"].bias;
-    q.out = nat_out; q.nA = nA; q.cnt = fused ? nat_cnt : nullptr; q.aidx = fused ? nat_aidx : nullptr;
+    q.out = f.nat_out; q.nA = nA; q.cnt = fused ? f.nat_cnt : nullptr; q.aidx = fused ? f.nat_aidx : nullptr;
     c->prof_flops = 2.0 * nA * (2.0 * 128 * (96 + 192 + 384) + 256.0 * 128);
     launch(c, "fpn_tail_kernel", fpn_tail_kernel, dim3(cdiv(nA, FPN_AG)), dim3(512), (size_t)FPN_LDS, q);
   } else {
@@ -1229,39 +1164,30 @@ int forward_impl(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
     float* Z = A_alloc<float>(c, (size_t)nA * 256);
     launch(c, "fpn_merge_kernel", fpn_merge_kernel, dim3(cdiv((long long)nA * 128, 256)), dim3(256), 0, (const float*)lat[0], (const float*)lat[1],
            (const float*)lat[2], nA, Z);
-    gemm(c, mk(Z, 256, nA, c->pw[HE + ".fpn_conv.last"], nat_out, 128), c->pw[HE + ".fpn_conv.last"], f.fp32);
+    gemm(c, mk(Z, 256, nA, c->pw[HE + ".fpn_conv.last"], f.nat_out, 128), c->pw[HE + ".fpn_conv.last"], f.fp32);
   }
-  // the longer chain (agent history: ~310 of the front's ~510 us at 256 scenes) stays on the caller's queue, so neither its start nor the
-  // join pays a cross-queue hop (12-15 us each by the kernel trace); the map / reference-line chain is the one that forks
-  if (forked) {
-    if (nat_aside) { HIPCHK(c, hipEventRecord(c->ev_join2, c->prep_stream)); c->stream = c->side; }
-    else if (c->nat_on_main) c->stream = c->side;
-    else { HIPCHK(c, hipEventRecord(c->ev_join, c->side)); c->stream = main_stream; }
-  }
-  if (dp_fill_late)      // (on the map chain's stream if there is one, else on the caller's: behind the previous forward's exchanges either way)
-    launch(c, "dp_kpm_fill_kernel", dp_kpm_fill_kernel, dim3(cdiv(f.kb, 256)), dim3(256), 0, (const uint8_t*)r_kpm, nL, c->dp.off * R, f.kb, c->dp.xchg);
-  tap(c, "nat_out", nat_out, (int64_t)nA * 128);
+  tap(c, "nat_out", f.nat_out, (int64_t)nA * 128);
+}
 
-  // ego state token (StateAttentionEncoder, agent_encoder.py:99-140)
+// ego state token (StateAttentionEncoder, agent_encoder.py:99-140)
+void ego_token(Fwd& f) {
+  RiftCtx* c = f.c;
+  const RiftFeatureBatch* B = f.B;
+  const int bs = f.bs;
   const std::string EG = "agent_encoder.ego_state_emb";
   bool fill_eq;
   float* eq = wconst_get(c, "ego_q", 128, f.fp32, &fill_eq);
   if (fill_eq) gemm(c, mk(fptr(c, EG + ".query"), 128, 1, c->pw[EG + ".attn.q"], eq, 128), c->pw[EG + ".attn.q"], f.fp32);
-  float* x_ego = front_fused ? x_ego_front : A_alloc<float>(c, (size_t)bs * 128);
-  if (front_fused && c->front_ego) {
-    if (f.drop) (void)f.next_stream();          // (the id the ego token's own launch used to take: the kernels behind it keep theirs)
-  } else if (!f.fp32 && c->ego_fused) {
+  f.x_ego = A_alloc<float>(c, (size_t)bs * 128);
+  if (!f.fp32 && c->ego_fused) {
     EgoP q; memset(&q, 0, sizeof(q));
-    if (front_fused) { q = ego_front; q.stream = f.drop ? f.next_stream() : 0; } else {
     q.cs = B->current_state; q.cs_ld = B->cs_ld; q.lw = c->ego_w; q.lb = c->ego_b; q.pos = fptr(c, EG + ".pos_embed");
     q.wkv = (const unsigned short*)c->pw[EG + ".attn.kv"].bf; q.bkv = c->pw[EG + ".attn.kv"].bias; q.q = eq;
     q.wo = (const unsigned short*)c->pw[EG + ".attn.out_proj"].bf; q.bo = c->pw[EG + ".attn.out_proj"].bias;
-    q.out = x_ego; q.bs = bs; q.drop_p = f.drop ? 0.75f : 0.f; q.seed = f.seed; q.stream = f.drop ? f.next_stream() : 0;
-    }
-    RIFT_SET_DS(q);
+    q.out = f.x_ego; q.bs = bs; q.drop_p = f.drop ? 0.75f : 0.f; q.seed = f.seed; q.stream = f.drop ? f.next_stream() : 0;
+    q.ds = f.ds;
     c->prof_flops = 2.0 * bs * (6.0 * 128 * 256 + 128.0 * 128);
-    // (diagnostic RIFT_EGO_NOFIT=1: 40 KB of unused dynamic LDS keep the workgroup from fitting beside the decoder's -- the round-3 behaviour, for A/B)
-    launch(c, "ego_fused_kernel", ego_fused_kernel, dim3(bs), dim3(256), (size_t)(c->ego_nofit ? 40960 : 0), q);
+    launch(c, "ego_fused_kernel", ego_fused_kernel, dim3(bs), dim3(256), 0, q);
   } else {
   float* E = A_alloc<float>(c, (size_t)bs * 6 * 128);
   launch(c, "ego_token_kernel", ego_token_kernel, dim3(cdiv((long long)bs * 6 * 128, 256)), dim3(256), 0, B->current_state, B->cs_ld,
@@ -1282,31 +1208,54 @@ int forward_impl(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
     p.o_outer = 1; p.o_inner = 0; p.o_stride = 0; p.mask = edrop; p.mask_quirk = 0; p.mask_mod = 1;
     run_mha(c, p, f.fp32);
   }
-  gemm(c, mk(EAO, 128, bs, c->pw[EG + ".attn.out_proj"], x_ego, 128), c->pw[EG + ".attn.out_proj"], f.fp32);
+  gemm(c, mk(EAO, 128, bs, c->pw[EG + ".attn.out_proj"], f.x_ego, 128), c->pw[EG + ".attn.out_proj"], f.fp32);
   }
-  tap(c, "x_ego", x_ego, (int64_t)bs * 128);
+  tap(c, "x_ego", f.x_ego, (int64_t)bs * 128);
+}
 
-  // ================= tokens =================
-  float* X = A_alloc<float>(c, (size_t)nT * 128);
+// decoder queries q0 = q_proj(cat[r_emb, m_emb]) (planning_decoder.py:149-154): they depend on the reference-line embedding only, so with the fused
+// embeddings done they are launched here, ahead of the join, and run beside the tail of the agent-history chain instead of between encoder and decoder
+int build_q0(Fwd& f) {
+  RiftCtx* c = f.c;
+  const int M = f.M, nL = f.nL, nQ = f.nQ;
+  bool fill;
+  float* Mb = wconst_get(c, "Mb", (size_t)M * 128, f.fp32, &fill);
+  if (fill) gemm(c, mk(fptr(c, PD + ".m_emb"), 128, M, c->pw[PD + ".q_proj.m"], Mb, 128), c->pw[PD + ".q_proj.m"], f.fp32);
+  f.Q = A_alloc<float>(c, (size_t)nQ * 128);
+  if (!f.fp32 && c->pi_fused) {
+    Q0P q; memset(&q, 0, sizeof(q));
+    q.r_emb = f.r_emb; q.nL = nL; q.M = M; q.wr = (const unsigned short*)c->pw[PD + ".q_proj.r"].bf; q.br = c->pw[PD + ".q_proj.r"].bias;
+    q.Mb = Mb; q.Q = f.Q;
+    c->prof_flops = 2.0 * nL * 128.0 * 128;
+    launch(c, "q0_fused_kernel", q0_fused_kernel, dim3(cdiv(nL, 16)), dim3(256), 0, q);
+  } else {
+    float* Ra = A_alloc<float>(c, (size_t)nL * 128);
+    gemm(c, mk(f.r_emb, 128, nL, c->pw[PD + ".q_proj.r"], Ra, 128), c->pw[PD + ".q_proj.r"], f.fp32);
+    launch(c, "build_q0_kernel", build_q0_kernel, dim3(cdiv((long long)nQ * 128, 256)), dim3(256), 0, (const float*)Ra, (const float*)Mb, nL, M, f.Q);
+  }
+  return RIFT_OK;
+}
+
+// ---- map chain: both PointsEncoders, the three Fourier embeddings, the decoder queries
+int map_and_embeddings(Fwd& f) {
+  RiftCtx* c = f.c;
+  const RiftFeatureBatch* B = f.B;
+  const int S = f.S, nP = f.nP, nL = f.nL, nT = f.nT;
   // map encoder (map_encoder.py:31-93)
   // reference-line features are input-only too: both PointsEncoders run side by side (fused path)
-  const std::string PD = "planning_decoder";
-  float *poly = nullptr, *r_emb = nullptr;
-  const bool pe_pair = !f.fp32 && c->pe_fused;
-  if (pe_pair) points_encoder_pair(f, F10, nP, B->map_valid_mask, "map_encoder.polygon_encoder", F6, nL, B->ref_valid_mask, PD + ".r_encoder", &poly, &r_emb);
-  else poly = points_encoder(f, F10, 10, nP, 20, B->map_valid_mask, "map_encoder.polygon_encoder");
-  tap(c, "poly_pe", poly, (int64_t)nP * 128);
+  f.pe_pair = !f.fp32 && c->pe_fused;
+  if (f.pe_pair) points_encoder_pair(f, f.F10, nP, B->map_valid_mask, "map_encoder.polygon_encoder", f.F6, nL, B->ref_valid_mask, PD + ".r_encoder", &f.poly, &f.r_emb);
+  else f.poly = points_encoder(f, f.F10, 10, nP, 20, B->map_valid_mask, "map_encoder.polygon_encoder");
+  tap(c, "poly_pe", f.poly, (int64_t)nP * 128);
   // the three Fourier embeddings (token positions, speed limits, reference-line positions) depend on inputs only: with both
   // PointsEncoders done they run as ONE launch, and the token kernels add the positional embedding on the way
-  const bool fo3 = pe_pair && !f.fp32 && c->fo_fused && S == 0;
-  float *speed_emb = nullptr, *PEtok = nullptr;
-  bool rpe_done = false;
-  if (fo3) {
-    tap(c, "r_pe", r_emb, (int64_t)nL * 128);
+  f.fo3 = f.pe_pair && !f.fp32 && c->fo_fused && S == 0;
+  if (f.fo3) {
+    tap(c, "r_pe", f.r_emb, (int64_t)nL * 128);
     FourierP3 q3; memset(&q3, 0, sizeof(q3));
-    q3.e[0] = fourier_desc(f, pos, 3, nT, 3, "pos_emb", 2, nullptr);
+    q3.e[0] = fourier_desc(f, f.pos, 3, nT, 3, "pos_emb", 2, nullptr);
     q3.e[1] = fourier_desc(f, B->map_polygon_speed_limit, 1, nP, 1, "map_encoder.speed_limit_emb", -1, nullptr);
-    q3.e[2] = fourier_desc(f, r_pos, 3, nL, 3, PD + ".r_pos_emb", -1, r_emb);
+    q3.e[2] = fourier_desc(f, f.r_pos, 3, nL, 3, PD + ".r_pos_emb", -1, f.r_emb);
     q3.nblk[0] = cdiv(nT, FO_ROWS); q3.nblk[1] = cdiv(nP, FO_ROWS); q3.nblk[2] = cdiv(nL, FO_ROWS); q3.count = 3;
     c->prof_flops = 2.0 * 128.0 * ((nT + nL) * (3 * 257.0 + 128.0) + nP * (257.0 + 128.0));
     if (c->fo_w) {          // wave-private form: one 16-row tile per wave, 8 tiles per pass, the one-dimensional embedding two passes per workgroup
@@ -1320,75 +1269,49 @@ int forward_impl(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
       launch_call(c, "fo_w_kernel", [&] { fow_launch(w, c->stream); });
     } else
     launch(c, "fourier_fused_kernel", fourier_fused_kernel, dim3(q3.nblk[0] + q3.nblk[1] + q3.nblk[2]), dim3(256), (size_t)FO_LDS, q3);
-    PEtok = q3.e[0].Y; speed_emb = q3.e[1].Y; rpe_done = true;
+    f.PEtok = q3.e[0].Y; f.speed_emb = q3.e[1].Y; f.rpe_done = true;
   } else {
-    speed_emb = fourier(f, B->map_polygon_speed_limit, 1, nP, 1, "map_encoder.speed_limit_emb", -1);
+    f.speed_emb = fourier(f, B->map_polygon_speed_limit, 1, nP, 1, "map_encoder.speed_limit_emb", -1);
   }
-  // decoder queries q0 = q_proj(cat[r_emb, m_emb]) (planning_decoder.py:149-154): they depend on the reference-line embedding only, so with the fused
-  // embeddings done they are launched here, ahead of the join, and run beside the tail of the agent-history chain instead of between encoder and decoder
-  float* Q = nullptr;
-  auto build_q0 = [&]() -> int {
-  bool fill;
-  float* Mb = wconst_get(c, "Mb", (size_t)M * 128, f.fp32, &fill);
-  if (fill) gemm(c, mk(fptr(c, PD + ".m_emb"), 128, M, c->pw[PD + ".q_proj.m"], Mb, 128), c->pw[PD + ".q_proj.m"], f.fp32);
-  Q = A_alloc<float>(c, (size_t)nQ * 128);
-  if (!f.fp32 && c->pi_fused) {
-    Q0P q; memset(&q, 0, sizeof(q));
-    q.r_emb = r_emb; q.nL = nL; q.M = M; q.wr = (const unsigned short*)c->pw[PD + ".q_proj.r"].bf; q.br = c->pw[PD + ".q_proj.r"].bias;
-    q.Mb = Mb; q.Q = Q;
-    c->prof_flops = 2.0 * nL * 128.0 * 128;
-    launch(c, "q0_fused_kernel", q0_fused_kernel, dim3(cdiv(nL, 16)), dim3(256), 0, q);
-  } else {
-    float* Ra = A_alloc<float>(c, (size_t)nL * 128);
-    gemm(c, mk(r_emb, 128, nL, c->pw[PD + ".q_proj.r"], Ra, 128), c->pw[PD + ".q_proj.r"], f.fp32);
-    launch(c, "build_q0_kernel", build_q0_kernel, dim3(cdiv((long long)nQ * 128, 256)), dim3(256), 0, (const float*)Ra, (const float*)Mb, nL, M, Q);
-  }
-    return RIFT_OK;
-  };
-  if (forked && rpe_done) { const int rc0 = build_q0(); if (rc0 != RIFT_OK) return rc0; }
-  // join: the agent tokens need both chains.  Small batches: the map chain waits for the history chain first, so that the caller's queue --
-  // token assembly, encoder, decoder: the step, below a chip-filling batch -- takes ONE cross-queue wait per forward (32 scenes: 0.233 ->
-  // 0.226 ms); at 128 scenes it makes no difference and at 256 it costs 1-3 % (the map chain of the step after next stalls behind the wait)
-  const bool join_once = nat_aside && (c->join_once >= 0 ? c->join_once != 0 : bs <= 64);
-  if (join_once) HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_join2, 0));
-  if (forked && (c->nat_on_main || nat_aside)) { HIPCHK(c, hipEventRecord(c->ev_join, c->side)); c->stream = main_stream; }
-  if (forked) HIPCHK(c, hipStreamWaitEvent(main_stream, c->ev_join, 0));
-  if (nat_aside && !join_once) HIPCHK(c, hipStreamWaitEvent(main_stream, c->ev_join2, 0));
-  // token assembly: fused into the scene encoder's prologue where that kernel runs (N <= 96, no static objects, position embedding from
-  // the one-launch Fourier pass), a launch of its own otherwise
-  const bool tok_fused = c->tok_fused && c->enc_fused && !f.fp32 && N <= 96 && S == 0 && fo3 && PEtok != nullptr;
-  TokenP tokq; memset(&tokq, 0, sizeof(tokq));
-  {
-    TokenP& q = tokq;
-    q.nat = nat_out; q.x_ego = x_ego; q.valid_agent = (const uint8_t*)valid_agent; q.category = B->agent_category; q.a_type_emb = fptr(c, "agent_encoder.type_emb.weight");
-    q.pooled = poly; q.ptype = B->map_polygon_type; q.on_route = B->map_polygon_on_route; q.tl = B->map_polygon_tl_status; q.has_sl = B->map_polygon_has_speed_limit;
-    q.speed_emb = speed_emb; q.p_type_emb = fptr(c, "map_encoder.type_emb.weight"); q.route_emb = fptr(c, "map_encoder.on_route_emb.weight");
-    q.tl_emb = fptr(c, "map_encoder.traffic_light_emb.weight"); q.unk_emb = fptr(c, "map_encoder.unknown_speed_emb.weight");
-    q.bs = bs; q.A = A; q.Mp = Mp; q.N = N; q.X = X; q.pe = PEtok;
-    q.nblk_a = cdiv((long long)nA * 32, 256);
-    if (!tok_fused) launch(c, "token_kernel", token_kernel, dim3(q.nblk_a + cdiv((long long)nP * 32, 256)), dim3(256), 0, q);
-  }
+  if (f.plan.forked && f.rpe_done) TRY(build_q0(f));      // ahead of the join
+  return RIFT_OK;
+}
+
+// ================= tokens =================
+void assemble_tokens(Fwd& f) {
+  RiftCtx* c = f.c;
+  const RiftFeatureBatch* B = f.B;
+  const int bs = f.bs, A = f.A, Mp = f.Mp, S = f.S, N = f.N, nA = f.nA, nP = f.nP, nT = f.nT;
+  f.X = A_alloc<float>(c, (size_t)nT * 128);
+  TokenP q; memset(&q, 0, sizeof(q));
+  q.nat = f.nat_out; q.x_ego = f.x_ego; q.valid_agent = (const uint8_t*)f.valid_agent; q.category = B->agent_category; q.a_type_emb = fptr(c, "agent_encoder.type_emb.weight");
+  q.pooled = f.poly; q.ptype = B->map_polygon_type; q.on_route = B->map_polygon_on_route; q.tl = B->map_polygon_tl_status; q.has_sl = B->map_polygon_has_speed_limit;
+  q.speed_emb = f.speed_emb; q.p_type_emb = fptr(c, "map_encoder.type_emb.weight"); q.route_emb = fptr(c, "map_encoder.on_route_emb.weight");
+  q.tl_emb = fptr(c, "map_encoder.traffic_light_emb.weight"); q.unk_emb = fptr(c, "map_encoder.unknown_speed_emb.weight");
+  q.bs = bs; q.A = A; q.Mp = Mp; q.N = N; q.X = f.X; q.pe = f.PEtok;
+  q.nblk_a = cdiv((long long)nA * 32, 256);
+  launch(c, "token_kernel", token_kernel, dim3(q.nblk_a + cdiv((long long)nP * 32, 256)), dim3(256), 0, q);
   if (S > 0) {
     float* semb = fourier(f, B->static_shape, 2, bs * S, 2, "static_objects_encoder.obj_encoder", -1);
     launch(c, "static_token_kernel", static_token_kernel, dim3(cdiv((long long)bs * S * 128, 256)), dim3(256), 0, (const float*)semb, B->static_category,
-           B->static_valid_mask, fptr(c, "static_objects_encoder.type_emb.weight"), bs, A, Mp, S, N, X);
+           B->static_valid_mask, fptr(c, "static_objects_encoder.type_emb.weight"), bs, A, Mp, S, N, f.X);
   }
-  if (!fo3) fourier(f, pos, 3, nT, 3, "pos_emb", 2, X);
-  tap(c, "x_tokens", X, (int64_t)nT * 128);
+  if (!f.fo3) fourier(f, f.pos, 3, nT, 3, "pos_emb", 2, f.X);
+  tap(c, "x_tokens", f.X, (int64_t)nT * 128);
+}
 
-  // ================= encoder blocks (transformer.py:73-94) =================
+// ================= encoder blocks (transformer.py:73-94) =================
+void scene_encoder(Fwd& f) {
+  RiftCtx* c = f.c;
+  const int bs = f.bs, R = f.R, N = f.N, nT = f.nT;
   static const float edpr[4] = {0.f, 0.2f / 3.f, 0.4f / 3.f, 0.2f};   // linspace(0, 0.2, 4), pluto_model.py:80-83
-  float* ENC = A_alloc<float>(c, (size_t)nT * 128);
-  unsigned short* enc_KT = nullptr;   // the decoder's cross-attention K | V^T operand fragments, written by the encoder kernel's tail
-  uint8_t* kpm_c = nullptr;           // (RIFT_ENC_COMPACT) the key padding of the compacted encoder rows (bs, 96): what the decoder masks those fragments with
-  float* enc_x0p = nullptr;   // cat_x_proj's ego-token half, written by the encoder kernel's tail
+  f.ENC = A_alloc<float>(c, (size_t)nT * 128);
   // 97 .. 112 token slots (what train_cbv collates: 49 + 60 = 109): the fused kernel on its 112-row layout (enc_fused.h: EncLay<112>) when the
   // decoder's eight-key-tile variant consumes its K | V^T image; RIFT_ENC112=0 keeps those shapes on enc_w_kernel
-  const bool enc_wide = N > 96 && N <= 112 && c->enc112 && c->dec_fused && R <= 8 && ENC_NW == 8 && !tok_fused;
-  if (c->enc_fused && !f.fp32 && (N <= 96 || enc_wide)) {
+  f.enc_wide = N > 96 && N <= 112 && c->enc112 && c->dec_fused && R <= 8 && ENC_NW == 8;
+  if (c->enc_fused && !f.fp32 && (N <= 96 || f.enc_wide)) {
     EncFusedP ep; memset(&ep, 0, sizeof(ep));
-    ep.X = X; ep.Y = ENC; ep.kpm = kpm; ep.bs = bs; ep.N = N; ep.seed = f.seed; ep.stream = f.next_stream(); f.stream_id += 8;
-    if (tok_fused) { ep.tok = tokq; ep.tok_on = 1; ep.Xout = c->keep_tokens ? X : nullptr; }
+    ep.X = f.X; ep.Y = f.ENC; ep.kpm = f.kpm; ep.bs = bs; ep.N = N; ep.seed = f.seed; ep.stream = f.next_stream(); f.stream_id += 8;
     for (int i = 0; i < 4; ++i) {
       const std::string p = "encoder_blocks." + std::to_string(i);
       EncBlockW& w = ep.blk[i];
@@ -1401,32 +1324,32 @@ int forward_impl(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
       w.droppath = f.drop ? edpr[i] : 0.f;
     }
     ep.norm_g = fptr(c, "norm.weight"); ep.norm_b = fptr(c, "norm.bias"); ep.nonfinite = c->nonfinite;
-    RIFT_SET_DS(ep);
+    ep.ds = f.ds;
     if (c->dg.enc_ts) { ep.ts = A_alloc<long long>(c, 256); tap(c, "enc_ts", (float*)ep.ts, 512); }
     c->prof_flops = 4.0 * bs * N * (2.0 * 128 * 384 + 4.0 * N * 128 + 2.0 * 128 * 128 + 4.0 * 128 * 512);
     if (c->dec_fused && R <= 8 && ENC_NW == 8) {   // the decoder kernel will run: emit its cross-attention K | V operand fragments here
-      enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * (enc_wide ? 96 : DECW_KV_FRAGS) * 512);      // (wide: the dense per-head image, dec_kv.h)
+      f.enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * (f.enc_wide ? 96 : DECW_KV_FRAGS) * 512);      // (wide: the dense per-head image, dec_kv.h)
       ep.wkv = (const unsigned short*)c->pw["planning_decoder.kv_all"].bf; ep.bkv = c->pw["planning_decoder.kv_all"].bias;
-      ep.KT = enc_KT;
+      ep.KT = f.enc_KT;
 #if RIFT_ENC_COMPACT
-      kpm_c = A_alloc<uint8_t>(c, (size_t)bs * (enc_wide ? 112 : 96)); ep.kpm_c = kpm_c;
+      f.kpm_c = A_alloc<uint8_t>(c, (size_t)bs * (f.enc_wide ? 112 : 96)); ep.kpm_c = f.kpm_c;
 #else
-      if (enc_wide) { kpm_c = A_alloc<uint8_t>(c, (size_t)bs * 112); ep.kpm_c = kpm_c; }
+      if (f.enc_wide) { f.kpm_c = A_alloc<uint8_t>(c, (size_t)bs * 112); ep.kpm_c = f.kpm_c; }
 #endif
-      enc_x0p = A_alloc<float>(c, (size_t)bs * 128);
-      ep.wx0 = (const unsigned short*)c->pw["planning_decoder.cat_x_proj.x"].bf; ep.x0p = enc_x0p;
+      f.enc_x0p = A_alloc<float>(c, (size_t)bs * 128);
+      ep.wx0 = (const unsigned short*)c->pw["planning_decoder.cat_x_proj.x"].bf; ep.x0p = f.enc_x0p;
       c->prof_flops += 2.0 * bs * N * 128.0 * 1024;
     }
-    if (enc_wide) launch_call(c, "enc_fused112_kernel", [&] { enc112_launch(ep, c->stream); });
+    if (f.enc_wide) launch_call(c, "enc_fused112_kernel", [&] { enc112_launch(ep, c->stream); });
     else launch(c, "enc_fused_kernel", enc_fused_kernel<ENC_NW>, dim3(bs), dim3(64 * ENC_NW), (size_t)RIFT_ENC_LDS_BYTES, ep);
   } else if (c->enc_fused && !f.fp32 && N <= 192) {   // dense-traffic shapes: the wave-private, weight-streaming encoder (two passes per layer)
     EncWP eq; memset(&eq, 0, sizeof(eq));
-    eq.X = X; eq.Y = ENC; eq.kpm = kpm; eq.bs = bs; eq.N = N; eq.seed = f.seed; eq.stream = f.next_stream(); f.stream_id += 8;
+    eq.X = f.X; eq.Y = f.ENC; eq.kpm = f.kpm; eq.bs = bs; eq.N = N; eq.seed = f.seed; eq.stream = f.next_stream(); f.stream_id += 8;
     eq.KVs = A_alloc<unsigned short>(c, (size_t)bs * 96 * 512);
     eq.img = c->encw_img; eq.par = c->encw_par; eq.nonfinite = c->nonfinite;
-    if (c->dec_fused && R <= 16) { enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * 96 * 512); eq.DKV = enc_KT; }   // the decoder's (dense-variant) operands
+    if (c->dec_fused && R <= 16) { f.enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * 96 * 512); eq.DKV = f.enc_KT; }   // the decoder's (dense-variant) operands
     for (int i = 0; i < 4; ++i) eq.droppath[i] = f.drop ? edpr[i] : 0.f;
-    RIFT_SET_DS(eq);
+    eq.ds = f.ds;
     c->prof_flops = 4.0 * bs * N * (2.0 * 128 * 384 + 4.0 * N * 128 + 2.0 * 128 * 128 + 4.0 * 128 * 512);
     launch_call(c, "enc_w_kernel", [&] { encw_launch(eq, c->stream); });
   } else {
@@ -1435,40 +1358,45 @@ int forward_impl(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
   float* H512 = A_alloc<float>(c, (size_t)nT * 512);
   for (int i = 0; i < 4; ++i) {
     const std::string p = "encoder_blocks." + std::to_string(i);
-    GemmP g = mk(X, 128, nT, c->pw[p + ".attn.qkv"], QKV, 384);
+    GemmP g = mk(f.X, 128, nT, c->pw[p + ".attn.qkv"], QKV, 384);
     g.pro = PRO_LN; g.pg = fptr(c, p + ".norm1.weight"); g.pb = fptr(c, p + ".norm1.bias");
     gemm(c, g, c->pw[p + ".attn.qkv"], f.fp32);
     MhaP m; memset(&m, 0, sizeof(m));
     m.Q = QKV; m.ldq = 384; m.K = QKV + 128; m.V = QKV + 256; m.ldkv = 384; m.O = AO; m.ldo = 128;
     m.nb_outer = bs; m.nb_inner = 1; m.H = 4; m.Lq = N; m.Lk = N;
     m.q_outer = N; m.q_stride = 1; m.kv_outer = N; m.kv_stride = 1; m.o_outer = N; m.o_stride = 1;
-    m.mask = kpm; m.mask_mod = 1;
+    m.mask = f.kpm; m.mask_mod = 1;
     run_mha(c, m, f.fp32);
-    GemmP g2 = mk(AO, 128, nT, c->pw[p + ".attn.out_proj"], X, 128);
-    g2.residual = X; g2.ldr = 128;
+    GemmP g2 = mk(AO, 128, nT, c->pw[p + ".attn.out_proj"], f.X, 128);
+    g2.residual = f.X; g2.ldr = 128;
     if (f.drop && edpr[i] > 0.f) { g2.droppath_p = edpr[i]; g2.dp_div = N; g2.seed = f.seed; g2.stream = f.next_stream(); }
     gemm(c, g2, c->pw[p + ".attn.out_proj"], f.fp32);
-    GemmP g3 = mk(X, 128, nT, c->pw[p + ".mlp.fc1"], H512, 512);
+    GemmP g3 = mk(f.X, 128, nT, c->pw[p + ".mlp.fc1"], H512, 512);
     g3.pro = PRO_LN; g3.pg = fptr(c, p + ".norm2.weight"); g3.pb = fptr(c, p + ".norm2.bias"); g3.act = ACT_GELU;
     gemm(c, g3, c->pw[p + ".mlp.fc1"], f.fp32);
-    GemmP g4 = mk(H512, 512, nT, c->pw[p + ".mlp.fc2"], X, 128);
-    g4.residual = X; g4.ldr = 128;
+    GemmP g4 = mk(H512, 512, nT, c->pw[p + ".mlp.fc2"], f.X, 128);
+    g4.residual = f.X; g4.ldr = 128;
     if (f.drop && edpr[i] > 0.f) { g4.droppath_p = edpr[i]; g4.dp_div = N; g4.seed = f.seed; g4.stream = f.next_stream(); }
     gemm(c, g4, c->pw[p + ".mlp.fc2"], f.fp32);
   }
-  layernorm(f, X, 128, ENC, 128, nT, 128, "norm");
+  layernorm(f, f.X, 128, f.ENC, 128, nT, 128, "norm");
   }
-  tap(c, "enc_out", ENC, (int64_t)nT * 128);
+  tap(c, "enc_out", f.ENC, (int64_t)nT * 128);
+}
 
-  // ================= agent predictor (agent_predictor.py:17-29) =================
+// ================= agent predictor (agent_predictor.py:17-29) =================
+void agent_predictor(Fwd& f) {
+  RiftCtx* c = f.c;
+  const RiftOutputs* out = f.out;
+  const int bs = f.bs, A = f.A, N = f.N;
   if (f.need_traj && out->prediction && A > 1) {
     const int rows = bs * (A - 1);
     if (!f.fp32 && c->heads_fused) {
       const std::string nm3[3] = {"agent_predictor.loc_predictor", "agent_predictor.yaw_predictor", "agent_predictor.vel_predictor"};
-      heads3_fused(f, ENC, 128, rows, A - 1, N, 1, nm3, out->prediction);
+      heads3_fused(f, f.ENC, 128, rows, A - 1, N, 1, nm3, out->prediction);
     } else {
     float* Xa = A_alloc<float>(c, (size_t)rows * 128);
-    launch(c, "gather_rows_kernel", gather_rows_kernel, dim3(cdiv((long long)rows * 128, 256)), dim3(256), 0, (const float*)ENC, 128, Xa, 128, rows, 128,
+    launch(c, "gather_rows_kernel", gather_rows_kernel, dim3(cdiv((long long)rows * 128, 256)), dim3(256), 0, (const float*)f.ENC, 128, Xa, 128, rows, 128,
            A - 1, N, 1);
     float* o3[3];
     const char* nm[3] = {"loc_predictor", "yaw_predictor", "vel_predictor"};
@@ -1480,35 +1408,120 @@ int forward_impl(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
            (const float*)o3[2], rows, out->prediction);
     }
   }
+}
 
-  // ================= planning decoder (planning_decoder.py:135-188) =================
-  if (!pe_pair) r_emb = points_encoder(f, F6, 6, nL, 120, B->ref_valid_mask, PD + ".r_encoder");
-  if (!rpe_done) {
-    tap(c, "r_pe", r_emb, (int64_t)nL * 128);
-    fourier(f, r_pos, 3, nL, 3, PD + ".r_pos_emb", -1, r_emb);
+// the four decoder blocks as GEMM / attention launches (fp32 mode, RIFT_DEC_UNFUSED=1, shapes outside the fused kernel's)
+void decoder_layerwise(Fwd& f, float dp) {
+  RiftCtx* c = f.c;
+  const int bs = f.bs, R = f.R, N = f.N, M = f.M, nL = f.nL, nQ = f.nQ, nT = f.nT;
+  float* DQKV = A_alloc<float>(c, (size_t)nQ * 384);
+  float* DAO = A_alloc<float>(c, (size_t)nQ * 128);
+  float* DQc = A_alloc<float>(c, (size_t)nQ * 128);
+  float* DH = A_alloc<float>(c, (size_t)nQ * 512);
+  float* KVm = A_alloc<float>(c, (size_t)nT * 256);
+  for (int i = 0; i < 4; ++i) {
+    const std::string p = PD + ".decoder_blocks." + std::to_string(i);
+    // ---- r2r self attention over the R reference lines of each (scene, mode), with the mask quirk
+    GemmP g = mk(f.Q, 128, nQ, c->pw[p + ".r2r_attn.qkv"], DQKV, 384);
+    g.pro = PRO_LN; g.pg = fptr(c, p + ".norm1.weight"); g.pb = fptr(c, p + ".norm1.bias");
+    gemm(c, g, c->pw[p + ".r2r_attn.qkv"], f.fp32);
+    {
+      MhaP m; memset(&m, 0, sizeof(m));
+      m.Q = DQKV; m.ldq = 384; m.K = DQKV + 128; m.V = DQKV + 256; m.ldkv = 384; m.O = DAO; m.ldo = 128;
+      m.nb_outer = bs; m.nb_inner = M; m.H = 4; m.Lq = R; m.Lk = R;
+      m.q_outer = R * M; m.q_inner = 1; m.q_stride = M; m.kv_outer = R * M; m.kv_inner = 1; m.kv_stride = M;
+      m.o_outer = R * M; m.o_inner = 1; m.o_stride = M;
+      m.mask = f.q_kpm; m.mask_quirk = 1; m.mask_mod = f.q_bs; m.mask_off = f.q_off * M;   // tgt_key_padding_mask.repeat(M, 1), planning_decoder.py:56-60
+      if (dp > 0.f) { m.dropout_p = dp; m.seed = f.seed; m.stream = f.next_stream(); }
+      run_mha(c, m, f.fp32);
+    }
+    GemmP g2 = mk(DAO, 128, nQ, c->pw[p + ".r2r_attn.out_proj"], f.Q, 128);
+    g2.residual = f.Q; g2.ldr = 128;
+    if (dp > 0.f) { g2.dropout_p = dp; g2.seed = f.seed; g2.stream = f.next_stream(); }
+    gemm(c, g2, c->pw[p + ".r2r_attn.out_proj"], f.fp32);
+    // ---- m2m self attention over the 12 modes: q = k = (h + m_pos) W + b, v = h W + b
+    bool fill_mp;
+    float* MP = wconst_get(c, p + ".mp", (size_t)M * 384, f.fp32, &fill_mp);
+    if (fill_mp) gemm(c, mk(fptr(c, PD + ".m_pos"), 128, M, c->pw[p + ".m2m_attn.qk0"], MP, 384), c->pw[p + ".m2m_attn.qk0"], f.fp32);
+    GemmP g3 = mk(f.Q, 128, nQ, c->pw[p + ".m2m_attn.qkv"], DQKV, 384);
+    g3.pro = PRO_LN; g3.pg = fptr(c, p + ".norm2.weight"); g3.pb = fptr(c, p + ".norm2.bias");
+    g3.gbias = MP; g3.gb_div = 1; g3.gb_mod = M;
+    gemm(c, g3, c->pw[p + ".m2m_attn.qkv"], f.fp32);
+    {
+      MhaP m; memset(&m, 0, sizeof(m));
+      m.Q = DQKV; m.ldq = 384; m.K = DQKV + 128; m.V = DQKV + 256; m.ldkv = 384; m.O = DAO; m.ldo = 128;
+      m.nb_outer = nL; m.nb_inner = 1; m.H = 4; m.Lq = M; m.Lk = M;
+      m.q_outer = M; m.q_stride = 1; m.kv_outer = M; m.kv_stride = 1; m.o_outer = M; m.o_stride = 1;
+      if (dp > 0.f) { m.dropout_p = dp; m.seed = f.seed; m.stream = f.next_stream(); }
+      run_mha(c, m, f.fp32);
+    }
+    GemmP g4 = mk(DAO, 128, nQ, c->pw[p + ".m2m_attn.out_proj"], f.Q, 128);
+    g4.residual = f.Q; g4.ldr = 128; g4.rowzero = f.r_kpm; g4.rz_div = M;   // rows of padded ref lines become 0 (:65-72)
+    if (dp > 0.f) { g4.dropout_p = dp; g4.seed = f.seed; g4.stream = f.next_stream(); }
+    gemm(c, g4, c->pw[p + ".m2m_attn.out_proj"], f.fp32);
+    // ---- cross attention: R*12 queries per scene against the encoder tokens
+    GemmP g5 = mk(f.Q, 128, nQ, c->pw[p + ".cross_attn.q"], DQc, 128);
+    g5.pro = PRO_LN; g5.pg = fptr(c, p + ".norm3.weight"); g5.pb = fptr(c, p + ".norm3.bias");
+    gemm(c, g5, c->pw[p + ".cross_attn.q"], f.fp32);
+    gemm(c, mk(f.ENC, 128, nT, c->pw[p + ".cross_attn.kv"], KVm, 256), c->pw[p + ".cross_attn.kv"], f.fp32);
+    {
+      MhaP m; memset(&m, 0, sizeof(m));
+      m.Q = DQc; m.ldq = 128; m.K = KVm; m.V = KVm + 128; m.ldkv = 256; m.O = DAO; m.ldo = 128;
+      m.nb_outer = bs; m.nb_inner = 1; m.H = 4; m.Lq = R * M; m.Lk = N;
+      m.q_outer = R * M; m.q_stride = 1; m.kv_outer = N; m.kv_stride = 1; m.o_outer = R * M; m.o_stride = 1;
+      m.mask = f.kpm; m.mask_mod = 1;
+      if (dp > 0.f) { m.dropout_p = dp; m.seed = f.seed; m.stream = f.next_stream(); }
+      run_mha(c, m, f.fp32);
+    }
+    GemmP g6 = mk(DAO, 128, nQ, c->pw[p + ".cross_attn.out_proj"], f.Q, 128);
+    g6.residual = f.Q; g6.ldr = 128;
+    if (dp > 0.f) { g6.dropout_p = dp; g6.seed = f.seed; g6.stream = f.next_stream(); }
+    gemm(c, g6, c->pw[p + ".cross_attn.out_proj"], f.fp32);
+    // ---- FFN
+    GemmP g7 = mk(f.Q, 128, nQ, c->pw[p + ".ffn.0"], DH, 512);
+    g7.pro = PRO_LN; g7.pg = fptr(c, p + ".norm4.weight"); g7.pb = fptr(c, p + ".norm4.bias"); g7.act = ACT_RELU;
+    if (dp > 0.f) { g7.dropout_p = dp; g7.seed = f.seed; g7.stream = f.next_stream(); }
+    gemm(c, g7, c->pw[p + ".ffn.0"], f.fp32);
+    GemmP g8 = mk(DH, 512, nQ, c->pw[p + ".ffn.3"], f.Q, 128);
+    g8.residual = f.Q; g8.ldr = 128;
+    if (dp > 0.f) { g8.dropout_p = dp; g8.seed = f.seed; g8.stream = f.next_stream(); }
+    gemm(c, g8, c->pw[p + ".ffn.3"], f.fp32);
   }
-  tap(c, "r_emb", r_emb, (int64_t)nL * 128);
-  if (!Q) { const int rc0 = build_q0(); if (rc0 != RIFT_OK) return rc0; }
-  tap(c, "q0", Q, (int64_t)nQ * 128);
+}
 
-  bool dec_deferred = false; DecWP dec_later; memset(&dec_later, 0, sizeof(dec_later));
+// ================= planning decoder (planning_decoder.py:135-188) =================
+int planning_decoder(Fwd& f) {
+  RiftCtx* c = f.c;
+  const RiftFeatureBatch* B = f.B;
+  const int flags = f.flags;
+  const int bs = f.bs, R = f.R, N = f.N, M = f.M, nL = f.nL, nQ = f.nQ;
+  if (!f.pe_pair) f.r_emb = points_encoder(f, f.F6, 6, nL, 120, B->ref_valid_mask, PD + ".r_encoder");
+  if (!f.rpe_done) {
+    tap(c, "r_pe", f.r_emb, (int64_t)nL * 128);
+    fourier(f, f.r_pos, 3, nL, 3, PD + ".r_pos_emb", -1, f.r_emb);
+  }
+  tap(c, "r_emb", f.r_emb, (int64_t)nL * 128);
+  if (!f.Q) TRY(build_q0(f));
+  tap(c, "q0", f.Q, (int64_t)nQ * 128);
+
+  f.dec_deferred = false; memset(&f.dec_later, 0, sizeof(f.dec_later));
   dp_exchange(f, 0);                      // (eval forward under data parallelism: the mask slots have not travelled yet)
   const float dp = f.drop ? 0.1f : 0.f;   // pluto_model.py:35,93
   const bool dec_dense = (R > 8 || N > 96) && R <= 16 && N <= 192;      // dense-traffic shapes: the kernel's round-of-eight-tiles variant
-  if (c->dec_fused && !f.fp32 && dec_dense && !enc_KT) {   // its K | V^T operand fragments from the (layer-wise) encoder's output
-    enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * 96 * 512);
+  if (c->dec_fused && !f.fp32 && dec_dense && !f.enc_KT) {   // its K | V^T operand fragments from the (layer-wise) encoder's output
+    f.enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * 96 * 512);
     DecKvP kq; memset(&kq, 0, sizeof(kq));
-    kq.ENC = ENC; kq.bs = bs; kq.N = N; kq.wkv = (const unsigned short*)c->pw[PD + ".kv_all"].bf; kq.bkv = c->pw[PD + ".kv_all"].bias; kq.KV = enc_KT;
+    kq.ENC = f.ENC; kq.bs = bs; kq.N = N; kq.wkv = (const unsigned short*)c->pw[PD + ".kv_all"].bf; kq.bkv = c->pw[PD + ".kv_all"].bias; kq.KV = f.enc_KT;
     c->prof_flops = 2.0 * bs * N * 128.0 * 1024;
     launch(c, "dec_kv_frag_kernel", dec_kv_frag_kernel, dim3(bs), dim3(512), (size_t)DEC_KV_LDS, kq);
   }
-  if (c->dec_fused && !f.fp32 && ((R <= 8 && N <= 96) || dec_dense) && enc_KT) {
+  if (c->dec_fused && !f.fp32 && ((R <= 8 && N <= 96) || dec_dense) && f.enc_KT) {
     DecWP dq; memset(&dq, 0, sizeof(dq));
-    dq.Q = Q; dq.kpm = kpm; dq.r_kpm = r_kpm; dq.q_kpm = q_kpm; dq.q_bs = q_bs; dq.q_off = q_off; dq.bs = bs; dq.N = N; dq.R = R; dq.dropout = dp; dq.seed = f.seed;
-    if (kpm_c) { dq.kpm = kpm_c; dq.N = enc_wide ? 112 : 96; dq.compact = 1; }      // (the encoder compacted its rows: its own key padding, valid keys a prefix)
+    dq.Q = f.Q; dq.kpm = f.kpm; dq.r_kpm = f.r_kpm; dq.q_kpm = f.q_kpm; dq.q_bs = f.q_bs; dq.q_off = f.q_off; dq.bs = bs; dq.N = N; dq.R = R; dq.dropout = dp; dq.seed = f.seed;
+    if (f.kpm_c) { dq.kpm = f.kpm_c; dq.N = f.enc_wide ? 112 : 96; dq.compact = 1; }      // (the encoder compacted its rows: its own key padding, valid keys a prefix)
     dq.stream = f.next_stream(); f.stream_id += 64;
-    dq.KV = enc_KT; dq.img = c->decw_img; dq.par = c->decw_par; dq.nonfinite = c->nonfinite;
-    RIFT_SET_DS(dq);
+    dq.KV = f.enc_KT; dq.img = c->decw_img; dq.par = c->decw_par; dq.nonfinite = c->nonfinite;
+    dq.ds = f.ds;
     if (c->dg.dec_ts) { dq.ts = A_alloc<long long>(c, 1024); tap(c, "dec_ts", (float*)dq.ts, 2048); }      // [0, 128): boundaries of wave 0; [128 + 112 w, ...): arrivals of wave w
     dq.dbg = c->dg.dec_dbg;
     c->prof_flops = 4.0 * bs * (R * M) * (2.0 * 128 * (384 + 128) * 2 + 2.0 * 128 * 128 * 2 + 4.0 * 128 * 512 + 4.0 * 128 * (N + R + M));
@@ -1526,117 +1539,51 @@ int forward_impl(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
     // Measured (ms per step, split / one launch): 64 scenes 0.217 / 0.229, 32 scenes 0.20 - 0.21 / 0.20 - 0.21 (the host issues a 32-scene step in 0.15 - 0.2 ms: it
     // bounds that one now); with the trajectory heads on the caller's queue carries the prediction head as well and the split LOSES (0.30 / 0.26 at 64): off there.
     uint32_t* rng_io = (dec_may_defer && c->dec_split && !f.need_traj) ? A_alloc<uint32_t>(c, (size_t)bs * 512 * 4) : nullptr;
-    dec_deferred = dec_may_defer && !c->dry && !dq.ts;
-    if (dec_deferred) {
-      dec_later = dq;
+    f.dec_deferred = dec_may_defer && !c->dry && !dq.ts;
+    if (f.dec_deferred) {
+      f.dec_later = dq;
       if (rng_io) {
         dq.l1 = 2; dq.rng_io = rng_io;
         launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });
-        dec_later.l0 = 2; dec_later.rng_io = rng_io;
+        f.dec_later.l0 = 2; f.dec_later.rng_io = rng_io;
       }
     } else launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });
-  } else {
-  float* DQKV = A_alloc<float>(c, (size_t)nQ * 384);
-  float* DAO = A_alloc<float>(c, (size_t)nQ * 128);
-  float* DQc = A_alloc<float>(c, (size_t)nQ * 128);
-  float* DH = A_alloc<float>(c, (size_t)nQ * 512);
-  float* KVm = A_alloc<float>(c, (size_t)nT * 256);
-  float* MP = A_alloc<float>(c, (size_t)M * 384);
-  for (int i = 0; i < 4; ++i) {
-    const std::string p = PD + ".decoder_blocks." + std::to_string(i);
-    // ---- r2r self attention over the R reference lines of each (scene, mode), with the mask quirk
-    GemmP g = mk(Q, 128, nQ, c->pw[p + ".r2r_attn.qkv"], DQKV, 384);
-    g.pro = PRO_LN; g.pg = fptr(c, p + ".norm1.weight"); g.pb = fptr(c, p + ".norm1.bias");
-    gemm(c, g, c->pw[p + ".r2r_attn.qkv"], f.fp32);
-    {
-      MhaP m; memset(&m, 0, sizeof(m));
-      m.Q = DQKV; m.ldq = 384; m.K = DQKV + 128; m.V = DQKV + 256; m.ldkv = 384; m.O = DAO; m.ldo = 128;
-      m.nb_outer = bs; m.nb_inner = M; m.H = 4; m.Lq = R; m.Lk = R;
-      m.q_outer = R * M; m.q_inner = 1; m.q_stride = M; m.kv_outer = R * M; m.kv_inner = 1; m.kv_stride = M;
-      m.o_outer = R * M; m.o_inner = 1; m.o_stride = M;
-      m.mask = q_kpm; m.mask_quirk = 1; m.mask_mod = q_bs; m.mask_off = q_off * M;   // tgt_key_padding_mask.repeat(M, 1), planning_decoder.py:56-60
-      if (dp > 0.f) { m.dropout_p = dp; m.seed = f.seed; m.stream = f.next_stream(); }
-      run_mha(c, m, f.fp32);
-    }
-    GemmP g2 = mk(DAO, 128, nQ, c->pw[p + ".r2r_attn.out_proj"], Q, 128);
-    g2.residual = Q; g2.ldr = 128;
-    if (dp > 0.f) { g2.dropout_p = dp; g2.seed = f.seed; g2.stream = f.next_stream(); }
-    gemm(c, g2, c->pw[p + ".r2r_attn.out_proj"], f.fp32);
-    // ---- m2m self attention over the 12 modes: q = k = (h + m_pos) W + b, v = h W + b
-    bool fill_mp;
-    float* MP = wconst_get(c, p + ".mp", (size_t)M * 384, f.fp32, &fill_mp);
-    if (fill_mp) gemm(c, mk(fptr(c, PD + ".m_pos"), 128, M, c->pw[p + ".m2m_attn.qk0"], MP, 384), c->pw[p + ".m2m_attn.qk0"], f.fp32);
-    GemmP g3 = mk(Q, 128, nQ, c->pw[p + ".m2m_attn.qkv"], DQKV, 384);
-    g3.pro = PRO_LN; g3.pg = fptr(c, p + ".norm2.weight"); g3.pb = fptr(c, p + ".norm2.bias");
-    g3.gbias = MP; g3.gb_div = 1; g3.gb_mod = M;
-    gemm(c, g3, c->pw[p + ".m2m_attn.qkv"], f.fp32);
-    {
-      MhaP m; memset(&m, 0, sizeof(m));
-      m.Q = DQKV; m.ldq = 384; m.K = DQKV + 128; m.V = DQKV + 256; m.ldkv = 384; m.O = DAO; m.ldo = 128;
-      m.nb_outer = nL; m.nb_inner = 1; m.H = 4; m.Lq = M; m.Lk = M;
-      m.q_outer = M; m.q_stride = 1; m.kv_outer = M; m.kv_stride = 1; m.o_outer = M; m.o_stride = 1;
-      if (dp > 0.f) { m.dropout_p = dp; m.seed = f.seed; m.stream = f.next_stream(); }
-      run_mha(c, m, f.fp32);
-    }
-    GemmP g4 = mk(DAO, 128, nQ, c->pw[p + ".m2m_attn.out_proj"], Q, 128);
-    g4.residual = Q; g4.ldr = 128; g4.rowzero = r_kpm; g4.rz_div = M;   // rows of padded ref lines become 0 (:65-72)
-    if (dp > 0.f) { g4.dropout_p = dp; g4.seed = f.seed; g4.stream = f.next_stream(); }
-    gemm(c, g4, c->pw[p + ".m2m_attn.out_proj"], f.fp32);
-    // ---- cross attention: R*12 queries per scene against the encoder tokens
-    GemmP g5 = mk(Q, 128, nQ, c->pw[p + ".cross_attn.q"], DQc, 128);
-    g5.pro = PRO_LN; g5.pg = fptr(c, p + ".norm3.weight"); g5.pb = fptr(c, p + ".norm3.bias");
-    gemm(c, g5, c->pw[p + ".cross_attn.q"], f.fp32);
-    gemm(c, mk(ENC, 128, nT, c->pw[p + ".cross_attn.kv"], KVm, 256), c->pw[p + ".cross_attn.kv"], f.fp32);
-    {
-      MhaP m; memset(&m, 0, sizeof(m));
-      m.Q = DQc; m.ldq = 128; m.K = KVm; m.V = KVm + 128; m.ldkv = 256; m.O = DAO; m.ldo = 128;
-      m.nb_outer = bs; m.nb_inner = 1; m.H = 4; m.Lq = R * M; m.Lk = N;
-      m.q_outer = R * M; m.q_stride = 1; m.kv_outer = N; m.kv_stride = 1; m.o_outer = R * M; m.o_stride = 1;
-      m.mask = kpm; m.mask_mod = 1;
-      if (dp > 0.f) { m.dropout_p = dp; m.seed = f.seed; m.stream = f.next_stream(); }
-      run_mha(c, m, f.fp32);
-    }
-    GemmP g6 = mk(DAO, 128, nQ, c->pw[p + ".cross_attn.out_proj"], Q, 128);
-    g6.residual = Q; g6.ldr = 128;
-    if (dp > 0.f) { g6.dropout_p = dp; g6.seed = f.seed; g6.stream = f.next_stream(); }
-    gemm(c, g6, c->pw[p + ".cross_attn.out_proj"], f.fp32);
-    // ---- FFN
-    GemmP g7 = mk(Q, 128, nQ, c->pw[p + ".ffn.0"], DH, 512);
-    g7.pro = PRO_LN; g7.pg = fptr(c, p + ".norm4.weight"); g7.pb = fptr(c, p + ".norm4.bias"); g7.act = ACT_RELU;
-    if (dp > 0.f) { g7.dropout_p = dp; g7.seed = f.seed; g7.stream = f.next_stream(); }
-    gemm(c, g7, c->pw[p + ".ffn.0"], f.fp32);
-    GemmP g8 = mk(DH, 512, nQ, c->pw[p + ".ffn.3"], Q, 128);
-    g8.residual = Q; g8.ldr = 128;
-    if (dp > 0.f) { g8.dropout_p = dp; g8.seed = f.seed; g8.stream = f.next_stream(); }
-    gemm(c, g8, c->pw[p + ".ffn.3"], f.fp32);
-  }
-  }
-  tap(c, "dec3", Q, (int64_t)nQ * 128);
+  } else decoder_layerwise(f, dp);
+  tap(c, "dec3", f.Q, (int64_t)nQ * 128);
+  return RIFT_OK;
+}
+
+// ================= policy head, hidden_proj / ref_free_decoder =================
+int policy_and_ego_heads(Fwd& f) {
+  RiftCtx* c = f.c;
+  const RiftOutputs* out = f.out;
+  const int flags = f.flags;
+  const int bs = f.bs, R = f.R, N = f.N, nQ = f.nQ;
   // cat_x_proj(cat[q, enc_emb[:, 0]]) (planning_decoder.py:177-179): ego-token part is a per-scene bias
-  float* x0p = enc_x0p;
+  float* x0p = f.enc_x0p;
   if (!x0p) {
     x0p = A_alloc<float>(c, (size_t)bs * 128);
-    gemm(c, mk(ENC, N * 128, bs, c->pw[PD + ".cat_x_proj.x"], x0p, 128), c->pw[PD + ".cat_x_proj.x"], f.fp32);
+    gemm(c, mk(f.ENC, N * 128, bs, c->pw[PD + ".cat_x_proj.x"], x0p, 128), c->pw[PD + ".cat_x_proj.x"], f.fp32);
   }
   // ---- the policy head (and the trajectory heads that read its q_final): right here, or -- RIFT_F_DEFER_HEAD -- later through
   // rift_forward_head on a stream of the caller's choice, so that it (and the loss / backward / update behind it) runs beside the next
   // forward's frozen trunk
   RiftCtx::Head hs;
-  hs.valid = true; hs.fp32 = f.fp32; hs.need_traj = f.need_traj && out->trajectory != nullptr; hs.Q = Q; hs.x0p = x0p; hs.r_kpm = r_kpm;
+  hs.valid = true; hs.fp32 = f.fp32; hs.need_traj = f.need_traj && out->trajectory != nullptr; hs.Q = f.Q; hs.x0p = x0p; hs.r_kpm = f.r_kpm;
   hs.bs = bs; hs.R = R; hs.nQ = nQ; hs.traj = out->trajectory;
   hs.QF = A_alloc<float>(c, (size_t)nQ * 128);
   hs.Hpi = A_alloc<float>(c, (size_t)nQ * 128);
   hs.prob = out->probability ? out->probability : A_alloc<float>(c, nQ);
   if (hs.need_traj && (f.fp32 || !c->heads_fused))      // layer-wise trajectory heads: their buffers come out of this forward's arena
     for (int i = 0; i < 3; ++i) { hs.oT[i] = A_alloc<float>(c, (size_t)nQ * 256); hs.o3[i] = A_alloc<float>(c, (size_t)nQ * 160); }
-  hs.dec_pending = dec_deferred; hs.dec = dec_later;
+  hs.dec_pending = f.dec_deferred; hs.dec = f.dec_later;
   if (flags & RIFT_F_DEFER_HEAD) { if (!c->dry) c->head[c->parity] = hs; }
   else TRY(head_impl(c, hs));
   // hidden_proj / ref_free_decoder on the ego token (pluto_model.py:173-180)
   if (!f.fp32 && c->heads_fused && (out->hidden || (f.need_traj && out->ref_free_trajectory))) {      // one launch (heads_fused.h: ego_heads_kernel)
     const PW &h0 = c->pw["hidden_proj.0"], &h2 = c->pw["hidden_proj.2"], &r0 = c->pw["ref_free_decoder.mlp.0"], &r3 = c->pw["ref_free_decoder.mlp.3"];
     EgoHeadsP q; memset(&q, 0, sizeof(q));
-    q.X = ENC; q.ldx = N * 128; q.rows = bs;
+    q.X = f.ENC; q.ldx = N * 128; q.rows = bs;
     q.wh0 = (const unsigned short*)h0.bf; q.wh2 = (const unsigned short*)h2.bf; q.wr0 = (const unsigned short*)r0.bf; q.wr3 = (const unsigned short*)r3.bf;
     q.bh0 = h0.bias; q.bh2 = h2.bias; q.br0 = r0.bias; q.br3 = r3.bias;
     q.lng = fptr(c, "ref_free_decoder.mlp.1.weight"); q.lnb = fptr(c, "ref_free_decoder.mlp.1.bias");
@@ -1647,16 +1594,84 @@ int forward_impl(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
   }
   if (out->hidden) {
     float* Th = A_alloc<float>(c, (size_t)bs * 128);
-    GemmP g = mk(ENC, N * 128, bs, c->pw["hidden_proj.0"], Th, 128);
+    GemmP g = mk(f.ENC, N * 128, bs, c->pw["hidden_proj.0"], Th, 128);
     g.act = ACT_RELU;
     gemm(c, g, c->pw["hidden_proj.0"], f.fp32);
     gemm(c, mk(Th, 128, bs, c->pw["hidden_proj.2"], out->hidden, 128), c->pw["hidden_proj.2"], f.fp32);
   }
   if (f.need_traj && out->ref_free_trajectory)
-    mlp_layer(f, ENC, N * 128, bs, "ref_free_decoder", out->ref_free_trajectory, 320, f.fp32);
+    mlp_layer(f, f.ENC, N * 128, bs, "ref_free_decoder", out->ref_free_trajectory, 320, f.fp32);
 
-#undef RIFT_SET_DS
   return RIFT_OK;
+}
+
+// The streams and events the plan needs, made on first use.
+int plan_resources(RiftCtx* c, const StreamPlan& p) {
+  if (p.prefetched && !c->ev_prep) HIPCHK(c, hipEventCreateWithFlags(&c->ev_prep, hipEventDisableTiming));
+  if (p.forked && !c->side) { HIPCHK(c, hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking)); c->side_owned = true; }
+  if (p.forked && !c->ev_fork) { HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming)); HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming)); }
+  if (p.nat_aside && !c->ev_join2) HIPCHK(c, hipEventCreateWithFlags(&c->ev_join2, hipEventDisableTiming));
+  return RIFT_OK;
+}
+
+StreamPlan plan_of(const RiftCtx* c, bool fp32, int bs) {
+  PlanIn in;
+  in.two_streams = c->two_streams; in.nat_fused = c->nat_fused; in.nat_aside = c->nat_aside; in.side_gate = c->side_gate;
+  in.fp32 = fp32; in.prof_on = c->prof_on; in.dry = c->dry; in.prep_set = c->prep_set; in.dp_on = c->dp.on; in.bs = bs;
+  return plan_streams(in);
+}
+
+// One forward on c->stream (the caller's), in the arena of c->parity; with c->dry set, the sizing pass: the same code, no launch.  The
+// stages switch c->stream by the plan (fwd_plan.h) and an early error return leaves it switched: rift_forward restores it.
+int forward_impl(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, int flags, uint32_t seed) {
+  Fwd f;
+  f.c = c; f.train = (flags & RIFT_F_TRAIN) != 0; f.drop = f.train && !(flags & RIFT_F_NO_DROP);
+  f.fp32 = (flags & RIFT_F_FP32) != 0; f.need_traj = (flags & RIFT_F_NEED_TRAJ) != 0;
+  f.bn_update = f.train && !(flags & RIFT_F_NO_BN_UPDATE); f.seed = seed;
+  f.B = B; f.out = out; f.flags = flags;
+  f.bs = B->bs; f.A = B->A; f.Mp = B->Mp; f.R = B->R; f.S = B->S; f.T = B->T;
+  f.N = f.A + f.Mp + f.S;
+  f.nA = f.bs * f.A; f.nP = f.bs * f.Mp; f.nL = f.bs * f.R; f.nQ = f.nL * f.M; f.nT = f.bs * f.N;
+  const StreamPlan& p = f.plan = plan_of(c, f.fp32, f.bs);
+  TRY(plan_resources(c, p));
+  f.on[ON_CALLER] = c->stream; f.on[ON_PREPARE] = c->prep_stream; f.on[ON_SIDE] = c->side;
+
+  c->stream = f.on[p.prep_on];
+  TRY(prepare_inputs(f));
+  c->stream = f.on[ON_CALLER];
+  if (p.prefetched) HIPCHK(c, hipEventRecord(c->ev_prep, f.on[ON_PREPARE]));
+  if (p.main_waits_prep) HIPCHK(c, hipStreamWaitEvent(f.on[ON_CALLER], c->ev_prep, 0));
+  TRY(dp_mask_and_drop_counters(f));
+  if (p.side_waits_prep) HIPCHK(c, hipStreamWaitEvent(f.on[ON_SIDE], c->ev_prep, 0));
+  if (p.fork_from_main) {
+    HIPCHK(c, hipEventRecord(c->ev_fork, f.on[ON_CALLER]));
+    HIPCHK(c, hipStreamWaitEvent(f.on[ON_SIDE], c->ev_fork, 0));
+  }
+
+  c->stream = f.on[p.history_on];
+  history_encoder(f);
+  if (p.nat_aside) HIPCHK(c, hipEventRecord(c->ev_join2, f.on[ON_PREPARE]));
+
+  c->stream = f.on[p.dp_fill_on];
+  if (p.dp_fill_late) dp_kpm_fill(f);      // (behind the previous forward's exchanges)
+  c->stream = f.on[p.map_on];
+  ego_token(f);
+  TRY(map_and_embeddings(f));
+
+  // join: the agent tokens need both chains
+  if (p.join_once) HIPCHK(c, hipStreamWaitEvent(f.on[ON_SIDE], c->ev_join2, 0));
+  if (p.forked) {
+    HIPCHK(c, hipEventRecord(c->ev_join, f.on[ON_SIDE]));
+    HIPCHK(c, hipStreamWaitEvent(f.on[ON_CALLER], c->ev_join, 0));
+  }
+  if (p.nat_aside && !p.join_once) HIPCHK(c, hipStreamWaitEvent(f.on[ON_CALLER], c->ev_join2, 0));
+
+  c->stream = f.on[ON_CALLER];
+  assemble_tokens(f);
+  scene_encoder(f);
+  agent_predictor(f);
+  TRY(planning_decoder(f));
+  return policy_and_ego_heads(f);
 }
 
 }  // namespace
@@ -1667,61 +1682,58 @@ int forward_impl(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
 // ============================================================================================
 namespace RIFT_NS { namespace abi {
 
+// The environment switches, read ONCE when the context is made.  Three idioms, kept as they grew: env_is (the first character decides),
+// env_flag (set: atoi != 0), env_int (set: the number).
+static bool env_is(const char* name, char ch) { const char* ev = getenv(name); return ev && ev[0] == ch; }
+static void env_flag(const char* name, bool* v) { const char* ev = getenv(name); if (ev) *v = atoi(ev) != 0; }
+static bool env_int(const char* name, int* v, int base = 10) { const char* ev = getenv(name); if (ev) *v = (int)strtol(ev, nullptr, base); return ev != nullptr; }
+
+static void read_switches(RiftCtx* c) {
+  c->nat_fused = !env_is("RIFT_NAT_UNFUSED", '1');        // 1: the history encoder's NAT levels layer-wise (GEMM / attention launches)
+  c->dec_fused = !env_is("RIFT_DEC_UNFUSED", '1');        // 1: the planning decoder layer-wise
+  c->enc_fused = !env_is("RIFT_ENC_UNFUSED", '1');        // 1: the scene encoder layer-wise
+  c->pe_fused = !env_is("RIFT_PE_UNFUSED", '1');          // 1: the PointsEncoders layer-wise, one after the other
+  c->fpn_fused = !env_is("RIFT_FPN_UNFUSED", '1');        // 1: the FPN tail as lateral GEMMs + merge
+  c->ego_fused = !env_is("RIFT_EGO_UNFUSED", '1');        // 1: the ego state token as five launches
+  c->heads_fused = !env_is("RIFT_HEADS_UNFUSED", '1');    // 1: trajectory / prediction / ego heads as MLPLayer GEMMs
+  c->pi_fused = !env_is("RIFT_PI_UNFUSED", '1');          // 1: cat_x_proj -> pi_head and the decoder queries as separate launches
+  c->fo_fused = !env_is("RIFT_FOURIER_UNFUSED", '1');     // 1: the Fourier embeddings layer-wise
+  c->pe_w = !env_is("RIFT_PE_W", '0');                    // 0: PointsEncoder pass B as the workgroup-tiled pe_mid_kernel
+  c->fo_w = !env_is("RIFT_FO_W", '0');                    // 0: the three Fourier embeddings through fourier_fused_kernel
+  c->two_streams = !env_is("RIFT_TWO_STREAMS", '0');      // 0: history and map chains one after the other on the caller's stream
+  { int g = 0; env_int("RIFT_NAT_GRID", &g); if (g > 0) c->nat_grid = g; }      // workgroups of the persistent launches (default 256: one per CU)
+  env_flag("RIFT_NAT_COMPACT", &c->nat_compact);          // 0: the history encoder on all agent slots, not the compacted valid ones
+  env_flag("RIFT_PE_LIVE", &c->pe_live);                  // 0: pass B over all rounds instead of the live ones of pass A's counts
+  env_flag("RIFT_PE_PACK", &c->pe_pack);                  // 0: reference lines of pass B in two-line rounds instead of packed valid-prefix tiles
+  env_flag("RIFT_RANK_IN_PREP", &c->rank_in_prep);        // 0: the ranking as its own launch behind the preparation (nat_rank_kernel)
+  env_flag("RIFT_ENC112", &c->enc112);                    // 0: scenes of 97 .. 112 token slots on enc_w_kernel
+  env_flag("RIFT_RANK_FAULT", &c->rank_fault);            // 1 (diagnostic): the first scene block of the in-launch ranking never publishes
+  env_int("RIFT_SIDE_GATE", &c->side_gate);               // 1: both front chains behind the caller's queue (fwd_plan.h)
+  env_flag("RIFT_NAT_ASIDE", &c->nat_aside);              // 0: the history chain on the caller's stream, not behind the preparation
+  env_int("RIFT_DEC_DEFER", &c->dec_defer_max);           // <n>: the decoder goes with the deferred head for bs <= n (0: never; unset: the measured table)
+  env_flag("RIFT_DEC_SPLIT", &c->dec_split);              // 0: the deferred decoder as one launch
+  env_flag("RIFT_RO8", &c->ro8);                          // 0: candidate rollout with one lane per candidate
+  if (env_int("RIFT_POISON_LDS", &c->poison_lds, 0)) c->poison_lds &= 0xff;                // <byte>: every CU's LDS filled ahead of every launch
+  if (env_int("RIFT_POISON_ARENA", &c->dg.poison_arena, 0)) c->dg.poison_arena &= 0xff;    // <byte>: the arena filled ahead of every forward
+  { const char* ev = getenv("RIFT_DELAY"); const char* col = ev ? strrchr(ev, ':') : nullptr;      // <launch label>:<us> (wall_clock64: 100 MHz)
+    if (col) { c->dg.delay_label.assign(ev, col - ev); c->dg.delay_ticks = (long long)(atof(col + 1) * 100.0); } }
+  env_int("RIFT_PE_TS", &c->dg.pe_ts);                    // the *_TS taps: phase timestamps of one workgroup
+  c->dg.pew_ts = env_is("RIFT_PEW_TS", '1');
+  env_int("RIFT_NAT_TS", &c->dg.nat_ts);
+  c->dg.enc_ts = getenv("RIFT_ENC_TS") != nullptr;
+  c->dg.dec_ts = getenv("RIFT_DEC_TS") != nullptr;
+  env_int("RIFT_PEW_DBG", &c->dg.pew_dbg);                // the *_DBG words: handed to the kernel as they are
+  env_int("RIFT_DEC_DBG", &c->dg.dec_dbg);
+  env_int("RIFT_GEMM_DBG", &c->gemm_dbg);
+}
+
 int rift_ctx_create(int device, RiftCtx** ctx) {
   if (!ctx) return RIFT_ERR_ARG;
   RiftCtx* c = new RiftCtx();
   c->opfmt = RIFT_OP_F16;
   c->device = device;
   if (hipSetDevice(device) != hipSuccess) { delete c; return RIFT_ERR_HIP; }
-  { const char* ev = getenv("RIFT_NAT_UNFUSED"); c->nat_fused = !(ev && ev[0] == '1'); }
-  { const char* ev = getenv("RIFT_DEC_UNFUSED"); c->dec_fused = !(ev && ev[0] == '1'); }
-  { const char* ev = getenv("RIFT_ENC_UNFUSED"); c->enc_fused = !(ev && ev[0] == '1'); }
-  { const char* ev = getenv("RIFT_PE_UNFUSED"); c->pe_fused = !(ev && ev[0] == '1'); }
-  { const char* ev = getenv("RIFT_FPN_UNFUSED"); c->fpn_fused = !(ev && ev[0] == '1'); }
-  { const char* ev = getenv("RIFT_EGO_UNFUSED"); c->ego_fused = !(ev && ev[0] == '1'); }
-  { const char* ev = getenv("RIFT_HEADS_UNFUSED"); c->heads_fused = !(ev && ev[0] == '1'); }
-  { const char* ev = getenv("RIFT_PI_UNFUSED"); c->pi_fused = !(ev && ev[0] == '1'); }
-  { const char* ev = getenv("RIFT_NAT_GRID"); if (ev && atoi(ev) > 0) c->nat_grid = atoi(ev); }
-  { const char* ev = getenv("RIFT_NAT_MAIN"); if (ev) c->nat_on_main = atoi(ev) != 0; }
-  { const char* ev = getenv("RIFT_NAT_COMPACT"); if (ev) c->nat_compact = atoi(ev) != 0; }
-  { const char* ev = getenv("RIFT_PE_LIVE"); if (ev) c->pe_live = atoi(ev) != 0; }
-  { const char* ev = getenv("RIFT_PE_PACK"); if (ev) c->pe_pack = atoi(ev) != 0; }
-  // (1: the scene encoder assembles its token rows in its prologue instead of token_kernel.  Measured and NOT kept as the default: one ~10 us
-  // launch less between the join and the encoder, but the step is 15 us LONGER (0.659 against 0.643 ms) -- six dependent gathers per
-  // thread in the prologue of a kernel that holds every CU whole, where token_kernel's 5000 small blocks ran beside the fronts' tails)
-  { const char* ev = getenv("RIFT_TOKEN_FUSED"); if (ev) c->tok_fused = atoi(ev) != 0; }
-  { const char* ev = getenv("RIFT_KEEP_TOKENS"); c->keep_tokens = ev && ev[0] == '1'; }
-  // (1: preparation and ranking in one launch, front.h.  Measured and NOT kept as the default: at 256 scenes both already run INSIDE the previous
-  // step's decoder (<= 64 VGPRs), so the launch saved is not on any chain -- 0.640 against 0.642 ms, noise -- while the ranking block, which then has
-  // to derive the marks from the raw validity (344 KB through one workgroup), makes the merged launch 34 us where the two took 24: a loss wherever
-  // the forward runs serially (get_action, small batches))
-  { const char* ev = getenv("RIFT_FRONT_FUSED"); if (ev) c->front_fused = atoi(ev) != 0; }
-  { const char* ev = getenv("RIFT_RANK_IN_PREP"); if (ev) c->rank_in_prep = atoi(ev) != 0; }
-  { const char* ev = getenv("RIFT_ENC112"); if (ev) c->enc112 = atoi(ev) != 0; }
-  { const char* ev = getenv("RIFT_RANK_FAULT"); if (ev) c->rank_fault = atoi(ev) != 0; }
-  { const char* ev = getenv("RIFT_EGO_NOFIT"); c->ego_nofit = ev && ev[0] == '1'; }
-  { const char* ev = getenv("RIFT_FRONT_EGO"); if (ev) c->front_ego = atoi(ev) != 0; }        // (1: the ego token as blocks of that launch too -- 116 VGPRs: it no longer fits beside the decoder's workgroups)
-  { const char* ev = getenv("RIFT_SIDE_GATE"); if (ev) c->side_gate = atoi(ev); }
-  { const char* ev = getenv("RIFT_NAT_ASIDE"); if (ev) c->nat_aside = atoi(ev) != 0; }
-  { const char* ev = getenv("RIFT_JOIN_ONCE"); if (ev) c->join_once = atoi(ev); }
-  { const char* ev = getenv("RIFT_DEC_DEFER"); if (ev) c->dec_defer_max = atoi(ev); }
-  { const char* ev = getenv("RIFT_DEC_SPLIT"); if (ev) c->dec_split = atoi(ev) != 0; }
-  { const char* ev = getenv("RIFT_RO8"); if (ev) c->ro8 = atoi(ev) != 0; }
-  { const char* ev = getenv("RIFT_POISON_LDS"); if (ev) c->poison_lds = (int)strtol(ev, nullptr, 0) & 0xff; }
-  { const char* ev = getenv("RIFT_POISON_ARENA"); if (ev) c->dg.poison_arena = (int)strtol(ev, nullptr, 0) & 0xff; }
-  { const char* ev = getenv("RIFT_PE_TS"); if (ev) c->dg.pe_ts = atoi(ev); }
-  { const char* ev = getenv("RIFT_DELAY"); const char* col = ev ? strrchr(ev, ':') : nullptr;      // wall_clock64: 100 MHz
-    if (col) { c->dg.delay_label.assign(ev, col - ev); c->dg.delay_ticks = (long long)(atof(col + 1) * 100.0); } }
-  { const char* ev = getenv("RIFT_PEW_DBG"); if (ev) c->dg.pew_dbg = atoi(ev); }
-  { const char* ev = getenv("RIFT_PEW_TS"); c->dg.pew_ts = ev && ev[0] == '1'; }
-  { const char* ev = getenv("RIFT_NAT_TS"); if (ev) c->dg.nat_ts = atoi(ev); }
-  c->dg.enc_ts = getenv("RIFT_ENC_TS") != nullptr; c->dg.dec_ts = getenv("RIFT_DEC_TS") != nullptr;
-  { const char* ev = getenv("RIFT_DEC_DBG"); if (ev) c->dg.dec_dbg = atoi(ev); }
-  { const char* ev = getenv("RIFT_FOURIER_UNFUSED"); c->fo_fused = !(ev && ev[0] == '1'); }
-  { const char* ev = getenv("RIFT_PE_W"); c->pe_w = !(ev && ev[0] == '0'); }
-  { const char* ev = getenv("RIFT_FO_W"); c->fo_w = !(ev && ev[0] == '0'); }
-  { const char* ev = getenv("RIFT_TWO_STREAMS"); c->two_streams = !(ev && ev[0] == '0'); }
-  { const char* ev = getenv("RIFT_GEMM_DBG"); c->gemm_dbg = ev ? atoi(ev) : 0; }
+  read_switches(c);
   if (hipMalloc((void**)&c->nonfinite, sizeof(int)) != hipSuccess || hipMemset(c->nonfinite, 0, sizeof(int)) != hipSuccess) { delete c; return RIFT_ERR_HIP; }
   for (int i = 0; i < RIFT_DEFER_SLOTS; ++i) {      // the in-launch ranking's published counts (kernels.h: rank_scene_body): zero = "never written"
     if (hipMalloc((void**)&c->rk_pub[i], 4096 * sizeof(unsigned long long)) != hipSuccess || hipMemset(c->rk_pub[i], 0, 4096 * sizeof(unsigned long long)) != hipSuccess) { delete c; return RIFT_ERR_HIP; }
@@ -1769,20 +1781,21 @@ void rift_ctx_destroy(RiftCtx* c) {
 
 const char* rift_last_error(RiftCtx* c) { return c ? c->err.c_str() : "null context"; }
 
-int rift_model_load(RiftCtx* c, const RiftTensorDesc* params, int n, void* stream) {
-  if (!c || !params) return RIFT_ERR_ARG;
-  c->err.clear();
-  c->stream = (hipStream_t)stream;
-  HIPCHK(c, hipSetDevice(c->device));
-  for (void* p : c->owned) (void)hipFree(p);
-  c->owned.clear(); c->pw.clear(); c->params.clear(); c->wconst.clear();
-  c->dry_need = 0;                      // (the first forward on new weights sizes its arena again: it also computes the weight-only products)
-  for (int i = 0; i < n; ++i) {
-    Param p; p.data = params[i].data; p.numel = params[i].numel; p.ndim = params[i].ndim;
-    for (int d = 0; d < 4; ++d) p.shape[d] = params[i].shape[d];
-    c->params[params[i].name] = p;
+// the parameters of the two NAT blocks of level lv, for the packers of the wave-private level kernels (NatL0WSrc / NatL1WSrc / NatL2WSrc)
+template <class Src>
+static void nat_blocks_src(RiftCtx* c, Src& q, int lv) {
+  for (int b = 0; b < 2; ++b) {
+    const std::string p = HE + ".levels." + std::to_string(lv) + ".blocks." + std::to_string(b);
+    auto& k = q.blk[b];
+    k.ln1_g = fptr(c, p + ".norm1.weight"); k.ln1_b = fptr(c, p + ".norm1.bias"); k.wqkv = fptr(c, p + ".attn.qkv.weight"); k.bqkv = fptr(c, p + ".attn.qkv.bias");
+    k.rpb = fptr(c, p + ".attn.rpb"); k.wproj = fptr(c, p + ".attn.proj.weight"); k.bproj = fptr(c, p + ".attn.proj.bias");
+    k.ln2_g = fptr(c, p + ".norm2.weight"); k.ln2_b = fptr(c, p + ".norm2.bias"); k.w1 = fptr(c, p + ".mlp.fc1.weight"); k.b1 = fptr(c, p + ".mlp.fc1.bias");
+    k.w2 = fptr(c, p + ".mlp.fc2.weight"); k.b2 = fptr(c, p + ".mlp.fc2.bias");
   }
-  const std::string HE = "agent_encoder.history_encoder";
+}
+
+// rift_model_load: the history encoder's GEMM images and the weight streams of its wave-private level kernels
+static int pack_history_encoder(RiftCtx* c) {
   TRY(pack_conv(c, HE + ".embed.proj"));
   for (int lv = 0; lv < 3; ++lv) {
     for (int b = 0; b < 2; ++b) {
@@ -1796,14 +1809,7 @@ int rift_model_load(RiftCtx* c, const RiftTensorDesc* params, int n, void* strea
   {  // wave-private level-0 kernel: K-permuted weight fragments + parameter block (nat_l0w.h)
     NatL0WSrc q; memset(&q, 0, sizeof(q));
     q.w_tok = fptr(c, HE + ".embed.proj.weight"); q.b_tok = fptr(c, HE + ".embed.proj.bias");
-    for (int b = 0; b < 2; ++b) {
-      const std::string p = HE + ".levels.0.blocks." + std::to_string(b);
-      NatL0WSrc::Blk& k = q.blk[b];
-      k.ln1_g = fptr(c, p + ".norm1.weight"); k.ln1_b = fptr(c, p + ".norm1.bias"); k.wqkv = fptr(c, p + ".attn.qkv.weight"); k.bqkv = fptr(c, p + ".attn.qkv.bias");
-      k.rpb = fptr(c, p + ".attn.rpb"); k.wproj = fptr(c, p + ".attn.proj.weight"); k.bproj = fptr(c, p + ".attn.proj.bias");
-      k.ln2_g = fptr(c, p + ".norm2.weight"); k.ln2_b = fptr(c, p + ".norm2.bias"); k.w1 = fptr(c, p + ".mlp.fc1.weight"); k.b1 = fptr(c, p + ".mlp.fc1.bias");
-      k.w2 = fptr(c, p + ".mlp.fc2.weight"); k.b2 = fptr(c, p + ".mlp.fc2.bias");
-    }
+    nat_blocks_src(c, q, 0);
     q.fn_g = fptr(c, HE + ".norm0.weight"); q.fn_b = fptr(c, HE + ".norm0.bias");
     q.w_ds = fptr(c, HE + ".levels.0.downsample.reduction.weight"); q.ds_g = fptr(c, HE + ".levels.0.downsample.norm.weight"); q.ds_b = fptr(c, HE + ".levels.0.downsample.norm.bias");
     if (!c->err.empty()) return RIFT_ERR_ARG;
@@ -1812,14 +1818,7 @@ int rift_model_load(RiftCtx* c, const RiftTensorDesc* params, int n, void* strea
   }
   {  // wave-private level-1 kernel (nat_l1w.h)
     NatL1WSrc q; memset(&q, 0, sizeof(q));
-    for (int b = 0; b < 2; ++b) {
-      const std::string p = HE + ".levels.1.blocks." + std::to_string(b);
-      NatL1WSrc::Blk& k = q.blk[b];
-      k.ln1_g = fptr(c, p + ".norm1.weight"); k.ln1_b = fptr(c, p + ".norm1.bias"); k.wqkv = fptr(c, p + ".attn.qkv.weight"); k.bqkv = fptr(c, p + ".attn.qkv.bias");
-      k.rpb = fptr(c, p + ".attn.rpb"); k.wproj = fptr(c, p + ".attn.proj.weight"); k.bproj = fptr(c, p + ".attn.proj.bias");
-      k.ln2_g = fptr(c, p + ".norm2.weight"); k.ln2_b = fptr(c, p + ".norm2.bias"); k.w1 = fptr(c, p + ".mlp.fc1.weight"); k.b1 = fptr(c, p + ".mlp.fc1.bias");
-      k.w2 = fptr(c, p + ".mlp.fc2.weight"); k.b2 = fptr(c, p + ".mlp.fc2.bias");
-    }
+    nat_blocks_src(c, q, 1);
     q.fn_g = fptr(c, HE + ".norm1.weight"); q.fn_b = fptr(c, HE + ".norm1.bias");
     q.w_ds = fptr(c, HE + ".levels.1.downsample.reduction.weight"); q.ds_g = fptr(c, HE + ".levels.1.downsample.norm.weight"); q.ds_b = fptr(c, HE + ".levels.1.downsample.norm.bias");
     if (!c->err.empty()) return RIFT_ERR_ARG;
@@ -1828,14 +1827,7 @@ int rift_model_load(RiftCtx* c, const RiftTensorDesc* params, int n, void* strea
   }
   {  // wave-private level-2 kernel (nat_l2w.h)
     NatL2WSrc q; memset(&q, 0, sizeof(q));
-    for (int b = 0; b < 2; ++b) {
-      const std::string p = HE + ".levels.2.blocks." + std::to_string(b);
-      NatL2WSrc::Blk& k = q.blk[b];
-      k.ln1_g = fptr(c, p + ".norm1.weight"); k.ln1_b = fptr(c, p + ".norm1.bias"); k.wqkv = fptr(c, p + ".attn.qkv.weight"); k.bqkv = fptr(c, p + ".attn.qkv.bias");
-      k.rpb = fptr(c, p + ".attn.rpb"); k.wproj = fptr(c, p + ".attn.proj.weight"); k.bproj = fptr(c, p + ".attn.proj.bias");
-      k.ln2_g = fptr(c, p + ".norm2.weight"); k.ln2_b = fptr(c, p + ".norm2.bias"); k.w1 = fptr(c, p + ".mlp.fc1.weight"); k.b1 = fptr(c, p + ".mlp.fc1.bias");
-      k.w2 = fptr(c, p + ".mlp.fc2.weight"); k.b2 = fptr(c, p + ".mlp.fc2.bias");
-    }
+    nat_blocks_src(c, q, 2);
     q.fn_g = fptr(c, HE + ".norm2.weight"); q.fn_b = fptr(c, HE + ".norm2.bias");
     if (!c->err.empty()) return RIFT_ERR_ARG;
     if (!c->l2w_img) { HIPCHK(c, hipMalloc((void**)&c->l2w_img, (size_t)2 * L2W_BLK_FRAGS * 1024)); HIPCHK(c, hipMalloc((void**)&c->l2w_par, (size_t)L2W_NPAR * 4)); }
@@ -1847,72 +1839,11 @@ int rift_model_load(RiftCtx* c, const RiftTensorDesc* params, int n, void* strea
     if (!w || !b) { c->err = "missing fpn_conv"; return RIFT_ERR_ARG; }
     TRY(pack(c, HE + ".fpn_conv.last", (const float*)w->data, 128, 128, 256, 0, 0, 0, 128, 0, 2, (const float*)b->data));
   }
-  const std::string EG = "agent_encoder.ego_state_emb";
-  TRY(pack_rows(c, EG + ".attn.q", EG + ".attn.in_proj_weight", EG + ".attn.in_proj_bias", 0, 128, 128));
-  TRY(pack_rows(c, EG + ".attn.kv", EG + ".attn.in_proj_weight", EG + ".attn.in_proj_bias", 128, 256, 256));
-  TRY(pack_linear(c, EG + ".attn.out_proj"));
-  if (!c->ego_w) { HIPCHK(c, hipMalloc((void**)&c->ego_w, 6 * 128 * 4)); HIPCHK(c, hipMalloc((void**)&c->ego_b, 6 * 128 * 4)); }
-  for (int i = 0; i < 6; ++i) {
-    const float* w = fptr(c, EG + ".linears." + std::to_string(i) + ".weight");
-    const float* b = fptr(c, EG + ".linears." + std::to_string(i) + ".bias");
-    if (!w || !b) return RIFT_ERR_ARG;
-    HIPCHK(c, hipMemcpyAsync(c->ego_w + i * 128, w, 128 * 4, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->ego_b + i * 128, b, 128 * 4, hipMemcpyDeviceToDevice, c->stream));
-  }
-  TRY(pack_points_encoder(c, "map_encoder.polygon_encoder"));
-  TRY(pack_fourier(c, "map_encoder.speed_limit_emb", 1));
-  TRY(pack_fourier(c, "static_objects_encoder.obj_encoder", 2));
-  TRY(pack_fourier(c, "pos_emb", 3));
-  for (int i = 0; i < 4; ++i) {
-    const std::string p = "encoder_blocks." + std::to_string(i);
-    TRY(pack_self_mha(c, p + ".attn"));
-    TRY(pack_linear(c, p + ".mlp.fc1")); TRY(pack_linear(c, p + ".mlp.fc2")); TRY(pack_hid(c, p + ".mlp.fc2"));
-  }
-  {  // chunked in_proj image for the fused encoder kernel: per 2-head chunk (q_h0 | k_h0 | q_h1 | k_h1 | v_h0 | v_h1)
-    int idx[384];
-    for (int ch = 0; ch < 2; ++ch)
-      for (int seg = 0; seg < 6; ++seg) {
-        const int part = seg < 4 ? (seg & 1) : 2;                 // 0 q, 1 k, 2 v
-        const int head = 2 * ch + (seg < 4 ? (seg >> 1) : (seg - 4));
-        for (int d = 0; d < 32; ++d) idx[ch * 192 + seg * 32 + d] = part * 128 + head * 32 + d;
-      }
-    if (!c->enc_idx) HIPCHK(c, hipMalloc((void**)&c->enc_idx, sizeof(idx)));
-    HIPCHK(c, hipMemcpyAsync(c->enc_idx, idx, sizeof(idx), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // idx is a stack buffer
-    for (int i = 0; i < 4; ++i) {
-      const std::string p = "encoder_blocks." + std::to_string(i) + ".attn";
-      const float* w = fptr(c, p + ".in_proj_weight"); const float* bsrc = fptr(c, p + ".in_proj_bias");
-      if (!w || !bsrc) return RIFT_ERR_ARG;
-      if (!c->enc_wqkv[i]) { HIPCHK(c, hipMalloc((void**)&c->enc_wqkv[i], 384 * 128 * 2)); HIPCHK(c, hipMalloc((void**)&c->enc_bqkv[i], 384 * 4)); }
-      hipLaunchKernelGGL(pack_rows_indexed_kernel, dim3(cdiv(384 * 128, 256)), dim3(256), 0, c->stream, w, bsrc, (const int*)c->enc_idx,
-                         384, 128, c->enc_wqkv[i], c->enc_bqkv[i]);
-    }
-  }
-  const char* ap[3] = {"loc_predictor", "yaw_predictor", "vel_predictor"};
-  for (int i = 0; i < 3; ++i) TRY(pack_mlp_layer(c, std::string("agent_predictor.") + ap[i]));
-  const std::string PD = "planning_decoder";
-  TRY(pack_points_encoder(c, PD + ".r_encoder"));
-  TRY(pack_fourier(c, PD + ".r_pos_emb", 3));
-  TRY(pack_cols(c, PD + ".q_proj.r", PD + ".q_proj", 0, 128, true));
-  TRY(pack_cols(c, PD + ".q_proj.m", PD + ".q_proj", 128, 128, false));
-  for (int i = 0; i < 4; ++i) {
-    const std::string p = PD + ".decoder_blocks." + std::to_string(i);
-    TRY(pack_self_mha(c, p + ".r2r_attn"));
-    TRY(pack_self_mha(c, p + ".m2m_attn"));
-    TRY(pack_rows(c, p + ".m2m_attn.qk0", p + ".m2m_attn.in_proj_weight", "", 0, 256, 384));
-    TRY(pack_rows(c, p + ".cross_attn.q", p + ".cross_attn.in_proj_weight", p + ".cross_attn.in_proj_bias", 0, 128, 128));
-    TRY(pack_rows(c, p + ".cross_attn.kv", p + ".cross_attn.in_proj_weight", p + ".cross_attn.in_proj_bias", 128, 256, 256));
-    TRY(pack_linear(c, p + ".cross_attn.out_proj"));
-    TRY(pack_linear(c, p + ".ffn.0")); TRY(pack_linear(c, p + ".ffn.3"));
-  }
-  {
-    std::vector<std::string> wn, bn;
-    for (int i = 0; i < 4; ++i) {
-      wn.push_back(PD + ".decoder_blocks." + std::to_string(i) + ".cross_attn.in_proj_weight");
-      bn.push_back(PD + ".decoder_blocks." + std::to_string(i) + ".cross_attn.in_proj_bias");
-    }
-    TRY(pack_stacked_rows(c, PD + ".kv_all", wn, bn, 128, 256));
-  }
+  return RIFT_OK;
+}
+
+// rift_model_load: the weight streams / parameter blocks of the wave-private encoder, Fourier, PointsEncoder and decoder kernels
+static int pack_streamed_images(RiftCtx* c) {
   {  // dense-traffic scene encoder (enc_w.h)
     EncWSrc q; memset(&q, 0, sizeof(q));
     for (int i = 0; i < 4; ++i) {
@@ -1981,6 +1912,89 @@ int rift_model_load(RiftCtx* c, const RiftTensorDesc* params, int n, void* strea
     if (!c->decw_img) { HIPCHK(c, hipMalloc((void**)&c->decw_img, (size_t)4 * DECW_LAYER_FRAGS * 1024)); HIPCHK(c, hipMalloc((void**)&c->decw_par, (size_t)4 * DECW_PAR_LAYER * 4)); }
     decw_pack(q, c->decw_img, c->decw_par, c->stream);
   }
+  return RIFT_OK;
+}
+
+int rift_model_load(RiftCtx* c, const RiftTensorDesc* params, int n, void* stream) {
+  if (!c || !params) return RIFT_ERR_ARG;
+  c->err.clear();
+  c->stream = (hipStream_t)stream;
+  HIPCHK(c, hipSetDevice(c->device));
+  for (void* p : c->owned) (void)hipFree(p);
+  c->owned.clear(); c->pw.clear(); c->params.clear(); c->wconst.clear();
+  c->dry_need = 0;                      // (the first forward on new weights sizes its arena again: it also computes the weight-only products)
+  for (int i = 0; i < n; ++i) {
+    Param p; p.data = params[i].data; p.numel = params[i].numel; p.ndim = params[i].ndim;
+    for (int d = 0; d < 4; ++d) p.shape[d] = params[i].shape[d];
+    c->params[params[i].name] = p;
+  }
+  TRY(pack_history_encoder(c));
+  const std::string EG = "agent_encoder.ego_state_emb";
+  TRY(pack_rows(c, EG + ".attn.q", EG + ".attn.in_proj_weight", EG + ".attn.in_proj_bias", 0, 128, 128));
+  TRY(pack_rows(c, EG + ".attn.kv", EG + ".attn.in_proj_weight", EG + ".attn.in_proj_bias", 128, 256, 256));
+  TRY(pack_linear(c, EG + ".attn.out_proj"));
+  if (!c->ego_w) { HIPCHK(c, hipMalloc((void**)&c->ego_w, 6 * 128 * 4)); HIPCHK(c, hipMalloc((void**)&c->ego_b, 6 * 128 * 4)); }
+  for (int i = 0; i < 6; ++i) {
+    const float* w = fptr(c, EG + ".linears." + std::to_string(i) + ".weight");
+    const float* b = fptr(c, EG + ".linears." + std::to_string(i) + ".bias");
+    if (!w || !b) return RIFT_ERR_ARG;
+    HIPCHK(c, hipMemcpyAsync(c->ego_w + i * 128, w, 128 * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->ego_b + i * 128, b, 128 * 4, hipMemcpyDeviceToDevice, c->stream));
+  }
+  TRY(pack_points_encoder(c, "map_encoder.polygon_encoder"));
+  TRY(pack_fourier(c, "map_encoder.speed_limit_emb", 1));
+  TRY(pack_fourier(c, "static_objects_encoder.obj_encoder", 2));
+  TRY(pack_fourier(c, "pos_emb", 3));
+  for (int i = 0; i < 4; ++i) {
+    const std::string p = "encoder_blocks." + std::to_string(i);
+    TRY(pack_self_mha(c, p + ".attn"));
+    TRY(pack_linear(c, p + ".mlp.fc1")); TRY(pack_linear(c, p + ".mlp.fc2")); TRY(pack_hid(c, p + ".mlp.fc2"));
+  }
+  {  // chunked in_proj image for the fused encoder kernel: per 2-head chunk (q_h0 | k_h0 | q_h1 | k_h1 | v_h0 | v_h1)
+    int idx[384];
+    for (int ch = 0; ch < 2; ++ch)
+      for (int seg = 0; seg < 6; ++seg) {
+        const int part = seg < 4 ? (seg & 1) : 2;                 // 0 q, 1 k, 2 v
+        const int head = 2 * ch + (seg < 4 ? (seg >> 1) : (seg - 4));
+        for (int d = 0; d < 32; ++d) idx[ch * 192 + seg * 32 + d] = part * 128 + head * 32 + d;
+      }
+    if (!c->enc_idx) HIPCHK(c, hipMalloc((void**)&c->enc_idx, sizeof(idx)));
+    HIPCHK(c, hipMemcpyAsync(c->enc_idx, idx, sizeof(idx), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // idx is a stack buffer
+    for (int i = 0; i < 4; ++i) {
+      const std::string p = "encoder_blocks." + std::to_string(i) + ".attn";
+      const float* w = fptr(c, p + ".in_proj_weight"); const float* bsrc = fptr(c, p + ".in_proj_bias");
+      if (!w || !bsrc) return RIFT_ERR_ARG;
+      if (!c->enc_wqkv[i]) { HIPCHK(c, hipMalloc((void**)&c->enc_wqkv[i], 384 * 128 * 2)); HIPCHK(c, hipMalloc((void**)&c->enc_bqkv[i], 384 * 4)); }
+      hipLaunchKernelGGL(pack_rows_indexed_kernel, dim3(cdiv(384 * 128, 256)), dim3(256), 0, c->stream, w, bsrc, (const int*)c->enc_idx,
+                         384, 128, c->enc_wqkv[i], c->enc_bqkv[i]);
+    }
+  }
+  const char* ap[3] = {"loc_predictor", "yaw_predictor", "vel_predictor"};
+  for (int i = 0; i < 3; ++i) TRY(pack_mlp_layer(c, std::string("agent_predictor.") + ap[i]));
+  TRY(pack_points_encoder(c, PD + ".r_encoder"));
+  TRY(pack_fourier(c, PD + ".r_pos_emb", 3));
+  TRY(pack_cols(c, PD + ".q_proj.r", PD + ".q_proj", 0, 128, true));
+  TRY(pack_cols(c, PD + ".q_proj.m", PD + ".q_proj", 128, 128, false));
+  for (int i = 0; i < 4; ++i) {
+    const std::string p = PD + ".decoder_blocks." + std::to_string(i);
+    TRY(pack_self_mha(c, p + ".r2r_attn"));
+    TRY(pack_self_mha(c, p + ".m2m_attn"));
+    TRY(pack_rows(c, p + ".m2m_attn.qk0", p + ".m2m_attn.in_proj_weight", "", 0, 256, 384));
+    TRY(pack_rows(c, p + ".cross_attn.q", p + ".cross_attn.in_proj_weight", p + ".cross_attn.in_proj_bias", 0, 128, 128));
+    TRY(pack_rows(c, p + ".cross_attn.kv", p + ".cross_attn.in_proj_weight", p + ".cross_attn.in_proj_bias", 128, 256, 256));
+    TRY(pack_linear(c, p + ".cross_attn.out_proj"));
+    TRY(pack_linear(c, p + ".ffn.0")); TRY(pack_linear(c, p + ".ffn.3"));
+  }
+  {
+    std::vector<std::string> wn, bn;
+    for (int i = 0; i < 4; ++i) {
+      wn.push_back(PD + ".decoder_blocks." + std::to_string(i) + ".cross_attn.in_proj_weight");
+      bn.push_back(PD + ".decoder_blocks." + std::to_string(i) + ".cross_attn.in_proj_bias");
+    }
+    TRY(pack_stacked_rows(c, PD + ".kv_all", wn, bn, 128, 256));
+  }
+  TRY(pack_streamed_images(c));
   TRY(pack_cols(c, PD + ".cat_x_proj.q", PD + ".cat_x_proj", 0, 128, true));
   TRY(pack_cols(c, PD + ".cat_x_proj.x", PD + ".cat_x_proj", 128, 128, false));
   const char* hd[3] = {"loc_head", "yaw_head", "vel_head"};
@@ -2039,7 +2053,7 @@ int rift_forward(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
   // diagnostic: RIFT_POISON_ARENA=<byte> fills the scratch arena before every forward (0xFF = NaN pattern), so that a kernel reading
   // scratch it never wrote shows up as NaN / as run-to-run differences instead of depending on what the memory held before
   // (on the prepare stream if the preparation runs there: every other stream of the forward waits for the preparation)
-  if (c->dg.poison_arena >= 0 && c->arena) { HIPCHK(c, hipMemsetAsync(c->arena, c->dg.poison_arena, c->arena_cap, c->prep_set && !c->prof_on ? c->prep_stream : c->stream)); }
+  if (c->dg.poison_arena >= 0 && c->arena) { HIPCHK(c, hipMemsetAsync(c->arena, c->dg.poison_arena, c->arena_cap, plan_of(c, (flags & RIFT_F_FP32) != 0, B->bs).prefetched ? c->prep_stream : c->stream)); }
   rc = forward_impl(c, B, out, flags, seed);
   c->stream = (hipStream_t)stream;
   if (rc != RIFT_OK) return rc;

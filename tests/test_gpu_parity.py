@@ -935,11 +935,12 @@ def test_hidden_layer_overflow_raises_the_non_finite_flag(ffi, mode):
 
 def test_ranking_inside_the_preparation_launch_equals_the_ranking_kernel(ffi, monkeypatch):
     """Round 6: the ranks of the compacted history-encoder launch written by the first bs blocks of prep_kernel (kernels.h: rank_scene_body,
-    last-block scan over per-scene class counts) against nat_rank_kernel behind the preparation (RIFT_RANK_IN_PREP=0) and against numpy:
+    decoupled look-back over the per-scene class counts each scene block publishes) against nat_rank_kernel behind the preparation (RIFT_RANK_IN_PREP=0) and against numpy:
     aidx[3 i + c] = the i-th valid non-ego agent slot of class c = slot % 3 in ascending order, cnt = the class counts -- integer arrays,
-    bit-exact; everything downstream bit-identical.  Shapes: the fixture (A = 64), a 200-scene synthetic batch (the scan's threads own one scene
-    each), the CARLA shape (A = 49: slot classes rotate with the scene), the dense-traffic shape (A = 128: two ballot words per scene), and a
-    batch without any sequence.  Twice per engine: the block counter must be back at zero after a launch."""
+    bit-exact; everything downstream bit-identical.  Shapes: the fixture (A = 64), a 200-scene synthetic batch (one look-back pass reads
+    up to 256 predecessors, one per thread), the CARLA shape (A = 49: slot classes rotate with the scene), the dense-traffic shape (A = 128: two ballot words per scene), and a
+    batch without any sequence.  Twice per engine: the published words persist between launches, and the second launch must take none of the
+    first one's for its own (they carry the launch's epoch)."""
     gold, batch, sd = H.load_case("full")
     cases = [batch["cur_pluto_feature_torch"], syn.collate_scenes([syn.make_scene(7000 + i) for i in range(200)])["cur_pluto_feature_torch"]]
     for A, Mp, r0, r1 in ((49, 60, 1, 6), (128, 40, 8, 16)):
@@ -1034,7 +1035,6 @@ def test_fused_fourier_embedding_matches_layerwise_path(ffi, monkeypatch):
     outs = {}
     for name, env, fp32 in (("fused", "0", False), ("lds", "0", False), ("layerwise", "1", False), ("fp32", "1", True)):
         monkeypatch.setenv("RIFT_FOURIER_UNFUSED", env)
-        monkeypatch.setenv("RIFT_KEEP_TOKENS", "1")                        # (the encoder's fused token assembly writes the rows out for the tap)
         monkeypatch.setenv("RIFT_FO_W", "0" if name == "lds" else "1")     # "lds": the LDS-resident fourier_fused_kernel instead of fo_w_kernel
         eng = ffi.Engine("cuda:0")
         eng.load_state_dict({k: v.clone() for k, v in sd.items()})

@@ -124,6 +124,100 @@ def test_ctypes_structs_match_the_header_as_a_c_compiler_lays_it_out(tmp_path):
         assert [getattr(st, f).offset for f, *_ in st._fields_] == [int(o) for o in offs], name
 
 
+def test_stream_plan_orders_every_reader_behind_the_preparation(tmp_path):
+    """csrc/fwd_plan.h (host-only) compiled by g++ and run over every combination of its inputs.  Checked against the placement table
+    written out here, independently of the header's formulas: where the preparation, the history chain, the map chain and the late
+    data-parallel mask fill run and which event waits are issued; that every stream carrying a reader of the preparation's outputs is
+    the preparation's stream or reaches it through waits issued before that reader; that nothing forks while profiling, sizing or fp32."""
+    import shutil
+    import subprocess
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    bools = ["two_streams", "nat_fused", "nat_aside", "fp32", "prof_on", "dry", "prep_set", "dp_on"]
+    outs = ["prefetched", "forked", "nat_aside", "prep_on", "history_on", "map_on", "dp_fill_on", "dp_fill_late", "side_waits_prep", "fork_from_main",
+            "main_waits_prep", "join_once"]
+    src = tmp_path / "plan.cpp"
+    names = bools + ["side_gate"]
+    src.write_text("\n".join(
+        ['#include <cstdio>', '#include "fwd_plan.h"', 'int main() {', '  const int sizes[4] = {32, 64, 65, 256};',
+         f'  for (int m = 0; m < {2 ** len(names)}; ++m) for (int s = 0; s < 4; ++s) {{', '    PlanIn in;']
+        + [f'    in.{b} = (m >> {k}) & 1;' for k, b in enumerate(names)]
+        + ['    in.bs = sizes[s];', '    const StreamPlan p = plan_streams(in);',
+           '    printf("%d %d ' + " ".join(["%d"] * len(outs)) + '\\n", m, in.bs, ' + ", ".join(f"(int)p.{o}" for o in outs) + ');', '  }', '  return 0;', '}']))
+    exe = tmp_path / "plan"
+    subprocess.check_call([gxx, "-std=c++17", "-I", os.path.join(repo, "rift_amd", "csrc"), str(src), "-o", str(exe)])
+    CALLER, PREPARE, SIDE = 0, 1, 2
+    n = 0
+    for line in subprocess.check_output([str(exe)], text=True).splitlines():
+        m, bs, *vals = map(int, line.split())
+        i = {b: (m >> k) & 1 for k, b in enumerate(names)}
+        i["bs"] = bs
+        p = dict(zip(outs, vals))
+        n += 1
+        quiet = not (i["prof_on"] or i["dry"])
+        forked = bool(i["two_streams"] and i["nat_fused"] and not i["fp32"] and quiet)
+        prefetched = bool(i["prep_set"] and quiet)
+        assert (p["forked"], p["prefetched"]) == (forked, prefetched), i
+        if i["prof_on"] or i["dry"] or i["fp32"]:
+            assert not p["forked"], i
+        # ---- the placement table: (prep launch, side waits, history chain, map chain, caller waits before token assembly)
+        side_waits, caller_waits = set(), set()
+        if p["side_waits_prep"]: side_waits.add("ev_prep")
+        if p["fork_from_main"]: side_waits.add("ev_fork")
+        if p["join_once"]: side_waits.add("ev_join2")
+        if p["main_waits_prep"]: caller_waits.add("ev_prep")
+        if p["forked"]: caller_waits.add("ev_join")
+        if p["nat_aside"] and not p["join_once"]: caller_waits.add("ev_join2")
+        row = (p["prep_on"], side_waits, p["history_on"], p["map_on"], caller_waits)
+        if not forked and not prefetched:
+            want = (CALLER, set(), CALLER, CALLER, set())
+        elif not forked:
+            want = (PREPARE, set(), CALLER, CALLER, {"ev_prep"})
+        elif not prefetched:
+            want = (CALLER, {"ev_fork"}, CALLER, SIDE, {"ev_join"})
+        elif i["side_gate"] > 0:
+            want = (PREPARE, {"ev_prep", "ev_fork"}, CALLER, SIDE, {"ev_prep", "ev_join"})
+        elif not i["nat_aside"]:
+            want = (PREPARE, {"ev_prep"}, CALLER, SIDE, {"ev_prep", "ev_join"})
+        elif i["bs"] > 64:
+            want = (PREPARE, {"ev_prep"}, PREPARE, SIDE, {"ev_join", "ev_join2"} | ({"ev_prep"} if i["dp_on"] else set()))
+        else:
+            want = (PREPARE, {"ev_prep", "ev_join2"}, PREPARE, SIDE, {"ev_join"} | ({"ev_prep"} if i["dp_on"] else set()))
+        assert row == want, (i, p)
+        assert not p["nat_aside"] or (forked and prefetched), i
+        # ---- the late mask fill: on the map chain's stream, and only with the preparation prefetched under data parallelism
+        assert p["dp_fill_late"] == int(bool(i["dp_on"]) and prefetched), i
+        assert p["dp_fill_on"] == (p["map_on"] if p["dp_fill_late"] else CALLER), i
+        # ---- ordering: edges stream -> stream of the event waits.  ev_prep is recorded on the prepare stream behind the preparation and
+        # ev_fork on the caller's behind whatever it holds by then: both precede the chains.  ev_join (side, behind the map chain) and
+        # ev_join2 (prepare, behind the history chain) order the token assembly only.
+        early = set()
+        if p["side_waits_prep"]: early.add((PREPARE, SIDE))
+        if p["fork_from_main"]: early.add((CALLER, SIDE))
+        if p["main_waits_prep"]: early.add((PREPARE, CALLER))
+        late = set(early)
+        if p["forked"]: late.add((SIDE, CALLER))
+        if p["nat_aside"]: late.add((PREPARE, SIDE) if p["join_once"] else (PREPARE, CALLER))
+
+        def reaches(edges, dst):
+            seen, todo = {p["prep_on"]}, [p["prep_on"]]
+            while todo:
+                s = todo.pop()
+                for a, b in edges:
+                    if a == s and b not in seen:
+                        seen.add(b)
+                        todo.append(b)
+            return dst in seen
+        assert reaches(early, p["history_on"]), ("history chain unordered", i, p)
+        assert reaches(early, p["map_on"]), ("map chain unordered", i, p)
+        if i["dp_on"]:
+            assert reaches(early, p["dp_fill_on"]), ("mask fill unordered", i, p)
+        assert reaches(late, CALLER), ("token assembly unordered", i, p)
+    assert n == 2 ** 9 * 4
+
+
 def test_product_package_never_touches_the_oracle():
     """oracle/ is test infrastructure: nothing under rift_amd/ may import or reference it."""
     import pathlib

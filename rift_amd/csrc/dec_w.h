@@ -11,6 +11,8 @@
 // tail) that LDS-DMA (`global_load_lds_dwordx4`, no staging registers) drops into a two-slot ring one group ahead; one barrier per
 // group both publishes the next slot and retires the previous one, and the residual hand-overs ride on those barriers.  20 barriers
 // per layer instead of ~28 barrier-separated LDS round trips, no activation traffic through LDS at all.
+// The tile of a PADDED reference line skips what the layer discards: m2m (the reference scatters the valid lines' m2m output into zeros) in
+// every layer, and the whole reference-line tiling of the last layer when nobody reads those rows (DecWP::prob_only); dec_w.hip, tiling B.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -71,7 +73,11 @@ struct DecWP {
   const unsigned short* img;    // pack_decw_kernel
   const float* par;
   float dropout; uint32_t seed, stream;
-  int dbg;                      // diagnostic: 1 = skip all compute (weight stream + barriers only), 8 = no stream, 16 = all eight waves carry the stream
+  int dbg;                      // diagnostic: 1 = skip all compute (weight stream + barriers only), 8 = no stream, 16 = all eight waves carry the stream,
+                                // 32 = MID shapes on the dense variant, 64 = padded reference lines compute what the step discards (RIFT_NO_SKIP)
+  int prob_only;                // 1: nobody reads the rows of padded reference lines behind the last layer (a forward without the trajectory heads:
+                                // pi_forward_kernel writes -1e6 there and the objectives mask them) -- their tiles skip the last layer's reference-line
+                                // tiling and leave zero rows in Q
   long long* ts;                // optional: clock of wave 0 of workgroup 0 at every group boundary (diagnostic, RIFT_DEC_TS)
   int* nonfinite;               // device flag: raised when a query row leaves the last layer with a NaN / Inf (planning_decoder.py:175)
   int l0, l1;                   // layers [l0, l1) of the four (l0 even): a launch per half lets a small-batch step run the halves on two queues

@@ -83,6 +83,15 @@ struct DecWRng { uint32_t x[4]; };
 __device__ __forceinline__ uint32_t decw_step(uint32_t x, uint32_t c) {
   return (x & 0xffffffu) * 214013u + c;          // both factors below 2^24: hipcc selects v_mad_u32_u24 and drops the mask (the ISA test of tools/checks counts them)
 }
+// n steps of a stream at once: x <- A^n x + C (A^n - 1) / (A - 1) (mod 2^24) -- the same v_mad_u32_u24 shape with other constants.  Bits 31..24
+// of the result are not those of n single steps; the next decw_step masks them (tests/test_lcg_jump.py restates both).
+constexpr uint32_t decw_jump_mul(int n) { uint32_t a = 1u; for (int i = 0; i < n; ++i) a = (a * 214013u) & 0xffffffu; return a; }
+constexpr uint32_t decw_jump_add(int n, uint32_t c) { uint32_t g = 0u; for (int i = 0; i < n; ++i) g = (g * 214013u + c) & 0xffffffu; return g; }
+template <int NSTEP>
+__device__ __forceinline__ uint32_t decw_jump(uint32_t x, uint32_t c) {
+  constexpr uint32_t AN = decw_jump_mul(NSTEP);
+  return (x & 0xffffffu) * AN + decw_jump_add(NSTEP, c);      // (c is a literal at the call sites: the sum folds)
+}
 typedef short decw_s16x2 __attribute__((ext_vector_type(2)));
 #if RIFT_ATTN_K16
 typedef h16x4 DecwVf;            // V^T of a 16-key tile: a K = 16 operand (opfmt.h: RIFT_ATTN_K16)
@@ -117,6 +126,9 @@ __device__ __forceinline__ h16x8 decw_words(uint32_t a, uint32_t b, uint32_t c, 
 // R <= 8 reference lines and 96 < N <= 128 token slots: what `train_cbv` really collates (49 agents + 60 polygons = 109 slots), which the
 // dense variant served at 1.5 x the standard kernel's time.  Eight key tiles make a head pair's K | V^T group exactly 32 fragments, one
 // ring slot; they are gathered out of the dense per-head image (dec_kv.h) in runs of four fragments.
+// Padded reference lines (all variants): their tiles skip m2m in every layer and, with DecWP::prob_only, the last layer's whole reference-line
+// tiling -- work whose result the layer overwrites with zeros or nobody reads (see tiling B; DecWP::dbg bit 64 = RIFT_NO_SKIP computes it).  A NaN /
+// Inf such a row would have carried out of the last layer no longer raises the non-finite flag here: the row leaves as zeros.
 template <bool DROP, bool DENSE, int NKE = (DENSE ? 12 : 6)>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void dec_w_kernel(DecWP p) {
   constexpr int M = 12, XS = DECW_XS;
@@ -349,6 +361,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     constexpr uint32_t C[4] = {2531011u, 1013904223u & 0xffffffu, 12345u, 7046029u};
     return rng.x[i] = decw_step(rng.x[i], C[i]);
   };
+  // what a skipped m2m sub-block would have drawn: self_attention two keep2 steps of every stream (heads h, h + 2 share a stream pair), residual
+  // four (keep4 of the n-tiles nt, nt + 2, nt + 4, nt + 6) -- six steps per stream, so that every later decision of the launch is the one it was
+  constexpr int M2M_STEPS = 2 + 4;
+  auto skip_m2m_draws = [&]() {
+    rng.x[0] = decw_jump<M2M_STEPS>(rng.x[0], 2531011u); rng.x[1] = decw_jump<M2M_STEPS>(rng.x[1], 1013904223u & 0xffffffu);
+    rng.x[2] = decw_jump<M2M_STEPS>(rng.x[2], 12345u); rng.x[3] = decw_jump<M2M_STEPS>(rng.x[3], 7046029u);
+  };
 #if RIFT_DROP_STATS
   auto dcount = [&](uint32_t keepmask, int n) { ddrawn[dsite] += n; dkept[dsite] += __builtin_popcount(keepmask & 0x00010001u); };
 #else
@@ -544,30 +563,45 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       set_tiles(0, rb);
       const int pb = DENSE ? 4 * RA + GB * rb : 4;                // first position of this round
       constexpr int KO = DENSE ? 9 : 7;                           // round-relative position of cross out_proj (behind the K | V^T groups)
-      if (actB) {
+      // A padded reference line (wave-uniform: the tile is the line).  The reference runs m2m on the valid lines and scatters into zeros
+      // (planning_decoder.py:63-72): its tile runs the four m2m boundaries, takes zero rows and steps its dropout streams past the draws it did
+      // not make.  Cross attention and the FFN of those rows stay: the r2r quirk lets another scene's mask expose them as keys of the next
+      // layer -- except behind the model's last layer in a forward that computes `probability` only (p.prob_only), where nobody reads them:
+      // there the tile runs the boundaries of the whole tiling and leaves zero rows in Q.  ONE branch around each region (run-time guards inside
+      // straight-line phases cost this kind of kernel its schedule, enc_fused.h).  dbg 64 (RIFT_NO_SKIP) and the statistics twin (its
+      // per-site draw counts are compared across sites) compute, then discard, as until round 7.
+      const bool skip_pad = !RIFT_DROP_STATS && !(p.dbg & 64) && actB && __builtin_amdgcn_readfirstlane((int)rz[tileB]) != 0;
+      const bool skip_all = skip_pad && p.prob_only && li == 3 && li + 1 == p.l1;
+      if (actB && !skip_all) {
         f32x4 res[8], acc[8];
         h16x8 xb[4], qf[4], kf[4], ao[4];
         DecwVf vf[8];
         bnd(li, pb + 0);                                        // ---- m2m q (+ m_pos)
         if (rb == 0) acquire();
-        read_xs(res, b_row, b_ok);
-        layer_norm(res, xb, parE + DECW_E_LN2);
-        init8(acc, parE + DECW_E_PB + (b_ok ? l15 : 0) * DECW_PBS); gemm(0, xb, acc);
-        to_heads(acc, qf);
-        init8(acc, parE + DECW_E_PB + (b_ok ? l15 : 0) * DECW_PBS + 128);
-        bnd(li, pb + 1);                                        // ---- m2m k (+ m_pos)
-        gemm(1, xb, acc);
-        to_heads(acc, kf);
-        bnd(li, pb + 2);                                        // ---- m2m v + attention over the modes
-        gemm_v(0, xb, vf, parE + DECW_E_BM2MV);
-        DSITE(2);
-        { const float mk = l4 == 3 ? -INFINITY : 0.f; self_attention((f32x4){mk, mk, mk, mk}, qf, kf, vf, ao); }   // keys 12..15 are padding slots
-        init8(acc, parE + DECW_E_BM2MO);
-        bnd(li, pb + 3);                                        // ---- m2m out_proj, residual, padded lines zeroed (:70-72), LayerNorm
-        gemm(1, ao, acc);
-        DSITE(3);
-        residual(res, acc, dpk);
-        if (rz[tileB]) zero8(res);
+        if (skip_pad) {
+          bnd(li, pb + 1); bnd(li, pb + 2); bnd(li, pb + 3);
+          if (DROP) skip_m2m_draws();
+          zero8(res);
+        } else {
+          read_xs(res, b_row, b_ok);
+          layer_norm(res, xb, parE + DECW_E_LN2);
+          init8(acc, parE + DECW_E_PB + (b_ok ? l15 : 0) * DECW_PBS); gemm(0, xb, acc);
+          to_heads(acc, qf);
+          init8(acc, parE + DECW_E_PB + (b_ok ? l15 : 0) * DECW_PBS + 128);
+          bnd(li, pb + 1);                                        // ---- m2m k (+ m_pos)
+          gemm(1, xb, acc);
+          to_heads(acc, kf);
+          bnd(li, pb + 2);                                        // ---- m2m v + attention over the modes
+          gemm_v(0, xb, vf, parE + DECW_E_BM2MV);
+          DSITE(2);
+          { const float mk = l4 == 3 ? -INFINITY : 0.f; self_attention((f32x4){mk, mk, mk, mk}, qf, kf, vf, ao); }   // keys 12..15 are padding slots
+          init8(acc, parE + DECW_E_BM2MO);
+          bnd(li, pb + 3);                                        // ---- m2m out_proj, residual, padded lines zeroed (:70-72), LayerNorm
+          gemm(1, ao, acc);
+          DSITE(3);
+          residual(res, acc, dpk);
+          if (rz[tileB]) zero8(res);
+        }
         layer_norm(res, xb, parL + DECW_L_LN3);
         init8(acc, parL + DECW_L_BCQ);
         bnd(li, pb + 4);                                        // ---- cross q
@@ -637,6 +671,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       } else {
 #pragma unroll 1
         for (int k = 0; k < GB; ++k) bnd(li, pb + k);
+        if (skip_all && b_ok) {
+#pragma unroll
+          for (int nt = 0; nt < 8; ++nt) *reinterpret_cast<float4*>(p.Q + (qrow0 + b_row) * 128 + nt * 16 + l4 * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
       }
     }
     publish();

@@ -5,6 +5,10 @@
 // LN -> qkv (2 heads at a time) -> MFMA attention -> out_proj -> +res -> LN -> fc1 -> GELU -> fc2 -> +res with
 // bf16 MFMA (fp32 accumulate) and never touches HBM in between.  Weights (0.39 MB bf16 per layer) stream from
 // L2 as MFMA B fragments requested one phase ahead.  Replaces ~44 launches and ~1 GB of HBM traffic per step.
+// Train mode: a branch DropPath drops for this scene (a workgroup-uniform decision) is not computed -- the layer keeps only the hand-over of
+// the register-resident weights and parameter vectors to the next phase.  The residual rows are what `x + 0 * branch` gave for every finite
+// branch; a NaN / Inf a dropped branch WOULD have produced (0 * Inf) no longer reaches the residual stream.  EncFusedP::dbg bit 0
+// (RIFT_NO_SKIP=1) computes the branch and adds zero times it, as until round 7.
 #pragma once
 #include "common.h"
 #include "dropstats.h"
@@ -35,6 +39,7 @@ struct EncFusedP {
   uint32_t seed, stream;
   long long* ts;                // optional phase timestamps of workgroup 0 (diagnostic)
   int* nonfinite;               // device flag: raised when a valid token row leaves the encoder with a NaN / Inf
+  int dbg;                      // diagnostic: 1 = compute the branches DropPath drops (RIFT_NO_SKIP)
   // ---- optional tail: the planning decoder's cross-attention K | V projections of this scene's encoder output, all four layers
   // (planning_decoder.py:74-79, nn.MultiheadAttention in_proj rows 128:384), written as bf16 operands of the decoder kernel
   const unsigned short* wkv;    // fragment-major bf16 [4 * 256][128]: per layer (k 128 rows | v 128 rows)
@@ -244,8 +249,11 @@ __device__ __forceinline__ void enc_fused_body(const EncFusedP& p, const bool ok
       ds_sample(p.ds, RIFT_DS_ENC(bi, 0), b, dpscale);
       ds_sample(p.ds, RIFT_DS_ENC(bi, 1), b, dpscale2);
     }
+    // a dropped branch is skipped as a whole: ONE workgroup-uniform branch around each block (guards inside the unrolled loops cost this
+    // kernel its schedule, see MTC above); the skipped side keeps the hand-over the block ends with
     par_commit();
     lds_barrier();
+    if (dpscale != 0.f || (p.dbg & 1)) {
     // ======== self attention ========
     layer_norm(par + P_LN1G, par + P_LN1B);
     lds_barrier();
@@ -401,6 +409,8 @@ __device__ __forceinline__ void enc_fused_body(const EncFusedP& p, const bool ok
     }
     lds_barrier();
     TS();
+    } else e_load_b(Bw, w.w1, C, 0, 0, wave, l15, l4, EWaves<NW>());             // (dropped: only the hand-over -- fc1 weights of hidden chunk 0)
+    if (dpscale2 != 0.f || (p.dbg & 1)) {
     // ======== MLP ========
     layer_norm(par + P_LN2G, par + P_LN2B);
     if (bi + 1 < 4) par_fetch(p.blk[bi + 1]);
@@ -457,7 +467,11 @@ __device__ __forceinline__ void enc_fused_body(const EncFusedP& p, const bool ok
         }
       }
     }
-    lds_barrier();
+    } else if (bi + 1 < 4) {      // (dropped: the next layer's parameter vectors and its first q | k | v weights)
+      par_fetch(p.blk[bi + 1]);
+      e_load_b(Bqkv, p.blk[bi + 1].wqkv, C, 0, 0, wave, l15, l4, EWaves<NW>(), 12);
+    }
+    lds_barrier();                // (also: this layer's reads of `par` are over before the next par_commit)
     TS();
   }
   // ---- final LayerNorm (fp32 out) -> global
@@ -573,10 +587,12 @@ __device__ __forceinline__ void enc_fused_body(const EncFusedP& p, const bool ok
   }
 }
 
-// 97 .. 112 token slots per scene (round 6): the same body on the 112-row layout (EncLay<112>), always compacting -- 5, 6 or 7 row tiles by
-// the scene's valid-token count; K | V^T for the decoder's eight-key-tile variant (dense per-head image), kpm_c is (bs, 112).
+// 97 .. 112 token slots per scene (round 6): the same body on the 112-row layout (EncLay<112>), compacting -- 5, 6 or 7 row tiles by the
+// scene's valid-token count; K | V^T for the decoder's eight-key-tile variant (dense per-head image), kpm_c is (bs, 112).  Builds that keep
+// the slot order (RIFT_ENC_COMPACT = 0) run all seven tiles: a valid token may sit in any of them.
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void enc_fused112_kernel(EncFusedP p) {
+#if RIFT_ENC_COMPACT
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_cnt[];
   int* cnt = reinterpret_cast<int*>(smem_cnt);
   const int tid = threadIdx.x, wave = tid >> 6, N = p.N;
@@ -591,6 +607,9 @@ __global__ __launch_bounds__(64 * NW) void enc_fused112_kernel(EncFusedP p) {
   if (!keep_order && nvv <= 80) enc_fused_body<NW, 5, 112>(p, ok, vmask, c0, nvv, false);
   else if (!keep_order && nvv <= 96) enc_fused_body<NW, 6, 112>(p, ok, vmask, c0, nvv, false);
   else enc_fused_body<NW, 7, 112>(p, ok, vmask, c0, nvv, keep_order);
+#else
+  enc_fused_body<NW, 7, 112>(p, false, 0ull, 0, 0, true);
+#endif
 }
 
 int enc112_set_attributes();                                   // enc112.hip

@@ -128,6 +128,8 @@ struct RiftCtx {
   // launch (prepare_inputs): a captured graph that replays the launch would replay a stale epoch, so that launch is never graph-replayed.
   unsigned long long* rk_pub[RIFT_DEFER_SLOTS] = {}; int rk_cap[RIFT_DEFER_SLOTS] = {}; unsigned int rk_epoch[RIFT_DEFER_SLOTS] = {};
   bool rank_fault = false;               // RIFT_RANK_FAULT=1 (diagnostic): the first scene block of the in-launch ranking never publishes its counts
+  bool no_skip = false;                  // RIFT_NO_SKIP=1: the scene encoder computes the branches DropPath drops and the decoder the padded reference lines' discarded
+                                         // sub-blocks, as until round 7 (the reference of tests/test_gpu_skip_discarded.py and the "before" leg of the A/B in one binary)
   bool enc112 = true;                    // RIFT_ENC112=0: scenes of 97 .. 112 token slots on enc_w_kernel (rounds 3 - 5) instead of the fused kernel's 112-row layout
   bool rank_in_prep = true;              // RIFT_RANK_IN_PREP=0: the ranking as its own launch behind the preparation (nat_rank_kernel, rounds 3 - 5)
   void* comm = nullptr; int comm_rank = 0, comm_world = 1;      // library-owned RCCL communicator (rift_comm_init), or null
@@ -1324,7 +1326,7 @@ void scene_encoder(Fwd& f) {
       w.droppath = f.drop ? edpr[i] : 0.f;
     }
     ep.norm_g = fptr(c, "norm.weight"); ep.norm_b = fptr(c, "norm.bias"); ep.nonfinite = c->nonfinite;
-    ep.ds = f.ds;
+    ep.ds = f.ds; ep.dbg = c->no_skip ? 1 : 0;
     if (c->dg.enc_ts) { ep.ts = A_alloc<long long>(c, 256); tap(c, "enc_ts", (float*)ep.ts, 512); }
     c->prof_flops = 4.0 * bs * N * (2.0 * 128 * 384 + 4.0 * N * 128 + 2.0 * 128 * 128 + 4.0 * 128 * 512);
     if (c->dec_fused && R <= 8 && ENC_NW == 8) {   // the decoder kernel will run: emit its cross-attention K | V operand fragments here
@@ -1523,7 +1525,8 @@ int planning_decoder(Fwd& f) {
     dq.KV = f.enc_KT; dq.img = c->decw_img; dq.par = c->decw_par; dq.nonfinite = c->nonfinite;
     dq.ds = f.ds;
     if (c->dg.dec_ts) { dq.ts = A_alloc<long long>(c, 1024); tap(c, "dec_ts", (float*)dq.ts, 2048); }      // [0, 128): boundaries of wave 0; [128 + 112 w, ...): arrivals of wave w
-    dq.dbg = c->dg.dec_dbg;
+    dq.dbg = c->dg.dec_dbg | (c->no_skip ? 64 : 0);
+    dq.prob_only = f.need_traj ? 0 : 1;      // no trajectory heads: the policy head and the objectives mask the rows of padded reference lines, nobody else reads them
     c->prof_flops = 4.0 * bs * (R * M) * (2.0 * 128 * (384 + 128) * 2 + 2.0 * 128 * 128 * 2 + 4.0 * 128 * 512 + 4.0 * 128 * (N + R + M));
     // (with the trajectory heads on, the tail behind the decoder is longer and the caller's queue carries the prediction head too: measured
     // worth it up to twice the batch -- 128 scenes 0.419 -> 0.391 ms, 256 scenes 0.707 -> 0.713)
@@ -1706,6 +1709,7 @@ static void read_switches(RiftCtx* c) {
   env_flag("RIFT_PE_LIVE", &c->pe_live);                  // 0: pass B over all rounds instead of the live ones of pass A's counts
   env_flag("RIFT_PE_PACK", &c->pe_pack);                  // 0: reference lines of pass B in two-line rounds instead of packed valid-prefix tiles
   env_flag("RIFT_RANK_IN_PREP", &c->rank_in_prep);        // 0: the ranking as its own launch behind the preparation (nat_rank_kernel)
+  env_flag("RIFT_NO_SKIP", &c->no_skip);                  // 1: compute, then discard (dropped encoder branches, padded reference lines of the decoder)
   env_flag("RIFT_ENC112", &c->enc112);                    // 0: scenes of 97 .. 112 token slots on enc_w_kernel
   env_flag("RIFT_RANK_FAULT", &c->rank_fault);            // 1 (diagnostic): the first scene block of the in-launch ranking never publishes
   env_int("RIFT_SIDE_GATE", &c->side_gate);               // 1: both front chains behind the caller's queue (fwd_plan.h)

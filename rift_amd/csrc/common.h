@@ -153,10 +153,9 @@ __device__ __forceinline__ float uniform01(uint32_t seed, uint32_t stream, uint3
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 // erf-form GELU (nn.GELU default) for the bf16 paths: erf(z) = z P(z^2) / Q(z^2) with z clamped to +-3.3 (a (3,3) rational minimax
 // fit, |erf error| <= 2.9e-6, |gelu error| <= 7.2e-6 measured over [-10, 10] -- two orders below the bf16 rounding the result gets
-// as an MFMA operand).  One transcendental (v_rcp_f32); every other step is a mul / fma that packs two elements per instruction
-// (v_pk_mul_f32 / v_pk_fma_f32) in gelu_fast2: 39 cycles per element against 49 for the rcp + exp2 Abramowitz-Stegun 7.1.25 form
-// and 2.6e-5 error (tools/ubench/gelu_rate.hip).  The LDS-resident encoder / NAT kernels are VALU-bound exactly in these epilogues.
-// fp32 mode keeps erff (gelu_erf).
+// as an MFMA operand).  One transcendental (v_rcp_f32); every other step is a mul / fma: 39 cycles per element against 49 for the
+// rcp + exp2 Abramowitz-Stegun 7.1.25 form and 2.6e-5 error (tools/ubench/gelu_rate.hip).  The layer-wise GEMM epilogue (gemm.h) uses it;
+// the fused kernels evaluate GELU in packed fp16 (gelu_pk16x2 below).  fp32 mode keeps erff (gelu_erf).
 #define RIFT_GELU_P0 1.12838531f
 #define RIFT_GELU_P1 0.153424003f
 #define RIFT_GELU_P2 0.0432474986f
@@ -172,18 +171,6 @@ __device__ __forceinline__ float gelu_fast(float x) {
   const float e = z * pn * __builtin_amdgcn_rcpf(qd);
   const float hx = 0.5f * x;
   return fmaf(hx, e, hx);
-}
-__device__ __forceinline__ f32x2_t gelu_fast2(f32x2_t x) {
-  typedef f32x2_t V;
-  V z = x * 0.70710678118654752440f;
-  z.x = __builtin_amdgcn_fmed3f(z.x, -3.3f, 3.3f); z.y = __builtin_amdgcn_fmed3f(z.y, -3.3f, 3.3f);
-  const V t = z * z;
-  const V pn = __builtin_elementwise_fma(t, __builtin_elementwise_fma(t, __builtin_elementwise_fma(t, (V)RIFT_GELU_P3, (V)RIFT_GELU_P2), (V)RIFT_GELU_P1), (V)RIFT_GELU_P0);
-  const V qd = __builtin_elementwise_fma(t, __builtin_elementwise_fma(t, __builtin_elementwise_fma(t, (V)RIFT_GELU_Q3, (V)RIFT_GELU_Q2), (V)RIFT_GELU_Q1), (V)1.0f);
-  V r; r.x = __builtin_amdgcn_rcpf(qd.x); r.y = __builtin_amdgcn_rcpf(qd.y);
-  const V e = z * pn * r;
-  const V hx = x * 0.5f;
-  return __builtin_elementwise_fma(hx, e, hx);
 }
 
 // fp32 += dot of two packed operand pairs (v_dot2c_f32_bf16 / v_dot2c_f32_f16): a 2-element q.k step without unpacking either operand
@@ -255,65 +242,25 @@ __device__ __forceinline__ void gelu_pk16x2(float x0, float x1, float x2, float 
   g0 = ra - pa; g1 = rb - pb;
 }
 
-// ---- MLP hidden-layer operands (opfmt.h: fp16 words whenever GELU is evaluated in packed fp16) ----
+// ---- MLP hidden-layer operands (opfmt.h: fp16 words in both builds) ----
 __device__ __forceinline__ f32x4 mfma_hid(h16x8 a, h16x8 b, f32x4 c) {
-#if RIFT_GELU_PK16
   typedef _Float16 v8 __attribute__((ext_vector_type(8)));
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(v8, a), __builtin_bit_cast(v8, b), c, 0, 0, 0);
-#else
-  return mfma_h(a, b, c, 0, 0, 0);
-#endif
 }
 // fp32 -> hidden-layer operand word (weight packers: the fc2 fragments)
 __device__ __forceinline__ unsigned short f2h_hid(float f) {
-#if RIFT_GELU_PK16
   unsigned int r;
   asm("v_cvt_pk_f16_f32 %0, %1, %2\n\ts_nop 0" : "=v"(r) : "v"(f), "v"(0.f));
   return (unsigned short)(r & 0xffffu);
-#else
-  return f2h(f);
-#endif
 }
-// fc1 accumulator -> hidden-layer operand words (4 consecutive hidden channels of one row).  Packed-fp16 build: the bias was the
-// accumulator's initial value (hid_init) and the words are fp16; otherwise the arithmetic of rounds 2 - 4, bit for bit (zero initial value,
-// bias added here): the fp16-operand build's results do not move with this round's change.
-__device__ __forceinline__ f32x4 hid_init(const float4 b) {
-#if RIFT_GELU_PK16
-  return (f32x4){b.x, b.y, b.z, b.w};
-#else
-  return (f32x4){0.f, 0.f, 0.f, 0.f};
-#endif
-}
-__device__ __forceinline__ uint2 gelu4_pack(const f32x4 a, const float4 b);
-__device__ __forceinline__ uint2 gelu4_hid(const f32x4 a, const float4 b) {
-#if RIFT_GELU_PK16
+// fc1 accumulator -> hidden-layer operand words (4 consecutive hidden channels of one row): the bias is the accumulator's initial
+// value (hid_init), the words are fp16.
+__device__ __forceinline__ f32x4 hid_init(const float4 b) { return (f32x4){b.x, b.y, b.z, b.w}; }
+__device__ __forceinline__ uint2 gelu4_hid(const f32x4 a) {
   gelu_h2 g0, g1;
   gelu_pk16x2(a[0], a[1], a[2], a[3], g0, g1);
   uint2 u; u.x = __builtin_bit_cast(unsigned int, g0); u.y = __builtin_bit_cast(unsigned int, g1);
   return u;
-#else
-  return gelu4_pack(a, b);
-#endif
-}
-
-// bias + GELU + operand pack of one MFMA accumulator fragment (4 consecutive output columns)
-__device__ __forceinline__ uint2 gelu4_pack(const f32x4 a, const float4 b) {
-#if !RIFT_GELU_PK16
-  f32x2_t lo, hi, bl, bh;
-  lo.x = a[0]; lo.y = a[1]; hi.x = a[2]; hi.y = a[3];
-  bl.x = b.x; bl.y = b.y; bh.x = b.z; bh.y = b.w;
-  lo = gelu_fast2(lo + bl); hi = gelu_fast2(hi + bh);
-  return pack_h4(lo.x, lo.y, hi.x, hi.y);
-#else
-  gelu_h2 g0, g1;
-  gelu_pk16x2(a[0] + b.x, a[1] + b.y, a[2] + b.z, a[3] + b.w, g0, g1);
-#if RIFT_OP_F16
-  uint2 u; u.x = __builtin_bit_cast(unsigned int, g0); u.y = __builtin_bit_cast(unsigned int, g1);      // (the result words ARE the build's operand format)
-  return u;
-#else
-  return pack_h4((float)g0[0], (float)g0[1], (float)g1[0], (float)g1[1]);
-#endif
-#endif
 }
 
 // Workgroup barrier for phases that hand data over through LDS only.  __syncthreads() makes hipcc drain EVERY outstanding memory
@@ -355,19 +302,14 @@ __device__ __forceinline__ float xmax32(float v) {
   return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
 }
 __device__ __forceinline__ float rows_sum(float v) { return xadd32(xadd16(v)); }   // over the 4 lanes {l, l^16, l^32, l^48}
-// Guard of the one-pass LayerNorm statistics (opfmt.h: RIFT_LN_FOLD).  var = E[x^2] - mean^2 in fp32 loses log2(1 + mean^2 / var) of its 24
+// Guard of the one-pass LayerNorm statistics (nat_l0w.h: l0w_layer_norm).  var = E[x^2] - mean^2 in fp32 loses log2(1 + mean^2 / var) of its 24
 // bits: nothing on the rows this model produces (|mean| of the order of the spread), but a row whose mean dwarfs its spread -- a
 // checkpoint with an outlier channel offset -- would get a variance of noise where torch's two-pass form is exact.  m2 = mean^2,
 // var1 = E[x^2] - m2: true (wave-uniform) when some row of the wave has lost more than 12 bits (|mean| > 64 sigma, or var1 <= 0 beside
 // a non-zero mean: at least 12 of fp32's 24 bits are left otherwise, one more than an fp16 operand keeps); the caller then takes the
 // variance of that LayerNorm from the centred values instead.  Two instructions and a scalar branch per row tile on the fast path.
-#ifdef RIFT_LN_NO_GUARD      // (diagnostic build define: the unguarded one-pass form of round 5, for A/B runs)
-__device__ __forceinline__ bool ln_row_cancels(float, float) { return false; }
-__device__ __forceinline__ bool ln_cancels(float, float) { return false; }
-#else
 __device__ __forceinline__ bool ln_row_cancels(float m2, float var1) { return m2 > 4096.0f * var1; }      // (per lane row; the caller ORs over its row tiles and ballots once)
 __device__ __forceinline__ bool ln_cancels(float m2, float var1) { return __builtin_amdgcn_ballot_w64(m2 > 4096.0f * var1) != 0ull; }
-#endif
 __device__ __forceinline__ float rows_max(float v) { return xmax32(xmax16(v)); }
 __device__ __forceinline__ float sum32(float v) { v = sum16(v); return xadd16(v); }
 // sum over groups of LPR consecutive lanes (LPR = 8, 16, 32, 64), result in every lane of the group

@@ -26,7 +26,7 @@ namespace RIFT_NS {
 #define DECW_LAYER_FRAGS (DECW_WGROUPS * 32)
 #define DECW_KV_FRAGS 48                        // per (scene, layer): heads {0,1}: 12 K + 12 V^T fragments | heads {2,3}: likewise
 // fp32 parameter block of a layer: region E (r2r + m2m) and region L (cross attention + FFN), resident in LDS on their own schedules
-#define DECW_E_LN1 0                            // g 128 | b 128
+#define DECW_E_LN1 0                            // g 128 | b 128  (the LN1 .. LN4 slots are no longer read -- dec_w.hip: layer_norm; they keep their place: every offset behind them stays)
 #define DECW_E_BR2R 256                         // q (pre-scaled by head_dim^-0.5 log2 e) 128 | k 128 | v 128
 #define DECW_E_BR2RO 640
 #define DECW_E_LN2 768
@@ -62,7 +62,7 @@ struct DecWSrc {
 struct DecWP {
   float* Q;                     // (bs*R*12, 128) fp32 decoder queries, updated in place
   const uint8_t* kpm;           // (bs*N) encoder key padding
-  int compact;                  // 1: the K | V^T fragments come from an encoder that compacted its rows (enc_fused.h, RIFT_ENC_COMPACT): kpm is that kernel's
+  int compact;                  // 1: the K | V^T fragments come from an encoder that compacted its rows (enc_fused.h): kpm is that kernel's
                                 // kpm_c (bs, 96) -- a scene's valid keys are a PREFIX, so the sixth key tile exists exactly when key 80 is valid
   const uint8_t* r_kpm;         // (bs*R) reference-line padding
   const uint8_t* q_kpm;         // (q_bs*R) padding rows the r2r quirk indexes (see DecFusedP)

@@ -17,7 +17,7 @@ __global__ void pack_decw_kernel(DecWSrc s, unsigned short* __restrict__ img, fl
     const int ch = l0w_chan(l4, j, 2 * ks), o = nt * 16 + l15;
     const DecWSrc::L& L = s.l[li];
     float v;
-    auto lg = [&](int n) { return RIFT_LN_FOLD ? L.ln[2 * n][ch] : 1.0f; };       // gamma of norm n + 1 folded into the GEMM it feeds (opfmt.h: RIFT_LN_FOLD)
+    auto lg = [&](int n) { return L.ln[2 * n][ch]; };       // gamma of norm n + 1 folded into the GEMM it feeds (layer_norm below)
     if (g < 3) v = L.r2r_w[(g * 128 + o) * 128 + ch] * (g == 0 ? SC : 1.0f) * lg(0);
     else if (g == 3) v = L.r2ro_w[o * 128 + ch];
     else if (g < 7) v = L.m2m_w[((g - 4) * 128 + o) * 128 + ch] * (g == 4 ? SC : 1.0f) * lg(1);
@@ -34,8 +34,8 @@ __global__ void pack_decw_kernel(DecWSrc s, unsigned short* __restrict__ img, fl
     const int li = e / DECW_PAR_LAYER, o = e % DECW_PAR_LAYER;
     const DecWSrc::L& L = s.l[li];
     float v = 0.f;
-    // (RIFT_LN_FOLD) beta of norm n + 1 through the rows of W into the bias: b + W beta
-    auto wb = [&](const float* Wm, int row, int n) { float a = 0.f; if (RIFT_LN_FOLD) for (int k = 0; k < 128; ++k) a += Wm[(size_t)row * 128 + k] * L.ln[2 * n + 1][k]; return a; };
+    // beta of norm n + 1 through the rows of W into the bias: b + W beta
+    auto wb = [&](const float* Wm, int row, int n) { float a = 0.f; for (int k = 0; k < 128; ++k) a += Wm[(size_t)row * 128 + k] * L.ln[2 * n + 1][k]; return a; };
     if (o < DECW_E_N) {
       if (o < 256) v = L.ln[o >> 7][o & 127];
       else if (o < 640) v = (L.r2r_b[o - 256] + wb(L.r2r_w, o - 256, 0)) * (o - 256 < 128 ? SC : 1.0f);
@@ -93,11 +93,7 @@ __device__ __forceinline__ uint32_t decw_jump(uint32_t x, uint32_t c) {
   return (x & 0xffffffu) * AN + decw_jump_add(NSTEP, c);      // (c is a literal at the call sites: the sum folds)
 }
 typedef short decw_s16x2 __attribute__((ext_vector_type(2)));
-#if RIFT_ATTN_K16
-typedef h16x4 DecwVf;            // V^T of a 16-key tile: a K = 16 operand (opfmt.h: RIFT_ATTN_K16)
-#else
-typedef h16x8 DecwVf;
-#endif
+typedef h16x4 DecwVf;            // V^T of a 16-key tile: a K = 16 operand (common.h: mfma_h16)
 // a word of two uniforms -> 0xffff where the half is KEPT (tm1 = the pair (tau - 1, tau - 1))
 __device__ __forceinline__ uint32_t decw_keep2(uint32_t w, uint32_t tm1) {
   const decw_s16x2 d = __builtin_elementwise_sub_sat(__builtin_bit_cast(decw_s16x2, tm1), __builtin_bit_cast(decw_s16x2, w));
@@ -292,45 +288,27 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   };
   auto publish = [&]() { if (DENSE) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); };     // after the last write_xs of a tiling, before its barrier
   auto acquire = [&]() { if (DENSE) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); };     // after that barrier, before the first read_xs
-  // res -> xb (bf16 operands of the four k-steps); g: gamma 128 | beta 128 in LDS.  Two-pass statistics as torch; vector (packed fp32) math.
-  auto layer_norm = [&](const f32x4 (&res)[8], h16x8 (&xb)[4], const float* g) {
+  // res -> xb (16-bit operands of the four k-steps).  No affine part: gamma / beta live in the consuming GEMM's weights and bias
+  // (pack_decw_kernel); one-pass statistics (nat_l0w.h: l0w_layer_norm); vector (packed fp32) math.
+  auto layer_norm = [&](const f32x4 (&res)[8], h16x8 (&xb)[4]) {
     f32x4 s4 = (res[0] + res[1]) + (res[2] + res[3]);
     s4 += (res[4] + res[5]) + (res[6] + res[7]);
     const float mean = rows_sum((s4[0] + s4[1]) + (s4[2] + s4[3])) * (1.0f / 128.0f);
-    if (RIFT_LN_FOLD && true) {     // (opfmt.h: gamma / beta live in the consuming GEMM's weights and bias; one-pass statistics)
-      f32x4 q4 = res[0] * res[0];
+    f32x4 q4 = res[0] * res[0];
 #pragma unroll
-      for (int nt = 1; nt < 8; ++nt) q4 += res[nt] * res[nt];
-      const float ex2 = rows_sum((q4[0] + q4[1]) + (q4[2] + q4[3])) * (1.0f / 128.0f);
-      const float m2 = mean * mean;
-      float var = ex2 - m2;
-      if (__builtin_expect(ln_cancels(m2, var), 0)) {      // (common.h: a row whose mean dwarfs its spread -- the centred form, as torch)
-        f32x4 d4 = {0.f, 0.f, 0.f, 0.f};
+    for (int nt = 1; nt < 8; ++nt) q4 += res[nt] * res[nt];
+    const float ex2 = rows_sum((q4[0] + q4[1]) + (q4[2] + q4[3])) * (1.0f / 128.0f);
+    const float m2 = mean * mean;
+    float var = ex2 - m2;
+    if (__builtin_expect(ln_cancels(m2, var), 0)) {      // (common.h: a row whose mean dwarfs its spread -- the centred form, as torch)
+      f32x4 d4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int nt = 0; nt < 8; ++nt) { const f32x4 d = res[nt] - mean; d4 += d * d; }
-        var = rows_sum((d4[0] + d4[1]) + (d4[2] + d4[3])) * (1.0f / 128.0f);
-      }
-      const float r = rsqrtf(fmaxf(var, 0.f) + 1e-5f), c = -mean * r;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) xb[ks] = l0w_pack8(res[2 * ks] * r + c, res[2 * ks + 1] * r + c);
-      return;
+      for (int nt = 0; nt < 8; ++nt) { const f32x4 d = res[nt] - mean; d4 += d * d; }
+      var = rows_sum((d4[0] + d4[1]) + (d4[2] + d4[3])) * (1.0f / 128.0f);
     }
-    f32x4 d[8];
-    f32x4 q4 = Z;
+    const float r = rsqrtf(fmaxf(var, 0.f) + 1e-5f), c = -mean * r;
 #pragma unroll
-    for (int nt = 0; nt < 8; ++nt) { d[nt] = res[nt] - mean; q4 += d[nt] * d[nt]; }
-    const float r = rsqrtf(rows_sum((q4[0] + q4[1]) + (q4[2] + q4[3])) * (1.0f / 128.0f) + 1e-5f);
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      f32x4 y[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int nt = 2 * ks + u;
-        const float4 gg = *reinterpret_cast<const float4*>(g + nt * 16 + l4 * 4), bb = *reinterpret_cast<const float4*>(g + 128 + nt * 16 + l4 * 4);
-        y[u] = d[nt] * ((f32x4){gg.x, gg.y, gg.z, gg.w} * r) + (f32x4){bb.x, bb.y, bb.z, bb.w};
-      }
-      xb[ks] = l0w_pack8(y[0], y[1]);
-    }
+    for (int ks = 0; ks < 4; ++ks) xb[ks] = l0w_pack8(res[2 * ks] * r + c, res[2 * ks + 1] * r + c);
   };
   // 16 rows x K=128 -> 128 output channels against the 32 fragments of a ring slot (swapped operands: lane = 4 channels of its row)
   auto gemm = [&](int slot, const h16x8 (&x)[4], f32x4 (&acc)[8]) {
@@ -349,11 +327,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     decw_gemm<true>((uint32_t)(uintptr_t)ring + (uint32_t)slot * 32768u + voff, xb, acc);
 #pragma unroll
     for (int nt = 0; nt < 8; ++nt) {
-#if RIFT_ATTN_K16
       vf[nt] = __builtin_bit_cast(h16x4, pack_h4(acc[nt][0], acc[nt][1], acc[nt][2], acc[nt][3]));
-#else
-      vf[nt] = l0w_from_u2(pack_h4(acc[nt][0], acc[nt][1], acc[nt][2], acc[nt][3]), make_uint2(0u, 0u));   // k slots 4..7 unused
-#endif
     }
   };
   // one step of stream i: a word of two 16-bit uniforms
@@ -396,15 +370,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const float lsum = rows_sum((ev[0] + ev[1]) + (ev[2] + ev[3]));
       uint2 pw = pack_h4(ev[0], ev[1], ev[2], ev[3]);
       if (DROP) { pw.x &= keep2(2 * (h & 1)); pw.y &= keep2(2 * (h & 1) + 1); }      // dropped weights are zero words; 1/(1-p) rides on 1/sum
-#if RIFT_ATTN_K16
       const h16x4 pf = __builtin_bit_cast(h16x4, pw);
       const f32x4 o0 = mfma_h16(vf[2 * h], pf, Z);
       const f32x4 o1 = mfma_h16(vf[2 * h + 1], pf, Z);
-#else
-      const h16x8 pf = l0w_from_u2(pw, make_uint2(0u, 0u));
-      const f32x4 o0 = mfma_h(vf[2 * h], pf, Z, 0, 0, 0);
-      const f32x4 o1 = mfma_h(vf[2 * h + 1], pf, Z, 0, 0, 0);
-#endif
       const float inv = __builtin_amdgcn_rcpf(lsum) * (DROP ? dpk : 1.0f);
       ao[h] = l0w_pack8(o0 * inv, o1 * inv);
     }
@@ -525,7 +493,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         bnd(li, pa + 0);                                        // ---- r2r q
         if (ra == 0) acquire();
         read_xs(res, a_row, a_ok);
-        layer_norm(res, xb, parE + DECW_E_LN1);
+        layer_norm(res, xb);
         init8(acc, parE + DECW_E_BR2R); gemm(0, xb, acc);
         to_heads(acc, qf);
         init8(acc, parE + DECW_E_BR2R + 128);                   // (bias rows are requested ahead of the barrier that hides their latency)
@@ -584,7 +552,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           zero8(res);
         } else {
           read_xs(res, b_row, b_ok);
-          layer_norm(res, xb, parE + DECW_E_LN2);
+          layer_norm(res, xb);
           init8(acc, parE + DECW_E_PB + (b_ok ? l15 : 0) * DECW_PBS); gemm(0, xb, acc);
           to_heads(acc, qf);
           init8(acc, parE + DECW_E_PB + (b_ok ? l15 : 0) * DECW_PBS + 128);
@@ -602,7 +570,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           residual(res, acc, dpk);
           if (rz[tileB]) zero8(res);
         }
-        layer_norm(res, xb, parL + DECW_L_LN3);
+        layer_norm(res, xb);
         init8(acc, parL + DECW_L_BCQ);
         bnd(li, pb + 4);                                        // ---- cross q
         gemm(0, xb, acc);
@@ -620,7 +588,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         gemm(KO & 1, ao, acc);
         DSITE(5);
         residual(res, acc, dpk);
-        layer_norm(res, xb, parL + DECW_L_LN4);
+        layer_norm(res, xb);
         DSITE(6);
         f32x4 acc2[8];
         init8(acc2, parL + DECW_L_BF2);

@@ -48,7 +48,7 @@ struct EncFusedP {
                                 // keys >= N undefined, masked by the decoder)
   const unsigned short* wx0;    // cat_x_proj columns 128:256 (planning_decoder.py:177-179), applied to the scene's ego token (row 0)
   float* x0p;                   // (bs, 128)
-  uint8_t* kpm_c;               // (RIFT_ENC_COMPACT) out, (bs, 96): the key padding of the COMPACTED rows (row i padded <=> i >= the scene's valid count) --
+  uint8_t* kpm_c;               // out, (bs, 96): the key padding of the COMPACTED rows (row i padded <=> i >= the scene's valid count) --
                                 // what the decoder's cross attention masks with when it reads this kernel's K | V^T fragments
   DropStats ds;                 // diagnostic build only (dropstats.h)
 };
@@ -94,7 +94,7 @@ __device__ __forceinline__ void e_load_b(EFrags<KS, NTW>& B, const unsigned shor
 // -> epilogues are 8/16-byte row-contiguous LDS accesses (2 v_cvt_pk + 1 ds_write_b64 per tile) instead of four
 // scattered 2-byte stores.  NSWAP trailing n-tiles (j >= NTW - NSWAP... see call sites) may keep the plain order:
 //   plain: acc[r] = out[row = mt*16 + 4*(lane>>4) + r][col = ntile*16 + (lane&15)]   (4 consecutive ROWS: transposed stores)
-// HID: A rows and weight fragments are hidden-layer operand words (opfmt.h: fp16 in the packed-fp16-GELU build)
+// HID: A rows and weight fragments are hidden-layer operand words (opfmt.h: fp16 in both builds)
 template <int MT, int KS, int NTW, int NPLAIN = 0, bool HID = false>
 __device__ __forceinline__ void e_mma(f32x4 (&acc)[MT][NTW], const unsigned short* A, int lda, const EFrags<KS, NTW>& B,
                                       int l15, int l4, int mtn = MT) {      // mtn (workgroup-uniform): row tiles that hold a valid row; the rest are skipped
@@ -193,13 +193,12 @@ __device__ __forceinline__ void enc_fused_body(const EncFusedP& p, const bool ok
   EFrags<2, NTC> Bo;     // (AO_HALF) out_proj, the K = 64 half of the current chunk's two heads
   e_load_b(Bqkv, p.blk[0].wqkv, C, 0, 0, wave, l15, l4, EWaves<NW>(), 12);
 
-  // ---- (RIFT_ENC_COMPACT) the scene's valid tokens first: srow[i] = the token slot LDS row i holds (valid slots in ascending order, then the
+  // ---- the scene's valid tokens first: srow[i] = the token slot LDS row i holds (valid slots in ascending order, then the
   // padded ones), nv = the valid count, mtn = the row (= key) tiles that hold a valid row: every loop over row tiles below stops there.
   // Slot 0 is the ego token, whose row the tail's cat_x_proj half reads as row 0: a scene whose slot 0 is padded (none in practice: the
-  // CBV itself) keeps the slot order (nv = -1).
+  // CBV itself) keeps the slot order (nv = -1).  (Another key order = another fp32 summation order: not bit-identical to the slot order.)
   unsigned char* srow = reinterpret_cast<unsigned char*>(par + RIFT_ENC_NPAR);        // [ROWS <= 128], lives to the end of the kernel (the output rows go back to their slots)
   int nv = -1;
-#if RIFT_ENC_COMPACT
   if (tid < ROWS) {
     const int rk = __builtin_popcountll(vmask & ((1ull << lane) - 1ull)) + (wave == 1 ? c0 : 0);      // valid slots before slot tid
     const int row = keep_order ? tid : ok ? rk : (tid < N ? nvv + (tid - rk) : tid);                 // (rows at or beyond N hold no slot: loaded as zeros)
@@ -207,19 +206,12 @@ __device__ __forceinline__ void enc_fused_body(const EncFusedP& p, const bool ok
   }
   lds_barrier();
   if (!keep_order) nv = nvv;
-#else
-  if (tid < ROWS) srow[tid] = (unsigned char)tid;      // slot order (read behind the barrier below)
-#endif
   auto slot_padded = [&](int i) { return (i >= N) || p.kpm[grow0 + (i < N ? i : 0)]; };
   for (int i = tid; i < ROWS * 32; i += NTH) {
     const int r = i >> 5, c4 = (i & 31) * 4;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (r < N) {
-#if RIFT_ENC_COMPACT
       const int sl = srow[r];
-#else
-      const int sl = r;
-#endif
       v = *reinterpret_cast<const float4*>(p.X + (grow0 + sl) * C + c4);
     }
     *reinterpret_cast<float4*>(xs + r * XS + c4) = v;
@@ -442,7 +434,7 @@ __device__ __forceinline__ void enc_fused_body(const EncFusedP& p, const bool ok
             for (int mt = 0; mt < MT; ++mt)
               if (mt < mtn)
                 *reinterpret_cast<uint2*>(cb + (mt * 16 + l15) * CB + col) =
-                    gelu4_hid(acc[mt][j], b4[j]);       // hidden-layer operand words (fc2's weight image matches: w.w2 = the `hid` image)
+                    gelu4_hid(acc[mt][j]);       // hidden-layer operand words (fc2's weight image matches: w.w2 = the `hid` image)
           }
         }
         if (hc + 1 < 4) e_load_b(Bw, w.w1, C, (hc + 1) * 128, 0, wave, l15, l4, EWaves<NW>());
@@ -588,11 +580,10 @@ __device__ __forceinline__ void enc_fused_body(const EncFusedP& p, const bool ok
 }
 
 // 97 .. 112 token slots per scene (round 6): the same body on the 112-row layout (EncLay<112>), compacting -- 5, 6 or 7 row tiles by the
-// scene's valid-token count; K | V^T for the decoder's eight-key-tile variant (dense per-head image), kpm_c is (bs, 112).  Builds that keep
-// the slot order (RIFT_ENC_COMPACT = 0) run all seven tiles: a valid token may sit in any of them.
+// scene's valid-token count; K | V^T for the decoder's eight-key-tile variant (dense per-head image), kpm_c is (bs, 112).  A scene that
+// keeps the slot order (padded ego slot) runs all seven tiles: a valid token may sit in any of them.
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void enc_fused112_kernel(EncFusedP p) {
-#if RIFT_ENC_COMPACT
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_cnt[];
   int* cnt = reinterpret_cast<int*>(smem_cnt);
   const int tid = threadIdx.x, wave = tid >> 6, N = p.N;
@@ -607,9 +598,6 @@ __global__ __launch_bounds__(64 * NW) void enc_fused112_kernel(EncFusedP p) {
   if (!keep_order && nvv <= 80) enc_fused_body<NW, 5, 112>(p, ok, vmask, c0, nvv, false);
   else if (!keep_order && nvv <= 96) enc_fused_body<NW, 6, 112>(p, ok, vmask, c0, nvv, false);
   else enc_fused_body<NW, 7, 112>(p, ok, vmask, c0, nvv, keep_order);
-#else
-  enc_fused_body<NW, 7, 112>(p, false, 0ull, 0, 0, true);
-#endif
 }
 
 int enc112_set_attributes();                                   // enc112.hip
@@ -617,7 +605,6 @@ void enc112_launch(const EncFusedP& p, hipStream_t stream);
 
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void enc_fused_kernel(EncFusedP p) {
-#if RIFT_ENC_COMPACT
   // the scene's valid-token count first (two ballots and one LDS hand-over), then the body built for its tile count
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_cnt[];
   int* cnt = reinterpret_cast<int*>(smem_cnt);          // (the head of the fp32 row buffer: rewritten by the body's row loads behind its first barrier)
@@ -632,9 +619,6 @@ __global__ __launch_bounds__(64 * NW) void enc_fused_kernel(EncFusedP p) {
   lds_barrier();                                        // (everybody has read the counts before the body's row loads overwrite them)
   if (!keep_order && nvv <= 80) enc_fused_body<NW, 5>(p, ok, vmask, c0, nvv, false);
   else enc_fused_body<NW, 6>(p, ok, vmask, c0, nvv, keep_order);
-#else
-  enc_fused_body<NW, 6>(p, false, 0ull, 0, 0, true);
-#endif
 }
 
 }  // namespace RIFT_NS

@@ -21,7 +21,7 @@ __global__ void pack_encw_kernel(EncWSrc s, unsigned short* __restrict__ img, fl
     const EncWSrc::L& L = s.l[li];
     float v;
     const bool hid = g >= 4 && ((g - 4) & 1);                       // fc2 fragments: hidden-layer operand words (common.h: f2h_hid)
-    const float g1 = RIFT_LN_FOLD ? L.ln1_g[ch] : 1.0f, g2 = RIFT_LN_FOLD ? L.ln2_g[ch] : 1.0f;     // (opfmt.h: gamma of the norm in front folded into the weights)
+    const float g1 = L.ln1_g[ch], g2 = L.ln2_g[ch];                // gamma of the norm in front folded into the weights (layer_norm below)
     if (g == 0) v = L.w_in[(128 + o) * 128 + ch] * g1;             // k
     else if (g == 1) v = L.w_in[(256 + o) * 128 + ch] * g1;        // v
     else if (g == 2) v = L.w_in[o * 128 + ch] * SC * g1;           // q
@@ -37,8 +37,8 @@ __global__ void pack_encw_kernel(EncWSrc s, unsigned short* __restrict__ img, fl
     if (e < ENCW_P_FN) {
       const int li = e / ENCW_P_LAYER, o = e % ENCW_P_LAYER;
       const EncWSrc::L& L = s.l[li];
-      // (RIFT_LN_FOLD) beta of the norm in front through the rows of W into the bias: b + W beta
-      auto wb = [&](const float* Wm, int row, const float* beta) { float a = 0.f; if (RIFT_LN_FOLD) for (int k = 0; k < 128; ++k) a += Wm[(size_t)row * 128 + k] * beta[k]; return a; };
+      // beta of the norm in front through the rows of W into the bias: b + W beta
+      auto wb = [&](const float* Wm, int row, const float* beta) { float a = 0.f; for (int k = 0; k < 128; ++k) a += Wm[(size_t)row * 128 + k] * beta[k]; return a; };
       if (o < 128) v = L.ln1_g[o];
       else if (o < 256) v = L.ln1_b[o - 128];
       else if (o < 384) v = (L.b_in[o - 256] + wb(L.w_in, o - 256, L.ln1_b)) * SC;
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     f32x4 s4 = (res[0] + res[1]) + (res[2] + res[3]);
     s4 += (res[4] + res[5]) + (res[6] + res[7]);
     const float mean = rows_sum((s4[0] + s4[1]) + (s4[2] + s4[3])) * (1.0f / 128.0f);
-    if (RIFT_LN_FOLD && !out) {     // (opfmt.h: gamma / beta live in the consuming GEMM's weights and bias; one-pass statistics.  The final norm keeps its affine part)
+    if (!out) {     // (gamma / beta live in the consuming GEMM's weights and bias; one-pass statistics: nat_l0w.h, l0w_layer_norm.  The final norm keeps its affine part)
       f32x4 q4 = res[0] * res[0];
 #pragma unroll
       for (int nt = 1; nt < 8; ++nt) q4 += res[nt] * res[nt];
@@ -300,11 +300,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           gemm(0, xb, acc);
           h16x8 hb[4];
 #pragma unroll
-          for (int ks = 0; ks < 4; ++ks) {
-            const float4 ba = *reinterpret_cast<const float4*>(pl + ENCW_P_B1 + c * 128 + (2 * ks) * 16 + l4 * 4);
-            const float4 bb = *reinterpret_cast<const float4*>(pl + ENCW_P_B1 + c * 128 + (2 * ks + 1) * 16 + l4 * 4);
-            hb[ks] = l0w_from_u2(gelu4_hid(acc[2 * ks], ba), gelu4_hid(acc[2 * ks + 1], bb));
-          }
+          for (int ks = 0; ks < 4; ++ks) hb[ks] = l0w_from_u2(gelu4_hid(acc[2 * ks]), gelu4_hid(acc[2 * ks + 1]));
           bnd(li, p2 + 7 + 2 * c);
           decw_gemm<false, true>((uint32_t)(uintptr_t)ring + 32768u + voff, hb, acc2);      // fc2: hidden-layer operand words (opfmt.h)
         }

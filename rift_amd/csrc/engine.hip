@@ -494,7 +494,7 @@ struct Fwd {
   // scene_encoder
   float* ENC = nullptr;
   unsigned short* enc_KT = nullptr;   // the decoder's cross-attention K | V^T operand fragments, written by the encoder kernel's tail
-  uint8_t* kpm_c = nullptr;           // (RIFT_ENC_COMPACT) the key padding of the compacted encoder rows (bs, 96): what the decoder masks those fragments with
+  uint8_t* kpm_c = nullptr;           // the key padding of the compacted encoder rows (bs, 96): what the decoder masks those fragments with
   float* enc_x0p = nullptr;           // cat_x_proj's ego-token half, written by the encoder kernel's tail
   bool enc_wide = false;
   // planning_decoder
@@ -1333,11 +1333,7 @@ void scene_encoder(Fwd& f) {
       f.enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * (f.enc_wide ? 96 : DECW_KV_FRAGS) * 512);      // (wide: the dense per-head image, dec_kv.h)
       ep.wkv = (const unsigned short*)c->pw["planning_decoder.kv_all"].bf; ep.bkv = c->pw["planning_decoder.kv_all"].bias;
       ep.KT = f.enc_KT;
-#if RIFT_ENC_COMPACT
       f.kpm_c = A_alloc<uint8_t>(c, (size_t)bs * (f.enc_wide ? 112 : 96)); ep.kpm_c = f.kpm_c;
-#else
-      if (f.enc_wide) { f.kpm_c = A_alloc<uint8_t>(c, (size_t)bs * 112); ep.kpm_c = f.kpm_c; }
-#endif
       f.enc_x0p = A_alloc<float>(c, (size_t)bs * 128);
       ep.wx0 = (const unsigned short*)c->pw["planning_decoder.cat_x_proj.x"].bf; ep.x0p = f.enc_x0p;
       c->prof_flops += 2.0 * bs * N * 128.0 * 1024;

@@ -33,7 +33,7 @@ __global__ void pack_weight_kernel(const float* __restrict__ src, void* dst, int
   if (BF16) reinterpret_cast<unsigned short*>(dst)[fm_index(n, k, Kp)] = f2h(v);   // fragment-major (common.h)
   else reinterpret_cast<float*>(dst)[idx] = v;
 }
-// the fragment-major image of an fc2 weight in hidden-layer operand words (opfmt.h: fp16 in the packed-fp16-GELU build), from the fp32 image
+// the fragment-major image of an fc2 weight in hidden-layer operand words (opfmt.h: fp16 in both builds), from the fp32 image
 __global__ void pack_weight_hid_kernel(const float* __restrict__ f32, unsigned short* __restrict__ dst, int Npad, int Kp) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= Npad * Kp) return;
@@ -75,12 +75,6 @@ __device__ __forceinline__ void agent_feature_body(const float* __restrict__ pos
     if (hist_agent) hist_agent[a] = (any && (a % A) != 0) ? 1 : 0;
   }
 }
-__global__ void agent_feature_kernel(const float* __restrict__ pos, const float* __restrict__ head,
-                                     const float* __restrict__ vel, const float* __restrict__ shp,
-                                     const uint8_t* __restrict__ valid, int nA, int Tfull,
-                                     float* __restrict__ F, uint8_t* __restrict__ valid_agent) {
-  agent_feature_body(pos, head, vel, shp, valid, nA, Tfull, F, valid_agent, blockIdx.x);
-}
 
 // map 10-channel point features (map_encoder.py:43-59) -> F[(b*Mp+m)*20 + p][10]
 __device__ __forceinline__ void map_feature_body(const float* __restrict__ pp, const float* __restrict__ pv,
@@ -102,11 +96,6 @@ __device__ __forceinline__ void map_feature_body(const float* __restrict__ pp, c
   o[6] = P1[0] - P0[0]; o[7] = P1[1] - P0[1];
   o[8] = P2[0] - P0[0]; o[9] = P2[1] - P0[1];
 }
-__global__ void map_feature_kernel(const float* __restrict__ pp, const float* __restrict__ pv,
-                                   const float* __restrict__ po, const float* __restrict__ center,
-                                   int nPoly, float* __restrict__ F) {
-  map_feature_body(pp, pv, po, center, nPoly, F, blockIdx.x);
-}
 
 // reference-line 6-channel features (planning_decoder.py:145-153) -> F[(b*R+r)*120 + p][6]
 __device__ __forceinline__ void ref_feature_body(const float* __restrict__ rp, const float* __restrict__ rv,
@@ -121,10 +110,6 @@ __device__ __forceinline__ void ref_feature_body(const float* __restrict__ rp, c
   o[2] = rv[(size_t)idx * 2]; o[3] = rv[(size_t)idx * 2 + 1];
   const float a = ro[idx];
   o[4] = cosf(a); o[5] = sinf(a);
-}
-__global__ void ref_feature_kernel(const float* __restrict__ rp, const float* __restrict__ rv,
-                                   const float* __restrict__ ro, int nLine, float* __restrict__ F) {
-  ref_feature_body(rp, rv, ro, nLine, F, blockIdx.x);
 }
 
 // Fourier features (fourier_embedding.py:49-50): row r, input dim d -> F[d][r][129] = [cos(2pi f x), sin(..), x]
@@ -520,11 +505,6 @@ __device__ __forceinline__ void token_mask_body(const uint8_t* __restrict__ vali
   } else pad = !static_valid[b * S + (t - A - Mp)];
   kpm[idx] = pad;
 }
-__global__ void token_mask_kernel(const uint8_t* __restrict__ valid_agent, const uint8_t* __restrict__ map_valid,
-                                  const uint8_t* __restrict__ static_valid, int bs, int A, int Mp, int S,
-                                  uint8_t* __restrict__ kpm) {
-  token_mask_body(valid_agent, map_valid, static_valid, bs, A, Mp, S, kpm, blockIdx.x);
-}
 
 // ref-line key padding: r_kpm[b*R + r] = !any(valid[b,r,:120])
 // (r_tiles, optional: the 16-row tiles of the line up to its LAST valid point, 0 .. 8 -- what pe_w_kernel's packed rounds hold of it, pe_fused.h)
@@ -536,9 +516,6 @@ __device__ __forceinline__ void refline_mask_body(const uint8_t* __restrict__ rv
   for (int i = 0; i < 120; ++i) if (rvalid[(size_t)l * 120 + i] != 0) last = i;
   r_kpm[l] = last < 0;
   if (r_tiles) r_tiles[l] = (uint8_t)((last + 16) >> 4);
-}
-__global__ void refline_mask_kernel(const uint8_t* __restrict__ rvalid, int nLine, uint8_t* __restrict__ r_kpm) {
-  refline_mask_body(rvalid, nLine, r_kpm, blockIdx.x);
 }
 
 // token positions for pos_emb: pos[b][tok][3] = (x, y, angle) (pluto_model.py:131-146; wrap applied in fourier kernel)
@@ -561,11 +538,6 @@ __device__ __forceinline__ void token_pos_body(const float* __restrict__ agent_p
     x = st_pos[o * 2]; y = st_pos[o * 2 + 1]; a = st_head[o];
   }
   pos[(size_t)idx * 3] = x; pos[(size_t)idx * 3 + 1] = y; pos[(size_t)idx * 3 + 2] = a;
-}
-__global__ void token_pos_kernel(const float* __restrict__ agent_pos, const float* __restrict__ agent_head, int Tfull,
-                                 const float* __restrict__ center, const float* __restrict__ st_pos,
-                                 const float* __restrict__ st_head, int bs, int A, int Mp, int S, float* __restrict__ pos) {
-  token_pos_body(agent_pos, agent_head, Tfull, center, st_pos, st_head, bs, A, Mp, S, pos, blockIdx.x);
 }
 
 // FPN top-down merge restricted to the positions the last output step depends on
@@ -666,10 +638,6 @@ __device__ __forceinline__ void refline_pos_body(const float* __restrict__ rp, c
   const int l = vblk * (int)blockDim.x + (int)threadIdx.x;
   if (l >= nLine) return;
   pos[l * 3] = rp[(size_t)l * 240]; pos[l * 3 + 1] = rp[(size_t)l * 240 + 1]; pos[l * 3 + 2] = ro[(size_t)l * 120];
-}
-__global__ void refline_pos_kernel(const float* __restrict__ rp, const float* __restrict__ ro, int nLine,
-                                   float* __restrict__ pos) {
-  refline_pos_body(rp, ro, nLine, pos, blockIdx.x);
 }
 
 // gather rows: Y[i] = X[rowidx(i)] with rowidx = (i / per) * stride_rows + off  (token 0 of each scene etc.)

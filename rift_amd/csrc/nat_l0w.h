@@ -5,14 +5,13 @@
 // of a workgroup, with a workgroup barrier between phases.  At C = 32 a phase is 2..6 MFMA n-tiles and 80 x 32 values of VALU work:
 // most waves idle, and the level's ~30 phases per tile are pure barrier latency (137 us for 13.7 GFLOP).  Here one WAVE owns a tile of
 // 4 agents x 20 steps = 80 rows for the whole level and nothing is ever exchanged between waves:
-//   * row (agent a, step t) lives in MFMA row tile mt = t / 4, lane row l15 = 4 a + t % 4 -- the 4 lanes of a DPP quad are 4
-//     consecutive steps of one agent, so the kernel-3 neighbourhood attention reads its neighbours with quad_perm DPP moves (plus the
-//     quad edge from the adjacent row tile's register);
+//   * row (agent a, step t) lives in MFMA row tile mt = t / 4, lane row l15 = 4 a + t % 4 -- a row tile holds 4 consecutive
+//     steps of each of its 4 agents, so every key of the kernel-3 neighbourhood of a query sits in its own or an adjacent row tile;
 //   * the fp32 residual stream is the MFMA C/D layout itself: x[mt][nt] holds, per lane, 4 consecutive channels of one row
 //     (40 VGPRs for 80 x 32).  A GEMM output in that layout IS the next GEMM's B operand: the contraction order is free, so the
 //     weights are packed with the K order "lane l4 holds channels {4 l4 .. +3} of n-tile 0 and of n-tile 1" -- no LDS round trip,
 //     no transposition between LayerNorm -> qkv, attention -> proj, LayerNorm -> fc1 -> GELU -> fc2;
-//   * q, k, v stay fp32 (VALU attention); only MFMA operands are bf16;
+//   * q, k, v and the attention weights are 16-bit MFMA operands (the neighbourhood attention runs on the matrix pipe, see the kernel);
 //   * weights (54 fragments of 1 KiB) and parameters sit in LDS, read as conflict-free 16-byte-per-lane fragment loads; the only other
 //     LDS use is a per-wave bf16 staging tile for the stride-2 downsample conv (rows change lanes there).
 // No workgroup barrier after the prologue.
@@ -27,6 +26,7 @@ namespace RIFT_NS {
 #define L0W_F_TOK 0                       // 2 n-tiles, K = 27 window values (tap-major: tap * 9 + cin)
 #define L0W_F_BLK(b) (2 + 20 * (b))      // + 0..5 qkv (q_h0 q_h1 k_h0 k_h1 v_h0 v_h1; q pre-scaled) | + 6..7 proj | + 8..13 fc1 | + 14 + 2 ks + nt fc2
 #define L0W_F_DS 42                       // + 4 tap + nt: downsample conv, K = 32 channels of one tap (natural order)
+// (the kernel no longer reads the ln1 / ln2 gamma / beta slots -- l0w_layer_norm; they keep their place: every offset behind them stays)
 // parameter block (fp32): b_tok 32 | per block: ln1_g 32, ln1_b 32, bqkv 96 (q part pre-scaled), rpb 16 (2 x 5 used), bproj 32, ln2_g 32, ln2_b 32,
 // b1 96, b2 32 | fn_g 32, fn_b 32 | ds_g 64, ds_b 64
 #define L0W_P_BLK(b) (32 + 400 * (b))
@@ -41,7 +41,7 @@ namespace RIFT_NS {
 #define L0W_PB_B2 368
 #define L0W_P_FN 832
 #define L0W_P_DS 896
-// (RIFT_NAT_MFMA_ATTN) score-accumulator table [block 2][head 2][tile class 3: first / middle / last][row 5: quad lane s of the query, 4 = "another
+// score-accumulator table [block 2][head 2][tile class 3: first / middle / last][row 5: quad lane s of the query, 4 = "another
 // agent's keys"][8: prev tile's key 3 | own tile's keys 0..3 | next tile's key 0 | pad 2] = rpb[h][key step - query step + 2] * log2 e for the
 // keys inside the query's window (start clamp(t - 1, 0, L - 3)), L0W_NEG for every other key
 #define L0W_P_TBL 1024
@@ -53,11 +53,7 @@ namespace RIFT_NS {
 #endif
 #define L0W_LDS (L0W_NFRAG * 1024 + L0W_NPAR * 4 + L0W_NWV * 80 * L0W_ST * 2)
 
-#if RIFT_NAT_MFMA_ATTN
-#define L0W_QSCALE (0.25f * 1.4426950408889634f)
-#else
-#define L0W_QSCALE 0.25f
-#endif
+#define L0W_QSCALE (0.25f * 1.4426950408889634f)      // head_dim^-0.5 x log2 e: the softmax is taken with exp2
 // One entry of the score-accumulator table of the MFMA neighbourhood attention (kernel 3) of a level with L steps in row tiles of 4 steps:
 // query = quad lane `row` of tile mt (row 4: a lane that holds another agent's keys), slot 0 = key 3 of tile mt - 1, 1..4 = keys 0..3 of
 // tile mt, 5 = key 0 of tile mt + 1.  natten's window of step t starts at clamp(t - 1, 0, L - 3); rpb index = key - query + 2.  A query step
@@ -93,7 +89,7 @@ __global__ void pack_l0w_kernel(NatL0WSrc s, unsigned short* __restrict__ img, f
     } else if (f < L0W_F_DS) {
       const int b = (f - 2) / 20, g = (f - 2) % 20;
       const NatL0WSrc::Blk& k = s.blk[b];
-      const float fg1 = RIFT_LN_FOLD ? k.ln1_g[l0w_chan(l4, j, 0)] : 1.0f, fg2 = RIFT_LN_FOLD ? k.ln2_g[l0w_chan(l4, j, 0)] : 1.0f;      // (opfmt.h: RIFT_LN_FOLD)
+      const float fg1 = k.ln1_g[l0w_chan(l4, j, 0)], fg2 = k.ln2_g[l0w_chan(l4, j, 0)];      // gamma of the norm in front folded into the weights (l0w_layer_norm)
       if (g < 6) v = k.wqkv[(g * 16 + l15) * 32 + l0w_chan(l4, j, 0)] * (g < 2 ? L0W_QSCALE : 1.0f) * fg1;  // q scaled by head_dim^-0.5 (x log2 e: MFMA attention)
       else if (g < 8) v = k.wproj[((g - 6) * 16 + l15) * 32 + l0w_chan(l4, j, 0)];
       else if (g < 14) v = k.w1[((g - 8) * 16 + l15) * 32 + l0w_chan(l4, j, 0)] * fg2;
@@ -113,8 +109,8 @@ __global__ void pack_l0w_kernel(NatL0WSrc s, unsigned short* __restrict__ img, f
       if (o < 32) v = k.ln1_g[o];
       else if (o < 64) v = k.ln1_b[o - 32];
       else if (o < 160) {
-        v = k.bqkv[o - 64];
-        if (RIFT_LN_FOLD) for (int ch = 0; ch < 32; ++ch) v += k.wqkv[(o - 64) * 32 + ch] * k.ln1_b[ch];
+        v = k.bqkv[o - 64];              // + W beta: beta of the norm in front through the weights into the bias
+        for (int ch = 0; ch < 32; ++ch) v += k.wqkv[(o - 64) * 32 + ch] * k.ln1_b[ch];
         v *= (o - 64 < 32 ? L0W_QSCALE : 1.0f);
       }
       else if (o < 176) v = (o - 160 < 10) ? k.rpb[o - 160] : 0.f;
@@ -123,7 +119,7 @@ __global__ void pack_l0w_kernel(NatL0WSrc s, unsigned short* __restrict__ img, f
       else if (o < 272) v = k.ln2_b[o - 240];
       else if (o < 368) {
         v = k.b1[o - 272];
-        if (RIFT_LN_FOLD) for (int ch = 0; ch < 32; ++ch) v += k.w1[(o - 272) * 32 + ch] * k.ln2_b[ch];
+        for (int ch = 0; ch < 32; ++ch) v += k.w1[(o - 272) * 32 + ch] * k.ln2_b[ch];
       }
       else v = k.b2[o - 368];
     } else if (e < L0W_P_DS) v = (e - L0W_P_FN < 32) ? s.fn_g[e - L0W_P_FN] : s.fn_b[e - L0W_P_FN - 32];
@@ -157,60 +153,39 @@ void l0w_pack(const NatL0WSrc& src, unsigned short* img, float* par, hipStream_t
 void l0w_launch(const NatL0WP& p, int grid, hipStream_t stream);
 
 #ifdef RIFT_NAT_L01_IMPL      // the kernels live in nat_l01w.hip (their own translation unit, built like nat_l2w.hip: -fno-honor-nans -mno-amdgpu-ieee)
-template <int CTRL>
-__device__ __forceinline__ f32x4 l0w_dpp4(const f32x4 v) {
-  return (f32x4){dpp_f<CTRL>(v[0]), dpp_f<CTRL>(v[1]), dpp_f<CTRL>(v[2]), dpp_f<CTRL>(v[3])};
-}
-__device__ __forceinline__ f32x4 l0w_sel(bool c, const f32x4 a, const f32x4 b) {
-  return (f32x4){c ? a[0] : b[0], c ? a[1] : b[1], c ? a[2] : b[2], c ? a[3] : b[3]};
-}
-
-// LayerNorm over the 32 channels of every row of x (8 per lane, 4 lanes per row) -> bf16 B operands (two-pass statistics, as torch)
-// FOLDED (opfmt.h: RIFT_LN_FOLD): gamma / beta live in the consuming layer's weights; the final / downsample norms keep the affine form
-template <bool FOLDED = false>
-__device__ __forceinline__ void l0w_layer_norm(const f32x4 (&x)[5][2], h16x8 (&xn)[5], const float* g, const float* b, int l4) {
-  if (FOLDED) {
-    // statistics of all five row tiles first, ONE cancellation test for the call (common.h: ln_cancels -- a branch per tile kept the
-    // scheduler from overlapping the tiles' reductions), then the normalisation
-    float mean[5], var[5];
-    bool bad = false;
-#pragma unroll
-    for (int mt = 0; mt < 5; ++mt) {
-      const f32x4 u = x[mt][0], w = x[mt][1];
-      const f32x4 s4 = u + w, q4 = u * u + w * w;
-      mean[mt] = rows_sum((s4[0] + s4[1]) + (s4[2] + s4[3])) * (1.0f / 32.0f);
-      const float ex2 = rows_sum((q4[0] + q4[1]) + (q4[2] + q4[3])) * (1.0f / 32.0f);
-      const float m2 = mean[mt] * mean[mt];
-      var[mt] = ex2 - m2;
-      bad |= ln_row_cancels(m2, var[mt]);
-    }
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(bad) != 0ull, 0)) {      // a row whose mean dwarfs its spread: the centred form, as torch
-#pragma unroll
-      for (int mt = 0; mt < 5; ++mt) {
-        const f32x4 du = x[mt][0] - mean[mt], dw = x[mt][1] - mean[mt], d4 = du * du + dw * dw;
-        var[mt] = rows_sum((d4[0] + d4[1]) + (d4[2] + d4[3])) * (1.0f / 32.0f);
-      }
-    }
-#pragma unroll
-    for (int mt = 0; mt < 5; ++mt) {
-      const float r = rsqrtf(fmaxf(var[mt], 0.f) + 1e-5f), c = -mean[mt] * r;
-      xn[mt] = l0w_pack8(x[mt][0] * r + c, x[mt][1] * r + c);
-    }
-    return;
-  }
-  const float4 g0 = *reinterpret_cast<const float4*>(g + l4 * 4), g1 = *reinterpret_cast<const float4*>(g + 16 + l4 * 4);
-  const float4 b0 = *reinterpret_cast<const float4*>(b + l4 * 4), b1 = *reinterpret_cast<const float4*>(b + 16 + l4 * 4);
+// LayerNorm over the 32 channels of every row of x (8 per lane, 4 lanes per row) -> 16-bit B operands, WITHOUT its affine part: every
+// LayerNorm of the pre-norm blocks feeds linear layers only and its gamma / beta are frozen, W (g n + b) + c = (W diag g) n + (W b + c), so
+// the packer folds gamma into the consuming weight image and beta into its bias (the final / downsample norms keep the affine form).
+// n = x r - mean r with r = rsqrt(E[x^2] - mean^2 + eps): both sums in one pass over the row, ~3.5 issue slots per element where the
+// two-pass form with its affine part took ~5.5, and the two cross-lane reductions do not wait for each other.  E[x^2] - mean^2 in fp32
+// loses log2(1 + mean^2 / var) of 24 bits -- nothing against the 8 / 11 bits the result is rounded to -- and is clamped at 0; rows that
+// lose more than that take the centred form (common.h: ln_row_cancels).
+__device__ __forceinline__ void l0w_layer_norm(const f32x4 (&x)[5][2], h16x8 (&xn)[5]) {
+  // statistics of all five row tiles first, ONE cancellation test for the call (common.h: ln_cancels -- a branch per tile kept the
+  // scheduler from overlapping the tiles' reductions), then the normalisation
+  float mean[5], var[5];
+  bool bad = false;
 #pragma unroll
   for (int mt = 0; mt < 5; ++mt) {
     const f32x4 u = x[mt][0], w = x[mt][1];
-    const float mean = rows_sum(((u[0] + u[1]) + (u[2] + u[3])) + ((w[0] + w[1]) + (w[2] + w[3]))) * (1.0f / 32.0f);
-    const f32x4 du = u - mean, dw = w - mean;
-    const float var = rows_sum(((du[0] * du[0] + du[1] * du[1]) + (du[2] * du[2] + du[3] * du[3])) +
-                               ((dw[0] * dw[0] + dw[1] * dw[1]) + (dw[2] * dw[2] + dw[3] * dw[3]))) * (1.0f / 32.0f);
-    const float r = rsqrtf(var + 1e-5f);
-    const f32x4 yu = {du[0] * r * g0.x + b0.x, du[1] * r * g0.y + b0.y, du[2] * r * g0.z + b0.z, du[3] * r * g0.w + b0.w};
-    const f32x4 yw = {dw[0] * r * g1.x + b1.x, dw[1] * r * g1.y + b1.y, dw[2] * r * g1.z + b1.z, dw[3] * r * g1.w + b1.w};
-    xn[mt] = l0w_pack8(yu, yw);
+    const f32x4 s4 = u + w, q4 = u * u + w * w;
+    mean[mt] = rows_sum((s4[0] + s4[1]) + (s4[2] + s4[3])) * (1.0f / 32.0f);
+    const float ex2 = rows_sum((q4[0] + q4[1]) + (q4[2] + q4[3])) * (1.0f / 32.0f);
+    const float m2 = mean[mt] * mean[mt];
+    var[mt] = ex2 - m2;
+    bad |= ln_row_cancels(m2, var[mt]);
+  }
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(bad) != 0ull, 0)) {      // a row whose mean dwarfs its spread: the centred form, as torch
+#pragma unroll
+    for (int mt = 0; mt < 5; ++mt) {
+      const f32x4 du = x[mt][0] - mean[mt], dw = x[mt][1] - mean[mt], d4 = du * du + dw * dw;
+      var[mt] = rows_sum((d4[0] + d4[1]) + (d4[2] + d4[3])) * (1.0f / 32.0f);
+    }
+  }
+#pragma unroll
+  for (int mt = 0; mt < 5; ++mt) {
+    const float r = rsqrtf(fmaxf(var[mt], 0.f) + 1e-5f), c = -mean[mt] * r;
+    xn[mt] = l0w_pack8(x[mt][0] * r + c, x[mt][1] * r + c);
   }
 }
 
@@ -281,7 +256,7 @@ __global__ __launch_bounds__(64 * L0W_NWV) void nat_l0w_kernel(NatL0WP p) {
       const int fb = L0W_F_BLK(bi);
       h16x8 xn[5];
       // ================= attention half =================
-      l0w_layer_norm<RIFT_LN_FOLD != 0>(x, xn, pb + L0W_PB_LN1G, pb + L0W_PB_LN1B, l4);
+      l0w_layer_norm(x, xn);
       // one head at a time (rolled loop: the live set is the residual, the LayerNorm operands and ONE head's k / v): its proj contribution
       // goes straight into the residual -- proj(concat(o_0, o_1)) = W[:, head 0] o_0 + W[:, head 1] o_1, each as a K = 32 step whose
       // other half is zero
@@ -289,7 +264,6 @@ __global__ __launch_bounds__(64 * L0W_NWV) void nat_l0w_kernel(NatL0WP p) {
       if (p.droppath[bi] > 0.f) dps = (uniform01(p.seed, p.stream + 2 * bi, (uint32_t)seq) < p.droppath[bi]) ? 0.f : 1.0f / (1.0f - p.droppath[bi]);
       if (p.droppath[bi] > 0.f) ds_sample(p.ds, RIFT_DS_NAT(0, bi, 0), seq_ok ? seq : -1, dps);
       const h16x8 wp0 = W(fb + 6), wp1 = W(fb + 7);
-#if RIFT_NAT_MFMA_ATTN
       // 1-D neighbourhood attention (kernel 3, window start clamp(t - 1, 0, L - 3)) on the matrix pipe, K = 16 MFMAs (a head is 16 dims: a
       // projection's C/D fragment IS the operand).  A lane row is (agent a, step 4 mt + s): the score tile S^T = K Q^T of row tile mt against
       // key tile mt' holds, in lane (query l15, l4), the four keys of AGENT l4 in tile mt' -- so every key a query may see sits in the ONE
@@ -298,7 +272,7 @@ __global__ __launch_bounds__(64 * L0W_NWV) void nat_l0w_kernel(NatL0WP p) {
       // out as P = 0, not NaN -- the row maximum is floored at -1e20 and 1 / sum is taken of max(sum, tiny)), so the softmax has no cross-lane
       // step at all; O^T = V^T P^T takes V^T out of a plain-order MFMA (level 2's scheme); DropPath rides on 1 / sum and proj (the head's 16
       // input channels = one half of the K = 32 weight fragment) accumulates straight into the residual.  ~40 VALU instructions per head and row
-      // tile against ~150 of the DPP form below.
+      // tile against ~150 of an fp32 VALU form that fetches the neighbours with quad_perm DPP moves.
       const int trow = (l4 == a) ? s : 4;
 #pragma unroll 1
       for (int h = 0; h < 2; ++h) {
@@ -341,66 +315,6 @@ __global__ __launch_bounds__(64 * L0W_NWV) void nat_l0w_kernel(NatL0WP p) {
           x[mt][1] = mfma_h16(wpb, ao, x[mt][1]);
         }
       }
-#else
-#pragma unroll 1
-      for (int h = 0; h < 2; ++h) {
-        f32x4 k[5], v[5];
-        const h16x8 wq = W(fb + h);
-        const float4 bq = *reinterpret_cast<const float4*>(pb + L0W_PB_BQKV + h * 16 + l4 * 4);
-        {
-          const h16x8 wk = W(fb + 2 + h), wv = W(fb + 4 + h);
-          const float4 bk = *reinterpret_cast<const float4*>(pb + L0W_PB_BQKV + 32 + h * 16 + l4 * 4);
-          const float4 bv = *reinterpret_cast<const float4*>(pb + L0W_PB_BQKV + 64 + h * 16 + l4 * 4);
-#pragma unroll
-          for (int mt = 0; mt < 5; ++mt) {
-            k[mt] = mfma_h(wk, xn[mt], Z, 0, 0, 0) + (f32x4){bk.x, bk.y, bk.z, bk.w};
-            v[mt] = mfma_h(wv, xn[mt], Z, 0, 0, 0) + (f32x4){bv.x, bv.y, bv.z, bv.w};
-          }
-        }
-        // 1-D neighbourhood attention, kernel 3, window start clamp(t - 1, 0, L - 3); keys of step t: (t-1, t, t+1), (0, 1, 2) at t = 0,
-        // (17, 18, 19) at t = 19.  The quad (4 lanes) holds steps 4 mt .. 4 mt + 3 of one agent: neighbours come through quad_perm DPP,
-        // the quad edges from the adjacent row tile's register.  Lane l4 holds 4 of the 16 head dims: partial dots summed over the 4 l4 lanes.
-        const float* rp = pb + L0W_PB_RPB + h * 5;
-#pragma unroll
-        for (int mt = 0; mt < 5; ++mt) {
-          const f32x4 qq = mfma_h(wq, xn[mt], Z, 0, 0, 0) + (f32x4){bq.x, bq.y, bq.z, bq.w};
-          // neighbours at t - 1 and t + 1 (generic case)
-          f32x4 km = l0w_dpp4<0x90>(k[mt]), kp = l0w_dpp4<0xF9>(k[mt]);            // quad_perm [0,0,1,2] / [1,2,3,3]
-          f32x4 vm = l0w_dpp4<0x90>(v[mt]), vp = l0w_dpp4<0xF9>(v[mt]);
-          if (mt > 0) { km = l0w_sel(s == 0, l0w_dpp4<0xFF>(k[mt - 1]), km); vm = l0w_sel(s == 0, l0w_dpp4<0xFF>(v[mt - 1]), vm); }
-          if (mt < 4) { kp = l0w_sel(s == 3, l0w_dpp4<0x00>(k[mt + 1]), kp); vp = l0w_sel(s == 3, l0w_dpp4<0x00>(v[mt + 1]), vp); }
-          f32x4 k0 = km, k1 = k[mt], k2 = kp, v0 = vm, v1 = v[mt], v2 = vp;
-          int shift = 0;                                                          // rpb index of key j: j + 1 + shift
-          if (mt == 0) {        // t = 0 (lane s = 0): keys (0, 1, 2) = (own, +1, +2)
-            const f32x4 kpp = l0w_dpp4<0xFE>(k[0]), vpp = l0w_dpp4<0xFE>(v[0]);   // quad_perm [2,3,3,3]
-            const bool e = s == 0;
-            k0 = l0w_sel(e, k[0], km); k1 = l0w_sel(e, kp, k[0]); k2 = l0w_sel(e, kpp, kp);
-            v0 = l0w_sel(e, v[0], vm); v1 = l0w_sel(e, vp, v[0]); v2 = l0w_sel(e, vpp, vp);
-            shift = e ? 1 : 0;
-          }
-          if (mt == 4) {        // t = 19 (lane s = 3): keys (17, 18, 19) = (-2, -1, own)
-            const f32x4 kmm = l0w_dpp4<0x40>(k[4]), vmm = l0w_dpp4<0x40>(v[4]);   // quad_perm [0,0,0,1]
-            const bool e = s == 3;
-            k0 = l0w_sel(e, kmm, km); k1 = l0w_sel(e, km, k[4]); k2 = l0w_sel(e, k[4], kp);
-            v0 = l0w_sel(e, vmm, vm); v1 = l0w_sel(e, vm, v[4]); v2 = l0w_sel(e, v[4], vp);
-            shift = e ? -1 : 0;
-          }
-          float s0 = (qq[0] * k0[0] + qq[1] * k0[1]) + (qq[2] * k0[2] + qq[3] * k0[3]);
-          float s1 = (qq[0] * k1[0] + qq[1] * k1[1]) + (qq[2] * k1[2] + qq[3] * k1[3]);
-          float s2 = (qq[0] * k2[0] + qq[1] * k2[1]) + (qq[2] * k2[2] + qq[3] * k2[3]);
-          s0 = rows_sum(s0) + rp[1 + shift]; s1 = rows_sum(s1) + rp[2 + shift]; s2 = rows_sum(s2) + rp[3 + shift];
-          const float mx = fmaxf(fmaxf(s0, s1), s2);
-          const float e0 = __expf(s0 - mx), e1 = __expf(s1 - mx), e2 = __expf(s2 - mx);
-          const float inv = __builtin_amdgcn_rcpf((e0 + e1) + e2);
-          const float p0 = e0 * inv, p1 = e1 * inv, p2 = e2 * inv;
-          const f32x4 oh = {p0 * v0[0] + p1 * v1[0] + p2 * v2[0], p0 * v0[1] + p1 * v1[1] + p2 * v2[1],
-                            p0 * v0[2] + p1 * v1[2] + p2 * v2[2], p0 * v0[3] + p1 * v1[3] + p2 * v2[3]};
-          const h16x8 ao = h == 0 ? l0w_pack8(oh, Z) : l0w_pack8(Z, oh);
-          x[mt][0] += mfma_h(wp0, ao, Z, 0, 0, 0) * dps;
-          x[mt][1] += mfma_h(wp1, ao, Z, 0, 0, 0) * dps;
-        }
-      }
-#endif
       {   // proj bias
         const float4 b0 = *reinterpret_cast<const float4*>(pb + L0W_PB_BP + l4 * 4), b1 = *reinterpret_cast<const float4*>(pb + L0W_PB_BP + 16 + l4 * 4);
 #pragma unroll
@@ -410,7 +324,7 @@ __global__ __launch_bounds__(64 * L0W_NWV) void nat_l0w_kernel(NatL0WP p) {
       }
       L0TS();
       // ================= MLP half: fc1 (32 -> 96) -> GELU -> fc2 (96 -> 32), the hidden layer 32 channels (one k-step) at a time =================
-      l0w_layer_norm<RIFT_LN_FOLD != 0>(x, xn, pb + L0W_PB_LN2G, pb + L0W_PB_LN2B, l4);
+      l0w_layer_norm(x, xn);
       {
         f32x4 acc2[5][2];
 #pragma unroll
@@ -424,7 +338,7 @@ __global__ __launch_bounds__(64 * L0W_NWV) void nat_l0w_kernel(NatL0WP p) {
           for (int mt = 0; mt < 5; ++mt) {
             const f32x4 ha = mfma_h(wa, xn[mt], hid_init(ba), 0, 0, 0);      // (packed-fp16 GELU: the bias is the accumulator's initial value)
             const f32x4 hb = mfma_h(wb, xn[mt], hid_init(bb), 0, 0, 0);
-            const h16x8 hop = l0w_from_u2(gelu4_hid(ha, ba), gelu4_hid(hb, bb));
+            const h16x8 hop = l0w_from_u2(gelu4_hid(ha), gelu4_hid(hb));
             acc2[mt][0] = mfma_hid(u0, hop, acc2[mt][0]);
             acc2[mt][1] = mfma_hid(u1, hop, acc2[mt][1]);
           }

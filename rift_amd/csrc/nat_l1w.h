@@ -1,8 +1,8 @@
 // Level 1 of the NAT-FPN history encoder (dim 64, 4 heads, kernel 3, L = 10; embedding.py:93-99,196-202) in the wave-private,
 // register-resident form of nat_l0w.h: one wave owns 4 agents x 10 steps (3 row tiles of 16: row (a, t) -> tile t / 4, lane row
 // 4 a + t % 4; the last two steps' quads are half empty) for both NATLayers, the residual stream is the MFMA C/D layout (48 VGPRs),
-// GEMM outputs chain as the next GEMM's operand through K-permuted weight images, neighbourhood attention reads its neighbours with
-// quad_perm DPP.  The level's weights (80 KiB per NATLayer + 48 KiB for the downsample conv) do not fit LDS together: the 8 waves of a
+// GEMM outputs chain as the next GEMM's operand through K-permuted weight images, neighbourhood attention runs on the matrix
+// pipe.  The level's weights (80 KiB per NATLayer + 48 KiB for the downsample conv) do not fit LDS together: the 8 waves of a
 // workgroup walk their tiles in step and swap the weight image between the layers (three swaps = six barriers per 32 agents, against
 // ~30 barriers per 8 agents in nat_level_kernel).
 #pragma once
@@ -20,6 +20,7 @@ namespace RIFT_NS {
 #define L1W_DS_FRAGS 48         // downsample conv: (tap, k-step of 32 channels, n-tile 0..7)
 #define L1W_F_DS(tap, ks, nt) (((tap) * 2 + (ks)) * 8 + (nt))
 #define L1W_NFRAG (2 * L1W_BLK_FRAGS + L1W_DS_FRAGS)
+// (the kernel no longer reads the ln1 / ln2 gamma / beta slots -- l1w_layer_norm; they keep their place: every offset behind them stays)
 // parameters (fp32): per block 800: ln1_g 64, ln1_b 64, bqkv 192 (q pre-scaled), rpb 32 (4 x 5 used), bproj 64, ln2_g 64, ln2_b 64, b1 192, b2 64 |
 // fn_g 64, fn_b 64 | ds_g 128, ds_b 128
 #define L1W_P_BLK(b) (800 * (b))
@@ -34,7 +35,7 @@ namespace RIFT_NS {
 #define L1W_PB_B2 736
 #define L1W_P_FN 1600
 #define L1W_P_DS 1728
-// (RIFT_NAT_MFMA_ATTN) score-accumulator table [block 2][head 4][row tile 3][row 5][8] (nat_l0w.h: nat_band_entry; tile 2 holds steps 8, 9 and two
+// score-accumulator table [block 2][head 4][row tile 3][row 5][8] (nat_l0w.h: nat_band_entry; tile 2 holds steps 8, 9 and two
 // rows beyond the sequence per agent, which see themselves only)
 #define L1W_P_TBL 2048
 #define L1W_NPAR (2048 + 2 * 4 * 3 * 5 * 8)
@@ -60,9 +61,9 @@ __global__ void pack_l1w_kernel(NatL1WSrc s, unsigned short* __restrict__ img, f
     if (f < 2 * L1W_BLK_FRAGS) {
       const int b = f / L1W_BLK_FRAGS, g = f % L1W_BLK_FRAGS;
       const NatL1WSrc::Blk& k = s.blk[b];
-      if (g < 24) { const int nt = g >> 1, ks = g & 1, ch = l0w_chan(l4, j, 2 * ks); v = k.wqkv[(nt * 16 + l15) * 64 + ch] * (nt < 4 ? L0W_QSCALE : 1.0f) * (RIFT_LN_FOLD ? k.ln1_g[ch] : 1.0f); }
+      if (g < 24) { const int nt = g >> 1, ks = g & 1, ch = l0w_chan(l4, j, 2 * ks); v = k.wqkv[(nt * 16 + l15) * 64 + ch] * (nt < 4 ? L0W_QSCALE : 1.0f) * k.ln1_g[ch]; }      // (gamma of the norm in front folded into the weights: nat_l0w.h, l0w_layer_norm)
       else if (g < 32) { const int nt = (g - 24) >> 1, ks = (g - 24) & 1; v = k.wproj[(nt * 16 + l15) * 64 + l0w_chan(l4, j, 2 * ks)]; }
-      else if (g < 56) { const int nt = (g - 32) >> 1, ks = (g - 32) & 1, ch = l0w_chan(l4, j, 2 * ks); v = k.w1[(nt * 16 + l15) * 64 + ch] * (RIFT_LN_FOLD ? k.ln2_g[ch] : 1.0f); }
+      else if (g < 56) { const int nt = (g - 32) >> 1, ks = (g - 32) & 1, ch = l0w_chan(l4, j, 2 * ks); v = k.w1[(nt * 16 + l15) * 64 + ch] * k.ln2_g[ch]; }
       else { const int ks = (g - 56) >> 2, nt = (g - 56) & 3; v = k.w2[(nt * 16 + l15) * 192 + l0w_chan(l4, j, 2 * ks)]; hid = true; }
     } else {
       const int g = f - 2 * L1W_BLK_FRAGS, nt = g & 7, ks = (g >> 3) & 1, tap = g >> 4;
@@ -77,9 +78,9 @@ __global__ void pack_l1w_kernel(NatL1WSrc s, unsigned short* __restrict__ img, f
       const NatL1WSrc::Blk& k = s.blk[b];
       if (o < 64) v = k.ln1_g[o];
       else if (o < 128) v = k.ln1_b[o - 64];
-      else if (o < 320) {             // (opfmt.h: RIFT_LN_FOLD -- beta through the weights into the bias)
+      else if (o < 320) {             // (beta of the norm in front through the weights into the bias)
         v = k.bqkv[o - 128];
-        if (RIFT_LN_FOLD) for (int ch = 0; ch < 64; ++ch) v += k.wqkv[(o - 128) * 64 + ch] * k.ln1_b[ch];
+        for (int ch = 0; ch < 64; ++ch) v += k.wqkv[(o - 128) * 64 + ch] * k.ln1_b[ch];
         v *= (o - 128 < 64 ? L0W_QSCALE : 1.0f);
       }
       else if (o < 352) v = (o - 320 < 20) ? k.rpb[o - 320] : 0.f;
@@ -88,7 +89,7 @@ __global__ void pack_l1w_kernel(NatL1WSrc s, unsigned short* __restrict__ img, f
       else if (o < 544) v = k.ln2_b[o - 480];
       else if (o < 736) {
         v = k.b1[o - 544];
-        if (RIFT_LN_FOLD) for (int ch = 0; ch < 64; ++ch) v += k.w1[(o - 544) * 64 + ch] * k.ln2_b[ch];
+        for (int ch = 0; ch < 64; ++ch) v += k.w1[(o - 544) * 64 + ch] * k.ln2_b[ch];
       }
       else v = k.b2[o - 736];
     } else if (e < L1W_P_DS) v = (e - L1W_P_FN < 64) ? s.fn_g[e - L1W_P_FN] : s.fn_b[e - L1W_P_FN - 64];
@@ -119,62 +120,35 @@ void l1w_pack(const NatL1WSrc& src, unsigned short* img, float* par, hipStream_t
 void l1w_launch(const NatL1WP& p, int grid, hipStream_t stream);
 
 #ifdef RIFT_NAT_L01_IMPL      // the kernels live in nat_l01w.hip
-template <bool FOLDED = false>      // (nat_l0w.h: l0w_layer_norm)
-__device__ __forceinline__ void l1w_layer_norm(const f32x4 (&x)[3][4], h16x8 (&xn)[3][2], const float* g, const float* b, int l4) {
-  if (FOLDED) {
-    // statistics of the three row tiles first, ONE cancellation test for the call (nat_l0w.h: l0w_layer_norm), then the normalisation
-    float mean[3], var[3];
-    bool bad = false;
-#pragma unroll
-    for (int mt = 0; mt < 3; ++mt) {
-      const f32x4 s4 = (x[mt][0] + x[mt][1]) + (x[mt][2] + x[mt][3]);
-      const f32x4 q4 = (x[mt][0] * x[mt][0] + x[mt][1] * x[mt][1]) + (x[mt][2] * x[mt][2] + x[mt][3] * x[mt][3]);
-      mean[mt] = rows_sum((s4[0] + s4[1]) + (s4[2] + s4[3])) * (1.0f / 64.0f);
-      const float ex2 = rows_sum((q4[0] + q4[1]) + (q4[2] + q4[3])) * (1.0f / 64.0f);
-      const float m2 = mean[mt] * mean[mt];
-      var[mt] = ex2 - m2;
-      bad |= ln_row_cancels(m2, var[mt]);
-    }
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(bad) != 0ull, 0)) {      // a row whose mean dwarfs its spread: the centred form, as torch
-#pragma unroll
-      for (int mt = 0; mt < 3; ++mt) {
-        f32x4 d4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) { const f32x4 d = x[mt][nt] - mean[mt]; d4 += d * d; }
-        var[mt] = rows_sum((d4[0] + d4[1]) + (d4[2] + d4[3])) * (1.0f / 64.0f);
-      }
-    }
-#pragma unroll
-    for (int mt = 0; mt < 3; ++mt) {
-      const float r = rsqrtf(fmaxf(var[mt], 0.f) + 1e-5f), c = -mean[mt] * r;
-      xn[mt][0] = l0w_pack8(x[mt][0] * r + c, x[mt][1] * r + c);
-      xn[mt][1] = l0w_pack8(x[mt][2] * r + c, x[mt][3] * r + c);
-    }
-    return;
-  }
-  float4 gg[4], bb[4];
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) { gg[nt] = *reinterpret_cast<const float4*>(g + nt * 16 + l4 * 4); bb[nt] = *reinterpret_cast<const float4*>(b + nt * 16 + l4 * 4); }
+// (nat_l0w.h: l0w_layer_norm -- no affine part, one-pass statistics)
+__device__ __forceinline__ void l1w_layer_norm(const f32x4 (&x)[3][4], h16x8 (&xn)[3][2]) {
+  // statistics of the three row tiles first, ONE cancellation test for the call (nat_l0w.h: l0w_layer_norm), then the normalisation
+  float mean[3], var[3];
+  bool bad = false;
 #pragma unroll
   for (int mt = 0; mt < 3; ++mt) {
-    float sm = 0.f;
+    const f32x4 s4 = (x[mt][0] + x[mt][1]) + (x[mt][2] + x[mt][3]);
+    const f32x4 q4 = (x[mt][0] * x[mt][0] + x[mt][1] * x[mt][1]) + (x[mt][2] * x[mt][2] + x[mt][3] * x[mt][3]);
+    mean[mt] = rows_sum((s4[0] + s4[1]) + (s4[2] + s4[3])) * (1.0f / 64.0f);
+    const float ex2 = rows_sum((q4[0] + q4[1]) + (q4[2] + q4[3])) * (1.0f / 64.0f);
+    const float m2 = mean[mt] * mean[mt];
+    var[mt] = ex2 - m2;
+    bad |= ln_row_cancels(m2, var[mt]);
+  }
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(bad) != 0ull, 0)) {      // a row whose mean dwarfs its spread: the centred form, as torch
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) sm += (x[mt][nt][0] + x[mt][nt][1]) + (x[mt][nt][2] + x[mt][nt][3]);
-    const float mean = rows_sum(sm) * (1.0f / 64.0f);
-    f32x4 d[4];
-    float qs = 0.f;
+    for (int mt = 0; mt < 3; ++mt) {
+      f32x4 d4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      d[nt] = x[mt][nt] - mean;
-      qs += (d[nt][0] * d[nt][0] + d[nt][1] * d[nt][1]) + (d[nt][2] * d[nt][2] + d[nt][3] * d[nt][3]);
+      for (int nt = 0; nt < 4; ++nt) { const f32x4 d = x[mt][nt] - mean[mt]; d4 += d * d; }
+      var[mt] = rows_sum((d4[0] + d4[1]) + (d4[2] + d4[3])) * (1.0f / 64.0f);
     }
-    const float r = rsqrtf(rows_sum(qs) * (1.0f / 64.0f) + 1e-5f);
-    f32x4 y[4];
+  }
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-      y[nt] = (f32x4){d[nt][0] * r * gg[nt].x + bb[nt].x, d[nt][1] * r * gg[nt].y + bb[nt].y, d[nt][2] * r * gg[nt].z + bb[nt].z, d[nt][3] * r * gg[nt].w + bb[nt].w};
-    xn[mt][0] = l0w_pack8(y[0], y[1]);
-    xn[mt][1] = l0w_pack8(y[2], y[3]);
+  for (int mt = 0; mt < 3; ++mt) {
+    const float r = rsqrtf(fmaxf(var[mt], 0.f) + 1e-5f), c = -mean[mt] * r;
+    xn[mt][0] = l0w_pack8(x[mt][0] * r + c, x[mt][1] * r + c);
+    xn[mt][1] = l0w_pack8(x[mt][2] * r + c, x[mt][3] * r + c);
   }
 }
 
@@ -225,11 +199,10 @@ __global__ __launch_bounds__(64 * L1W_NWV) void nat_l1w_kernel(NatL1WP p) {
       const float* pb = par + L1W_P_BLK(bi);
       h16x8 xn[3][2];
       // ================= attention half =================
-      l1w_layer_norm<RIFT_LN_FOLD != 0>(x, xn, pb + L1W_PB_LN1G, pb + L1W_PB_LN1B, l4);
+      l1w_layer_norm(x, xn);
       float dps = 1.f;
       if (p.droppath[bi] > 0.f) dps = (uniform01(p.seed, p.stream + 2 * bi, (uint32_t)seq) < p.droppath[bi]) ? 0.f : 1.0f / (1.0f - p.droppath[bi]);
       if (p.droppath[bi] > 0.f) ds_sample(p.ds, RIFT_DS_NAT(1, bi, 0), seq_ok ? seq : -1, dps);
-#if RIFT_NAT_MFMA_ATTN
       // neighbourhood attention on the matrix pipe (nat_l0w.h describes the scheme): 4 heads x 3 row tiles, K = 16 MFMAs
       const int trow = (l4 == a) ? s : 4;
 #pragma unroll 1
@@ -278,70 +251,6 @@ __global__ __launch_bounds__(64 * L1W_NWV) void nat_l1w_kernel(NatL1WP p) {
           for (int nt = 0; nt < 4; ++nt) x[mt][nt] = mfma_h16(wp[nt], ao, x[mt][nt]);
         }
       }
-#else
-#pragma unroll 1
-      for (int h = 0; h < 4; ++h) {
-        f32x4 k[3], v[3];
-        {
-          const h16x8 wk0 = W(L1W_F_QKV(4 + h, 0)), wk1 = W(L1W_F_QKV(4 + h, 1)), wv0 = W(L1W_F_QKV(8 + h, 0)), wv1 = W(L1W_F_QKV(8 + h, 1));
-          const float4 bk = *reinterpret_cast<const float4*>(pb + L1W_PB_BQKV + 64 + h * 16 + l4 * 4);
-          const float4 bv = *reinterpret_cast<const float4*>(pb + L1W_PB_BQKV + 128 + h * 16 + l4 * 4);
-#pragma unroll
-          for (int mt = 0; mt < 3; ++mt) {
-            k[mt] = mfma_h(wk0, xn[mt][0], Z, 0, 0, 0);
-            k[mt] = mfma_h(wk1, xn[mt][1], k[mt], 0, 0, 0) + (f32x4){bk.x, bk.y, bk.z, bk.w};
-            v[mt] = mfma_h(wv0, xn[mt][0], Z, 0, 0, 0);
-            v[mt] = mfma_h(wv1, xn[mt][1], v[mt], 0, 0, 0) + (f32x4){bv.x, bv.y, bv.z, bv.w};
-          }
-        }
-        const h16x8 wq0 = W(L1W_F_QKV(h, 0)), wq1 = W(L1W_F_QKV(h, 1));
-        const float4 bq = *reinterpret_cast<const float4*>(pb + L1W_PB_BQKV + h * 16 + l4 * 4);
-        const int pks = h >> 1;                                    // proj k-step that holds this head's 16 channels (its lower / upper half)
-        h16x8 wp[4];
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) wp[nt] = W(L1W_F_PROJ(nt, pks));
-        const float* rp = pb + L1W_PB_RPB + h * 5;
-        // neighbourhood attention, kernel 3: keys of step t are (t-1, t, t+1), (0, 1, 2) at t = 0, (7, 8, 9) at t = 9 = (tile 2, quad lane 1)
-#pragma unroll
-        for (int mt = 0; mt < 3; ++mt) {
-          f32x4 qq = mfma_h(wq0, xn[mt][0], Z, 0, 0, 0);
-          qq = mfma_h(wq1, xn[mt][1], qq, 0, 0, 0) + (f32x4){bq.x, bq.y, bq.z, bq.w};
-          f32x4 km = l0w_dpp4<0x90>(k[mt]), kp = l0w_dpp4<0xF9>(k[mt]);
-          f32x4 vm = l0w_dpp4<0x90>(v[mt]), vp = l0w_dpp4<0xF9>(v[mt]);
-          if (mt > 0) { km = l0w_sel(s == 0, l0w_dpp4<0xFF>(k[mt - 1]), km); vm = l0w_sel(s == 0, l0w_dpp4<0xFF>(v[mt - 1]), vm); }
-          if (mt < 2) { kp = l0w_sel(s == 3, l0w_dpp4<0x00>(k[mt + 1]), kp); vp = l0w_sel(s == 3, l0w_dpp4<0x00>(v[mt + 1]), vp); }
-          f32x4 k0 = km, k1 = k[mt], k2 = kp, v0 = vm, v1 = v[mt], v2 = vp;
-          int shift = 0;
-          if (mt == 0) {        // t = 0: keys (own, +1, +2)
-            const f32x4 kpp = l0w_dpp4<0xFE>(k[0]), vpp = l0w_dpp4<0xFE>(v[0]);
-            const bool e = s == 0;
-            k0 = l0w_sel(e, k[0], km); k1 = l0w_sel(e, kp, k[0]); k2 = l0w_sel(e, kpp, kp);
-            v0 = l0w_sel(e, v[0], vm); v1 = l0w_sel(e, vp, v[0]); v2 = l0w_sel(e, vpp, vp);
-            shift = e ? 1 : 0;
-          }
-          if (mt == 2) {        // t = 9 (quad lane 1): keys (7, 8, 9) = (previous tile's lane 3, this quad's lane 0, own)
-            const f32x4 k7 = l0w_dpp4<0xFF>(k[1]), v7 = l0w_dpp4<0xFF>(v[1]);
-            const bool e = s == 1;
-            k0 = l0w_sel(e, k7, km); k1 = l0w_sel(e, km, k[2]); k2 = l0w_sel(e, k[2], kp);
-            v0 = l0w_sel(e, v7, vm); v1 = l0w_sel(e, vm, v[2]); v2 = l0w_sel(e, v[2], vp);
-            shift = e ? -1 : 0;
-          }
-          float s0 = (qq[0] * k0[0] + qq[1] * k0[1]) + (qq[2] * k0[2] + qq[3] * k0[3]);
-          float s1 = (qq[0] * k1[0] + qq[1] * k1[1]) + (qq[2] * k1[2] + qq[3] * k1[3]);
-          float s2 = (qq[0] * k2[0] + qq[1] * k2[1]) + (qq[2] * k2[2] + qq[3] * k2[3]);
-          s0 = rows_sum(s0) + rp[1 + shift]; s1 = rows_sum(s1) + rp[2 + shift]; s2 = rows_sum(s2) + rp[3 + shift];
-          const float mx = fmaxf(fmaxf(s0, s1), s2);
-          const float e0 = __expf(s0 - mx), e1 = __expf(s1 - mx), e2 = __expf(s2 - mx);
-          const float inv = __builtin_amdgcn_rcpf((e0 + e1) + e2);
-          const float p0 = e0 * inv, p1 = e1 * inv, p2 = e2 * inv;
-          const f32x4 oh = {p0 * v0[0] + p1 * v1[0] + p2 * v2[0], p0 * v0[1] + p1 * v1[1] + p2 * v2[1],
-                            p0 * v0[2] + p1 * v1[2] + p2 * v2[2], p0 * v0[3] + p1 * v1[3] + p2 * v2[3]};
-          const h16x8 ao = (h & 1) ? l0w_pack8(Z, oh) : l0w_pack8(oh, Z);
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt) x[mt][nt] += mfma_h(wp[nt], ao, Z, 0, 0, 0) * dps;
-        }
-      }
-#endif
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) {
         const float4 b4 = *reinterpret_cast<const float4*>(pb + L1W_PB_BP + nt * 16 + l4 * 4);
@@ -349,7 +258,7 @@ __global__ __launch_bounds__(64 * L1W_NWV) void nat_l1w_kernel(NatL1WP p) {
         for (int mt = 0; mt < 3; ++mt) x[mt][nt] += (f32x4){b4.x, b4.y, b4.z, b4.w} * dps;
       }
       // ================= MLP half: fc1 (64 -> 192) -> GELU -> fc2 (192 -> 64), 32 hidden channels (one fc2 k-step) at a time =================
-      l1w_layer_norm<RIFT_LN_FOLD != 0>(x, xn, pb + L1W_PB_LN2G, pb + L1W_PB_LN2B, l4);
+      l1w_layer_norm(x, xn);
       {
         f32x4 acc2[3][4];
 #pragma unroll
@@ -370,7 +279,7 @@ __global__ __launch_bounds__(64 * L1W_NWV) void nat_l1w_kernel(NatL1WP p) {
             ha = mfma_h(wa1, xn[mt][1], ha, 0, 0, 0);
             f32x4 hb = mfma_h(wb0, xn[mt][0], hid_init(bb), 0, 0, 0);
             hb = mfma_h(wb1, xn[mt][1], hb, 0, 0, 0);
-            const h16x8 hop = l0w_from_u2(gelu4_hid(ha, ba), gelu4_hid(hb, bb));
+            const h16x8 hop = l0w_from_u2(gelu4_hid(ha), gelu4_hid(hb));
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) acc2[mt][nt] = mfma_hid(u[nt], hop, acc2[mt][nt]);
           }

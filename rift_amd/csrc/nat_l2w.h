@@ -15,6 +15,7 @@ namespace RIFT_NS {
 #define L2W_GROUPS 10                           // per NATLayer: q | k | v | proj | (fc1 chunk c, fc2 k-range c) x 3
 #define L2W_BLK_FRAGS (L2W_GROUPS * 32)
 // fp32 parameters in LDS: per block 1664: ln1 g,b 256 | bqkv 384 (q pre-scaled) | rpb 8 x 9 (x log2 e) padded to 128 | bproj 128 | ln2 g,b 256 | b1 384 | b2 128
+// (the kernel no longer reads the ln1 / ln2 slots -- its LayerNorm has no affine part; they keep their place: every offset behind them stays)
 #define L2W_P_BLK(b) (1664 * (b))
 #define L2W_PB_LN1 0
 #define L2W_PB_BQKV 256

@@ -17,11 +17,11 @@ __global__ void pack_l2w_kernel(NatL2WSrc s, unsigned short* __restrict__ img, f
     const NatL2WSrc::Blk& k = s.blk[bi];
     float v;
     const bool hid = g >= 4 && ((g - 4) & 1);      // fc2 fragments: hidden-layer operand words (common.h: f2h_hid)
-    if (g < 3) v = k.wqkv[(g * 128 + o) * 128 + ch] * (g == 0 ? SC : 1.0f) * (RIFT_LN_FOLD ? k.ln1_g[ch] : 1.0f);
+    if (g < 3) v = k.wqkv[(g * 128 + o) * 128 + ch] * (g == 0 ? SC : 1.0f) * k.ln1_g[ch];      // (gamma of the norm in front folded into the weights: layer_norm below)
     else if (g == 3) v = k.wproj[o * 128 + ch];
     else {
       const int c = (g - 4) >> 1;
-      v = ((g - 4) & 1) ? k.w2[o * 384 + c * 128 + ch] : k.w1[(c * 128 + o) * 128 + ch] * (RIFT_LN_FOLD ? k.ln2_g[ch] : 1.0f);
+      v = ((g - 4) & 1) ? k.w2[o * 384 + c * 128 + ch] : k.w1[(c * 128 + o) * 128 + ch] * k.ln2_g[ch];
     }
     img[e] = hid ? f2h_hid(v) : f2h(v);
   }
@@ -32,9 +32,9 @@ __global__ void pack_l2w_kernel(NatL2WSrc s, unsigned short* __restrict__ img, f
       const NatL2WSrc::Blk& k = s.blk[bi];
       if (o < 128) v = k.ln1_g[o];
       else if (o < 256) v = k.ln1_b[o - 128];
-      else if (o < 640) {             // (opfmt.h: RIFT_LN_FOLD -- beta through the weights into the bias)
+      else if (o < 640) {             // (beta of the norm in front through the weights into the bias)
         v = k.bqkv[o - 256];
-        if (RIFT_LN_FOLD) for (int ch = 0; ch < 128; ++ch) v += k.wqkv[(o - 256) * 128 + ch] * k.ln1_b[ch];
+        for (int ch = 0; ch < 128; ++ch) v += k.wqkv[(o - 256) * 128 + ch] * k.ln1_b[ch];
         v *= (o - 256 < 128 ? SC : 1.0f);
       }
       else if (o < 768) {             // [head 8][16]: rpb[h][0..8] x log2 e, then -inf (slot 9 = "a key of another agent": the lanes read it unconditionally)
@@ -46,7 +46,7 @@ __global__ void pack_l2w_kernel(NatL2WSrc s, unsigned short* __restrict__ img, f
       else if (o < 1152) v = k.ln2_b[o - 1024];
       else if (o < 1536) {
         v = k.b1[o - 1152];
-        if (RIFT_LN_FOLD) for (int ch = 0; ch < 128; ++ch) v += k.w1[(o - 1152) * 128 + ch] * k.ln2_b[ch];
+        for (int ch = 0; ch < 128; ++ch) v += k.w1[(o - 1152) * 128 + ch] * k.ln2_b[ch];
       }
       else v = k.b2[o - 1536];
     } else if (e < L2W_P_FN + 256) v = (e - L2W_P_FN < 128) ? s.fn_g[e - L2W_P_FN] : s.fn_b[e - L2W_P_FN - 128];
@@ -76,11 +76,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // at 32 scenes; waves without a tile only keep the operand stream's protocol.  Same tiles, same arithmetic: bit-identical either way.
   const int ntiles = (sq_n + 2) / 3;
   const int G = (int)gridDim.x, nrounds = (ntiles + 7) >> 3;
-#ifdef RIFT_L2_TILE_MAJOR      // (diagnostic build define: tile-major whatever the size)
-  const bool wave_major = false;
-#else
   const bool wave_major = ntiles <= 4 * G;      // (at most one wave per SIMD; between 4 G and 8 G tiles -- 64 scenes -- wave-major measured slower: 0.195 against 0.185 ms per step)
-#endif
   const int full = wave_major ? 0 : ((int)blockIdx.x < nrounds ? (nrounds - 1 - (int)blockIdx.x) / G + 1 : 0);
   const int trem = wave_major ? ntiles : 0;
   const int my_rounds = full + ((int)blockIdx.x < trem ? 1 : 0);
@@ -115,44 +111,26 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
     for (int nt = 0; nt < 8; ++nt) { const float4 v = *reinterpret_cast<const float4*>(bias + nt * 16 + l4 * 4); a[nt] = (f32x4){v.x, v.y, v.z, v.w}; }
   };
-  auto layer_norm = [&](const f32x4 (&res)[8], h16x8 (&xb)[4], const float* g) {
+  // LayerNorm without its affine part (gamma / beta live in the consuming GEMM's weights and bias), one-pass statistics (nat_l0w.h: l0w_layer_norm)
+  auto layer_norm = [&](const f32x4 (&res)[8], h16x8 (&xb)[4]) {
     f32x4 s4 = (res[0] + res[1]) + (res[2] + res[3]);
     s4 += (res[4] + res[5]) + (res[6] + res[7]);
     const float mean = rows_sum((s4[0] + s4[1]) + (s4[2] + s4[3])) * (1.0f / 128.0f);
-    if (RIFT_LN_FOLD && true) {     // (opfmt.h: gamma / beta live in the consuming GEMM's weights and bias; one-pass statistics)
-      f32x4 q4 = res[0] * res[0];
+    f32x4 q4 = res[0] * res[0];
 #pragma unroll
-      for (int nt = 1; nt < 8; ++nt) q4 += res[nt] * res[nt];
-      const float ex2 = rows_sum((q4[0] + q4[1]) + (q4[2] + q4[3])) * (1.0f / 128.0f);
-      const float m2 = mean * mean;
-      float var = ex2 - m2;
-      if (__builtin_expect(ln_cancels(m2, var), 0)) {      // (common.h: a row whose mean dwarfs its spread -- the centred form, as torch)
-        f32x4 d4 = {0.f, 0.f, 0.f, 0.f};
+    for (int nt = 1; nt < 8; ++nt) q4 += res[nt] * res[nt];
+    const float ex2 = rows_sum((q4[0] + q4[1]) + (q4[2] + q4[3])) * (1.0f / 128.0f);
+    const float m2 = mean * mean;
+    float var = ex2 - m2;
+    if (__builtin_expect(ln_cancels(m2, var), 0)) {      // (common.h: a row whose mean dwarfs its spread -- the centred form, as torch)
+      f32x4 d4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int nt = 0; nt < 8; ++nt) { const f32x4 d = res[nt] - mean; d4 += d * d; }
-        var = rows_sum((d4[0] + d4[1]) + (d4[2] + d4[3])) * (1.0f / 128.0f);
-      }
-      const float r = rsqrtf(fmaxf(var, 0.f) + 1e-5f), c = -mean * r;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) xb[ks] = l0w_pack8(res[2 * ks] * r + c, res[2 * ks + 1] * r + c);
-      return;
+      for (int nt = 0; nt < 8; ++nt) { const f32x4 d = res[nt] - mean; d4 += d * d; }
+      var = rows_sum((d4[0] + d4[1]) + (d4[2] + d4[3])) * (1.0f / 128.0f);
     }
-    f32x4 d[8];
-    f32x4 q4 = Z;
+    const float r = rsqrtf(fmaxf(var, 0.f) + 1e-5f), c = -mean * r;
 #pragma unroll
-    for (int nt = 0; nt < 8; ++nt) { d[nt] = res[nt] - mean; q4 += d[nt] * d[nt]; }
-    const float r = rsqrtf(rows_sum((q4[0] + q4[1]) + (q4[2] + q4[3])) * (1.0f / 128.0f) + 1e-5f);
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      f32x4 y[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int nt = 2 * ks + u;
-        const float4 gg = *reinterpret_cast<const float4*>(g + nt * 16 + l4 * 4), bb = *reinterpret_cast<const float4*>(g + 128 + nt * 16 + l4 * 4);
-        y[u] = d[nt] * ((f32x4){gg.x, gg.y, gg.z, gg.w} * r) + (f32x4){bb.x, bb.y, bb.z, bb.w};
-      }
-      xb[ks] = l0w_pack8(y[0], y[1]);
-    }
+    for (int ks = 0; ks < 4; ++ks) xb[ks] = l0w_pack8(res[2 * ks] * r + c, res[2 * ks + 1] * r + c);
   };
 
   int s = 0;                                             // sequence number of the next group to open
@@ -196,11 +174,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const float* pb = par + L2W_P_BLK(bi);
       f32x4 acc[8];
       h16x8 xb[4], qf[4], kp[4], ao[4];
-#if RIFT_ATTN_K16
       h16x4 vf[8];
-#else
-      h16x8 vf[8];
-#endif
       float dps = 1.f, dp2 = 1.f;
       if (p.droppath[bi] > 0.f) {
         dps = (uniform01(p.seed, p.stream + 2 * bi, (uint32_t)seq) < p.droppath[bi]) ? 0.f : 1.0f / (1.0f - p.droppath[bi]);
@@ -209,7 +183,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         ds_sample(p.ds, RIFT_DS_NAT(2, bi, 1), row_ok ? seq : -1, dp2);
       }
       // ---- group 0: q
-      layer_norm(res, xb, pb + L2W_PB_LN1);
+      layer_norm(res, xb);
       init8(acc, pb + L2W_PB_BQKV);
       boundary(s); gemm(slot_off(s), xb, acc); ++s;
 #pragma unroll
@@ -227,11 +201,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         boundary(s); decw_gemm<true>((uint32_t)(uintptr_t)ring + slot_off(s) + voff, xb, av); ++s;
 #pragma unroll
         for (int nt = 0; nt < 8; ++nt) {
-#if RIFT_ATTN_K16
           vf[nt] = __builtin_bit_cast(h16x4, pack_h4(av[nt][0], av[nt][1], av[nt][2], av[nt][3]));
-#else
-          vf[nt] = l0w_from_u2(pack_h4(av[nt][0], av[nt][1], av[nt][2], av[nt][3]), make_uint2(0u, 0u));
-#endif
         }
       }
 #pragma unroll
@@ -243,24 +213,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           f32x4 mb;
 #pragma unroll
           for (int i = 0; i < 4; ++i) mb[i] = pb[L2W_PB_RPB + h * 16 + ridx[i]];      // (a select here became four exec-masked loads per head)
-#if RIFT_ATTN_K16
           // head h's 16 dims are one half of the projection's fragment: a K = 16 operand as it is
           const f32x4 sc = mfma_h16(u == 0 ? h16x4_lo(kp[j]) : h16x4_hi(kp[j]), u == 0 ? h16x4_lo(qf[j]) : h16x4_hi(qf[j]), mb);
-#else
-          // head h's 16 dims are one half of the k-step: the other half of the K operand is zero
-          h16x8 kh = kp[j];
-          if (u == 0) { kh[4] = 0; kh[5] = 0; kh[6] = 0; kh[7] = 0; } else { kh[0] = 0; kh[1] = 0; kh[2] = 0; kh[3] = 0; }
-          const f32x4 sc = mfma_h(kh, qf[j], mb, 0, 0, 0);
-#endif
           const float m = rows_max(fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3])));
           const f32x4 ev = {__builtin_amdgcn_exp2f(sc[0] - m), __builtin_amdgcn_exp2f(sc[1] - m), __builtin_amdgcn_exp2f(sc[2] - m), __builtin_amdgcn_exp2f(sc[3] - m)};
           const float inv = __builtin_amdgcn_rcpf(rows_sum((ev[0] + ev[1]) + (ev[2] + ev[3])));
-#if RIFT_ATTN_K16
           o[u] = mfma_h16(vf[h], __builtin_bit_cast(h16x4, pack_h4(ev[0], ev[1], ev[2], ev[3])), Z) * inv;
-#else
-          const h16x8 pf = l0w_from_u2(pack_h4(ev[0], ev[1], ev[2], ev[3]), make_uint2(0u, 0u));
-          o[u] = mfma_h(vf[h], pf, Z, 0, 0, 0) * inv;
-#endif
         }
         ao[j] = l0w_pack8(o[0], o[1]);
       }
@@ -270,7 +228,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
       for (int nt = 0; nt < 8; ++nt) res[nt] += acc[nt] * dps;
       // ---- groups 4..9: fc1 chunk -> GELU -> fc2 partial
-      layer_norm(res, xb, pb + L2W_PB_LN2);
+      layer_norm(res, xb);
       f32x4 acc2[8];
       init8(acc2, pb + L2W_PB_B2);
 #pragma unroll 1
@@ -281,11 +239,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         gemm(slot_off(s), xb, acc); ++s;
         h16x8 hb[4];
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          const float4 ba = *reinterpret_cast<const float4*>(pb + L2W_PB_B1 + c * 128 + (2 * ks) * 16 + l4 * 4);
-          const float4 bb = *reinterpret_cast<const float4*>(pb + L2W_PB_B1 + c * 128 + (2 * ks + 1) * 16 + l4 * 4);
-          hb[ks] = l0w_from_u2(gelu4_hid(acc[2 * ks], ba), gelu4_hid(acc[2 * ks + 1], bb));
-        }
+        for (int ks = 0; ks < 4; ++ks) hb[ks] = l0w_from_u2(gelu4_hid(acc[2 * ks]), gelu4_hid(acc[2 * ks + 1]));
         boundary(s); decw_gemm<false, true>((uint32_t)(uintptr_t)ring + slot_off(s) + voff, hb, acc2); ++s;
       }
 #pragma unroll

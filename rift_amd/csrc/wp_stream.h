@@ -48,7 +48,7 @@ __device__ __forceinline__ void decw_dma_share(const unsigned char* src, uint32_
 // One group GEMM (16 rows x K = 128 against the 32 fragments at LDS address `addr` + 1024 f) as a hand-scheduled stream: the 8 fragments of
 // k-step ks + 1 are requested under the 8 MFMAs of k-step ks (lgkmcnt(8) = the fragment 8 requests back has landed), so an MFMA never waits a
 // full LDS round trip; hipcc's own schedule of the same loop kept 1-2 reads in flight.  PLAIN = activations as the A operand (V^T tiles).
-// HID: the weight fragments and x are operands of the MLP hidden layer (common.h: RIFT_MFMA_HID_ASM -- fp16 words in the bf16 build)
+// HID: the weight fragments and x are operands of the MLP hidden layer (opfmt.h: RIFT_MFMA_HID_ASM -- fp16 words in both builds)
 #define DECW_GEMM_SWAPPED_ASM(MN) \
         "ds_read_b128 %[w0], %[a] offset:0\n\t" \
         "ds_read_b128 %[w1], %[a] offset:1024\n\t" \

@@ -20,7 +20,7 @@ Tolerances (written here, per the parity contract):
              same step time as bf16).  11 significand bits instead of 8.  Measured on MI355X (tests/diagnostics/operand_report.py):
                logits 2.5e-3 / 1.8e-3 (small / full), 4.1e-3 on the 256-scene batch                      bar 8e-3
              Two arithmetics have been measured.  Rounds 2 - 4 (fp32 VALU neighbourhood attention, two-pass LayerNorm with its affine
-             part, slot-ordered encoder keys; build define RIFT_F16_R4) / round 5 (the bf16 build's arithmetic: csrc/opfmt.h -- MFMA
+             part, slot-ordered encoder keys; retired; last buildable at 5b8fdbd) / round 5 (the bf16 build's arithmetic: DESIGN.md 4 -- MFMA
              neighbourhood attention, folded one-pass LayerNorm, compacted encoder rows, K = 16 attention MFMAs; 5 % faster; the default):
                RIFT loss 4.5e-5 / 2.8e-5 / 8.2e-6 | 7.2e-5 / 1.7e-5 / 1.1e-5 (small / full / 256 scenes)  bar 1e-4 (north_star)
                GRPO / REINFORCE / PPO: 256 scenes 4.0e-5 / 2.3e-5 / 1.7e-5 | 3.1e-5 / 1.7e-5 / (see the test's print)   bar 1e-4

@@ -1,5 +1,5 @@
 // VALU-rate microbenchmark for the GELU epilogue at its real interface: one MFMA accumulator fragment (4 fp32) + bias -> 4 operand words.
-//   V0  rational erf in packed fp32 (csrc/common.h: gelu_fast2), bf16 operand words      (round 2 .. 4)
+//   V0  rational erf in packed fp32 (the packed form of csrc/common.h: gelu_fast), bf16 operand words      (round 2 .. 4)
 //   V1  relu(x) - h(|x|) with the bump h(a) = a Phi(-a) as a degree-7 polynomial in PACKED FP16 (v_pk_fma_f16: two elements per full-rate
 //       instruction), result converted to bf16 operand words                            (round 5, bf16 build)
 //   V2  V0 with fp16 operand words

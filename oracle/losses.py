@@ -81,10 +81,11 @@ def reinforce_loss(probability, r_pad, returns):
     return -torch.mean(chosen * returns.detach()), r_idx, m_idx
 
 
-def pi_head_loss_and_grads(sd_flat: Dict[str, torch.Tensor], q_final, kind: str, batch: Dict, r_pad):
+def pi_head_loss_and_grads(sd_flat: Dict[str, torch.Tensor], q_final, kind: str, batch: Dict, r_pad,
+                           clip_epsilon=0.2, lambda_entropy=0.01):
     """Run pi_head (planning_decoder.py:184) on `q_final` (bs,R,M,128) with autograd,
     apply the -1e6 model mask (pluto_model.py:203) and the chosen objective; return
-    (loss, {param: grad}, logits)."""
+    (loss, {param: grad}, logits).  `clip_epsilon` / `lambda_entropy` reach the PPO actor loss only."""
     prefix = "planning_decoder.pi_head."
     params = {k: sd_flat[prefix + k].clone().requires_grad_(True) for k in PI_KEYS}
     sd = SD({prefix + k: v for k, v in params.items()}, prefix)
@@ -98,7 +99,7 @@ def pi_head_loss_and_grads(sd_flat: Dict[str, torch.Tensor], q_final, kind: str,
                          batch["group_advantage_torch"], batch["group_advantage_mask_torch"])
     elif kind == "ppo":
         loss = ppo_actor_loss(prob, r_pad, batch["action_mode_torch"], batch["advantage_torch"],
-                              batch["old_log_prob_torch"])
+                              batch["old_log_prob_torch"], clip_epsilon, lambda_entropy)
     elif kind == "reinforce":
         loss, _, _ = reinforce_loss(prob, r_pad, batch["return_torch"])
     elif kind == "sft":

@@ -379,6 +379,38 @@ int rift_group_advantage_tick(RiftCtx* ctx, const float* trajectory, int Rb, int
                               float* turn_buf, int32_t* turn_ptr, int32_t* turn_len, float* speed_buf, int32_t* speed_ptr, int32_t* speed_len,
                               double gamma, double* advantage, void* stream);
 
+/* The decision of every CBV of one rollout tick in ONE call: what PLUTO.get_action does between the model forward and the CARLA control call
+ * (rift/cbv/planning/pluto/pluto.py:142-279 -- _trim_candidates :196-247, _global_to_local :262-279 --, controller/pid_controller.py:13-100,
+ * and the chosen mode / old log-probability columns of the RLFT policies, fine_tuner/rlft/rift_pluto/rift_pluto.py:95-109), on the raw
+ * outputs of that tick's rift_forward.  Per CBV, in this order:
+ *   top-k    the `topk` largest of the row's Rb * 12 logits in descending order, padded lines included (the reference does not exclude them
+ *            either); exact ties go to the lower flat index;
+ *   scores   softmax over the kept logits in fp32; with a ref-free trajectory it joins LAST with score 0.25; choice = first maximum (a
+ *            learned candidate wins a tie with 0.25);
+ *   path     x, y of the chosen candidate's Tfull frames, fp32 -> fp64, rotated + translated to the global frame, first point re-anchored on
+ *            the rear axle, rotated into the vehicle frame -- the reference's operations in fp64, not the shortcut cand - cand[0];
+ *   control  PIDController.control_pid with `sample_interval`: thinning path[k-1::k], target speed = mean spacing, aim range
+ *            clamp(0.5 v + 2.5, 5, 8), aim point = first minimum over the thinned points but the last, brake when target < 0.4 or (then
+ *            only) v / target > 1.1, both windowed PIDs step on every call, steer clamped to [-1, 1].
+ * pid_state: (n_slots, 44) f64, caller-owned and persistent between calls like the rollout's PID buffers in RiftRolloutIO; a row is
+ *   [0,20) turn-PID ring | [20,40) speed-PID ring | 40, 41 turn head (slot of the oldest sample, stored as a double) and last error |
+ *   42, 43 the same two for the speed PID.  An all-zero row is a freshly constructed PIDController: the host resets a slot with a memset.
+ * decision: (K, 8) f64 = throttle, steer, brake (0 / 1), flat index r * 12 + m of the chosen candidate (-1: ref-free), its position in the
+ *   kept list, its score, desired_speed, delta_angle (the controller's diagnostics of the call).
+ * RIFT_ERR_ARG, decided on the host before any launch: K < 0; topk < 1 or > Rb * 12; sample_interval < 1; Tfull < 2 * sample_interval; a
+ * slot outside [0, n_slots); two CBVs with the same slot; a batch_index < 0; Rb * 12 > 1024 (the kernel holds at most 16 logits per lane).
+ * K == 0 returns RIFT_OK without a launch.  `cbvs` is a HOST array of K entries. */
+typedef struct RiftControlCBV {
+  int32_t batch_index;         /* row of the tick's collated batch */
+  int32_t slot;                /* row of pid_state owned by this CBV; distinct within one call */
+  double x, y, heading;        /* rear-axle pose (CenterState.x / y / heading) */
+  double speed;                /* CenterState.pid_speed() */
+} RiftControlCBV;              /* 40 bytes */
+int rift_control_tick(RiftCtx* ctx, const float* trajectory /*(bs,Rb,12,Tfull,6)*/, const float* probability /*(bs,Rb,12) logits*/,
+                      const float* ref_free_trajectory /*(bs,Tfull,4) or NULL: no ref-free candidate*/, int Rb, int Tfull,
+                      const RiftControlCBV* cbvs, int K, int topk, int sample_interval, double* pid_state /*(n_slots,44) f64, in/out*/,
+                      int n_slots, double* decision /*(K,8) f64*/, void* stream);
+
 /* Device-side collation (PlutoFeature.collate, pluto_feature.py:83-94 + RIFTCollate,
  * rift_datamodule.py:33-49): gather `bs` scenes by index from a replay arena whose tensors
  * are stored padded to (A, Mp, Rcap, S) per scene, writing a batch padded to R = batch max. */

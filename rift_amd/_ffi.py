@@ -89,6 +89,12 @@ class RiftTickCBV(C.Structure):        # include/rift_hip.h: one CBV of rift_gro
                 ("pose", C.c_double * 3)]
 
 
+class RiftControlCBV(C.Structure):     # include/rift_hip.h: one CBV of rift_control_tick (40 bytes)
+    _fields_ = [("batch_index", C.c_int32), ("slot", C.c_int32), ("x", C.c_double), ("y", C.c_double), ("heading", C.c_double),
+                ("speed", C.c_double)]
+
+
+CONTROL_STATE = 44     # doubles per pid_state row of rift_control_tick: turn ring (20) | speed ring (20) | turn head, last | speed head, last
 OPERANDS = {"bf16": 0, "fp16": 1}       # RIFT_OPERANDS_* of include/rift_hip.h: the 16-bit MFMA operand format of a context's fused kernels
 EXPORTS = [
     "rift_ctx_create", "rift_ctx_create_ex", "rift_ctx_operand_format", "rift_ctx_destroy", "rift_last_error", "rift_model_load", "rift_forward", "rift_forward_head", "rift_forward_head_back", "rift_loss_backward",
@@ -98,6 +104,7 @@ EXPORTS = [
     "rift_critic_forward", "rift_critic_loss_backward", "rift_critic_finalize", "rift_clip_grad_norm", "rift_adamw_step", "rift_update_tail", "rift_collision_matrix", "rift_off_road_matrix", "rift_other_vehicle_rollout", "rift_sft_teacher_mode",
     "rift_check_finite", "rift_set_dp", "rift_set_prepare_stream", "rift_set_side_stream",
     "rift_comm_unique_id", "rift_comm_init", "rift_comm_all_reduce", "rift_comm_destroy", "rift_group_advantage_tick",
+    "rift_control_tick",
 ]
 CRITIC_NPARAM = 99331
 CRITIC_KEYS = ("net.0.weight", "net.0.bias", "net.2.weight", "net.2.bias", "net.4.weight", "net.4.bias",
@@ -144,6 +151,7 @@ def load_library(variant: str = "") -> C.CDLL:
     lib.rift_comm_init.argtypes = [vp, vp, C.c_int, C.c_int]
     lib.rift_comm_all_reduce.argtypes = [vp, vp, C.c_int64, vp]
     lib.rift_group_advantage_tick.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(RiftTickCBV), C.c_int, vp, vp, vp, vp, vp, vp, C.c_double, vp, vp]
+    lib.rift_control_tick.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(RiftControlCBV), C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]
     lib.rift_comm_destroy.argtypes = [vp]
     lib.rift_loss_finalize_clip.argtypes = [vp, C.POINTER(RiftLossOut), C.c_int, C.c_float, vp, vp]
     lib.rift_tap.argtypes = [vp, C.c_char_p, vp, C.POINTER(C.c_int64), vp]
@@ -297,6 +305,7 @@ class Engine:
         self._keep = []
         self._stage_host = self._stage_dev = None
         self._stage_off = 0
+        self._ctl_state = None         # control_tick: (n_slots, 44) f64, grow-only
 
     # ---- small host inputs (the rollout tick's per-CBV readings) ---------------------------------
     _STAGE_BYTES = 8 << 20
@@ -847,6 +856,57 @@ class Engine:
                                                        _ptr(pid_state["turn_len"]), _ptr(pid_state["speed_buf"]), _ptr(pid_state["speed_ptr"]),
                                                        _ptr(pid_state["speed_len"]), float(gamma), _ptr(out), _stream()), "rift_group_advantage_tick")
         self._keep_tick = (traj, up)
+        return out
+
+    def control_state(self, n_slots: int = 0) -> torch.Tensor:
+        """The (n_slots, 44) f64 controller state of control_tick, owned by the engine and grow-only (a zero row = a fresh PIDController);
+        growing copies the rows in use into a NEW tensor, on the current stream: a tensor returned earlier is the state only until the next
+        growth (ask again instead of keeping it)."""
+        cur = self._ctl_state
+        if cur is None or cur.shape[0] < n_slots:
+            cap = max(16, n_slots, 2 * (cur.shape[0] if cur is not None else 0))
+            new = torch.zeros(cap, CONTROL_STATE, dtype=torch.float64, device=self.device)
+            if cur is not None:
+                new[:cur.shape[0]].copy_(cur)
+            self._ctl_state = new
+        return self._ctl_state
+
+    def adopt_control_state(self, other: "Engine"):
+        """Take over the controller state of `other` (the engine a model was bound to before a precision / device change): the CBVs' rows
+        and their content carry over."""
+        if other._ctl_state is not None:
+            self._ctl_state = other._ctl_state.to(self.device)
+            other._ctl_state = None
+
+    def control_reset(self, slots):
+        """Zero the controller state of `slots` (a CBV that left; stream-ordered, so a control_tick issued behind it sees a fresh controller)."""
+        if self._ctl_state is not None:
+            for s in slots:
+                if 0 <= int(s) < self._ctl_state.shape[0]:
+                    self._ctl_state[int(s)].zero_()          # (a memset per slot: an index list would be a blocking upload)
+
+    def control_tick(self, trajectory, probability, ref_free_trajectory, cbvs, topk: int = 10, sample_interval: int = 10):
+        """The decisions of one tick's CBVs in one C-ABI call (rift_control_tick): `trajectory` (bs, Rb, 12, Tfull, 6), `probability`
+        (bs, Rb, 12) and `ref_free_trajectory` ((bs, Tfull, 4) or None) are the raw outputs of the tick's forward; `cbvs` is a list of
+        (batch_index, slot, x, y, heading, speed).  Returns the (K, 8) f64 device tensor of rift_hip.h: throttle, steer, brake, flat
+        index (-1: ref-free), kept position, score, desired_speed, delta_angle.  Enqueued on the current stream; no synchronisation."""
+        dev = self.device
+        traj = _dev(trajectory, torch.float32, dev)
+        prob = _dev(probability, torch.float32, dev)
+        rf = None if ref_free_trajectory is None else _dev(ref_free_trajectory, torch.float32, dev)
+        bs, Rb, M, Tfull, Cc = traj.shape
+        assert M == 12 and Cc == 6 and tuple(prob.shape) == (bs, Rb, 12) and (rf is None or tuple(rf.shape) == (bs, Tfull, 4))
+        K = len(cbvs)
+        arr = (RiftControlCBV * max(K, 1))()
+        for t, (b, slot, x, y, heading, speed) in zip(arr, cbvs):
+            if not 0 <= int(b) < bs:
+                raise ValueError(f"control_tick: batch_index {b} outside the batch of {bs}")
+            t.batch_index, t.slot, t.x, t.y, t.heading, t.speed = int(b), int(slot), float(x), float(y), float(heading), float(speed)
+        state = self.control_state(max([int(v[1]) + 1 for v in cbvs if int(v[1]) >= 0], default=0))
+        out = torch.empty(K, 8, dtype=torch.float64, device=dev)
+        self._check(self.lib.rift_control_tick(self.ctx, _ptr(traj), _ptr(prob), _ptr(rf), Rb, Tfull, arr, K, int(topk), int(sample_interval),
+                                               _ptr(state), state.shape[0], _ptr(out), _stream()), "rift_control_tick")
+        self._keep_ctl = (traj, prob, rf)
         return out
 
     def sft_teacher_mode(self, trajectory, teacher_infos, frame_rate: int = 10):

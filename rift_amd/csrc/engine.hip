@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <set>
 #include <cmath>
 #include <string>
@@ -37,6 +38,7 @@
 #include "pi_fused.h"
 #include "rollout.h"
 #include "tick_multi.h"
+#include "control.h"
 
 #define ENC_NW 8
 
@@ -2685,6 +2687,55 @@ int rift_group_advantage_tick(RiftCtx* c, const float* trajectory, int Rb, int T
     hipLaunchKernelGGL(tick_multi_kernel<5>, dim3(cdiv(gmax, 4), a.K), dim3(256), 0, st, a);
     hipLaunchKernelGGL(tick_multi_kernel<6>, dim3(1, a.K), dim3(256), 0, st, a);
     (void)gy;
+    HIPCHK(c, hipGetLastError());
+  }
+  return RIFT_OK;
+}
+
+// One rollout tick's decisions (rift_hip.h): every refusal is decided here, on the host, before anything is launched; then one wave per CBV
+// (control.h), RIFT_CTL_CHUNK descriptors per launch.  The logits of a row are held MAXPL per lane: dispatched as loss_kernel<MAXPL> is.
+int rift_control_tick(RiftCtx* c, const float* trajectory, const float* probability, const float* ref_free_trajectory, int Rb, int Tfull,
+                      const RiftControlCBV* cbvs, int K, int topk, int sample_interval, double* pid_state, int n_slots, double* decision,
+                      void* stream) {
+  if (!c) return RIFT_ERR_ARG;
+  auto refuse = [&](const char* why) { c->err = std::string("rift_control_tick: ") + why; return (int)RIFT_ERR_ARG; };
+  if (K < 0) return refuse("K < 0");
+  if (Rb < 1) return refuse("Rb < 1");
+  const long long G = (long long)Rb * 12;
+  if (topk < 1 || topk > G) return refuse("topk outside [1, Rb * 12]");
+  if (sample_interval < 1) return refuse("sample_interval < 1");
+  if (Tfull < 2 * (long long)sample_interval) return refuse("Tfull < 2 * sample_interval (the thinned path needs two points)");
+  if (G > 64 * 16) return refuse("Rb * 12 above 1024 candidates (16 logits per lane)");
+  if (n_slots < 0) return refuse("n_slots < 0");
+  if (K > 0 && (!trajectory || !probability || !cbvs || !pid_state || !decision)) return refuse("null pointer");
+  std::vector<int> slots((size_t)K);
+  for (int k = 0; k < K; ++k) {
+    if (cbvs[k].batch_index < 0) return refuse("batch_index < 0");
+    if (cbvs[k].slot < 0 || cbvs[k].slot >= n_slots) return refuse("slot outside [0, n_slots)");
+    slots[(size_t)k] = cbvs[k].slot;
+  }
+  std::sort(slots.begin(), slots.end());
+  if (std::adjacent_find(slots.begin(), slots.end()) != slots.end()) return refuse("two CBVs with the same slot");
+  c->err.clear();
+  if (K == 0) return RIFT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const hipStream_t st = (hipStream_t)stream;
+  for (int k0 = 0; k0 < K; k0 += RIFT_CTL_CHUNK) {
+    CtlArr a; memset(&a, 0, sizeof(a));
+    a.K = std::min(RIFT_CTL_CHUNK, K - k0); a.G = (int)G; a.Tfull = Tfull; a.topk = topk; a.interval = sample_interval;
+    for (int j = 0; j < a.K; ++j) {
+      const RiftControlCBV& v = cbvs[k0 + j];
+      CtlK& d = a.d[j];
+      d.traj = trajectory + (size_t)v.batch_index * (size_t)G * Tfull * 6;
+      d.prob = probability + (size_t)v.batch_index * (size_t)G;
+      d.rf = ref_free_trajectory ? ref_free_trajectory + (size_t)v.batch_index * Tfull * 4 : nullptr;
+      d.state = pid_state + (size_t)v.slot * RIFT_CTL_STATE;
+      d.dec = decision + (size_t)(k0 + j) * 8;
+      d.ox = v.x; d.oy = v.y; d.ch = std::cos(v.heading); d.sh = std::sin(v.heading); d.speed = v.speed;
+    }
+    if (G <= 64 * 2) hipLaunchKernelGGL(control_tick_kernel<2>, dim3(a.K), dim3(64), 0, st, a);
+    else if (G <= 64 * 4) hipLaunchKernelGGL(control_tick_kernel<4>, dim3(a.K), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(control_tick_kernel<16>, dim3(a.K), dim3(64), 0, st, a);
     HIPCHK(c, hipGetLastError());
   }
   return RIFT_OK;

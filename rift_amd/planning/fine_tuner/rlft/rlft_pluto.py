@@ -134,8 +134,8 @@ class RLFTPluto(PLUTO):
 
     def _per_cbv(self, env_id, cbv_id, obs, data, out, index, state, decision):
         """rlft_pluto.py:172-176: log of the chosen candidate's softmax score and its (r, m) -- integer, bit-exact."""
-        flat = int(decision.flat_index[decision.best])
-        return {'CBVs_actions_old_log_prob': np.log(decision.score[decision.best] + 1e-12),
+        flat = decision.chosen_flat                 # (device path: decision elements 3 and 5 of rift_control_tick)
+        return {'CBVs_actions_old_log_prob': np.log(decision.chosen_score + 1e-12),
                 'CBVs_actions_mode': (flat // decision.n_mode, flat % decision.n_mode)}
 
     def save_model(self, episode):  # checkpoints are written by train(); rlft_pluto.py:295-296
@@ -493,7 +493,8 @@ class _GroupRelativePluto(RLFTPluto):
         self._tick_columns = {}
         if self.mode != 'train':
             return
-        for key in ("candidate_trajectories", "probability", "output_ref_free_trajectory", "ref_probability") + (("output_prediction",) if self._render and self._use_prediction else ()):
+        host_keys = ("probability", "ref_probability") if self.device_control else ("candidate_trajectories", "probability", "output_ref_free_trajectory", "ref_probability")
+        for key in host_keys + (("output_prediction",) if self._render and self._use_prediction else ()):
             if key in out:
                 self._host(out, key)
         src = self.state_source

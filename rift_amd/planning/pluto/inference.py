@@ -49,6 +49,54 @@ def action_mode_of(orig_index: int, n_mode: int) -> Tuple[int, int]:
     return int(orig_index) // n_mode, int(orig_index) % n_mode
 
 
+class ControlSlots:
+    """Which row of the device-side controller state (rift_control_tick's `pid_state`) belongs to which CBV.  A key -- (env_id, cbv_id) --
+    gets a row that holds zeros, i.e. a freshly constructed PIDController: a row never used before, or a released one the caller has
+    zeroed since.  release() only parks a row; it is handed out again after zeroed() has confirmed the memset."""
+
+    def __init__(self):
+        self._slot: Dict = {}
+        self._free: list = []          # zeroed, reusable
+        self._released: list = []      # left by their CBV, still holding its state
+        self._rows = 0                 # rows handed out so far (rows beyond them have never been written)
+
+    def slot(self, key) -> int:
+        if key not in self._slot:
+            if self._free:
+                self._slot[key] = self._free.pop()
+            else:
+                self._slot[key] = self._rows
+                self._rows += 1
+        return self._slot[key]
+
+    def release(self, key):
+        if key in self._slot:
+            self._released.append(self._slot.pop(key))
+
+    def pending(self) -> list:
+        """Rows released and not zeroed yet."""
+        return list(self._released)
+
+    def zeroed(self, slots):
+        """The caller has zeroed `slots` (rows reported by pending()): they may be handed out again."""
+        for s in slots:
+            self._released.remove(s)
+            self._free.append(s)
+
+    def keys(self):
+        return list(self._slot)
+
+    def __contains__(self, key):
+        return key in self._slot
+
+    def __len__(self):
+        return len(self._slot)
+
+    @property
+    def rows(self) -> int:
+        return self._rows
+
+
 class PlutoInference:
     """Eval-mode policy step for a batch of CBVs: HIP forward with every output, then per-CBV candidate selection and PID control."""
 

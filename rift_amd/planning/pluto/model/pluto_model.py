@@ -330,13 +330,16 @@ class PlanningModel(TorchModuleWrapper):
             self._engine = None
             self._bound_version = None
 
-    def forward(self, data: FeaturesType, engine=None) -> TargetsType:
+    def forward(self, data: FeaturesType, engine=None, finish: bool = True) -> TargetsType:
         """`engine`: the result of a self.engine() call the caller made for THIS forward already (the rollout tick binds first, to stage
-        its inputs through the engine's pinned arena): skips the second walk over the parameters."""
+        its inputs through the engine's pinned arena): skips the second walk over the parameters.  `finish=False`: the raw outputs of
+        rift_forward only (a caller that hands them to rift_control_tick needs none of the derived tensors of finish_outputs)."""
         eng = engine if engine is not None else self.engine()
         self._seed += 1
         out = eng.forward(data, train=self.training, need_traj=self.need_traj, fp32=self.compute_precision == "fp32",
                           no_drop=self._no_drop, seed=self._seed)
+        if not finish:
+            return out
         return finish_outputs(out, data, self.history_steps, self.need_traj)
 
 

@@ -18,7 +18,7 @@ import torch
 
 from rift_amd.planning.pluto.controller.pid_controller import PIDController
 from rift_amd.planning.pluto.feature_builder.pluto_feature import PlutoFeature
-from rift_amd.planning.pluto.inference import global_to_local, trim_candidates
+from rift_amd.planning.pluto.inference import ControlSlots, global_to_local, trim_candidates
 from rift_amd.planning.pluto.model.pluto_model import PlanningModel
 
 
@@ -183,7 +183,9 @@ class CBVBasePolicy:   # rift/cbv/planning/base_policy.py:9-52
 
 
 class Candidates(NamedTuple):
-    """One CBV's decision of a tick."""
+    """One CBV's decision of a tick.  On the device path (config['device_control']) the candidate set stays on the device: `trajectory` and
+    `kept` are None, `flat_index` and `score` are the chosen candidate's own (scalars) and `best` its position in the kept list.
+    `chosen_flat` / `chosen_score` mean the same on both paths: what a policy variant's columns are built from."""
     control: tuple                 # (throttle, steer, brake)
     trajectory: np.ndarray         # (79, 3) chosen global trajectory
     kept: np.ndarray               # (k [+1], 80, 3) kept candidates, global frame
@@ -192,6 +194,8 @@ class Candidates(NamedTuple):
     best: int
     n_mode: int
     probability: np.ndarray        # (R, M) raw logits of this CBV
+    chosen_flat: int = -1          # r * M + m of the chosen candidate (-1: ref-free)
+    chosen_score: float = 0.25     # its score
 
 
 @contextlib.contextmanager
@@ -255,6 +259,12 @@ class PLUTO(CBVBasePolicy):
         self._state_source: Optional[CBVStateSource] = config.get('state_source')
         self._render = config.get('need_video_render', False)
         self._host_threads = config.get('host_threads', 4)     # torch intra-op threads during a tick (capped_host_threads; 0: leave them alone)
+        # opt-in: candidate choice + waypoint PID of every CBV in one device call per environment (rift_control_tick) instead of _decide;
+        # the video renderer needs the candidate set on the host, so rendering keeps the host path
+        self._device_control = bool(config.get('device_control', False))
+        self._control_slots = ControlSlots()
+        self._control_engine = None                            # the engine whose control_state() the slots index
+        self._control_pinned = None                            # (K, 8) f64 pinned: the tick's one read-back
         self.mode = 'eval'
         if self._render:
             self.reset_render_data()
@@ -313,7 +323,7 @@ class PLUTO(CBVBasePolicy):
         data = eng.stage_tree(PlutoFeature.collate([o['raw_pluto_feature'] for o in CBVs_obs.values()]).data)      # instead of ~36 blocking ones)
         need, model.need_traj = model.need_traj, True
         try:
-            out = model(data, engine=eng)
+            out = model(data, engine=eng, finish=not self.device_control)      # (the device path consumes the raw outputs)
         finally:
             model.need_traj = need
         return data, out
@@ -338,7 +348,49 @@ class PLUTO(CBVBasePolicy):
         trajectory = kept[best, 1:]
         local = global_to_local(trajectory, origin, float(state.heading))
         control = self.controllers[env_id][cbv_id].control_pid(local[:, :2], state.pid_speed())      # centre speed, pluto.py:252
-        return Candidates(control, trajectory, kept, score, flat, best, n_mode, prob)
+        return Candidates(control, trajectory, kept, score, flat, best, n_mode, prob, int(flat[best]), score[best])
+
+    # ---- the device path of _decide (config['device_control']) ----------------------------------------------------------------
+    @property
+    def device_control(self) -> bool:
+        return self._device_control and not self._render
+
+    def _issue_control(self, env_id, CBVs_obs, out, states):
+        """One rift_control_tick for the environment's CBVs on the current stream, behind its forward, and the asynchronous copy of the
+        (K, 8) decision buffer into pinned memory; returns the event behind that copy.  Slots released since the last tick are zeroed
+        first, on the same stream, and only then handed out again."""
+        eng = self.pluto_model._engine
+        if self._control_engine is not eng:                    # the model re-bound (precision / device change): the controller state moves along
+            if self._control_engine is not None:
+                eng.adopt_control_state(self._control_engine)
+            self._control_engine = eng
+        slots = self._control_slots
+        stale = slots.pending()
+        eng.control_reset(stale)
+        slots.zeroed(stale)
+        cbvs = []
+        for index, cbv_id in enumerate(CBVs_obs):
+            st = states[cbv_id]
+            cbvs.append((index, slots.slot((env_id, cbv_id)), st.x, st.y, st.heading, st.pid_speed()))
+        decision = eng.control_tick(out["trajectory"], out["probability"], out.get("ref_free_trajectory"), cbvs, topk=self._topk,
+                                    sample_interval=self._frame_rate)
+        K = len(cbvs)
+        if self._control_pinned is None or self._control_pinned.shape[0] < K:
+            self._control_pinned = torch.empty(max(K, 16), 8, dtype=torch.float64).pin_memory()
+        self._control_pinned[:K].copy_(decision, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        return done, K
+
+    def _read_control(self, issued, out) -> List[Candidates]:
+        """The tick's decisions on the host: one wait, one (K, 8) array."""
+        done, K = issued
+        done.synchronize()
+        dec = self._control_pinned[:K].numpy().copy()
+        prob = self._host(out, "probability")
+        n_mode = prob.shape[2]
+        return [Candidates((float(d[0]), float(d[1]), bool(d[2] != 0.0)), None, None, float(d[5]), int(d[3]), int(d[4]), n_mode, prob[k],
+                           int(d[3]), float(d[5])) for k, d in enumerate(dec)]
 
     def _record_render(self, env_id, cbv_id, obs, state, decision: Candidates, out, index):
         rd = self._render_data[env_id]
@@ -377,10 +429,14 @@ class PLUTO(CBVBasePolicy):
             env_id = info['env_id']
             data, out = self._forward(CBVs_obs)
             states = {cbv_id: self.state_source.center_state(env_id, cbv_id) for cbv_id in CBVs_obs}
+            # device path: the decisions are issued AHEAD of a variant's own device work (_begin_env: the group advantages, same stream) and
+            # read behind it, so the controls do not wait for the advantages
+            issued = self._issue_control(env_id, CBVs_obs, out, states) if self.device_control else None
             self._begin_env(env_id, CBVs_obs, data, out, states)
+            decisions = self._read_control(issued, out) if issued is not None else None
             for index, (cbv_id, obs) in enumerate(CBVs_obs.items()):
                 state = states[cbv_id]
-                decision = self._decide(out, index, env_id, cbv_id, state)
+                decision = decisions[index] if decisions is not None else self._decide(out, index, env_id, cbv_id, state)
                 result['CBVs_actions'][env_id][cbv_id] = decision.control
                 for key, value in self._per_cbv(env_id, cbv_id, obs, data, out, index, state, decision).items():
                     result[key][env_id][cbv_id] = value
@@ -415,6 +471,8 @@ class PLUTO(CBVBasePolicy):
         """Drop the PID state of CBVs that left the scene (pluto.py:112-123)."""
         for info, CBVs_obs in zip(infos, CBVs_obs_list):
             env_id = info['env_id']
+            for key in [k for k in self._control_slots.keys() if k[0] == env_id and k[1] not in CBVs_obs]:
+                self._control_slots.release(key)                # (device path: zeroed in front of the next control tick, then reusable)
             if env_id not in self.controllers:
                 continue
             for cbv_id in [c for c in self.controllers[env_id] if c not in CBVs_obs]:

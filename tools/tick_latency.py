@@ -2,7 +2,9 @@
 -> PID) and of RIFTPluto in train mode (that + the device-side group advantage of every CBV: rollout, neighbour forecast, collision and
 off-road flags, return, z-score) for K CBVs of one environment at the CARLA shapes (49 agent slots, 60 polygon slots, 1..6 reference
 lines): host wall time per tick (the caller waits for the controls), median / p90 of N ticks.
-    python tools/tick_latency.py [--ticks 60] [--cbvs 1,2,4,8] [--profile rift_pluto/4]"""
+    python tools/tick_latency.py [--ticks 60] [--cbvs 1,2,4,8] [--profile rift_pluto/4] [--device-control]
+--device-control: the A/B of config['device_control'] (candidate choice + waypoint PID in one device call, rift_control_tick) in ONE process:
+the host leg, the device leg, the host leg again (its run-to-run spread is the yardstick of the difference)."""
 import argparse, json, os, sys, tempfile, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -46,7 +48,8 @@ def _ticks(n, ids):
     return out
 
 
-def run(ticks=40, cbvs=(1, 8), precision="fp16", policies=(("pluto", "eval"), ("rift_pluto", "train")), profile="", verbose=False):
+def run(ticks=40, cbvs=(1, 8), precision="fp16", policies=(("pluto", "eval"), ("rift_pluto", "train")), profile="", verbose=False,
+        device_control=False):
     """{"<policy>/<mode>/K=<k>": {"median_ms", "p90_ms", "min_ms"}}"""
     from rift_amd.planning import CBV_POLICY_LIST
     from rift_amd.planning.pluto.model.pluto_model import PlanningModel
@@ -58,7 +61,7 @@ def run(ticks=40, cbvs=(1, 8), precision="fp16", policies=(("pluto", "eval"), ("
             if profile and profile.split("/")[0] != name:
                 continue
             cfg = {'num_scenario': 1, 'ROOT_DIR': tmp, 'model_path': 'ckpt', 'device': 'cuda:0', 'state_source': _source(),
-                   'compute_precision': precision}
+                   'compute_precision': precision, 'device_control': bool(device_control)}
             pol = CBV_POLICY_LIST[name](cfg, None)
             pol.pluto_model.load_state_dict(sd)
             pol.set_mode(mode)
@@ -97,7 +100,16 @@ def main():
     ap.add_argument("--cbvs", default="1,2,4,8")
     ap.add_argument("--precision", default="fp16")
     ap.add_argument("--profile", default="", help="policy/K to run under cProfile instead, e.g. rift_pluto/4")
+    ap.add_argument("--device-control", action="store_true", help="A/B of config['device_control']: host, device, host again, in this process")
     args = ap.parse_args()
+    if args.device_control:
+        legs = {}
+        for leg, on in (("host", False), ("device", True), ("host_again", False)):
+            print(f"-- {leg} leg (device_control={on})", flush=True)
+            legs[leg] = run(args.ticks, [int(k) for k in args.cbvs.split(",")], args.precision, profile=args.profile, verbose=True, device_control=on)
+        if not args.profile:
+            print(json.dumps(legs))
+        return
     out = run(args.ticks, [int(k) for k in args.cbvs.split(",")], args.precision, profile=args.profile, verbose=True)
     if out:
         print(json.dumps(out))

@@ -262,6 +262,21 @@ int rift_loss_finalize(RiftCtx* ctx, const RiftLossOut* out, int accumulate, voi
  * custom_lightning.yaml:40-41).  total_norm: device float, may be NULL.  Not for PPO (the critic's gradients join the norm). */
 int rift_loss_finalize_clip(RiftCtx* ctx, const RiftLossOut* out, int accumulate, float max_norm, float* total_norm, void* stream);
 
+/* The vector-Jacobian product of planning_decoder.pi_head for an objective the CALLER wrote in PyTorch: what `loss.backward()` does through
+ * MLPLayer (layers/mlp_layer.py:8-13) in the reference's LightningModule trainers, for any loss over `probability` (an entropy bonus on
+ * get_rift_loss, another clip, a KL to a reference policy, a pairwise loss) -- rift_loss_backward covers the five compiled-in objectives only.
+ * dlogits = d loss / d probability as torch autograd hands it over, (bs,R,12) f32 with the bs and R of the latest rift_forward whose policy
+ * head has run (RIFT_F_DEFER_HEAD forwards are not meant); its activations are used, so the call belongs between that forward and the next.
+ *   out->flat_grad_sum[16897] = sum_rows dz[row] * d logit[row] / d theta: positive sign, no division by a count.  dz = dlogits, except
+ *   dz = 0 on the rows of padded reference lines, where `probability` is the constant -1e6 whatever the parameters are;
+ *   the six out->grad_* pointers that are not NULL receive that vector: overwritten (accumulate == 0) or added to (accumulate != 0, the
+ *   semantics of autograd's .grad);
+ *   out->stats, out->loss, out->argmax_rm and out->exchange are neither read nor written.
+ * From dz onward the arithmetic is that of rift_loss_backward (same backward and reduction kernels, same summation order).
+ * RIFT_ERR_STATE before any forward; RIFT_ERR_ARG when bs / R differ from that forward's: both decided on the host before any launch. */
+int rift_head_backward(RiftCtx* ctx, const float* dlogits /*(bs,R,12) f32*/, int bs, int R, const RiftLossOut* out, int accumulate,
+                       void* stream);
+
 /* Per-launch HIP-event profiling of the forward/loss kernels on the caller's stream (bench roofline leg).
  * rift_prof_report synchronises and writes a JSON object {label: {count, ms, flops}} into buf. */
 int rift_prof_enable(RiftCtx* ctx, int on);
@@ -476,6 +491,13 @@ int rift_critic_loss_backward(RiftCtx* ctx, const RiftCritic* w, const float* st
 int rift_critic_finalize(RiftCtx* ctx, const float* flat_grad_sum, const double* stats, float* g_w0, float* g_b0, float* g_w1,
                          float* g_b1, float* g_w2, float* g_b2, float* g_state_avg, float* g_state_std, float* g_value_avg,
                          float* g_value_std, void* stream);
+
+/* The vector-Jacobian product of value_net for an objective the caller wrote in PyTorch: what `loss.backward()` does through CriticPPO
+ * (net.py:420-431) in the reference's PPO / RTR trainers (ppo_trainer.py:161-183), for any loss over `value`.  dvalue = d loss / d value (n) f32;
+ * flat_grad_sum[RIFT_CRITIC_NPARAM_C] = sum_i dvalue[i] * d value_i / d theta over all ten tensors (positive sign, no count), in the layout
+ * and with the fixed summation order of rift_critic_loss_backward.  Stateless like that entry: the forward is recomputed from `state`. */
+int rift_critic_backward(RiftCtx* ctx, const RiftCritic* w, const float* state /*(n,128)*/, const float* dvalue /*(n)*/, int n,
+                         float* flat_grad_sum /*[RIFT_CRITIC_NPARAM_C]*/, void* stream);
 
 #ifdef __cplusplus
 }

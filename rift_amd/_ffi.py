@@ -104,9 +104,12 @@ EXPORTS = [
     "rift_critic_forward", "rift_critic_loss_backward", "rift_critic_finalize", "rift_clip_grad_norm", "rift_adamw_step", "rift_update_tail", "rift_collision_matrix", "rift_off_road_matrix", "rift_other_vehicle_rollout", "rift_sft_teacher_mode",
     "rift_check_finite", "rift_set_dp", "rift_set_prepare_stream", "rift_set_side_stream",
     "rift_comm_unique_id", "rift_comm_init", "rift_comm_all_reduce", "rift_comm_destroy", "rift_group_advantage_tick",
-    "rift_control_tick",
+    "rift_control_tick", "rift_head_backward", "rift_critic_backward",
 ]
 CRITIC_NPARAM = 99331
+PI_KEYS = ("mlp.0.weight", "mlp.0.bias", "mlp.1.weight", "mlp.1.bias", "mlp.3.weight", "mlp.3.bias")       # flat order of PI_NPARAM
+PI_SIZES = (128 * 128, 128, 128, 128, 128, 1)
+CRITIC_SIZES = (256 * 128, 256, 256 * 256, 256, 256, 1, 128, 128, 1, 1)                                       # flat order of CRITIC_NPARAM
 CRITIC_KEYS = ("net.0.weight", "net.0.bias", "net.2.weight", "net.2.bias", "net.4.weight", "net.4.bias",
                "state_avg", "state_std", "value_avg", "value_std")
 
@@ -142,6 +145,8 @@ def load_library(variant: str = "") -> C.CDLL:
     lib.rift_forward_head_back.argtypes = [vp, C.c_int, vp]
     lib.rift_loss_backward.argtypes = [vp, C.c_int, C.POINTER(RiftLossIn), C.POINTER(RiftLossOut), vp]
     lib.rift_loss_finalize.argtypes = [vp, C.POINTER(RiftLossOut), C.c_int, vp]
+    lib.rift_head_backward.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(RiftLossOut), C.c_int, vp]
+    lib.rift_critic_backward.argtypes = [vp, C.POINTER(RiftCritic), vp, vp, C.c_int, vp, vp]
     lib.rift_set_param_event.argtypes = [vp, vp]
     lib.rift_check_finite.argtypes = [vp, vp]
     lib.rift_set_dp.argtypes = [vp, C.POINTER(RiftDp)]
@@ -306,6 +311,8 @@ class Engine:
         self._stage_host = self._stage_dev = None
         self._stage_off = 0
         self._ctl_state = None         # control_tick: (n_slots, 44) f64, grow-only
+        self.generation = 0            # counts the calls that overwrite the policy head's activations (forward, forward_raw, forward_head):
+                                       # head_backward refers to the latest one, a caller that kept a graph compares (rift_amd/autograd.py)
 
     # ---- small host inputs (the rollout tick's per-CBV readings) ---------------------------------
     _STAGE_BYTES = 8 << 20
@@ -461,6 +468,7 @@ class Engine:
                 (F_NO_DROP if no_drop else 0) | (0 if bn_update else F_NO_BN_UPDATE)
         self._check(self.lib.rift_forward(self.ctx, C.byref(fb), C.byref(o), flags, C.c_uint32(seed & 0xFFFFFFFF),
                                           _stream()), "rift_forward")
+        self.generation += 1
         self._keep = keep + list(out.values())
         self._bs = bs
         return out
@@ -468,6 +476,7 @@ class Engine:
     def forward_raw(self, fb: RiftFeatureBatch, out: RiftOutputs, flags: int, seed: int):
         """Hot-loop entry: prebuilt descriptors, no tensor conversion, no allocation."""
         rc = self.lib.rift_forward(self.ctx, C.byref(fb), C.byref(out), flags, C.c_uint32(seed & 0xFFFFFFFF), _stream())
+        self.generation += 1
         if rc != 0:
             self._check(rc, "rift_forward")
         self._bs = fb.bs
@@ -492,6 +501,7 @@ class Engine:
         """The policy head of the last F_DEFER_HEAD forward -- or of the one `back` forwards before it -- on the current stream (the caller
         has ordered it behind that forward)."""
         rc = self.lib.rift_forward_head_back(self.ctx, back, _stream())
+        self.generation += 1
         if rc != 0:
             self._check(rc, "rift_forward_head")
 
@@ -671,6 +681,25 @@ class Engine:
         self._check(self.lib.rift_loss_finalize(self.ctx, C.byref(lo), 1 if accumulate else 0, _stream()),
                     "rift_loss_finalize")
         return loss
+
+    def head_backward(self, dlogits: torch.Tensor, grads: Optional[Dict[str, torch.Tensor]] = None, accumulate: bool = False) -> torch.Tensor:
+        """rift_head_backward: the gradient sums of the six pi_head tensors for an upstream gradient `dlogits` = d loss / d probability
+        (bs, R, 12) over the activations of the latest forward.  Returns flat[16897] = sum_rows dz * d logit / d theta (PI_KEYS order, no
+        sign, no count; rows of padded reference lines contribute nothing); `grads` (keyed like loss_finalize's) are overwritten with it or,
+        with `accumulate`, added to.  A data-parallel host all-reduces `flat` itself."""
+        if dlogits.dim() != 3 or dlogits.shape[2] != 12:
+            raise ValueError(f"head_backward: dlogits must be (bs, R, 12), got {tuple(dlogits.shape)}")
+        dz = _dev(dlogits, torch.float32, self.device)
+        flat = torch.empty(PI_NPARAM, dtype=torch.float32, device=self.device)
+        lo = RiftLossOut()
+        lo.flat_grad_sum = flat.data_ptr()
+        g = grads or {}
+        lo.grad_w1, lo.grad_b1 = _ptr(g.get("mlp.0.weight")), _ptr(g.get("mlp.0.bias"))
+        lo.grad_ln_w, lo.grad_ln_b = _ptr(g.get("mlp.1.weight")), _ptr(g.get("mlp.1.bias"))
+        lo.grad_w2, lo.grad_b2 = _ptr(g.get("mlp.3.weight")), _ptr(g.get("mlp.3.bias"))
+        self._check(self.lib.rift_head_backward(self.ctx, _ptr(dz), dz.shape[0], dz.shape[1], C.byref(lo), 1 if accumulate else 0, _stream()),
+                    "rift_head_backward")
+        return flat
 
     # ---- single ops ---------------------------------------------------------------------------
     def op_linear(self, x, w, b=None, ln_w=None, ln_b=None, act=0, fp32=False):
@@ -985,6 +1014,25 @@ class Engine:
         w = self.critic_desc(sd)
         self._check(self.lib.rift_critic_forward(self.ctx, C.byref(w), _ptr(st), st.shape[0], _ptr(out), _stream()), "rift_critic_forward")
         return out
+
+    def critic_backward(self, sd: Dict[str, torch.Tensor], state: torch.Tensor, dvalue: torch.Tensor,
+                        grads: Optional[Dict[str, torch.Tensor]] = None, accumulate: bool = False) -> torch.Tensor:
+        """rift_critic_backward: flat[99331] = sum_i dvalue[i] * d value_net(state)[i] / d theta over the ten critic tensors (CRITIC_KEYS
+        order; no sign, no count) for an upstream gradient `dvalue` = d loss / d value (n).  `grads` (keyed by CRITIC_KEYS, any subset)
+        receive their segments of it -- copied, or added with `accumulate`.  The forward is recomputed from `state`: no forward needs to
+        have run."""
+        st = _dev(state, torch.float32, self.device)
+        dv = _dev(dvalue, torch.float32, self.device).reshape(-1)
+        if st.dim() != 2 or st.shape[1] != 128 or dv.numel() != st.shape[0]:
+            raise ValueError(f"critic_backward: state (n, 128) and dvalue (n), got {tuple(st.shape)} and {tuple(dvalue.shape)}")
+        flat = torch.empty(CRITIC_NPARAM, dtype=torch.float32, device=self.device)
+        w = self.critic_desc(sd)
+        self._check(self.lib.rift_critic_backward(self.ctx, C.byref(w), _ptr(st), _ptr(dv), st.shape[0], _ptr(flat), _stream()), "rift_critic_backward")
+        if grads:
+            for k, seg in zip(CRITIC_KEYS, flat.split(CRITIC_SIZES)):
+                if grads.get(k) is not None:
+                    (grads[k].add_ if accumulate else grads[k].copy_)(seg.view_as(grads[k]))
+        return flat
 
     def critic_loss_backward_raw(self, w: "RiftCritic", state: torch.Tensor, reward_sum: torch.Tensor, stats: torch.Tensor, flat: torch.Tensor):
         rc = self.lib.rift_critic_loss_backward(self.ctx, C.byref(w), _ptr(state), _ptr(reward_sum), state.shape[0], _ptr(stats), _ptr(flat), _stream())

@@ -29,11 +29,12 @@ struct CriticW { const float *w0, *b0, *w1, *b1, *w2, *b2, *savg, *sstd, *vavg, 
 struct CriticRowsP {
   CriticW w;
   const float* state;      // (n, 128)
-  const float* target;     // (n) reward_sum, or null: forward only
+  const float* target;     // (n) reward_sum, or null
+  const float* dvalue;     // (n) upstream d L / d value (rift_critic_backward) in place of the SmoothL1 derivative, or null; both null: forward only
   int n;
   float* value;            // (n) or null
   float *sn, *h1, *h2;     // (n,128) (n,256) (n,256): saved activations (backward only)
-  float *dh1, *dh2, *dout; // (n,256) (n,256) (n): d SmoothL1_r / d pre-activation (sum reduction, no 1/n)
+  float *dh1, *dh2, *dout; // (n,256) (n,256) (n): d SmoothL1_r / d pre-activation (sum reduction, no 1/n); with dvalue: dvalue_r * d value_r / d ...
   float *gsa, *gss;        // (n,128) (n,128): d SmoothL1_r / d state_avg, d state_std
   float *gva, *gvs;        // (n) (n): d SmoothL1_r / d value_avg, d value_std
   double* sl1_part;        // [gridDim.x] per-workgroup sum of SmoothL1
@@ -114,11 +115,16 @@ __global__ __launch_bounds__(256) void critic_rows_kernel(CriticRowsP p) {
       float d = 0.f, l = 0.f;
       if (r0 + r < p.n) {
         if (p.value) p.value[r0 + r] = v;
-        if (p.target) {
-          const float e = v - p.target[r0 + r];
-          const float ae = fabsf(e);
-          l = ae < 1.f ? 0.5f * e * e : ae - 0.5f;                  // SmoothL1, beta = 1
-          const float dl = ae < 1.f ? e : (e > 0.f ? 1.f : -1.f);   // d l / d value
+        if (p.target || p.dvalue) {
+          float dl;                                                 // d l / d value
+          if (p.target) {
+            const float e = v - p.target[r0 + r];
+            const float ae = fabsf(e);
+            l = ae < 1.f ? 0.5f * e * e : ae - 0.5f;                // SmoothL1, beta = 1
+            dl = ae < 1.f ? e : (e > 0.f ? 1.f : -1.f);
+          } else {
+            dl = p.dvalue[r0 + r];                                  // the caller's objective (autograd)
+          }
           d = dl * vstd;                                            // d l / d (net output)
           p.dout[r0 + r] = d;
           p.gva[r0 + r] = dl;                                       // value = net * value_std + value_avg
@@ -128,7 +134,7 @@ __global__ __launch_bounds__(256) void critic_rows_kernel(CriticRowsP p) {
       dv[r] = d; sl[r] = l;
     }
   }
-  if (!p.target) return;
+  if (!p.target && !p.dvalue) return;
   __syncthreads();
   {   // dh2 = dout * w2 * (a2 > 0): thread c; kept in a2's place for the next step
     const int c = tid;

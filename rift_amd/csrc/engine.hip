@@ -99,6 +99,7 @@ struct RiftCtx {
   // loss scratch
   double* l_S = nullptr; double* l_cnt = nullptr; float* l_dz = nullptr; float* l_partial = nullptr;
   size_t l_cap_bs = 0, l_cap_rows = 0, l_cap_wg = 0;
+  double* l_sink = nullptr;   // [2] where loss_reduce_kernel's objective sums go when there is no objective (rift_head_backward)
   float* ego_w = nullptr; float* ego_b = nullptr;   // packed (6,128) linears of StateAttentionEncoder
   bool nat_fused = true; int gemm_dbg = 0;
   unsigned short* l0w_img = nullptr; float* l0w_par = nullptr;   // wave-private level-0 NAT kernel (nat_l0w.h)
@@ -1759,6 +1760,7 @@ void rift_ctx_destroy(RiftCtx* c) {
   if (c->l_cnt) (void)hipFree(c->l_cnt);
   if (c->l_dz) (void)hipFree(c->l_dz);
   if (c->l_partial) (void)hipFree(c->l_partial);
+  if (c->l_sink) (void)hipFree(c->l_sink);
   if (c->ego_w) (void)hipFree(c->ego_w);
   if (c->ego_b) (void)hipFree(c->ego_b);
   if (c->enc_idx) (void)hipFree(c->enc_idx);
@@ -2094,6 +2096,21 @@ int rift_forward_head_back(RiftCtx* c, int back, void* stream) {
 
 int rift_forward_head(RiftCtx* c, void* stream) { return abi::rift_forward_head_back(c, 0, stream); }
 
+// scratch of pi_backward_kernel: dz per row and one 16897-float partial per workgroup of RIFT_PI_BWD_ROWS rows (grow-only)
+static int pi_backward_scratch(RiftCtx* c, int rows, int nwg) {
+  if ((size_t)rows > c->l_cap_rows) {
+    if (c->l_dz) (void)hipFree(c->l_dz);
+    c->l_dz = nullptr; c->l_cap_rows = 0;
+    HIPCHK(c, hipMalloc((void**)&c->l_dz, (size_t)rows * 4)); c->l_cap_rows = rows;
+  }
+  if ((size_t)nwg > c->l_cap_wg) {
+    if (c->l_partial) (void)hipFree(c->l_partial);
+    c->l_partial = nullptr; c->l_cap_wg = 0;
+    HIPCHK(c, hipMalloc((void**)&c->l_partial, (size_t)nwg * RIFT_PI_NPARAM * 4)); c->l_cap_wg = nwg;
+  }
+  return RIFT_OK;
+}
+
 int rift_loss_backward(RiftCtx* c, int kind, const RiftLossIn* in, const RiftLossOut* out, void* stream) {
   if (!c || !in || !out || !out->stats || !out->flat_grad_sum) return RIFT_ERR_ARG;
   c->err.clear();
@@ -2107,14 +2124,7 @@ int rift_loss_backward(RiftCtx* c, int kind, const RiftLossIn* in, const RiftLos
     if (c->l_S) { (void)hipFree(c->l_S); (void)hipFree(c->l_cnt); }
     HIPCHK(c, hipMalloc((void**)&c->l_S, bs * 8)); HIPCHK(c, hipMalloc((void**)&c->l_cnt, bs * 8)); c->l_cap_bs = bs;
   }
-  if ((size_t)rows > c->l_cap_rows) {
-    if (c->l_dz) (void)hipFree(c->l_dz);
-    HIPCHK(c, hipMalloc((void**)&c->l_dz, (size_t)rows * 4)); c->l_cap_rows = rows;
-  }
-  if ((size_t)nwg > c->l_cap_wg) {
-    if (c->l_partial) (void)hipFree(c->l_partial);
-    HIPCHK(c, hipMalloc((void**)&c->l_partial, (size_t)nwg * RIFT_PI_NPARAM * 4)); c->l_cap_wg = nwg;
-  }
+  TRY(pi_backward_scratch(c, rows, nwg));
   LossP p; memset(&p, 0, sizeof(p));
   p.kind = kind; p.bs = bs; p.G = G; p.M = M; p.prob = c->last_prob; p.r_kpm = c->last_rkpm;
   p.old_logits = in->old_group_logits; p.ref_logits = in->ref_group_logits; p.adv64 = in->group_advantage;
@@ -2137,6 +2147,35 @@ int rift_loss_backward(RiftCtx* c, int kind, const RiftLossIn* in, const RiftLos
          c->l_partial);
   launch(c, "loss_reduce_kernel", loss_reduce_kernel, dim3(cdiv(RIFT_PI_NPARAM, 256)), dim3(256), 0, (const float*)c->l_partial, nwg,
          out->flat_grad_sum, (const double*)c->l_S, (const double*)c->l_cnt, bs, out->stats, out->exchange);
+  HIPCHK(c, hipGetLastError());
+  return RIFT_OK;
+}
+
+int rift_head_backward(RiftCtx* c, const float* dlogits, int bs, int R, const RiftLossOut* out, int accumulate, void* stream) {
+  if (!c || !dlogits || !out || !out->flat_grad_sum) return RIFT_ERR_ARG;
+  c->err.clear();
+  if (!c->last_qfinal) { c->err = "rift_head_backward before rift_forward"; return RIFT_ERR_STATE; }
+  if (bs != c->last_bs || R != c->last_R) {
+    c->err = "rift_head_backward: dlogits of (" + std::to_string(bs) + ", " + std::to_string(R) + ", 12) against a forward of (" +
+             std::to_string(c->last_bs) + ", " + std::to_string(c->last_R) + ", 12)";
+    return RIFT_ERR_ARG;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  c->stream = (hipStream_t)stream; c->dry = false;
+  const int M = 12, rows = bs * R * M, nwg = cdiv(rows, RIFT_PI_BWD_ROWS);
+  TRY(pi_backward_scratch(c, rows, nwg));
+  if (!c->l_sink) HIPCHK(c, hipMalloc((void**)&c->l_sink, 2 * sizeof(double)));
+  launch(c, "head_dz_kernel", head_dz_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, dlogits, (const uint8_t*)c->last_rkpm, rows, M, c->l_dz);
+  const std::string PH = "planning_decoder.pi_head.mlp.";
+  launch(c, "pi_backward_kernel", pi_backward_kernel, dim3(nwg), dim3(256), 0, (const float*)c->last_qfinal, (const float*)c->last_hpi,
+         (const float*)c->l_dz, rows, fptr(c, PH + "1.weight"), fptr(c, PH + "1.bias"), fptr(c, PH + "3.weight"), 1e-5f,
+         c->l_partial);
+  // (no objective: zero scenes, the two sums land in the sink)
+  launch(c, "loss_reduce_kernel", loss_reduce_kernel, dim3(cdiv(RIFT_PI_NPARAM, 256)), dim3(256), 0, (const float*)c->l_partial, nwg,
+         out->flat_grad_sum, (const double*)nullptr, (const double*)nullptr, 0, c->l_sink, (double*)nullptr);
+  if (out->grad_w1 || out->grad_b1 || out->grad_ln_w || out->grad_ln_b || out->grad_w2 || out->grad_b2)
+    launch(c, "head_scatter_kernel", head_scatter_kernel, dim3(cdiv(RIFT_PI_NPARAM, 256)), dim3(256), 0, (const float*)out->flat_grad_sum,
+           out->grad_w1, out->grad_b1, out->grad_ln_w, out->grad_ln_b, out->grad_w2, out->grad_b2, accumulate);
   HIPCHK(c, hipGetLastError());
   return RIFT_OK;
 }
@@ -2403,32 +2442,50 @@ int rift_critic_forward(RiftCtx* c, const RiftCritic* w, const float* state, int
   return RIFT_OK;
 }
 
+// The critic's backward for n rows: forward recomputed by critic_rows_kernel, whose per-row output delta is the SmoothL1 derivative against
+// `target` or the caller's `dvalue`; then flat = scale * sum_rows delta_row * d value_row / d theta -- one thread per parameter, rows summed in order
+static int critic_backward_sums(RiftCtx* c, const RiftCritic* w, const float* state, const float* target, const float* dvalue, int n, float scale,
+                                float* flat) {
+  TRY(critic_scratch(c, n));
+  const int np = (n + 15) / 16 * 16, nwg = cdiv(n, 16);
+  CriticRowsP p; memset(&p, 0, sizeof(p));
+  p.w = critic_w(w); p.state = state; p.target = target; p.dvalue = dvalue; p.n = n;
+  p.sn = c->cr_buf; p.h1 = p.sn + (size_t)np * 128; p.h2 = p.h1 + (size_t)np * 256; p.dh1 = p.h2 + (size_t)np * 256;
+  p.dh2 = p.dh1 + (size_t)np * 256; p.dout = p.dh2 + (size_t)np * 256; p.sl1_part = c->cr_part;
+  p.gsa = p.dout + np; p.gss = p.gsa + (size_t)np * 128; p.gva = p.gss + (size_t)np * 128; p.gvs = p.gva + np;
+  launch(c, "critic_rows_kernel", critic_rows_kernel, dim3(nwg), dim3(256), 0, p);
+  launch(c, "critic_outer_sum_kernel", critic_outer_sum_kernel, dim3(cdiv(256 * 128, 256)), dim3(256), 0, (const float*)p.dh1, 256, (const float*)p.sn, 128, n, scale, flat);
+  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(256), 0, (const float*)p.dh1, 256, n, scale, flat + RIFT_CRITIC_OFF_B0);
+  launch(c, "critic_outer_sum_kernel", critic_outer_sum_kernel, dim3(cdiv(256 * 256, 256)), dim3(256), 0, (const float*)p.dh2, 256, (const float*)p.h1, 256, n, scale, flat + RIFT_CRITIC_OFF_W1);
+  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(256), 0, (const float*)p.dh2, 256, n, scale, flat + RIFT_CRITIC_OFF_B1);
+  launch(c, "critic_outer_sum_kernel", critic_outer_sum_kernel, dim3(1), dim3(256), 0, (const float*)p.dout, 1, (const float*)p.h2, 256, n, scale, flat + RIFT_CRITIC_OFF_W2);
+  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(64), 0, (const float*)p.dout, 1, n, scale, flat + RIFT_CRITIC_OFF_B2);
+  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(128), 0, (const float*)p.gsa, 128, n, scale, flat + RIFT_CRITIC_OFF_SAVG);
+  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(128), 0, (const float*)p.gss, 128, n, scale, flat + RIFT_CRITIC_OFF_SSTD);
+  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(64), 0, (const float*)p.gva, 1, n, scale, flat + RIFT_CRITIC_OFF_VAVG);
+  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(64), 0, (const float*)p.gvs, 1, n, scale, flat + RIFT_CRITIC_OFF_VSTD);
+  return RIFT_OK;
+}
+
 int rift_critic_loss_backward(RiftCtx* c, const RiftCritic* w, const float* state, const float* reward_sum, int n, double* stats,
                               float* flat, void* stream) {
   if (!c || !w || !state || !reward_sum || !stats || !flat || n <= 0) return RIFT_ERR_ARG;
   c->err.clear();
   HIPCHK(c, hipSetDevice(c->device));
   c->stream = (hipStream_t)stream; c->dry = false;
-  TRY(critic_scratch(c, n));
-  const int np = (n + 15) / 16 * 16, nwg = cdiv(n, 16);
-  CriticRowsP p; memset(&p, 0, sizeof(p));
-  p.w = critic_w(w); p.state = state; p.target = reward_sum; p.n = n;
-  p.sn = c->cr_buf; p.h1 = p.sn + (size_t)np * 128; p.h2 = p.h1 + (size_t)np * 256; p.dh1 = p.h2 + (size_t)np * 256;
-  p.dh2 = p.dh1 + (size_t)np * 256; p.dout = p.dh2 + (size_t)np * 256; p.sl1_part = c->cr_part;
-  p.gsa = p.dout + np; p.gss = p.gsa + (size_t)np * 128; p.gva = p.gss + (size_t)np * 128; p.gvs = p.gva + np;
-  launch(c, "critic_rows_kernel", critic_rows_kernel, dim3(nwg), dim3(256), 0, p);
-  // flat = -sum_rows d SmoothL1 / d theta: one thread per parameter, rows summed in order
-  launch(c, "critic_outer_sum_kernel", critic_outer_sum_kernel, dim3(cdiv(256 * 128, 256)), dim3(256), 0, (const float*)p.dh1, 256, (const float*)p.sn, 128, n, -1.f, flat);
-  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(256), 0, (const float*)p.dh1, 256, n, -1.f, flat + RIFT_CRITIC_OFF_B0);
-  launch(c, "critic_outer_sum_kernel", critic_outer_sum_kernel, dim3(cdiv(256 * 256, 256)), dim3(256), 0, (const float*)p.dh2, 256, (const float*)p.h1, 256, n, -1.f, flat + RIFT_CRITIC_OFF_W1);
-  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(256), 0, (const float*)p.dh2, 256, n, -1.f, flat + RIFT_CRITIC_OFF_B1);
-  launch(c, "critic_outer_sum_kernel", critic_outer_sum_kernel, dim3(1), dim3(256), 0, (const float*)p.dout, 1, (const float*)p.h2, 256, n, -1.f, flat + RIFT_CRITIC_OFF_W2);
-  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(64), 0, (const float*)p.dout, 1, n, -1.f, flat + RIFT_CRITIC_OFF_B2);
-  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(128), 0, (const float*)p.gsa, 128, n, -1.f, flat + RIFT_CRITIC_OFF_SAVG);
-  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(128), 0, (const float*)p.gss, 128, n, -1.f, flat + RIFT_CRITIC_OFF_SSTD);
-  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(64), 0, (const float*)p.gva, 1, n, -1.f, flat + RIFT_CRITIC_OFF_VAVG);
-  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(64), 0, (const float*)p.gvs, 1, n, -1.f, flat + RIFT_CRITIC_OFF_VSTD);
-  launch(c, "critic_stats_kernel", critic_stats_kernel, dim3(1), dim3(64), 0, (const double*)c->cr_part, nwg, stats);
+  // flat = -sum_rows d SmoothL1 / d theta
+  TRY(critic_backward_sums(c, w, state, reward_sum, nullptr, n, -1.f, flat));
+  launch(c, "critic_stats_kernel", critic_stats_kernel, dim3(1), dim3(64), 0, (const double*)c->cr_part, cdiv(n, 16), stats);
+  HIPCHK(c, hipGetLastError());
+  return RIFT_OK;
+}
+
+int rift_critic_backward(RiftCtx* c, const RiftCritic* w, const float* state, const float* dvalue, int n, float* flat, void* stream) {
+  if (!c || !w || !state || !dvalue || !flat || n <= 0) return RIFT_ERR_ARG;
+  c->err.clear();
+  HIPCHK(c, hipSetDevice(c->device));
+  c->stream = (hipStream_t)stream; c->dry = false;
+  TRY(critic_backward_sums(c, w, state, nullptr, dvalue, n, 1.f, flat));
   HIPCHK(c, hipGetLastError());
   return RIFT_OK;
 }

@@ -408,6 +408,34 @@ __global__ void loss_finalize_kernel(const float* __restrict__ flat, const doubl
   dst[o] = accumulate ? dst[o] + v : v;
 }
 
+// ---- the vector-Jacobian product of pi_head for an upstream gradient that torch autograd produced (rift_head_backward): the two
+// kernels around pi_backward_kernel + loss_reduce_kernel, which it shares with the fixed-function objectives from dz onward.
+// dz = d L / d logit of the caller's objective; rows of padded reference lines carry the constant -1e6 in `probability`, so nothing
+// flows through them whatever the caller's gradient holds there
+__global__ void head_dz_kernel(const float* __restrict__ dlogits /*[rows]*/, const uint8_t* __restrict__ r_kpm /*[rows/M]*/, int rows, int M,
+                               float* __restrict__ dz /*[rows]*/) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= rows) return;
+  dz[row] = r_kpm[row / M] ? 0.f : dlogits[row];
+}
+
+// grads (+)= flat, scattered into the six caller-owned tensors: no sign, no count (loss_finalize_kernel's segment table)
+__global__ void head_scatter_kernel(const float* __restrict__ flat, float* gW1, float* gb1, float* gg, float* gbe, float* gw2, float* gb2,
+                                    int accumulate) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= RIFT_PI_NPARAM) return;
+  float* dst; int o;
+  if (i < 16384) { dst = gW1; o = i; }
+  else if (i < 16384 + 128) { dst = gb1; o = i - 16384; }
+  else if (i < 16384 + 256) { dst = gg; o = i - 16384 - 128; }
+  else if (i < 16384 + 384) { dst = gbe; o = i - 16384 - 256; }
+  else if (i < 16384 + 512) { dst = gw2; o = i - 16384 - 384; }
+  else { dst = gb2; o = 0; }
+  if (!dst) return;
+  const float v = flat[i];
+  dst[o] = accumulate ? dst[o] + v : v;
+}
+
 // loss_finalize + clip_grad_norm_ over exactly the six pi_head gradients in ONE single-workgroup launch (the update's tail is a
 // chain of latency-bound launches; these were three).  Same arithmetic: grads = -sum/count (+ existing .grad when accumulating),
 // total = sqrt(sum of squares in f64), grads *= min(1, max_norm / (total + 1e-6)).

@@ -32,6 +32,9 @@ class CriticPPO(nn.Module):
         self.value_avg = nn.Parameter(torch.zeros((1,)), requires_grad=False)
         self.value_std = nn.Parameter(torch.ones((1,)), requires_grad=False)
         self._engine = None
+        # True: in grad mode, with a trainable parameter, `value` carries autograd history (rift_amd/autograd.py: CriticValue) and an objective
+        # written in PyTorch over it trains the critic through the HIP backward kernels.  False: a plain tensor
+        self.differentiable = False
 
     def bind(self, engine: "_ffi.Engine"):
         self._engine = engine
@@ -40,4 +43,7 @@ class CriticPPO(nn.Module):
     def forward(self, state: torch.Tensor) -> torch.Tensor:
         if self._engine is None or not state.is_cuda:
             raise RuntimeError("CriticPPO.forward needs the HIP engine (bind(engine)) and device tensors; there is no CPU path")
+        if self.differentiable and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            from rift_amd.autograd import critic_value
+            return critic_value(self, state, self._engine)
         return self._engine.critic_forward(dict(self.named_parameters()), state)

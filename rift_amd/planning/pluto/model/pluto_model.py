@@ -248,6 +248,10 @@ class PlanningModel(TorchModuleWrapper):
         self.compute_precision = "fp16"
         self.need_traj = True                # trajectory heads are dead work for the RLFT losses; trainers switch it off
         self._seed = 0
+        # True: in grad mode, with a trainable pi_head parameter, `probability` carries autograd history (rift_amd/autograd.py: HeadLogits) --
+        # an objective written in PyTorch over it trains pi_head through the HIP backward kernels, as the reference's own trainers expect.
+        # One backward per forward, before the next forward of this model.  False: the outputs are plain tensors (RLFTTrainer, the rollout tick)
+        self.differentiable_head = False
 
     def _init_weights(self, m):   # pluto_model.py:108-120
         if isinstance(m, nn.Linear):
@@ -338,6 +342,11 @@ class PlanningModel(TorchModuleWrapper):
         self._seed += 1
         out = eng.forward(data, train=self.training, need_traj=self.need_traj, fp32=self.compute_precision == "fp32",
                           no_drop=self._no_drop, seed=self._seed)
+        if self.differentiable_head and torch.is_grad_enabled():
+            pi_head = self.planning_decoder.pi_head
+            if any(p.requires_grad for p in pi_head.parameters()):
+                from rift_amd.autograd import head_logits
+                out["probability"] = head_logits(pi_head, out["probability"], eng)
         if not finish:
             return out
         return finish_outputs(out, data, self.history_steps, self.need_traj)

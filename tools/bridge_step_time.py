@@ -1,0 +1,144 @@
+"""What the autograd bridge costs per update step (profiles/NOTES_r11.md): the 256-scene RIFT step three ways in ONE process, torch events
+around `--steps` steps after `--warmup` warm-up steps each, legs alternated `--rounds` times.
+
+  pipelined   RLFTTrainer.gather + training_step as bench.py runs it: device collate, deferred head, tail on the update stream
+  serial      the same fixed-function step on one stream: forward + rift_loss_backward + rift_update_tail on pre-gathered batches
+  bridge      PlanningModel(differentiable_head=True).forward + the RIFT objective in PyTorch + loss.backward() (rift_head_backward) +
+              torch clip_grad_norm_ + fused torch AdamW, on pre-staged device batches, one stream
+
+serial vs bridge is the price of writing the objective in PyTorch; pipelined vs serial is what the step pipeline adds on top, which a
+LightningModule-style loop does not have.
+
+    python tools/bridge_step_time.py [--steps 200] [--warmup 20] [--rounds 3] [--precision bf16]
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+BATCH, NBATCH = 256, 4
+
+
+def rift_objective(prob, r_pad, old_logits, adv, valid):
+    """The dual-clip group-relative objective of get_rift_loss (rift_trainer.py:140-182) as a trainer writes it: in-place mask of the model
+    output, log-softmax over a scene's candidates, ratio to the old policy, clip to [0.8, 1.2], lower bound 3 A for negative advantages."""
+    bs = prob.shape[0]
+    pad = r_pad.unsqueeze(-1)
+    prob.masked_fill_(pad, -1e8)
+    lp = torch.log_softmax(prob.view(bs, -1), dim=1)
+    lp_old = torch.log_softmax(old_logits.masked_fill(pad, -1e8).view(bs, -1), dim=1)
+    a = adv.view(bs, -1)
+    ratio = torch.exp(lp - lp_old)
+    low = torch.min(a * ratio, a * ratio.clamp(0.8, 1.2))
+    obj = torch.where(a < 0, torch.max(low, 3.0 * a), low)
+    return -obj[valid.view(bs, -1)].mean()
+
+
+def to_device(d, dev):
+    return {k: to_device(v, dev) if isinstance(v, dict) else (v.to(dev) if torch.is_tensor(v) else v) for k, v in d.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--precision", default="bf16")
+    ap.add_argument("--out", default=None, help="also write the JSON result here")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a HIP device: a step time is a device measurement"
+    from rift_amd import synthetic as syn
+    from rift_amd.planning.fine_tuner.rlft import trainer as T
+    from rift_amd.planning.pluto.model.pluto_model import PlanningModel
+    from rift_amd.replay import DeviceReplay
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    scenes = [syn.make_scene(i) for i in range(NBATCH * BATCH)]
+    sd = syn.perturbed_state_dict({k: list(v.shape) for k, v in PlanningModel(radius=120).state_dict().items()})
+    replay = DeviceReplay(scenes, dev, rcap=6)
+    g = torch.Generator().manual_seed(1000)
+    picks = [torch.randperm(len(scenes), generator=g)[:BATCH] for _ in range(NBATCH)]
+    idx = [p.to(torch.int32).to(dev) for p in picks]
+
+    def model():
+        m = PlanningModel(radius=120)
+        m.load_state_dict(sd)
+        m.to(dev)
+        m.compute_precision, m.need_traj = args.precision, False
+        return m.train()
+
+    # ---- pipelined
+    tr_p = T.RLFTTrainer(model(), kind="rift", seed=1)
+
+    def step_pipelined(i):
+        fb, b = tr_p.gather(replay, idx[i % NBATCH])
+        tr_p.training_step(fb, b)
+
+    # ---- serial (the switches are read when the trainer is built)
+    os.environ["RIFT_OVERLAP"], os.environ["RIFT_PIPELINE"] = "0", "0"
+    tr_s = T.RLFTTrainer(model(), kind="rift", seed=1)
+    del os.environ["RIFT_OVERLAP"], os.environ["RIFT_PIPELINE"]
+    assert not tr_s.pipeline and not tr_s.overlap_update
+    gathered = [replay.collate(tr_s.engine, idx[k], slot=100 + k) for k in range(NBATCH)]
+
+    def step_serial(i):
+        fb, b = gathered[i % NBATCH]
+        tr_s.training_step(fb, b)
+
+    # ---- bridge
+    mb = model()
+    T.freeze_parameters(mb, [T.PI_HEAD])
+    opt = T.configure_optimizer(mb, 1e-4, 1e-5)
+    mb.differentiable_head = True
+    params = [p for p in mb.parameters() if p.requires_grad]
+    staged = []
+    for p in picks:
+        b = syn.collate_scenes([scenes[int(j)] for j in p])
+        data = to_device(b["cur_pluto_feature_torch"], dev)
+        staged.append((data, (~data["reference_line"]["valid_mask"].any(-1)), b["old_group_logits_torch"].to(dev),
+                       b["group_advantage_torch"].to(dev), b["group_advantage_mask_torch"].to(dev)))
+
+    def step_bridge(i):
+        data, r_pad, old, adv, valid = staged[i % NBATCH]
+        loss = rift_objective(mb(data)["probability"], r_pad, old, adv, valid)
+        loss.backward()
+        torch.nn.utils.clip_grad_norm_(params, 0.5)
+        opt.step()
+        opt.zero_grad(set_to_none=True)
+
+    legs = {"pipelined": (step_pipelined, tr_p.wait_update), "serial": (step_serial, tr_s.wait_update), "bridge": (step_bridge, lambda: None)}
+    ms = {k: [] for k in legs}
+    for r in range(args.rounds):
+        for name, (step, drain) in legs.items():
+            for i in range(args.warmup):
+                step(i)
+            drain()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(args.warmup, args.warmup + args.steps):
+                step(i)
+            drain()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[name].append(e0.elapsed_time(e1) / args.steps)
+            print(f"round {r} {name:10s} {ms[name][-1]:.4f} ms/step", file=sys.stderr, flush=True)
+    res = {"batch": BATCH, "precision": args.precision, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
+           "median_ms": {k: sorted(v)[len(v) // 2] for k, v in ms.items()}}
+    res["bridge_minus_serial_ms"] = res["median_ms"]["bridge"] - res["median_ms"]["serial"]
+    res["bridge_minus_pipelined_ms"] = res["median_ms"]["bridge"] - res["median_ms"]["pipelined"]
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

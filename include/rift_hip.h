@@ -394,6 +394,48 @@ int rift_group_advantage_tick(RiftCtx* ctx, const float* trajectory, int Rb, int
                               float* turn_buf, int32_t* turn_ptr, int32_t* turn_len, float* speed_buf, int32_t* speed_ptr, int32_t* speed_len,
                               double gamma, double* advantage, void* stream);
 
+/* The evaluator's settings at run time: the reward model of the rollout return and the constructor / call arguments of the reference's
+ * TrajEvaluator (traj_eval/traj_evaluator.py:83-103 bbox_inflation_ratio, resolution; :333 gamma; :160 near_lane_change).  The nine weights
+ * are DenseRewardModel.params (gym_carla/reward/reward_model.py:22-32), which the reference keeps in a dict meant to be edited; the
+ * thresholds inside the reward (4, 0.5, 3, 20, 0.25, 0.05 / exp(. - 0.5)) are literals there and here.
+ * RIFT_REWARD_SPARSE is SparseRewardModel (:60-91) inside the loop of get_rollout_return (same discount, same stop after the first
+ * collision): only alpha_collision and alpha_boundary are read, and there is no |speed| in the collision term. */
+enum { RIFT_REWARD_DENSE = 0, RIFT_REWARD_SPARSE = 1 };
+typedef struct RiftEvalParams {
+  int32_t reward_model;        /* RIFT_REWARD_* */
+  int32_t near_lane_change;    /* get_other_vehicle_rollout's flag; reference default 1 */
+  double  gamma;               /* 0.98 */
+  double  alpha_collision, alpha_boundary, alpha_comfort, alpha_l_align, alpha_vel_align,
+          alpha_l_center, alpha_center_bias, alpha_velocity, alpha_timestep;   /* reward_model.py:22-32 */
+  double  bbox_inflation_ratio;/* 1.1 */
+  double  resolution;          /* 0.5: pixel = coord / (res, -res) + (H/2, W/2); rounded to fp32 first, as the reference's resolution_hw */
+} RiftEvalParams;              /* 104 bytes */
+/* The reference's defaults with the dense model: 20, 5, 0.8, 0.5, 0.05, 0.6, 0, 0.1, 0.1; gamma 0.98, near_lane_change 1, 1.1, 0.5. */
+int rift_eval_params_default(RiftCtx* ctx, RiftEvalParams* out);
+
+/* rift_rollout_return with the reward model and gamma of `params` (its other fields are checked and not used).  terms: (G,8) f64 or NULL;
+ * a row = the discounted sums of R_collision, R_offroad, R_comfort, R_l_align, R_l_center, R_velocity, R_timestep over the steps that
+ * count (columns 0-6; 2-6 are 0 with the sparse model), and the number of steps counted as a double (column 7: the first colliding step
+ * index + 1, or Ts).  The return is the same bits with and without `terms`, and with rift_eval_params_default the same bits as
+ * rift_rollout_return.
+ * RIFT_ERR_ARG with a message in rift_last_error, decided on the host before any launch (both _ex entries): params == NULL; reward_model
+ * outside {0, 1}; any field not finite; gamma < 0; bbox_inflation_ratio <= 0; resolution <= 0. */
+int rift_rollout_return_ex(RiftCtx* ctx, const float* delta_dis, const float* delta_angle, const float* speed,
+                           const float* acc, const float* ang_vel, const float* ang_acc, const uint8_t* collision,
+                           int collision_ld, const uint8_t* off_road, int off_road_ld, int G, int Ts, const RiftEvalParams* params,
+                           double* returns, double* terms, void* stream);
+
+/* rift_group_advantage_tick with the settings of `params`: the neighbours' forecast takes near_lane_change and bbox_inflation_ratio, the
+ * off-road lookup takes resolution and a pixel offset per CBV from its OWN raster, the return takes gamma and the reward model.  The
+ * offset is the reference constructor's (traj_evaluator.py:102-103, :324-327): x gets + H / 2 and y gets + W / 2 -- the HEIGHT goes to x, a
+ * quirk of the reference that shows on a raster that is not square and is reproduced here (rift_group_advantage_tick keeps 200, 200
+ * whatever the raster).  returns: (K, Rb, 12) f64 or NULL, the discounted returns the z-scores are formed from; terms: (K, Rb, 12, 8) f64
+ * or NULL, rows as in rift_rollout_return_ex; rows r >= R of a CBV stay untouched in both, as in `advantage`.  The launches are those of
+ * rift_group_advantage_tick; advantage and returns are the same bits with and without `terms`. */
+int rift_group_advantage_tick_ex(RiftCtx* ctx, const float* trajectory, int Rb, int Tfull, const RiftTickCBV* cbvs, int K,
+                                 float* turn_buf, int32_t* turn_ptr, int32_t* turn_len, float* speed_buf, int32_t* speed_ptr, int32_t* speed_len,
+                                 const RiftEvalParams* params, double* advantage, double* returns, double* terms, void* stream);
+
 /* The decision of every CBV of one rollout tick in ONE call: what PLUTO.get_action does between the model forward and the CARLA control call
  * (rift/cbv/planning/pluto/pluto.py:142-279 -- _trim_candidates :196-247, _global_to_local :262-279 --, controller/pid_controller.py:13-100,
  * and the chosen mode / old log-probability columns of the RLFT policies, fine_tuner/rlft/rift_pluto/rift_pluto.py:95-109), on the raw

@@ -94,6 +94,37 @@ class RiftControlCBV(C.Structure):     # include/rift_hip.h: one CBV of rift_con
                 ("speed", C.c_double)]
 
 
+class RiftEvalParams(C.Structure):     # include/rift_hip.h: the evaluator's run-time settings (104 bytes)
+    _fields_ = [("reward_model", C.c_int32), ("near_lane_change", C.c_int32), ("gamma", C.c_double)] + \
+               [(n, C.c_double) for n in ("alpha_collision", "alpha_boundary", "alpha_comfort", "alpha_l_align", "alpha_vel_align", "alpha_l_center",
+                                          "alpha_center_bias", "alpha_velocity", "alpha_timestep", "bbox_inflation_ratio", "resolution")]
+
+
+REWARD_MODELS = {"dense": 0, "sparse": 1}       # RIFT_REWARD_* of include/rift_hip.h
+
+
+def eval_params(reward_model=None, gamma: float = 0.98, bbox_inflation_ratio: float = 1.1, resolution: float = 0.5,
+                near_lane_change: bool = True) -> RiftEvalParams:
+    """RiftEvalParams from a reward model of rift_amd.gym_carla.reward.reward_model (None: DenseRewardModel's defaults) and the reference's
+    TrajEvaluator arguments.  The sparse model carries two weights; the other seven stay at the dense defaults (the device does not read
+    them).  Refusals (a NaN, gamma < 0, ...) are the library's, at the call that takes the struct."""
+    from rift_amd.gym_carla.reward.reward_model import DenseRewardModel
+    p = RiftEvalParams()
+    weights = DenseRewardModel().get_params()
+    kind = "dense"
+    if reward_model is not None:
+        kind = reward_model.kind
+        unknown = sorted(set(reward_model.get_params()) - set(weights))
+        if kind not in REWARD_MODELS or unknown:
+            raise ValueError(f"reward model {kind!r} with parameter(s) {unknown}: known models {sorted(REWARD_MODELS)}, known parameters {sorted(weights)}")
+        weights.update(reward_model.get_params())
+    p.reward_model, p.near_lane_change, p.gamma = REWARD_MODELS[kind], 1 if near_lane_change else 0, float(gamma)
+    for k, v in weights.items():
+        setattr(p, k, float(v))
+    p.bbox_inflation_ratio, p.resolution = float(bbox_inflation_ratio), float(resolution)
+    return p
+
+
 CONTROL_STATE = 44     # doubles per pid_state row of rift_control_tick: turn ring (20) | speed ring (20) | turn head, last | speed head, last
 OPERANDS = {"bf16": 0, "fp16": 1}       # RIFT_OPERANDS_* of include/rift_hip.h: the 16-bit MFMA operand format of a context's fused kernels
 EXPORTS = [
@@ -105,6 +136,7 @@ EXPORTS = [
     "rift_check_finite", "rift_set_dp", "rift_set_prepare_stream", "rift_set_side_stream",
     "rift_comm_unique_id", "rift_comm_init", "rift_comm_all_reduce", "rift_comm_destroy", "rift_group_advantage_tick",
     "rift_control_tick", "rift_head_backward", "rift_critic_backward",
+    "rift_eval_params_default", "rift_rollout_return_ex", "rift_group_advantage_tick_ex",
 ]
 CRITIC_NPARAM = 99331
 PI_KEYS = ("mlp.0.weight", "mlp.0.bias", "mlp.1.weight", "mlp.1.bias", "mlp.3.weight", "mlp.3.bias")       # flat order of PI_NPARAM
@@ -156,6 +188,10 @@ def load_library(variant: str = "") -> C.CDLL:
     lib.rift_comm_init.argtypes = [vp, vp, C.c_int, C.c_int]
     lib.rift_comm_all_reduce.argtypes = [vp, vp, C.c_int64, vp]
     lib.rift_group_advantage_tick.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(RiftTickCBV), C.c_int, vp, vp, vp, vp, vp, vp, C.c_double, vp, vp]
+    lib.rift_group_advantage_tick_ex.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(RiftTickCBV), C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(RiftEvalParams),
+                                                 vp, vp, vp, vp]
+    lib.rift_eval_params_default.argtypes = [vp, C.POINTER(RiftEvalParams)]
+    lib.rift_rollout_return_ex.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(RiftEvalParams), vp, vp, vp]
     lib.rift_control_tick.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(RiftControlCBV), C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]
     lib.rift_comm_destroy.argtypes = [vp]
     lib.rift_loss_finalize_clip.argtypes = [vp, C.POINTER(RiftLossOut), C.c_int, C.c_float, vp, vp]
@@ -811,13 +847,24 @@ class Engine:
                         "rift_other_vehicle_rollout")
         return out
 
-    def group_advantage_tick(self, trajectory, cbvs, pid_state, gamma: float = 0.98):
+    def eval_params(self, reward_model=None, gamma: float = 0.98, bbox_inflation_ratio: float = 1.1, resolution: float = 0.5,
+                    near_lane_change: bool = True) -> RiftEvalParams:
+        """The RiftEvalParams of rollout_return / group_advantage_tick (module-level eval_params)."""
+        return eval_params(reward_model, gamma, bbox_inflation_ratio, resolution, near_lane_change)
+
+    def group_advantage_tick(self, trajectory, cbvs, pid_state, gamma: float = 0.98, *, params: Optional[RiftEvalParams] = None,
+                             want_returns: bool = False, want_terms: bool = False):
         """The group advantages of one tick's CBVs in one C-ABI call (rift_group_advantage_tick): `trajectory` (bs, Rb, 12, Tfull, 6) the tick's
         model output (device), `cbvs` a list of dicts in tick order --
             batch_index, center_state (6), ref_pos / ref_angle (lists of the valid lines' valid points, host), actors (None or the dict of
             nearby-actor readings of other_vehicle_rollout), off_road (None or (mask (H, W) uint8, (x, y, heading)))
         -- whose valid reference lines are a prefix of their rows.  Everything host-side goes up in ONE staged copy.  Returns the (K, Rb, 12) f64
-        device tensor; rows r >= R of a CBV are zero."""
+        device tensor; rows r >= R of a CBV are zero.
+        `params` (eval_params; its gamma replaces the argument's) sends the call through rift_group_advantage_tick_ex: reward model, gamma,
+        bbox_inflation_ratio, near_lane_change, resolution and a pixel offset from each CBV's own raster.  With want_returns / want_terms the
+        result is a dict: "advantage" (K, Rb, 12), "returns" (K, Rb, 12), "terms" (K, Rb, 12, 8) -- the ones asked for, views of the ONE device
+        tensor "packed" (K * Rb * 12 * 10 doubles, zero where nothing is written), so that a tick reads all of it back in one copy.  With
+        params None and nothing wanted the call is rift_group_advantage_tick, as ever."""
         dev = self.device
         traj = _dev(trajectory, torch.float32, dev)
         bs, Rb, M, Tfull, Cc = traj.shape
@@ -880,12 +927,28 @@ class Engine:
         Gmax = 12 * max(e["R"] for e in plan)
         for k in ("turn_buf", "turn_ptr", "turn_len", "speed_buf", "speed_ptr", "speed_len"):
             assert pid_state[k].shape[0] >= Gmax
-        out = torch.zeros(K, Rb, 12, dtype=torch.float64, device=dev)
-        self._check(self.lib.rift_group_advantage_tick(self.ctx, _ptr(traj), Rb, Tfull, arr, K, _ptr(pid_state["turn_buf"]), _ptr(pid_state["turn_ptr"]),
-                                                       _ptr(pid_state["turn_len"]), _ptr(pid_state["speed_buf"]), _ptr(pid_state["speed_ptr"]),
-                                                       _ptr(pid_state["speed_len"]), float(gamma), _ptr(out), _stream()), "rift_group_advantage_tick")
+        pid = [_ptr(pid_state[k]) for k in ("turn_buf", "turn_ptr", "turn_len", "speed_buf", "speed_ptr", "speed_len")]
+        if params is None and not want_returns and not want_terms:
+            out = torch.zeros(K, Rb, 12, dtype=torch.float64, device=dev)
+            self._check(self.lib.rift_group_advantage_tick(self.ctx, _ptr(traj), Rb, Tfull, arr, K, *pid, float(gamma), _ptr(out), _stream()),
+                        "rift_group_advantage_tick")
+            self._keep_tick = (traj, up)
+            return out
+        if params is None:
+            params = eval_params(gamma=gamma)
+        n = K * Rb * 12
+        packed = torch.zeros(n * 10, dtype=torch.float64, device=dev)
+        res = {"packed": packed, "advantage": packed[:n].view(K, Rb, 12), "returns": packed[n:2 * n].view(K, Rb, 12),
+               "terms": packed[2 * n:].view(K, Rb, 12, 8)}
+        self._check(self.lib.rift_group_advantage_tick_ex(self.ctx, _ptr(traj), Rb, Tfull, arr, K, *pid, C.byref(params), _ptr(res["advantage"]),
+                                                          _ptr(res["returns"]) if want_returns else None, _ptr(res["terms"]) if want_terms else None,
+                                                          _stream()), "rift_group_advantage_tick_ex")
         self._keep_tick = (traj, up)
-        return out
+        if not want_returns and not want_terms:
+            return res["advantage"]
+        if not want_returns: del res["returns"]
+        if not want_terms: del res["terms"]
+        return res
 
     def control_state(self, n_slots: int = 0) -> torch.Tensor:
         """The (n_slots, 44) f64 controller state of control_tick, owned by the engine and grow-only (a zero row = a fresh PIDController);
@@ -1075,12 +1138,22 @@ class Engine:
         self._check(self.lib.rift_group_advantage(self.ctx, _ptr(r), ng, G, _ptr(out), _stream()), "rift_group_advantage")
         return out
 
-    def rollout_return(self, delta_dis, delta_angle, speed, acc, ang_vel, ang_acc, collision, off_road, gamma=0.98):
+    def rollout_return(self, delta_dis, delta_angle, speed, acc, ang_vel, ang_acc, collision, off_road, gamma=0.98, *, reward_model=None,
+                       terms: bool = False):
+        """The discounted return of G candidates, (G,) f64.  reward_model (rift_amd.gym_carla.reward.reward_model) or terms=True send the call
+        through rift_rollout_return_ex; terms=True returns (returns, terms (G, 8)): the seven discounted term sums and the steps counted.
+        reward_model may also be a ready RiftEvalParams (its gamma then replaces the argument's)."""
         dev = self.device
         f = [_dev(t, torch.float32, dev) for t in (delta_dis, delta_angle, speed, acc, ang_vel, ang_acc)]
         col, off = self.stage(collision, torch.bool), self.stage(off_road, torch.bool)
         G, Ts = f[1].shape
         out = torch.empty(G, dtype=torch.float64, device=dev)
-        self._check(self.lib.rift_rollout_return(self.ctx, *[_ptr(t) for t in f], _ptr(col), col.shape[1], _ptr(off),
-                                                 off.shape[1], G, Ts, gamma, _ptr(out), _stream()), "rift_rollout_return")
-        return out
+        if reward_model is None and not terms:
+            self._check(self.lib.rift_rollout_return(self.ctx, *[_ptr(t) for t in f], _ptr(col), col.shape[1], _ptr(off),
+                                                     off.shape[1], G, Ts, gamma, _ptr(out), _stream()), "rift_rollout_return")
+            return out
+        p = reward_model if isinstance(reward_model, RiftEvalParams) else eval_params(reward_model, gamma)
+        tm = torch.empty(G, 8, dtype=torch.float64, device=dev) if terms else None
+        self._check(self.lib.rift_rollout_return_ex(self.ctx, *[_ptr(t) for t in f], _ptr(col), col.shape[1], _ptr(off),
+                                                    off.shape[1], G, Ts, C.byref(p), _ptr(out), _ptr(tm), _stream()), "rift_rollout_return_ex")
+        return (out, tm) if terms else out

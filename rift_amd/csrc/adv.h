@@ -91,39 +91,80 @@ __device__ __forceinline__ void group_zscore_body(const double* __restrict__ ret
 }
 __global__ void group_zscore_kernel(const double* __restrict__ ret, int n_groups, int G, double* __restrict__ adv) { group_zscore_body(ret, n_groups, G, adv); }
 
-// Dense reward (gym_carla/reward/reward_model.py:34-50) with the dtype promotion of the
-// reference environment (numpy 1.24: np.float32 scalar (op) python float -> float64; f32 (op) f32 -> f32).
-__device__ __forceinline__ double dense_reward(float dd_abs, float da_abs, float speed, float acc, float ang_acc,
-                                               int collision, int offroad) {
+// The reward model of the rollout return as the kernels take it, by value (RiftEvalParams' reward half, rift_hip.h): the nine weights of
+// DenseRewardModel.params (gym_carla/reward/reward_model.py:22-32) and the dense / sparse switch.
+struct RewardP {
+  double collision, boundary, comfort, l_align, vel_align, l_center, center_bias, velocity, timestep;
+  int sparse;
+};
+// The reference's defaults as a compile-time tag: the same body instantiated on it folds the weights as literals, which is the arithmetic
+// of the entries that have no parameters (run-time weights contract their FMAs differently: measured, the returns differ in the last bit).
+// Parameters EQUAL to the defaults are dispatched to this instance as well (reward_is_default), so "no parameters" and "the default
+// parameters" are the same bits.
+struct RewardDefaults {
+  static constexpr double collision = 20.0, boundary = 5.0, comfort = 0.8, l_align = 0.5, vel_align = 0.05, l_center = 0.6, center_bias = 0.0,
+                          velocity = 0.1, timestep = 0.1;
+  static constexpr int sparse = 0;
+};
+inline bool reward_is_default(const RewardP& p) {
+  using D = RewardDefaults;
+  return !p.sparse && p.collision == D::collision && p.boundary == D::boundary && p.comfort == D::comfort && p.l_align == D::l_align &&
+         p.vel_align == D::vel_align && p.l_center == D::l_center && p.center_bias == D::center_bias && p.velocity == D::velocity &&
+         p.timestep == D::timestep;
+}
+struct RewardTerms {                                          // R_collision, R_offroad, R_comfort, R_l_align, R_l_center, R_velocity, R_timestep
+  double t[7];
+  __device__ __forceinline__ double sum() const { return t[0] + t[1] + t[2] + t[3] + t[4] + t[5] + t[6]; }      // the reference's order
+};
+
+// The seven reward terms of one step.  Dense (reward_model.py:34-50) with the dtype promotion of the reference environment (numpy 1.24:
+// np.float32 scalar (op) python float -> float64; f32 (op) f32 -> f32); sparse (SparseRewardModel, :76-85): the two infraction terms,
+// no |speed| in the collision term, the other five 0.  The thresholds (4, 0.5, 3, 20, 0.25, 0.05 / exp(. - 0.5)) are literals there too.
+template <class RP>      // RewardP (run time) or RewardDefaults (compile time)
+__device__ __forceinline__ RewardTerms reward_terms(const RP& p, float dd_abs, float da_abs, float speed, float acc, float ang_acc,
+                                                    int collision, int offroad) {
+  RewardTerms r;
+  if (p.sparse) {
+    r.t[0] = -p.collision * (double)collision;
+    r.t[1] = -p.boundary * (double)offroad;
+    r.t[2] = r.t[3] = r.t[4] = r.t[5] = r.t[6] = 0.0;
+    return r;
+  }
   const float aspeed = fabsf(speed);
-  const double r_collision = -(20.0 + (double)aspeed) * (double)collision;
-  const double r_offroad = -5.0 * (double)offroad;
-  const double r_comfort = -0.8 * (double)((fabsf(acc) > 4.f ? 1 : 0) + (fabsf(ang_acc) > 4.f ? 1 : 0));
+  r.t[0] = -(p.collision + (double)aspeed) * (double)collision;
+  r.t[1] = -p.boundary * (double)offroad;
+  r.t[2] = -p.comfort * (double)((fabsf(acc) > 4.f ? 1 : 0) + (fabsf(ang_acc) > 4.f ? 1 : 0));
   const float c = cosf(da_abs);
   const float cs = c * speed;                                  // f32 * f32
-  const double r_l_align = 0.5 * ((double)fminf(c, 0.f) + 0.05 * (double)fminf(cs, 0.f) +
-                                  0.25 * (1.0 - (double)da_abs / (3.141592653589793 / 2.0)));
-  const double dd = (double)dd_abs;                            // abs(delta_dis - 0.0) in f64
-  const double r_l_center = -0.6 * (double)(c > 0.5f ? 1 : 0) * (dd - 0.05 / exp(dd - 0.5));
-  const double r_velocity = 0.1 * (double)fmaxf(c, 0.f) * (double)((aspeed > 3.f && aspeed < 20.f) ? 1 : 0) * (double)aspeed;
-  const double r_timestep = -0.1 * (double)((aspeed > 0.f || fabsf(acc) > 0.f) ? 1 : 0);
-  return r_collision + r_offroad + r_comfort + r_l_align + r_l_center + r_velocity + r_timestep;
+  r.t[3] = p.l_align * ((double)fminf(c, 0.f) + p.vel_align * (double)fminf(cs, 0.f) +
+                        0.25 * (1.0 - (double)da_abs / (3.141592653589793 / 2.0)));
+  const double dd = fabs((double)dd_abs - p.center_bias);      // abs(delta_dis - alpha_center_bias) in f64
+  r.t[4] = -p.l_center * (double)(c > 0.5f ? 1 : 0) * (dd - 0.05 / exp(dd - 0.5));
+  r.t[5] = p.velocity * (double)fmaxf(c, 0.f) * (double)((aspeed > 3.f && aspeed < 20.f) ? 1 : 0) * (double)aspeed;
+  r.t[6] = -p.timestep * (double)((aspeed > 0.f || fabsf(acc) > 0.f) ? 1 : 0);
+  return r;
 }
 
-// get_rollout_return (traj_evaluator.py:333-370): one WAVE per candidate, lane j = time step j (Ts <= 64): the 7-term dense reward
+// get_rollout_return (traj_evaluator.py:333-370): one WAVE per candidate, lane j = time step j (Ts <= 64): the 7-term reward
 // and gamma^j of every step in parallel, the first colliding step from a ballot (steps after it are dropped, the colliding step
 // itself counts), one wave sum in fp64.  (One lane per candidate walking 40 steps with a double pow each took 39 us per group.)
+// TERMS: also the discounted sum of each of the seven terms and the number of steps counted, as a row of eight doubles of `terms` --
+// seven more wave sums per round, compiled in only here; the return is formed the same way in both instances (same bits).
+template <bool TERMS, class RP>
 __device__ __forceinline__ void rollout_return_body(const float* __restrict__ delta_dis, const float* __restrict__ delta_angle,
                                       const float* __restrict__ speed, const float* __restrict__ acc,
                                       const float* __restrict__ ang_vel, const float* __restrict__ ang_acc,
                                       const uint8_t* __restrict__ collision, int col_ld,
-                                      const uint8_t* __restrict__ off_road, int off_ld, int G, int Ts, double gamma,
-                                      double* __restrict__ ret, int ro_ld) {          // ro_ld: row stride of speed / acc / ang_acc (Ts, or the rollout's 80)
+                                      const uint8_t* __restrict__ off_road, int off_ld, int G, int Ts, double gamma, const RP& rp,
+                                      double* __restrict__ ret, int ro_ld,            // ro_ld: row stride of speed / acc / ang_acc (Ts, or the rollout's 80)
+                                      double* __restrict__ terms) {                   // (G, 8), TERMS only
   const int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (i >= G) return;
   (void)ang_vel;
   double r = 0.0;
+  double ts[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  int steps = 0;
   for (int j0 = 0; j0 < Ts; j0 += 64) {                     // one round for Ts <= 64
     const int j = j0 + lane;
     const bool live = j < Ts;
@@ -133,20 +174,41 @@ __device__ __forceinline__ void rollout_return_body(const float* __restrict__ de
     const unsigned long long hit = __ballot(col);
     const int first = hit ? __ffsll((long long)hit) - 1 : 64;          // lane of the first collision of this round
     double term = 0.0;
-    if (live && lane <= first)
-      term = dense_reward(fabsf(delta_dis[o]), fabsf(delta_angle[o]), speed[o2], acc[o2], ang_acc[o2], col, off) * pow(gamma, (double)j);
+    RewardTerms t = {{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}};
+    if (live && lane <= first) {
+      const double disc = pow(gamma, (double)j);
+      t = reward_terms(rp, fabsf(delta_dis[o]), fabsf(delta_angle[o]), speed[o2], acc[o2], ang_acc[o2], col, off);
+      term = t.sum() * disc;
+      if (TERMS) {
+#pragma unroll
+        for (int k = 0; k < 7; ++k) t.t[k] *= disc;
+      }
+    }
     r += wave_sum_d(term);
+    if (TERMS) {
+#pragma unroll
+      for (int k = 0; k < 7; ++k) ts[k] += wave_sum_d(t.t[k]);
+      steps += hit ? first + 1 : min(64, Ts - j0);
+    }
     if (hit) break;
   }
-  if (lane == 0) ret[i] = r;
+  if (lane == 0) {
+    ret[i] = r;
+    if (TERMS) {
+#pragma unroll
+      for (int k = 0; k < 7; ++k) terms[(size_t)i * 8 + k] = ts[k];
+      terms[(size_t)i * 8 + 7] = (double)steps;
+    }
+  }
 }
+template <bool TERMS, class RP>
 __global__ __launch_bounds__(256) void rollout_return_kernel(const float* __restrict__ delta_dis, const float* __restrict__ delta_angle,
                                       const float* __restrict__ speed, const float* __restrict__ acc,
                                       const float* __restrict__ ang_vel, const float* __restrict__ ang_acc,
                                       const uint8_t* __restrict__ collision, int col_ld,
-                                      const uint8_t* __restrict__ off_road, int off_ld, int G, int Ts, double gamma,
-                                      double* __restrict__ ret, int ro_ld) {
-  rollout_return_body(delta_dis, delta_angle, speed, acc, ang_vel, ang_acc, collision, col_ld, off_road, off_ld, G, Ts, gamma, ret, ro_ld);
+                                      const uint8_t* __restrict__ off_road, int off_ld, int G, int Ts, double gamma, const RP rp,
+                                      double* __restrict__ ret, int ro_ld, double* __restrict__ terms) {
+  rollout_return_body<TERMS>(delta_dis, delta_angle, speed, acc, ang_vel, ang_acc, collision, col_ld, off_road, off_ld, G, Ts, gamma, rp, ret, ro_ld, terms);
 }
 
 // get_other_vehicle_rollout (traj_evaluator.py:160-239): constant-control kinematic-bicycle forecast of the nearby actors

@@ -16,6 +16,7 @@
 
 #include "../../include/rift_hip.h"
 #include "adv.h"
+#include "eval_params.h"
 #include "gemm.h"
 #include "kernels.h"
 #include "loss.h"
@@ -2634,12 +2635,49 @@ int rift_group_advantage(RiftCtx* c, const double* returns, int n_groups, int G,
   return RIFT_OK;
 }
 
+// The reward half of RiftEvalParams as the kernels take it (adv.h)
+static RewardP reward_of(const RiftEvalParams& e) {
+  return RewardP{e.alpha_collision, e.alpha_boundary, e.alpha_comfort, e.alpha_l_align, e.alpha_vel_align, e.alpha_l_center, e.alpha_center_bias,
+                 e.alpha_velocity, e.alpha_timestep, e.reward_model == RIFT_REWARD_SPARSE ? 1 : 0};
+}
+
+int rift_eval_params_default(RiftCtx* c, RiftEvalParams* out) {
+  if (!c || !out) return RIFT_ERR_ARG;
+  rift_eval_params_set_default(out);
+  return RIFT_OK;
+}
+
+template <bool TERMS, class RP>
+static void launch_rollout_return(const float* delta_dis, const float* delta_angle, const float* speed, const float* acc, const float* ang_vel,
+                                  const float* ang_acc, const uint8_t* collision, int collision_ld, const uint8_t* off_road, int off_road_ld,
+                                  int G, int Ts, double gamma, const RP& rp, double* returns, double* terms, void* stream) {
+  hipLaunchKernelGGL((rollout_return_kernel<TERMS, RP>), dim3(cdiv(G, 4)), dim3(256), 0, (hipStream_t)stream, delta_dis, delta_angle, speed,
+                     acc, ang_vel, ang_acc, collision, collision_ld, off_road, off_road_ld, G, Ts, gamma, rp, returns, Ts, terms);
+}
+
 int rift_rollout_return(RiftCtx* c, const float* delta_dis, const float* delta_angle, const float* speed, const float* acc,
                         const float* ang_vel, const float* ang_acc, const uint8_t* collision, int collision_ld,
                         const uint8_t* off_road, int off_road_ld, int G, int Ts, double gamma, double* returns, void* stream) {
   if (!c || G <= 0 || Ts <= 0) return RIFT_ERR_ARG;
-  hipLaunchKernelGGL(rollout_return_kernel, dim3(cdiv(G, 4)), dim3(256), 0, (hipStream_t)stream, delta_dis, delta_angle, speed,
-                     acc, ang_vel, ang_acc, collision, collision_ld, off_road, off_road_ld, G, Ts, gamma, returns, Ts);
+  launch_rollout_return<false>(delta_dis, delta_angle, speed, acc, ang_vel, ang_acc, collision, collision_ld, off_road, off_road_ld, G, Ts, gamma,
+                               RewardDefaults(), returns, nullptr, stream);
+  HIPCHK(c, hipGetLastError());
+  return RIFT_OK;
+}
+
+int rift_rollout_return_ex(RiftCtx* c, const float* delta_dis, const float* delta_angle, const float* speed, const float* acc,
+                           const float* ang_vel, const float* ang_acc, const uint8_t* collision, int collision_ld,
+                           const uint8_t* off_road, int off_road_ld, int G, int Ts, const RiftEvalParams* params, double* returns,
+                           double* terms, void* stream) {
+  if (!c) return RIFT_ERR_ARG;
+  if (const char* why = rift_eval_params_refusal(params)) { c->err = std::string("rift_rollout_return_ex: ") + why; return RIFT_ERR_ARG; }
+  if (G <= 0 || Ts <= 0 || !returns) { c->err = "rift_rollout_return_ex: G <= 0, Ts <= 0 or returns == NULL"; return RIFT_ERR_ARG; }
+  const RewardP rp = reward_of(*params);
+  const double g = params->gamma;
+#define RIFT_RR(TERMS, RP) launch_rollout_return<TERMS>(delta_dis, delta_angle, speed, acc, ang_vel, ang_acc, collision, collision_ld, off_road, off_road_ld, G, Ts, g, RP, returns, terms, stream)
+  if (reward_is_default(rp)) { if (terms) RIFT_RR(true, RewardDefaults()); else RIFT_RR(false, RewardDefaults()); }      // the default weights: the old entry's instance
+  else { if (terms) RIFT_RR(true, rp); else RIFT_RR(false, rp); }
+#undef RIFT_RR
   HIPCHK(c, hipGetLastError());
   return RIFT_OK;
 }
@@ -2679,9 +2717,10 @@ int rift_rollout(RiftCtx* c, const RiftRolloutIO* io, void* stream) {
 // One rollout tick's group advantages (rift_hip.h).  Everything but the candidate rollouts is independent between the CBVs: one launch per
 // stage serves a chunk of up to RIFT_TICK_CHUNK of them (tick_multi.h) -- reference-line deviations and neighbour forecasts first, then the
 // rollouts CBV by CBV in list order (the shared PID state), then kinematics, flags, returns and z-scores: K + 7 launches instead of 9 K.
-int rift_group_advantage_tick(RiftCtx* c, const float* trajectory, int Rb, int Tfull, const RiftTickCBV* cbvs, int K,
-                              float* turn_buf, int32_t* turn_ptr, int32_t* turn_len, float* speed_buf, int32_t* speed_ptr, int32_t* speed_len,
-                              double gamma, double* advantage, void* stream) {
+// (own_offset: the pixel offset of a CBV comes from its own raster -- the _ex entry; else 200, 200 whatever the raster)
+static int group_advantage_tick(RiftCtx* c, const float* trajectory, int Rb, int Tfull, const RiftTickCBV* cbvs, int K,
+                                float* turn_buf, int32_t* turn_ptr, int32_t* turn_len, float* speed_buf, int32_t* speed_ptr, int32_t* speed_len,
+                                const RiftEvalParams& ev, bool own_offset, double* advantage, double* returns, double* terms, void* stream) {
   if (!c || !trajectory || !cbvs || K <= 0 || Rb <= 0 || Tfull < 80 || !advantage || !turn_buf || !turn_ptr || !turn_len || !speed_buf || !speed_ptr || !speed_len) return RIFT_ERR_ARG;
   c->err.clear();
   HIPCHK(c, hipSetDevice(c->device));
@@ -2710,7 +2749,9 @@ int rift_group_advantage_tick(RiftCtx* c, const float* trajectory, int Rb, int T
   const hipStream_t st = (hipStream_t)stream;
   for (int k0 = 0; k0 < K; k0 += RIFT_TICK_CHUNK) {
     TickArr a; memset(&a, 0, sizeof(a));
-    a.K = std::min(RIFT_TICK_CHUNK, K - k0); a.gamma = gamma;
+    a.K = std::min(RIFT_TICK_CHUNK, K - k0); a.gamma = ev.gamma; a.near_lane_change = ev.near_lane_change ? 1 : 0; a.inflation = ev.bbox_inflation_ratio;
+    a.res = (double)(float)ev.resolution;                       // resolution_hw is a float32 array in the reference (traj_evaluator.py:102)
+    a.reward = reward_of(ev); a.reward_default = reward_is_default(a.reward) ? 1 : 0;
     int gmax = 0, nmax = 0;
     for (int j = 0; j < a.K; ++j) {
       const RiftTickCBV& v = cbvs[k0 + j];
@@ -2727,7 +2768,10 @@ int rift_group_advantage_tick(RiftCtx* c, const float* trajectory, int Rb, int T
       p.ang_vel = (float*)(S + o_av); p.ang_acc = (float*)(S + o_aa); p.vertices = (float*)(S + o_vert);
       p.closest_index = (int*)(S + o_cl); p.aim_idx = (int*)(S + o_aim); p.raw_speed = (float*)(S + o_raw);
       d.mask = v.off_road_mask; d.ox = v.pose[0]; d.oy = v.pose[1]; d.ch = std::cos(v.pose[2]); d.sh = std::sin(v.pose[2]);
-      d.col = (uint8_t*)(S + o_col); d.offr = (uint8_t*)(S + o_offr); d.ret = (double*)(S + o_ret);
+      d.off_x = own_offset ? (double)(float)(v.H / 2.0) : 200.0; d.off_y = own_offset ? (double)(float)(v.W / 2.0) : 200.0;   // x gets H / 2: the reference's quirk (rift_hip.h)
+      d.col = (uint8_t*)(S + o_col); d.offr = (uint8_t*)(S + o_offr);
+      d.ret = returns ? returns + (size_t)(k0 + j) * Rb * M : (double*)(S + o_ret);       // straight to the caller's tensor when asked for
+      d.terms = terms ? terms + (size_t)(k0 + j) * Rb * M * 8 : nullptr;
       d.adv = advantage + (size_t)(k0 + j) * Rb * M;
       gmax = std::max(gmax, d.G); nmax = std::max(nmax, d.N);
     }
@@ -2747,6 +2791,25 @@ int rift_group_advantage_tick(RiftCtx* c, const float* trajectory, int Rb, int T
     HIPCHK(c, hipGetLastError());
   }
   return RIFT_OK;
+}
+
+int rift_group_advantage_tick(RiftCtx* c, const float* trajectory, int Rb, int Tfull, const RiftTickCBV* cbvs, int K,
+                              float* turn_buf, int32_t* turn_ptr, int32_t* turn_len, float* speed_buf, int32_t* speed_ptr, int32_t* speed_len,
+                              double gamma, double* advantage, void* stream) {
+  RiftEvalParams ev;
+  rift_eval_params_set_default(&ev);
+  ev.gamma = gamma;
+  return group_advantage_tick(c, trajectory, Rb, Tfull, cbvs, K, turn_buf, turn_ptr, turn_len, speed_buf, speed_ptr, speed_len, ev, false,
+                              advantage, nullptr, nullptr, stream);
+}
+
+int rift_group_advantage_tick_ex(RiftCtx* c, const float* trajectory, int Rb, int Tfull, const RiftTickCBV* cbvs, int K,
+                                 float* turn_buf, int32_t* turn_ptr, int32_t* turn_len, float* speed_buf, int32_t* speed_ptr, int32_t* speed_len,
+                                 const RiftEvalParams* params, double* advantage, double* returns, double* terms, void* stream) {
+  if (!c) return RIFT_ERR_ARG;
+  if (const char* why = rift_eval_params_refusal(params)) { c->err = std::string("rift_group_advantage_tick_ex: ") + why; return RIFT_ERR_ARG; }
+  return group_advantage_tick(c, trajectory, Rb, Tfull, cbvs, K, turn_buf, turn_ptr, turn_len, speed_buf, speed_ptr, speed_len, *params, true,
+                              advantage, returns, terms, stream);
 }
 
 // One rollout tick's decisions (rift_hip.h): every refusal is decided here, on the host, before anything is launched; then one wave per CBV

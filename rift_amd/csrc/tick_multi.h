@@ -18,10 +18,23 @@ struct TickK {                                   // one CBV: inputs and its own 
   const double* actors; double* ov;              // [actions | speed | location | yaw | extent]; (N, 40, 4, 2)
   RolloutP ro;                                   // rollout outputs (and the closed-loop kernel's own arguments)
   const uint8_t* mask; double ox, oy, ch, sh;    // raster, origin, cos / sin of its heading
+  double off_x, off_y;                           // pixel offset of this CBV's raster (the old entry: 200, 200 whatever the raster)
   uint8_t *col, *offr;                           // (G, 40), (G, 80)
-  double *ret, *adv;                             // (G), (G)
+  double *ret, *adv;                             // (G): scratch, or the caller's `returns` rows; (G)
+  double* terms;                                 // (G, 8) of the caller's `terms`, or NULL
 };
-struct TickArr { TickK d[RIFT_TICK_CHUNK]; int K; double gamma; };
+struct TickArr {                                 // the evaluator's settings are those of RiftEvalParams (the old entry: the reference's defaults)
+  TickK d[RIFT_TICK_CHUNK]; int K, near_lane_change; double gamma, inflation, res;
+  RewardP reward; int reward_default;            // reward_default: the weights are the reference's defaults -> the instance that folds them (adv.h)
+};
+static_assert(sizeof(TickArr) <= 4096, "TickArr travels as a kernel argument");
+
+template <class RP>
+__device__ __forceinline__ void tick_return(const TickK& d, double gamma, const RP& rp) {
+  constexpr int Ts = 40, TR = RIFT_RO_LEN;
+  if (d.terms) rollout_return_body<true>(d.dd, d.da, d.ro.speed, d.ro.acc, d.ro.ang_vel, d.ro.ang_acc, d.col, Ts, d.offr, TR, d.G, Ts, gamma, rp, d.ret, TR, d.terms);
+  else rollout_return_body<false>(d.dd, d.da, d.ro.speed, d.ro.acc, d.ro.ang_vel, d.ro.ang_acc, d.col, Ts, d.offr, TR, d.G, Ts, gamma, rp, d.ret, TR, (double*)nullptr);
+}
 
 // STAGE 0: reference-line deviations (block 128)   1: neighbour forecast (block 64)   2: kinematics + corners (block 256)
 //       3: collision flags (256)   4: off-road flags (256)   5: returns (256)   6: z-score (256)
@@ -31,14 +44,17 @@ __global__ void tick_multi_kernel(const TickArr a) {
   const TickK& d = a.d[blockIdx.y];
   constexpr int Ts = 40, M = 12, TR = RIFT_RO_LEN;
   if (STAGE == 0) ref_line_info_body(d.traj, d.G, d.Tfull, Ts, M, d.ref_pos, d.ref_ang, d.ref_len, d.Pmax, d.dd, d.da, d.ci);
-  if (STAGE == 1) { if (d.N > 0) { const double* p = d.actors; const size_t N = (size_t)d.N; other_vehicle_rollout_body(p, p + 3 * N, p + 4 * N, p + 7 * N, p + 8 * N, d.N, Ts, 1, 1.1, d.ov); } }
+  if (STAGE == 1) { if (d.N > 0) { const double* p = d.actors; const size_t N = (size_t)d.N; other_vehicle_rollout_body(p, p + 3 * N, p + 4 * N, p + 7 * N, p + 8 * N, d.N, Ts, a.near_lane_change, a.inflation, d.ov); } }
   if (STAGE == 2) rollout_kinematics_body(d.ro);
   if (STAGE == 3) collision_matrix_body(d.ro.vertices, d.G, TR, d.ov, d.N, Ts, d.col);          // (no neighbours: the loop over them is empty, every flag 0)
   if (STAGE == 4) {
-    if (d.mask) off_road_body(d.ro.center, d.G * TR, d.mask, d.H, d.W, d.ox, d.oy, d.ch, d.sh, 0.5, -0.5, 200.0, 200.0, d.offr);
+    if (d.mask) off_road_body(d.ro.center, d.G * TR, d.mask, d.H, d.W, d.ox, d.oy, d.ch, d.sh, a.res, -a.res, d.off_x, d.off_y, d.offr);
     else { const int i = blockIdx.x * 256 + threadIdx.x; if (i < d.G * TR) d.offr[i] = 0; }
   }
-  if (STAGE == 5) rollout_return_body(d.dd, d.da, d.ro.speed, d.ro.acc, d.ro.ang_vel, d.ro.ang_acc, d.col, Ts, d.offr, TR, d.G, Ts, a.gamma, d.ret, TR);
+  if (STAGE == 5) {                                // (wave-uniform branches: nothing of the breakdown runs without `terms`)
+    if (a.reward_default) tick_return(d, a.gamma, RewardDefaults());
+    else tick_return(d, a.gamma, a.reward);
+  }
   if (STAGE == 6) group_zscore_body(d.ret, 1, d.G, d.adv);
 }
 

@@ -11,6 +11,11 @@ actors (or `nearby_actor_states`, the raw actor readings, forecast by rift_other
 through rift_collision_matrix (the reference's STRtree query is an envelope test), and
 `off_road_mask` + `center_pose` -- the raster the reference draws from the HD map with cv2.fillPoly -- gives the off-road matrix
 through rift_off_road_matrix.
+
+The constructor takes the reference's arguments (traj_evaluator.py:83-103): bbox_inflation_ratio (the neighbours' footprints),
+map_width / map_height / resolution (the raster lookup: pixel = coord / (res, -res) + (map_height / 2, map_width / 2) -- the height goes
+to x, as in the reference), and the reward model (rift_amd.gym_carla.reward.reward_model; None = DenseRewardModel's defaults) and gamma
+of the return.  With all of them at their defaults every call is the one made without them.
 """
 from typing import Dict, List, Optional
 
@@ -19,23 +24,30 @@ import torch
 
 
 class TrajEvaluator:
-    def __init__(self, engine, dt: float = 0.1, num_frames: int = 40, pid_capacity: int = 256):
+    def __init__(self, engine, dt: float = 0.1, num_frames: int = 40, pid_capacity: int = 256, *, bbox_inflation_ratio: float = 1.1,
+                 map_width: int = 400, map_height: int = 400, resolution: float = 0.5, reward_model=None, gamma: float = 0.98):
         assert abs(dt - 0.1) < 1e-9 and num_frames == 40, "kernels are built for dt = 0.1 s, 40 evaluated frames"
         self.engine, self.dt, self.num_frames = engine, dt, num_frames
+        self.bbox_inflation_ratio, self.map_width, self.map_height, self.resolution = bbox_inflation_ratio, map_width, map_height, resolution
+        self.reward_model, self.gamma = reward_model, gamma
         self.pid_state = engine.new_pid_state(pid_capacity)     # BatchPIDTorch state: never reset (reference behaviour)
         self.last_rollout: Optional[Dict[str, torch.Tensor]] = None
 
     def get_grpo_advantage(self, center_state, trajectories: torch.Tensor, ref_line_pos: List[torch.Tensor],
-                           ref_line_angle: List[torch.Tensor], collision_matrix=None, off_road_matrix=None, gamma: float = 0.98,
-                           other_vehicle_vertices=None, off_road_mask=None, center_pose=None, nearby_actor_states=None, to_host: bool = True):
+                           ref_line_angle: List[torch.Tensor], collision_matrix=None, off_road_matrix=None, gamma: Optional[float] = None,
+                           other_vehicle_vertices=None, off_road_mask=None, center_pose=None, nearby_actor_states=None, to_host: bool = True,
+                           near_lane_change: bool = True, return_terms: bool = False):
         """center_state: (x, y, heading, speed, width, length) of the CBV rear axle / footprint.
         trajectories: (R, M, 80, 6) raw model output of the valid reference lines.
         collision_matrix (G, >=40) / off_road_matrix (G, >=40): bool flags per candidate and frame, OR
         other_vehicle_vertices (N, >=40, 4, 2) float64 and off_road_mask (H, W) uint8 + center_pose (x, y, heading of the footprint
         centre, get_off_road_matrix's origin / angle) to have them computed on the device from this call's rollout; OR, instead of
         other_vehicle_vertices, nearby_actor_states = dict(steer, throttle, brake, speed, location (N,3), yaw_deg, extent (N,2)) read
-        off the CARLA actors, forecast on the device (get_other_vehicle_rollout)."""
+        off the CARLA actors, forecast on the device (get_other_vehicle_rollout, with near_lane_change and the constructor's
+        bbox_inflation_ratio).  gamma None: the constructor's.  return_terms: also "returns" (R, M) and "terms" (R, M, 8), the seven
+        discounted reward-term sums and the steps counted of every candidate."""
         eng = self.engine
+        gamma = self.gamma if gamma is None else gamma
         R, M = trajectories.shape[:2]
         G = R * M
         dd, da, _ = eng.ref_line_info(trajectories, ref_line_pos, ref_line_angle, Ts=self.num_frames)
@@ -45,17 +57,28 @@ class TrajEvaluator:
         T = self.num_frames
         if collision_matrix is None:
             if other_vehicle_vertices is None and nearby_actor_states is not None:
-                other_vehicle_vertices = eng.other_vehicle_rollout(num_future_frames=T, **nearby_actor_states)
+                other_vehicle_vertices = eng.other_vehicle_rollout(num_future_frames=T, near_lane_change=near_lane_change,
+                                                                   bbox_inflation_ratio=self.bbox_inflation_ratio, **nearby_actor_states)
             if other_vehicle_vertices is None:
                 raise ValueError("pass collision_matrix, other_vehicle_vertices or nearby_actor_states")
             collision_matrix = eng.collision_matrix(ro["vertices"], other_vehicle_vertices, Ts=T)
         if off_road_matrix is None:
             if off_road_mask is None or center_pose is None:
                 raise ValueError("pass off_road_matrix or off_road_mask + center_pose")
-            off_road_matrix = eng.off_road_matrix(ro["center"], off_road_mask, center_pose[:2], float(center_pose[2]))
+            res = float(np.float32(self.resolution))                       # resolution_hw is a float32 array in the reference (:102)
+            off_road_matrix = eng.off_road_matrix(ro["center"], off_road_mask, center_pose[:2], float(center_pose[2]), resolution_hw=(res, -res),
+                                                  offset=(self.map_height / 2, self.map_width / 2))
+        kw = {}
+        if self.reward_model is not None or return_terms:               # (neither: the call made before the reward model could vary)
+            kw = {"reward_model": self.reward_model, "terms": return_terms}
         ret = eng.rollout_return(dd, da, ro["speed"][:, :T].contiguous(), ro["acc"][:, :T].contiguous(),
                                  ro["ang_vel"][:, :T].contiguous(), ro["ang_acc"][:, :T].contiguous(),
-                                 torch.as_tensor(collision_matrix), torch.as_tensor(off_road_matrix), gamma)
+                                 torch.as_tensor(collision_matrix), torch.as_tensor(off_road_matrix), gamma, **kw)
+        ret, terms = ret if return_terms else (ret, None)
         adv = eng.group_advantage(ret.view(1, G)).view(R, M)
         # (to_host=False: the advantage stays a device tensor -- a rollout tick reads all its CBVs' columns back at once)
-        return {"advantage": adv.cpu().numpy() if to_host else adv, "valid_mask": np.ones((R, M), dtype=np.bool_)}
+        host = (lambda t: t.cpu().numpy()) if to_host else (lambda t: t)
+        out = {"advantage": host(adv), "valid_mask": np.ones((R, M), dtype=np.bool_)}
+        if return_terms:
+            out["returns"], out["terms"] = host(ret.view(R, M)), host(terms.view(R, M, 8))
+        return out

@@ -2,7 +2,8 @@
 -> PID) and of RIFTPluto in train mode (that + the device-side group advantage of every CBV: rollout, neighbour forecast, collision and
 off-road flags, return, z-score) for K CBVs of one environment at the CARLA shapes (49 agent slots, 60 polygon slots, 1..6 reference
 lines): host wall time per tick (the caller waits for the controls), median / p90 of N ticks.
-    python tools/tick_latency.py [--ticks 60] [--cbvs 1,2,4,8] [--profile rift_pluto/4] [--device-control]
+    python tools/tick_latency.py [--ticks 60] [--cbvs 1,2,4,8] [--profile rift_pluto/4] [--device-control] [--traj-eval '{"breakdown": true}']
+--traj-eval: the policies' config['traj_eval'] section as JSON (reward model and evaluator settings at run time, the per-term breakdown).
 --device-control: the A/B of config['device_control'] (candidate choice + waypoint PID in one device call, rift_control_tick) in ONE process:
 the host leg, the device leg, the host leg again (its run-to-run spread is the yardstick of the difference)."""
 import argparse, json, os, sys, tempfile, time
@@ -49,7 +50,7 @@ def _ticks(n, ids):
 
 
 def run(ticks=40, cbvs=(1, 8), precision="fp16", policies=(("pluto", "eval"), ("rift_pluto", "train")), profile="", verbose=False,
-        device_control=False):
+        device_control=False, traj_eval=None):
     """{"<policy>/<mode>/K=<k>": {"median_ms", "p90_ms", "min_ms"}}"""
     from rift_amd.planning import CBV_POLICY_LIST
     from rift_amd.planning.pluto.model.pluto_model import PlanningModel
@@ -62,6 +63,8 @@ def run(ticks=40, cbvs=(1, 8), precision="fp16", policies=(("pluto", "eval"), ("
                 continue
             cfg = {'num_scenario': 1, 'ROOT_DIR': tmp, 'model_path': 'ckpt', 'device': 'cuda:0', 'state_source': _source(),
                    'compute_precision': precision, 'device_control': bool(device_control)}
+            if traj_eval is not None:
+                cfg['traj_eval'] = traj_eval
             pol = CBV_POLICY_LIST[name](cfg, None)
             pol.pluto_model.load_state_dict(sd)
             pol.set_mode(mode)
@@ -101,16 +104,20 @@ def main():
     ap.add_argument("--precision", default="fp16")
     ap.add_argument("--profile", default="", help="policy/K to run under cProfile instead, e.g. rift_pluto/4")
     ap.add_argument("--device-control", action="store_true", help="A/B of config['device_control']: host, device, host again, in this process")
+    ap.add_argument("--traj-eval", default="", help="config['traj_eval'] as JSON, e.g. '{\"breakdown\": true}'")
+    ap.add_argument("--policies", default="", help="comma-separated subset of pluto,rift_pluto")
     args = ap.parse_args()
+    traj_eval = json.loads(args.traj_eval) if args.traj_eval else None
     if args.device_control:
         legs = {}
         for leg, on in (("host", False), ("device", True), ("host_again", False)):
             print(f"-- {leg} leg (device_control={on})", flush=True)
-            legs[leg] = run(args.ticks, [int(k) for k in args.cbvs.split(",")], args.precision, profile=args.profile, verbose=True, device_control=on)
+            legs[leg] = run(args.ticks, [int(k) for k in args.cbvs.split(",")], args.precision, profile=args.profile, verbose=True, device_control=on, traj_eval=traj_eval)
         if not args.profile:
             print(json.dumps(legs))
         return
-    out = run(args.ticks, [int(k) for k in args.cbvs.split(",")], args.precision, profile=args.profile, verbose=True)
+    policies = tuple(p for p in (("pluto", "eval"), ("rift_pluto", "train")) if not args.policies or p[0] in args.policies.split(","))
+    out = run(args.ticks, [int(k) for k in args.cbvs.split(",")], args.precision, policies=policies, profile=args.profile, verbose=True, traj_eval=traj_eval)
     if out:
         print(json.dumps(out))
 

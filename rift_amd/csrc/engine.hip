@@ -722,7 +722,7 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
   // pass B's live rounds and workgroup split, from pass A's counts (pe_fused.h: PeLiveP): one extra block of the BatchNorm-1 finalize
   PeLiveP lv; memset(&lv, 0, sizeof(lv));
   const bool live = stats_p && c->pe_live;
-  int pew_grid = c->nat_grid, pew_ga = 0;
+  int pew_grid = std::max(c->nat_grid, 2), pew_ga = 0;      // (two sides: at one workgroup the split below leaves the polygons none -- RIFT_NAT_GRID=1)
   if (c->pe_w) pew_split(cdiv(q.a.rows, PEW_ROUND_ROWS), cdiv(q.b.rows, PEW_ROUND_ROWS), &pew_grid, &pew_ga);
   if (live || packb) {
     const PeP* sd[2] = {&q.a, &q.b};
@@ -1050,6 +1050,7 @@ int dp_mask_and_drop_counters(Fwd& f) {
   }
 #endif
   if (f.nat_compact) { tap(c, "nat_aidx", (float*)f.nat_aidx, nA); tap(c, "nat_cnt", (float*)f.nat_cnt, 3); }      // (int32 words read back through the float tap)
+  tap(c, "nat_f9", f.F9, (int64_t)nA * 20 * 9);      // the prepared 9-channel rows, all nA slots (prep_kernel)
   return RIFT_OK;
 }
 
@@ -1107,6 +1108,8 @@ void history_encoder(Fwd& f) {
         continue;
       }
     }
+    // level boundaries of the fused path, rows in the launch's own (compacted) order: the downsampled inputs of levels 1 and 2
+    tap(c, "nat_x1", Xin[1], (int64_t)nA * 10 * 64); tap(c, "nat_x2", Xin[2], (int64_t)nA * 5 * 128);
   } else {
     float* X0 = A_alloc<float>(c, (size_t)nA * 20 * 32);
     {
@@ -1145,6 +1148,13 @@ void history_encoder(Fwd& f) {
                Ll[i] * Cl[i], Oc[i] + (size_t)j * Cl[i], 3 * Cl[i], nA, Cl[i],
                fptr(c, HE + ".norm" + std::to_string(i) + ".weight"), fptr(c, HE + ".norm" + std::to_string(i) + ".bias"),
                1e-5f, 0);
+  }
+  // the FPN inputs (LayerNorm of the last three steps of level i): as the 16-bit operand words the fused tail receives (two per float of
+  // the tap, in the launch's compacted order), else fp32 rows of all nA slots
+  for (int i = 0; i < 3; ++i) {
+    const std::string nm = "nat_oc" + std::to_string(i);
+    if (oc_bf16) tap(c, nm.c_str(), (float*)Ocb[i], (int64_t)nA * 3 * Cl[i] / 2);
+    else tap(c, nm.c_str(), Oc[i], (int64_t)nA * 3 * Cl[i]);
   }
   // FPN restricted to what out[:, :, -1] depends on
   f.nat_out = A_alloc<float>(c, (size_t)nA * 128);

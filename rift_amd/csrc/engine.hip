@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/rift_hip.h"
+#include "devmem.h"
 #include "adv.h"
 #include "eval_params.h"
 #include "gemm.h"
@@ -49,10 +50,11 @@ namespace {
 
 struct Param { void* data; int64_t numel; int ndim; int64_t shape[4]; };
 
-struct PW {   // packed weight image of one linear map Y = X W^T (+ b)
-  void* bf = nullptr; float* f32 = nullptr; const float* bias = nullptr;
-  int N = 0, K = 0, Kp = 0, Npad = 0;
-  void* hid = nullptr;          // (fc2 weights of the fused encoder only) the same image in hidden-layer operand words (opfmt.h); pack_hid
+struct PWShape { int N = 0, K = 0, Kp = 0, Npad = 0; const float* bias = nullptr; };
+struct PW : PWShape {   // packed weight image of one linear map Y = X W^T (+ b); owns its images, lives in RiftCtx::pw and is handed on by reference
+  DevBuf<unsigned short> bf; DevBuf<float> f32;
+  DevBuf<unsigned short> hid;   // (fc2 weights of the fused encoder only) the same image in hidden-layer operand words (opfmt.h); pack_hid
+  DevBuf<float> own_bias;       // (pack_stacked_rows only) the stacked bias that `bias` points to
 };
 
 struct Tap { float* p; int64_t numel; };
@@ -65,15 +67,14 @@ struct RiftCtx {
   std::string err;
   std::unordered_map<std::string, Param> params;
   std::unordered_map<std::string, PW> pw;
-  std::vector<void*> owned;          // packed weight allocations
-  struct WConst { float* p = nullptr; bool ready = false; };
+  struct WConst { DevBuf<float> p; bool ready = false; };
   std::unordered_map<std::string, WConst> wconst;   // activations that depend on (frozen) weights only, computed once per model load
   // activation arena (bump allocator, reset every forward).  A forward with RIFT_F_DEFER_HEAD alternates between two arenas, so that the
   // policy head / loss / backward of step k (rift_forward_head, rift_loss_backward on another stream) read step k's activations while the
   // frozen trunk of step k + 1 already writes its own.
-  char* arena = nullptr; size_t arena_cap = 0, arena_off = 0;
+  char* arena = nullptr; size_t arena_cap = 0, arena_off = 0;      // (the current slot of `arenas`, as A_alloc reads it)
   long long dry_key[11] = {}; size_t dry_need = 0;      // the arena size of the last sized forward and what it depended on
-  char* arenas[RIFT_DEFER_SLOTS] = {}; size_t arena_caps[RIFT_DEFER_SLOTS] = {}; int parity = 0;     // (parity: the arena of the current forward)
+  DevBuf<char> arenas[RIFT_DEFER_SLOTS]; int parity = 0;     // (parity: the arena of the current forward)
   struct Head {   // what the policy head of a forward needs (pi_forward .. trajectory heads); kept per arena for the deferred form
     bool valid = false, fp32 = false, need_traj = false;
     float *Q = nullptr, *x0p = nullptr, *QF = nullptr, *Hpi = nullptr, *prob = nullptr, *traj = nullptr, *o3[3] = {nullptr, nullptr, nullptr}, *oT[3] = {nullptr, nullptr, nullptr};
@@ -87,8 +88,8 @@ struct RiftCtx {
   // arena (four slots).  Which batch sizes: forward_impl's measured table, or bs <= RIFT_DEC_DEFER (0 = never).
   int dec_defer_max = -1; bool dec_split = true;   // (-1: the measured table in forward_impl; RIFT_DEC_DEFER=<n>: bs <= n)            // (RIFT_DEC_SPLIT=0: the deferred decoder as one launch)
   bool ro8 = true;                                         // candidate rollout with eight lanes per candidate (rollout.h; RIFT_RO8=0: one lane, the round-1 form)
-  float* ro_raw = nullptr; size_t ro_cap = 0;              // rift_rollout: the unsmoothed speed history handed from the closed-loop kernel to the kinematics kernel
-  char* tick_scratch = nullptr; size_t tick_cap = 0;       // rift_group_advantage_tick: per-CBV intermediates (reused CBV by CBV in stream order)
+  DevBuf<float> ro_raw;             // rift_rollout: the unsmoothed speed history handed from the closed-loop kernel to the kinematics kernel
+  DevBuf<char> tick_scratch;      // rift_group_advantage_tick: per-CBV intermediates (reused CBV by CBV in stream order)
   // (Measured and not kept: the deferred decoder on a third stream of the engine's own, so that decoder k would also run beside tail k - 1 --
   // 0.21 -> 0.40 ms at 32 scenes, with 4 or 8 hardware queues; every stream beyond the four the step uses has made cross-queue waits slower.)
   bool dry = false;
@@ -98,18 +99,17 @@ struct RiftCtx {
   float* last_qfinal = nullptr; float* last_hpi = nullptr; float* last_prob = nullptr;
   uint8_t* last_rkpm = nullptr; int last_bs = 0, last_R = 0;
   // loss scratch
-  double* l_S = nullptr; double* l_cnt = nullptr; float* l_dz = nullptr; float* l_partial = nullptr;
-  size_t l_cap_bs = 0, l_cap_rows = 0, l_cap_wg = 0;
-  double* l_sink = nullptr;   // [2] where loss_reduce_kernel's objective sums go when there is no objective (rift_head_backward)
-  float* ego_w = nullptr; float* ego_b = nullptr;   // packed (6,128) linears of StateAttentionEncoder
+  DevBuf<double> l_S, l_cnt; DevBuf<float> l_dz, l_partial;
+  DevBuf<double> l_sink;   // [2] where loss_reduce_kernel's objective sums go when there is no objective (rift_head_backward)
+  DevBuf<float> ego_w, ego_b;   // packed (6,128) linears of StateAttentionEncoder
   bool nat_fused = true; int gemm_dbg = 0;
-  unsigned short* l0w_img = nullptr; float* l0w_par = nullptr;   // wave-private level-0 NAT kernel (nat_l0w.h)
-  unsigned short* encw_img = nullptr; float* encw_par = nullptr;   // weight stream / parameters of the dense-traffic scene encoder (enc_w.h)
-  unsigned short* l2w_img = nullptr; float* l2w_par = nullptr;   // wave-private, weight-streaming level-2 NAT kernel (nat_l2w.h)
-  unsigned short* l1w_img = nullptr; float* l1w_par = nullptr;   // wave-private level-1 NAT kernel (nat_l1w.h)
-  unsigned short* enc_wqkv[4] = {nullptr, nullptr, nullptr, nullptr};   // chunked (q|k|q|k|v|v) bf16 in_proj images
-  float* enc_bqkv[4] = {nullptr, nullptr, nullptr, nullptr};
-  int* enc_idx = nullptr; bool enc_fused = true;
+  DevBuf<unsigned short> l0w_img; DevBuf<float> l0w_par;   // wave-private level-0 NAT kernel (nat_l0w.h)
+  DevBuf<unsigned short> encw_img; DevBuf<float> encw_par;   // weight stream / parameters of the dense-traffic scene encoder (enc_w.h)
+  DevBuf<unsigned short> l2w_img; DevBuf<float> l2w_par;   // wave-private, weight-streaming level-2 NAT kernel (nat_l2w.h)
+  DevBuf<unsigned short> l1w_img; DevBuf<float> l1w_par;   // wave-private level-1 NAT kernel (nat_l1w.h)
+  DevBuf<unsigned short> enc_wqkv[4];   // chunked (q|k|q|k|v|v) bf16 in_proj images
+  DevBuf<float> enc_bqkv[4];
+  DevBuf<int> enc_idx; bool enc_fused = true;
   int poison_lds = -1;                   // RIFT_POISON_LDS diagnostic (see lds_poison_kernel)
   // the per-call diagnostic switches of the environment, read ONCE when the context is made (nine getenv calls per forward were ~10 us of a
   // call whose host time bounds a small-batch step): RIFT_{PE,PEW,NAT,ENC,DEC}_TS, RIFT_{PEW,DEC}_DBG, RIFT_POISON_ARENA
@@ -120,24 +120,24 @@ struct RiftCtx {
   hipStream_t prep_stream = nullptr; bool prep_set = false; hipEvent_t ev_prep = nullptr; int side_gate = 0;      // rift_set_prepare_stream
   hipEvent_t ev_join2 = nullptr; bool nat_aside = true;      // (the history chain behind the preparation on the prepare stream: its join event)
   hipStream_t side = nullptr; bool side_owned = false; hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // (RIFT_TWO_STREAMS=0 switches it off) the agent-history chain (NAT levels + FPN tail) on a second stream beside the map / reference-line chain
-  bool fo_w = true; unsigned short* fow_img[3] = {nullptr, nullptr, nullptr}; float* fow_par[3] = {nullptr, nullptr, nullptr};   // wave-private Fourier embeddings (fo_w.h): tokens, speed limits, reference-line positions
-  bool pe_w = true; unsigned short* pew_img[2] = {nullptr, nullptr};   // wave-private PointsEncoder pass B (pe_w.h): weight streams of the map / reference-line encoders
-  unsigned short* decw_img = nullptr; float* decw_par = nullptr;   // weight stream / parameter blocks of the decoder kernel (dec_w.h)
-  double* clip_part = nullptr;
+  bool fo_w = true; DevBuf<unsigned short> fow_img[3]; DevBuf<float> fow_par[3];   // wave-private Fourier embeddings (fo_w.h): tokens, speed limits, reference-line positions
+  bool pe_w = true; DevBuf<unsigned short> pew_img[2];   // wave-private PointsEncoder pass B (pe_w.h): weight streams of the map / reference-line encoders
+  DevBuf<unsigned short> decw_img; DevBuf<float> decw_par;   // weight stream / parameter blocks of the decoder kernel (dec_w.h)
+  DevBuf<double> clip_part;
   struct Dp { bool on = false; int off = 0, gbs = 0; double* xchg = nullptr; long long len = 0; RiftExchangeFn fn = nullptr; void* user = nullptr; } dp;   // rift_set_dp
-  int* nonfinite = nullptr;              // device flag set by the policy-head kernels when the decoder output is not finite
+  DevBuf<int> nonfinite;            // device flag set by the policy-head kernels when the decoder output is not finite
   // the in-launch ranking's published per-scene counts (kernels.h: rank_scene_body), one array per arena; they persist between launches
   // (a word is valid when it carries the launch's epoch; zero at allocation, epochs start at 1)
   // The look-back over these words relies on ONE preparation launch in flight per arena slot and on an epoch fixed on the host for each
   // launch (prepare_inputs): a captured graph that replays the launch would replay a stale epoch, so that launch is never graph-replayed.
-  unsigned long long* rk_pub[RIFT_DEFER_SLOTS] = {}; int rk_cap[RIFT_DEFER_SLOTS] = {}; unsigned int rk_epoch[RIFT_DEFER_SLOTS] = {};
+  DevBuf<unsigned long long> rk_pub[RIFT_DEFER_SLOTS]; unsigned int rk_epoch[RIFT_DEFER_SLOTS] = {};
   bool rank_fault = false;               // RIFT_RANK_FAULT=1 (diagnostic): the first scene block of the in-launch ranking never publishes its counts
   bool no_skip = false;                  // RIFT_NO_SKIP=1: the scene encoder computes the branches DropPath drops and the decoder the padded reference lines' discarded
                                          // sub-blocks, as until round 7 (the reference of tests/test_gpu_skip_discarded.py and the "before" leg of the A/B in one binary)
   bool enc112 = true;                    // RIFT_ENC112=0: scenes of 97 .. 112 token slots on enc_w_kernel (rounds 3 - 5) instead of the fused kernel's 112-row layout
   bool rank_in_prep = true;              // RIFT_RANK_IN_PREP=0: the ranking as its own launch behind the preparation (nat_rank_kernel, rounds 3 - 5)
   void* comm = nullptr; int comm_rank = 0, comm_world = 1;      // library-owned RCCL communicator (rift_comm_init), or null
-  float* cr_buf = nullptr; size_t cr_cap = 0; double* cr_part = nullptr;   // PPO critic scratch (rows x 1153 floats)
+  DevBuf<float> cr_buf; DevBuf<double> cr_part;   // PPO critic scratch (rows x 1153 floats)
   bool pe_fused = true; bool fo_fused = true; int nat_grid = 256; bool fpn_fused = true; bool ego_fused = true; bool heads_fused = true; bool pi_fused = true;
   bool loaded = false;
   // optional per-launch HIP-event profiling (bench roofline leg; off on the timed path)
@@ -146,6 +146,12 @@ struct RiftCtx {
   std::vector<hipEvent_t> prof_pool; size_t prof_used = 0;
   struct Rec { const char* label; hipEvent_t e0, e1; double flops; };
   std::vector<Rec> prof_recs;
+  ~RiftCtx() {      // (the DevBuf members free the device memory)
+    if (ev_prep) (void)hipEventDestroy(ev_prep);
+    if (ev_join2) (void)hipEventDestroy(ev_join2);
+    if (side && side_owned) (void)hipStreamDestroy(side);
+    if (ev_fork) { (void)hipEventDestroy(ev_fork); (void)hipEventDestroy(ev_join); }
+  }
 };
 
 static void prof_events(RiftCtx* c, hipEvent_t* e0, hipEvent_t* e1) {
@@ -164,6 +170,13 @@ static void prof_push(RiftCtx* c, const char* label, hipEvent_t e0, hipEvent_t e
       return RIFT_ERR_HIP;                                                                \
     }                                                                                     \
   } while (0)
+#define DEVCHK(ctx, expr) HIPCHK(ctx, (hipError_t)(expr))      // DevBuf::reserve: the allocation hook hands the runtime's error through
+
+// devmem.h's hooks: every device allocation and release of the library (defined once: by the bf16 build, which every library holds)
+#if !RIFT_OP_F16
+__attribute__((visibility("hidden"))) int rift_dev_alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+__attribute__((visibility("hidden"))) void rift_dev_free(void* p) { (void)hipFree(p); }
+#endif
 
 namespace {
 
@@ -247,10 +260,10 @@ void launch_gemm(RiftCtx* c, const char* label, void (*kern)(KArgs...), dim3 gri
 // Returns the buffer and whether the caller must fill it now.
 float* wconst_get(RiftCtx* c, const std::string& key, size_t n, bool fp32, bool* fill) {
   RiftCtx::WConst& w = c->wconst[key + (fp32 ? "#32" : "#16")];
-  if (!w.p) { if (hipMalloc((void**)&w.p, n * sizeof(float)) != hipSuccess) { w.p = nullptr; *fill = false; return nullptr; } c->owned.push_back(w.p); }
+  if (w.p.reserve(n) != 0) { *fill = false; return nullptr; }
   *fill = !w.ready && !c->dry;
   if (!c->dry) w.ready = true;
-  return w.p;
+  return w.p.get();
 }
 
 const Param* find(RiftCtx* c, const std::string& name) {
@@ -270,15 +283,14 @@ int pack(RiftCtx* c, const std::string& key, const float* src, int n_src, int N,
   PW w;
   w.N = N; w.K = K; w.Kp = (K + 31) & ~31; w.Npad = (N + 15) & ~15; w.bias = bias;
   const size_t cnt = (size_t)w.Npad * w.Kp;
-  HIPCHK(c, hipMalloc(&w.bf, cnt * 2));
-  HIPCHK(c, hipMalloc((void**)&w.f32, cnt * 4));
-  c->owned.push_back(w.bf); c->owned.push_back(w.f32);
+  DEVCHK(c, w.bf.reserve(cnt));
+  DEVCHK(c, w.f32.reserve(cnt));
   const int blocks = cdiv((long long)cnt, 256);
-  hipLaunchKernelGGL(pack_weight_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, src + src_col_off, w.bf, n_src, K,
+  hipLaunchKernelGGL(pack_weight_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, src + src_col_off, (void*)w.bf.get(), n_src, K,
                      w.Npad, w.Kp, conv_C, tap_lo, tap_n, src_row_off, src_ld);
-  hipLaunchKernelGGL(pack_weight_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, src + src_col_off, (void*)w.f32,
+  hipLaunchKernelGGL(pack_weight_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, src + src_col_off, (void*)w.f32.get(),
                      n_src, K, w.Npad, w.Kp, conv_C, tap_lo, tap_n, src_row_off, src_ld);
-  c->pw[key] = w;
+  c->pw[key] = std::move(w);
   return RIFT_OK;
 }
 
@@ -286,9 +298,8 @@ int pack(RiftCtx* c, const std::string& key, const float* src, int n_src, int N,
 int pack_hid(RiftCtx* c, const std::string& key) {
   PW& w = c->pw[key];
   const size_t cnt = (size_t)w.Npad * w.Kp;
-  HIPCHK(c, hipMalloc(&w.hid, cnt * 2));
-  c->owned.push_back(w.hid);
-  hipLaunchKernelGGL(pack_weight_hid_kernel, dim3(cdiv((long long)cnt, 256)), dim3(256), 0, c->stream, (const float*)w.f32, (unsigned short*)w.hid, w.Npad, w.Kp);
+  DEVCHK(c, w.hid.reserve(cnt));
+  hipLaunchKernelGGL(pack_weight_hid_kernel, dim3(cdiv((long long)cnt, 256)), dim3(256), 0, c->stream, (const float*)w.f32.get(), w.hid.get(), w.Npad, w.Kp);
   return RIFT_OK;
 }
 
@@ -340,25 +351,24 @@ int pack_stacked_rows(RiftCtx* c, const std::string& key, const std::vector<std:
   w.N = ns * n; w.K = K; w.Kp = (K + 31) & ~31; w.Npad = (w.N + 15) & ~15;
   if (n % 16) { c->err = "pack_stacked_rows: n % 16"; return RIFT_ERR_ARG; }
   const size_t cnt = (size_t)w.Npad * w.Kp;
-  float* bias = nullptr;
-  HIPCHK(c, hipMalloc(&w.bf, cnt * 2));
-  HIPCHK(c, hipMalloc((void**)&w.f32, cnt * 4));
-  HIPCHK(c, hipMalloc((void**)&bias, (size_t)w.N * 4));
-  c->owned.push_back(w.bf); c->owned.push_back(w.f32); c->owned.push_back(bias);
+  DEVCHK(c, w.bf.reserve(cnt));
+  DEVCHK(c, w.f32.reserve(cnt));
+  DEVCHK(c, w.own_bias.reserve((size_t)w.N));
+  float* bias = w.own_bias.get();
   for (int i = 0; i < ns; ++i) {
     const Param* wi = find(c, wnames[i]);
     const Param* bi = find(c, bnames[i]);
     if (!wi || !bi || wi->shape[1] != K) { c->err = "missing matrix " + wnames[i]; return RIFT_ERR_ARG; }
     const size_t off = (size_t)i * n * w.Kp;     // a 16-row block of a fragment-major image starts at the row-major offset of its first row
     const int blocks = cdiv((long long)n * w.Kp, 256);
-    hipLaunchKernelGGL(pack_weight_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, (const float*)wi->data, (void*)((unsigned short*)w.bf + off),
+    hipLaunchKernelGGL(pack_weight_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, (const float*)wi->data, (void*)(w.bf.get() + off),
                        n, K, n, w.Kp, 0, 0, 0, r0, K);
-    hipLaunchKernelGGL(pack_weight_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, (const float*)wi->data, (void*)(w.f32 + off),
+    hipLaunchKernelGGL(pack_weight_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, (const float*)wi->data, (void*)(w.f32.get() + off),
                        n, K, n, w.Kp, 0, 0, 0, r0, K);
     HIPCHK(c, hipMemcpyAsync(bias + (size_t)i * n, (const float*)bi->data + r0, (size_t)n * 4, hipMemcpyDeviceToDevice, c->stream));
   }
   w.bias = bias;
-  c->pw[key] = w;
+  c->pw[key] = std::move(w);
   return RIFT_OK;
 }
 
@@ -388,7 +398,7 @@ int pack_self_mha(RiftCtx* c, const std::string& p) {
 }
 
 // ---- GEMM dispatch -----------------------------------------------------------------------
-GemmP mk(const float* X, int ldx, int M, const PW& w, float* Y, int ldy) {
+GemmP mk(const float* X, int ldx, int M, const PWShape& w, float* Y, int ldy) {
   GemmP g;
   memset(&g, 0, sizeof(g));
   g.X = X; g.ldx = ldx; g.M = M; g.N = w.N; g.K = w.K; g.Kp = w.Kp; g.bias = w.bias; g.Y = Y; g.ldy = ldy;
@@ -423,7 +433,7 @@ void gemm_launch(RiftCtx* c, GemmP g) {
   }
 }
 
-void gemm(RiftCtx* c, GemmP g, const PW& w, bool fp32) {
+void gemm(RiftCtx* c, GemmP g, const void* W, bool fp32) {      // W: the image of the precision (PW::f32 / PW::bf)
   if (g.M <= 0) return;
   // vectorised A staging needs 16-byte aligned rows: dense conv windows (C % 4 == 0) or ldx % 4 == 0, K % 4 == 0
   const bool conv = g.amode == AMODE_CONV3;
@@ -435,9 +445,11 @@ void gemm(RiftCtx* c, GemmP g, const PW& w, bool fp32) {
   g.evec = (g.N % 4 == 0) && (g.ldy % 4 == 0) && ((((uintptr_t)g.Y) & 15) == 0) &&
            (!g.bias || (((uintptr_t)g.bias) & 15) == 0) && (!g.gbias || (((uintptr_t)g.gbias) & 15) == 0) &&
            (!g.residual || ((g.ldr % 4 == 0) && (((uintptr_t)g.residual) & 15) == 0));
-  if (fp32) { g.W = w.f32; gemm_launch<false>(c, g); }
-  else { g.W = w.bf; gemm_launch<true>(c, g); }
+  g.W = W;
+  if (fp32) gemm_launch<false>(c, g);
+  else gemm_launch<true>(c, g);
 }
+void gemm(RiftCtx* c, const GemmP& g, const PW& w, bool fp32) { gemm(c, g, fp32 ? (const void*)w.f32.get() : (const void*)w.bf.get(), fp32); }
 
 int set_lds_attrs(RiftCtx* c) {
   const int big = 160 * 1024;
@@ -577,12 +589,12 @@ FourierP fourier_desc(Fwd& f, const float* in, int in_ld, int rows, int D, const
   for (int d = 0; d < D; ++d) {
     const std::string m = p + ".mlps." + std::to_string(d);
     const PW &lo = c->pw[m + ".0.lo"], &last = c->pw[m + ".0.last"], &w3 = c->pw[m + ".3"];
-    q.w0[d] = (const unsigned short*)lo.bf; q.b0[d] = lo.bias; q.wl[d] = last.f32; q.wl_ld = last.Kp;
+    q.w0[d] = lo.bf.get(); q.b0[d] = lo.bias; q.wl[d] = last.f32.get(); q.wl_ld = last.Kp;
     q.lng[d] = fptr(c, m + ".1.weight"); q.lnb[d] = fptr(c, m + ".1.bias");
-    q.w3[d] = (const unsigned short*)w3.bf; q.b3[d] = w3.bias;
+    q.w3[d] = w3.bf.get(); q.b3[d] = w3.bias;
   }
   q.og = fptr(c, p + ".to_out.0.weight"); q.ob = fptr(c, p + ".to_out.0.bias");
-  q.wo = (const unsigned short*)c->pw[p + ".to_out.2"].bf; q.bo = c->pw[p + ".to_out.2"].bias;
+  q.wo = c->pw[p + ".to_out.2"].bf.get(); q.bo = c->pw[p + ".to_out.2"].bias;
   q.Y = add_to ? add_to : A_alloc<float>(c, (size_t)rows * 128);
   q.accumulate = add_to ? 1 : 0;
   return q;
@@ -655,8 +667,8 @@ static void pe_fill(Fwd& f, PeP& q, const float* F, int Cin, int groups, int n, 
   q.F = F; q.Cin = Cin; q.valid = valid; q.rows = rows; q.ntiles = cdiv(rows, 120);
   const PW &w1 = c->pw[p + ".first_mlp.0"], &w2 = c->pw[p + ".first_mlp.3"], &w3a = c->pw[p + ".second_mlp.0.feat"],
            &w3b = c->pw[p + ".second_mlp.0.pool"], &w4 = c->pw[p + ".second_mlp.3"];
-  q.w1 = (const unsigned short*)w1.bf; q.w2 = (const unsigned short*)w2.bf; q.w3a = (const unsigned short*)w3a.bf;
-  q.w3b = (const unsigned short*)w3b.bf; q.w4 = (const unsigned short*)w4.bf;
+  q.w1 = w1.bf.get(); q.w2 = w2.bf.get(); q.w3a = w3a.bf.get();
+  q.w3b = w3b.bf.get(); q.w4 = w4.bf.get();
   q.b1 = w1.bias; q.b2 = w2.bias; q.b3 = w3a.bias; q.b4 = w4.bias;
   q.s1 = A_alloc<float>(c, 128); q.t1 = A_alloc<float>(c, 128); q.s2 = A_alloc<float>(c, 256); q.t2 = A_alloc<float>(c, 256);
   q.part1 = A_alloc<float>(c, (size_t)2 * 128 * q.ntiles);
@@ -757,7 +769,7 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
     for (int i = 0; i < 2; ++i) {
       const PeP& o = *src[i]; PeWSide& d = *dst[i];
       d.F = o.F; d.Cin = o.Cin; d.valid = o.valid; d.rows = o.rows; d.npts = npts[i]; d.nrounds = cdiv(o.rows, PEW_ROUND_ROWS);
-      d.img = c->pew_img[i]; d.w3b = o.w3b; d.b1 = o.b1; d.b2 = o.b2; d.b3 = o.b3; d.s1 = o.s1; d.t1 = o.t1;
+      d.img = c->pew_img[i].get(); d.w3b = o.w3b; d.b1 = o.b1; d.b2 = o.b2; d.b3 = o.b3; d.s1 = o.s1; d.t1 = o.t1;
       d.live = (live && !(i == 1 && packb)) ? lv.live[i] : nullptr;
       if (i == 1) { d.ptab = pk_tab; d.phdr = pk_hdr; }
       d.part2 = A_alloc<float>(c, (size_t)2 * 256 * std::max(nwg[i], 1)); d.cnt2 = A_alloc<int>(c, std::max(nwg[i], 1));
@@ -873,7 +885,7 @@ void heads3_fused(Fwd& f, const float* X, int ldx, int rows, int g_per, int g_st
   q.X = X; q.ldx = ldx; q.rows = rows; q.gather_per = g_per; q.gather_stride = g_stride; q.gather_off = g_off; q.out = out;
   for (int i = 0; i < 3; ++i) {
     const PW &w1 = c->pw[names[i] + ".mlp.0"], &w2 = c->pw[names[i] + ".mlp.3"];
-    q.w1[i] = (const unsigned short*)w1.bf; q.b1[i] = w1.bias; q.w2[i] = (const unsigned short*)w2.bf; q.b2[i] = w2.bias;
+    q.w1[i] = w1.bf.get(); q.b1[i] = w1.bias; q.w2[i] = w2.bf.get(); q.b2[i] = w2.bias;
     q.lng[i] = fptr(c, names[i] + ".mlp.1.weight"); q.lnb[i] = fptr(c, names[i] + ".mlp.1.bias");
   }
   c->prof_flops = 3.0 * 2.0 * rows * (128.0 * 256 + 256.0 * 160);
@@ -912,11 +924,11 @@ int head_impl(RiftCtx* c, const RiftCtx::Head& h) {
     // cat_x_proj (bf16) -> pi_head first Linear (exact fp32, live parameters) -> LayerNorm -> ReLU -> Linear -> masked logits: one launch
     PiFwdP q; memset(&q, 0, sizeof(q));
     q.Q = h.Q; q.rows = nQ; q.rows_per_scene = R * M;
-    q.wq = (const unsigned short*)c->pw[PD + ".cat_x_proj.q"].bf; q.bq = c->pw[PD + ".cat_x_proj.q"].bias; q.x0p = h.x0p;
+    q.wq = c->pw[PD + ".cat_x_proj.q"].bf.get(); q.bq = c->pw[PD + ".cat_x_proj.q"].bias; q.x0p = h.x0p;
     q.w1 = fptr(c, PD + ".pi_head.mlp.0.weight"); q.b1 = fptr(c, PD + ".pi_head.mlp.0.bias");
     q.lng = fptr(c, PD + ".pi_head.mlp.1.weight"); q.lnb = fptr(c, PD + ".pi_head.mlp.1.bias");
     q.w2 = fptr(c, PD + ".pi_head.mlp.3.weight"); q.b2 = fptr(c, PD + ".pi_head.mlp.3.bias");
-    q.r_kpm = h.r_kpm; q.M = M; q.eps = 1e-5f; q.QF = h.QF; q.Hpi = h.Hpi; q.prob = h.prob; q.nonfinite = c->nonfinite;
+    q.r_kpm = h.r_kpm; q.M = M; q.eps = 1e-5f; q.QF = h.QF; q.Hpi = h.Hpi; q.prob = h.prob; q.nonfinite = c->nonfinite.get();
     c->prof_flops = 2.0 * nQ * (2.0 * 128 * 128 + 128);
     launch(c, "pi_forward_kernel", pi_forward_kernel, dim3(cdiv(nQ, PI_ROWS)), dim3(512), (size_t)PI_LDS, q);
   } else {
@@ -924,12 +936,11 @@ int head_impl(RiftCtx* c, const RiftCtx::Head& h) {
     g.gbias = h.x0p; g.gb_div = R * M; g.gb_mod = 0;
     gemm(c, g, c->pw[PD + ".cat_x_proj.q"], h.fp32);
     // pi head: first Linear straight from the live (trainable) fp32 parameters, exact-fp32 MFMA
-    PW w; w.N = 128; w.K = 128; w.Kp = 128; w.Npad = 128;
-    w.f32 = (float*)fptr(c, PD + ".pi_head.mlp.0.weight"); w.bias = fptr(c, PD + ".pi_head.mlp.0.bias");
-    gemm(c, mk(h.QF, 128, nQ, w, h.Hpi, 128), w, true);
+    PWShape w; w.N = 128; w.K = 128; w.Kp = 128; w.Npad = 128; w.bias = fptr(c, PD + ".pi_head.mlp.0.bias");
+    gemm(c, mk(h.QF, 128, nQ, w, h.Hpi, 128), (const void*)fptr(c, PD + ".pi_head.mlp.0.weight"), true);
     launch(c, "pi_tail_kernel", pi_tail_kernel, dim3(cdiv(nQ, 4)), dim3(256), 0, (const float*)h.Hpi, nQ, M, fptr(c, PD + ".pi_head.mlp.1.weight"),
            fptr(c, PD + ".pi_head.mlp.1.bias"), fptr(c, PD + ".pi_head.mlp.3.weight"), fptr(c, PD + ".pi_head.mlp.3.bias"),
-           (const uint8_t*)h.r_kpm, 1e-5f, h.prob, c->nonfinite);
+           (const uint8_t*)h.r_kpm, 1e-5f, h.prob, c->nonfinite.get());
   }
   tap(c, "q_final", h.QF, (int64_t)nQ * 128);
   if (h.need_traj && !h.fp32 && c->heads_fused) {
@@ -995,16 +1006,16 @@ int prepare_inputs(Fwd& f) {
   const bool rank_in_prep = f.nat_compact && c->rank_in_prep && A <= 256;
   if (rank_in_prep) {
     const int sl = c->parity;
-    if (c->rk_cap[sl] < bs) {                          // (a batch beyond the arrays of rift_ctx_create: a fresh zeroed array, epochs start over)
-      HIPCHK(c, hipDeviceSynchronize());               // nothing in flight reads the old array; and the zeros below are in place before ANY stream's launch
-      if (c->rk_pub[sl]) { HIPCHK(c, hipFree(c->rk_pub[sl])); c->rk_pub[sl] = nullptr; c->rk_cap[sl] = 0; }
-      const int cap = std::max(2 * bs, 4096);
-      HIPCHK(c, hipMalloc((void**)&c->rk_pub[sl], (size_t)cap * sizeof(unsigned long long)));
-      HIPCHK(c, hipMemset(c->rk_pub[sl], 0, (size_t)cap * sizeof(unsigned long long)));
+    DevBuf<unsigned long long>& pub = c->rk_pub[sl];
+    bool fresh = false;                                // (a batch beyond the arrays of rift_ctx_create: a fresh zeroed array, epochs start over)
+    if (pub.cap() < (size_t)bs) HIPCHK(c, hipDeviceSynchronize());      // nothing in flight reads the old array; and the zeros below are in place before ANY stream's launch
+    DEVCHK(c, pub.reserve((size_t)bs, (size_t)std::max(2 * bs, 4096), &fresh));
+    if (fresh) {
+      HIPCHK(c, hipMemset(pub.get(), 0, pub.cap() * sizeof(unsigned long long)));
       HIPCHK(c, hipDeviceSynchronize());               // (hipMemset of device memory may return before the fill has run, and the preparation is launched on a non-blocking stream)
-      c->rk_cap[sl] = cap; c->rk_epoch[sl] = 0;
+      c->rk_epoch[sl] = 0;
     }
-    q.nrk = bs; q.rk_pub = c->rk_pub[sl]; q.aidx = f.nat_aidx; q.cnt = f.nat_cnt; q.fail = c->nonfinite; q.rk_fault = c->rank_fault ? 1 : 0;
+    q.nrk = bs; q.rk_pub = c->rk_pub[sl].get(); q.aidx = f.nat_aidx; q.cnt = f.nat_cnt; q.fail = c->nonfinite.get(); q.rk_fault = c->rank_fault ? 1 : 0;
     if (!c->dry) { if (++c->rk_epoch[sl] == 0u) c->rk_epoch[sl] = 1u; }      // (epoch 0 = "never written")
     q.rk_epoch = c->rk_epoch[sl];
     q.hist_agent = nullptr;                            // (the scene blocks derive the marks themselves)
@@ -1075,7 +1086,7 @@ void history_encoder(Fwd& f) {
       if (lv == 0) {   // level 0 as wave-private, register-resident tiles (no workgroup barriers): nat_l0w.h
         NatL0WP q; memset(&q, 0, sizeof(q));
         q.aidx = f.nat_aidx; q.cnt = f.nat_cnt;
-        q.F9 = f.F9; q.nseq = nA; q.img = c->l0w_img; q.par = c->l0w_par; q.Oc = Oc[0]; q.Ocb = Ocb[0]; q.Xnext = Xin[1];
+        q.F9 = f.F9; q.nseq = nA; q.img = c->l0w_img.get(); q.par = c->l0w_par.get(); q.Oc = Oc[0]; q.Ocb = Ocb[0]; q.Xnext = Xin[1];
         { if (c->dg.nat_ts == 1) { q.ts = A_alloc<long long>(c, 64); tap(c, "nat_ts", (float*)q.ts, 128); } }
         q.droppath[0] = f.drop ? dpr[0] : 0.f; q.droppath[1] = f.drop ? dpr[1] : 0.f; q.seed = f.seed; q.stream = f.next_stream(); f.stream_id += 4;
         q.ds = f.ds;
@@ -1086,7 +1097,7 @@ void history_encoder(Fwd& f) {
       if (lv == 1) {   // level 1 likewise (weights swapped through LDS between the two layers): nat_l1w.h
         NatL1WP q; memset(&q, 0, sizeof(q));
         q.cnt = f.nat_cnt;
-        q.X = Xin[1]; q.nseq = nA; q.img = c->l1w_img; q.par = c->l1w_par; q.Oc = Oc[1]; q.Ocb = Ocb[1]; q.Xnext = Xin[2];
+        q.X = Xin[1]; q.nseq = nA; q.img = c->l1w_img.get(); q.par = c->l1w_par.get(); q.Oc = Oc[1]; q.Ocb = Ocb[1]; q.Xnext = Xin[2];
         q.droppath[0] = f.drop ? dpr[2] : 0.f; q.droppath[1] = f.drop ? dpr[3] : 0.f; q.seed = f.seed; q.stream = f.next_stream(); f.stream_id += 4;
         q.ds = f.ds;
         c->prof_flops = 2.0 * rows * (20.0 * C * C + 4.0 * ksz * C) + (rows / 2) * 2.0 * 3 * C * 2 * C;
@@ -1096,7 +1107,7 @@ void history_encoder(Fwd& f) {
       {   // level 2: wave-private tiles of 3 agents, the two layers' weights streamed through LDS (nat_l2w.h)
         NatL2WP q; memset(&q, 0, sizeof(q));
         q.cnt = f.nat_cnt;
-        q.X = Xin[2]; q.nseq = nA; q.img = c->l2w_img; q.par = c->l2w_par; q.Oc = Oc[2]; q.Ocb = Ocb[2];
+        q.X = Xin[2]; q.nseq = nA; q.img = c->l2w_img.get(); q.par = c->l2w_par.get(); q.Oc = Oc[2]; q.Ocb = Ocb[2];
         q.droppath[0] = f.drop ? dpr[4] : 0.f; q.droppath[1] = f.drop ? dpr[5] : 0.f; q.seed = f.seed; q.stream = f.next_stream(); f.stream_id += 4;
         q.ds = f.ds;
         { if (c->dg.nat_ts == 3) { q.ts = A_alloc<long long>(c, 64); tap(c, "nat_ts", (float*)q.ts, 128); } }
@@ -1162,9 +1173,9 @@ void history_encoder(Fwd& f) {
     FpnP q; memset(&q, 0, sizeof(q));
     for (int i = 0; i < 3; ++i) {
       const PW& w = c->pw[HE + ".lateral_convs." + std::to_string(i)];
-      q.oc[i] = Oc[i]; q.ocb[i] = Ocb[i]; q.wl[i] = (const unsigned short*)w.bf; q.bl[i] = w.bias;
+      q.oc[i] = Oc[i]; q.ocb[i] = Ocb[i]; q.wl[i] = w.bf.get(); q.bl[i] = w.bias;
     }
-    q.wf = (const unsigned short*)c->pw[HE + ".fpn_conv.last"].bf; q.bf_ = c->pw[HE + ".fpn_conv.last"].bias;
+    q.wf = c->pw[HE + ".fpn_conv.last"].bf.get(); q.bf_ = c->pw[HE + ".fpn_conv.last"].bias;
     q.out = f.nat_out; q.nA = nA; q.cnt = fused ? f.nat_cnt : nullptr; q.aidx = fused ? f.nat_aidx : nullptr;
     c->prof_flops = 2.0 * nA * (2.0 * 128 * (96 + 192 + 384) + 256.0 * 128);
     launch(c, "fpn_tail_kernel", fpn_tail_kernel, dim3(cdiv(nA, FPN_AG)), dim3(512), (size_t)FPN_LDS, q);
@@ -1197,9 +1208,9 @@ void ego_token(Fwd& f) {
   f.x_ego = A_alloc<float>(c, (size_t)bs * 128);
   if (!f.fp32 && c->ego_fused) {
     EgoP q; memset(&q, 0, sizeof(q));
-    q.cs = B->current_state; q.cs_ld = B->cs_ld; q.lw = c->ego_w; q.lb = c->ego_b; q.pos = fptr(c, EG + ".pos_embed");
-    q.wkv = (const unsigned short*)c->pw[EG + ".attn.kv"].bf; q.bkv = c->pw[EG + ".attn.kv"].bias; q.q = eq;
-    q.wo = (const unsigned short*)c->pw[EG + ".attn.out_proj"].bf; q.bo = c->pw[EG + ".attn.out_proj"].bias;
+    q.cs = B->current_state; q.cs_ld = B->cs_ld; q.lw = c->ego_w.get(); q.lb = c->ego_b.get(); q.pos = fptr(c, EG + ".pos_embed");
+    q.wkv = c->pw[EG + ".attn.kv"].bf.get(); q.bkv = c->pw[EG + ".attn.kv"].bias; q.q = eq;
+    q.wo = c->pw[EG + ".attn.out_proj"].bf.get(); q.bo = c->pw[EG + ".attn.out_proj"].bias;
     q.out = f.x_ego; q.bs = bs; q.drop_p = f.drop ? 0.75f : 0.f; q.seed = f.seed; q.stream = f.drop ? f.next_stream() : 0;
     q.ds = f.ds;
     c->prof_flops = 2.0 * bs * (6.0 * 128 * 256 + 128.0 * 128);
@@ -1207,7 +1218,7 @@ void ego_token(Fwd& f) {
   } else {
   float* E = A_alloc<float>(c, (size_t)bs * 6 * 128);
   launch(c, "ego_token_kernel", ego_token_kernel, dim3(cdiv((long long)bs * 6 * 128, 256)), dim3(256), 0, B->current_state, B->cs_ld,
-         (const float*)c->ego_w, (const float*)c->ego_b, fptr(c, EG + ".pos_embed"), bs, E);
+         (const float*)c->ego_w.get(), (const float*)c->ego_b.get(), fptr(c, EG + ".pos_embed"), bs, E);
   float* EKV = A_alloc<float>(c, (size_t)bs * 6 * 256);
   gemm(c, mk(E, 128, bs * 6, c->pw[EG + ".attn.kv"], EKV, 256), c->pw[EG + ".attn.kv"], f.fp32);
   uint8_t* edrop = nullptr;
@@ -1240,7 +1251,7 @@ int build_q0(Fwd& f) {
   f.Q = A_alloc<float>(c, (size_t)nQ * 128);
   if (!f.fp32 && c->pi_fused) {
     Q0P q; memset(&q, 0, sizeof(q));
-    q.r_emb = f.r_emb; q.nL = nL; q.M = M; q.wr = (const unsigned short*)c->pw[PD + ".q_proj.r"].bf; q.br = c->pw[PD + ".q_proj.r"].bias;
+    q.r_emb = f.r_emb; q.nL = nL; q.M = M; q.wr = c->pw[PD + ".q_proj.r"].bf.get(); q.br = c->pw[PD + ".q_proj.r"].bias;
     q.Mb = Mb; q.Q = f.Q;
     c->prof_flops = 2.0 * nL * 128.0 * 128;
     launch(c, "q0_fused_kernel", q0_fused_kernel, dim3(cdiv(nL, 16)), dim3(256), 0, q);
@@ -1279,7 +1290,7 @@ int map_and_embeddings(Fwd& f) {
       w.count = 3;
       for (int i = 0; i < 3; ++i) {
         const FourierP& o = q3.e[i]; FoWSide& d = w.e[i];
-        d.in = o.in; d.in_ld = o.in_ld; d.rows = o.rows; d.D = o.D; d.wrap_dim = o.wrap_dim; d.img = c->fow_img[i]; d.par = c->fow_par[i];
+        d.in = o.in; d.in_ld = o.in_ld; d.rows = o.rows; d.D = o.D; d.wrap_dim = o.wrap_dim; d.img = c->fow_img[i].get(); d.par = c->fow_par[i].get();
         d.Y = o.Y; d.accumulate = o.accumulate; d.rep = o.D == 1 ? 2 : 1; d.nwg = cdiv(cdiv(o.rows, 16), 8 * d.rep);
       }
       launch_call(c, "fo_w_kernel", [&] { fow_launch(w, c->stream); });
@@ -1333,23 +1344,23 @@ void scene_encoder(Fwd& f) {
       EncBlockW& w = ep.blk[i];
       w.ln1_g = fptr(c, p + ".norm1.weight"); w.ln1_b = fptr(c, p + ".norm1.bias");
       w.ln2_g = fptr(c, p + ".norm2.weight"); w.ln2_b = fptr(c, p + ".norm2.bias");
-      w.wqkv = c->enc_wqkv[i]; w.bqkv = c->enc_bqkv[i];
-      w.wo = (const unsigned short*)c->pw[p + ".attn.out_proj"].bf; w.bo = c->pw[p + ".attn.out_proj"].bias;
-      w.w1 = (const unsigned short*)c->pw[p + ".mlp.fc1"].bf; w.b1 = c->pw[p + ".mlp.fc1"].bias;
-      w.w2 = (const unsigned short*)c->pw[p + ".mlp.fc2"].hid; w.b2 = c->pw[p + ".mlp.fc2"].bias;      // (hidden-layer operand words: pack_hid)
+      w.wqkv = c->enc_wqkv[i].get(); w.bqkv = c->enc_bqkv[i].get();
+      w.wo = c->pw[p + ".attn.out_proj"].bf.get(); w.bo = c->pw[p + ".attn.out_proj"].bias;
+      w.w1 = c->pw[p + ".mlp.fc1"].bf.get(); w.b1 = c->pw[p + ".mlp.fc1"].bias;
+      w.w2 = c->pw[p + ".mlp.fc2"].hid.get(); w.b2 = c->pw[p + ".mlp.fc2"].bias;      // (hidden-layer operand words: pack_hid)
       w.droppath = f.drop ? edpr[i] : 0.f;
     }
-    ep.norm_g = fptr(c, "norm.weight"); ep.norm_b = fptr(c, "norm.bias"); ep.nonfinite = c->nonfinite;
+    ep.norm_g = fptr(c, "norm.weight"); ep.norm_b = fptr(c, "norm.bias"); ep.nonfinite = c->nonfinite.get();
     ep.ds = f.ds; ep.dbg = c->no_skip ? 1 : 0;
     if (c->dg.enc_ts) { ep.ts = A_alloc<long long>(c, 256); tap(c, "enc_ts", (float*)ep.ts, 512); }
     c->prof_flops = 4.0 * bs * N * (2.0 * 128 * 384 + 4.0 * N * 128 + 2.0 * 128 * 128 + 4.0 * 128 * 512);
     if (c->dec_fused && R <= 8 && ENC_NW == 8) {   // the decoder kernel will run: emit its cross-attention K | V operand fragments here
       f.enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * (f.enc_wide ? 96 : DECW_KV_FRAGS) * 512);      // (wide: the dense per-head image, dec_kv.h)
-      ep.wkv = (const unsigned short*)c->pw["planning_decoder.kv_all"].bf; ep.bkv = c->pw["planning_decoder.kv_all"].bias;
+      ep.wkv = c->pw["planning_decoder.kv_all"].bf.get(); ep.bkv = c->pw["planning_decoder.kv_all"].bias;
       ep.KT = f.enc_KT;
       f.kpm_c = A_alloc<uint8_t>(c, (size_t)bs * (f.enc_wide ? 112 : 96)); ep.kpm_c = f.kpm_c;
       f.enc_x0p = A_alloc<float>(c, (size_t)bs * 128);
-      ep.wx0 = (const unsigned short*)c->pw["planning_decoder.cat_x_proj.x"].bf; ep.x0p = f.enc_x0p;
+      ep.wx0 = c->pw["planning_decoder.cat_x_proj.x"].bf.get(); ep.x0p = f.enc_x0p;
       c->prof_flops += 2.0 * bs * N * 128.0 * 1024;
     }
     if (f.enc_wide) launch_call(c, "enc_fused112_kernel", [&] { enc112_launch(ep, c->stream); });
@@ -1358,7 +1369,7 @@ void scene_encoder(Fwd& f) {
     EncWP eq; memset(&eq, 0, sizeof(eq));
     eq.X = f.X; eq.Y = f.ENC; eq.kpm = f.kpm; eq.bs = bs; eq.N = N; eq.seed = f.seed; eq.stream = f.next_stream(); f.stream_id += 8;
     eq.KVs = A_alloc<unsigned short>(c, (size_t)bs * 96 * 512);
-    eq.img = c->encw_img; eq.par = c->encw_par; eq.nonfinite = c->nonfinite;
+    eq.img = c->encw_img.get(); eq.par = c->encw_par.get(); eq.nonfinite = c->nonfinite.get();
     if (c->dec_fused && R <= 16) { f.enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * 96 * 512); eq.DKV = f.enc_KT; }   // the decoder's (dense-variant) operands
     for (int i = 0; i < 4; ++i) eq.droppath[i] = f.drop ? edpr[i] : 0.f;
     eq.ds = f.ds;
@@ -1523,7 +1534,7 @@ int planning_decoder(Fwd& f) {
   if (c->dec_fused && !f.fp32 && dec_dense && !f.enc_KT) {   // its K | V^T operand fragments from the (layer-wise) encoder's output
     f.enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * 96 * 512);
     DecKvP kq; memset(&kq, 0, sizeof(kq));
-    kq.ENC = f.ENC; kq.bs = bs; kq.N = N; kq.wkv = (const unsigned short*)c->pw[PD + ".kv_all"].bf; kq.bkv = c->pw[PD + ".kv_all"].bias; kq.KV = f.enc_KT;
+    kq.ENC = f.ENC; kq.bs = bs; kq.N = N; kq.wkv = c->pw[PD + ".kv_all"].bf.get(); kq.bkv = c->pw[PD + ".kv_all"].bias; kq.KV = f.enc_KT;
     c->prof_flops = 2.0 * bs * N * 128.0 * 1024;
     launch(c, "dec_kv_frag_kernel", dec_kv_frag_kernel, dim3(bs), dim3(512), (size_t)DEC_KV_LDS, kq);
   }
@@ -1532,7 +1543,7 @@ int planning_decoder(Fwd& f) {
     dq.Q = f.Q; dq.kpm = f.kpm; dq.r_kpm = f.r_kpm; dq.q_kpm = f.q_kpm; dq.q_bs = f.q_bs; dq.q_off = f.q_off; dq.bs = bs; dq.N = N; dq.R = R; dq.dropout = dp; dq.seed = f.seed;
     if (f.kpm_c) { dq.kpm = f.kpm_c; dq.N = f.enc_wide ? 112 : 96; dq.compact = 1; }      // (the encoder compacted its rows: its own key padding, valid keys a prefix)
     dq.stream = f.next_stream(); f.stream_id += 64;
-    dq.KV = f.enc_KT; dq.img = c->decw_img; dq.par = c->decw_par; dq.nonfinite = c->nonfinite;
+    dq.KV = f.enc_KT; dq.img = c->decw_img.get(); dq.par = c->decw_par.get(); dq.nonfinite = c->nonfinite.get();
     dq.ds = f.ds;
     if (c->dg.dec_ts) { dq.ts = A_alloc<long long>(c, 1024); tap(c, "dec_ts", (float*)dq.ts, 2048); }      // [0, 128): boundaries of wave 0; [128 + 112 w, ...): arrivals of wave w
     dq.dbg = c->dg.dec_dbg | (c->no_skip ? 64 : 0);
@@ -1597,7 +1608,7 @@ int policy_and_ego_heads(Fwd& f) {
     const PW &h0 = c->pw["hidden_proj.0"], &h2 = c->pw["hidden_proj.2"], &r0 = c->pw["ref_free_decoder.mlp.0"], &r3 = c->pw["ref_free_decoder.mlp.3"];
     EgoHeadsP q; memset(&q, 0, sizeof(q));
     q.X = f.ENC; q.ldx = N * 128; q.rows = bs;
-    q.wh0 = (const unsigned short*)h0.bf; q.wh2 = (const unsigned short*)h2.bf; q.wr0 = (const unsigned short*)r0.bf; q.wr3 = (const unsigned short*)r3.bf;
+    q.wh0 = h0.bf.get(); q.wh2 = h2.bf.get(); q.wr0 = r0.bf.get(); q.wr3 = r3.bf.get();
     q.bh0 = h0.bias; q.bh2 = h2.bias; q.br0 = r0.bias; q.br3 = r3.bias;
     q.lng = fptr(c, "ref_free_decoder.mlp.1.weight"); q.lnb = fptr(c, "ref_free_decoder.mlp.1.bias");
     q.hidden = out->hidden; q.ref = (f.need_traj && out->ref_free_trajectory) ? out->ref_free_trajectory : nullptr;
@@ -1748,10 +1759,9 @@ int rift_ctx_create(int device, RiftCtx** ctx) {
   c->device = device;
   if (hipSetDevice(device) != hipSuccess) { delete c; return RIFT_ERR_HIP; }
   read_switches(c);
-  if (hipMalloc((void**)&c->nonfinite, sizeof(int)) != hipSuccess || hipMemset(c->nonfinite, 0, sizeof(int)) != hipSuccess) { delete c; return RIFT_ERR_HIP; }
+  if (c->nonfinite.reserve(1) != 0 || hipMemset(c->nonfinite.get(), 0, sizeof(int)) != hipSuccess) { delete c; return RIFT_ERR_HIP; }
   for (int i = 0; i < RIFT_DEFER_SLOTS; ++i) {      // the in-launch ranking's published counts (kernels.h: rank_scene_body): zero = "never written"
-    if (hipMalloc((void**)&c->rk_pub[i], 4096 * sizeof(unsigned long long)) != hipSuccess || hipMemset(c->rk_pub[i], 0, 4096 * sizeof(unsigned long long)) != hipSuccess) { delete c; return RIFT_ERR_HIP; }
-    c->rk_cap[i] = 4096;
+    if (c->rk_pub[i].reserve(4096) != 0 || hipMemset(c->rk_pub[i].get(), 0, 4096 * sizeof(unsigned long long)) != hipSuccess) { delete c; return RIFT_ERR_HIP; }
   }
   if (hipDeviceSynchronize() != hipSuccess) { delete c; return RIFT_ERR_HIP; }      // (the zeros are in place before any stream launches a kernel that reads them)
   int rc = set_lds_attrs(c);
@@ -1763,34 +1773,6 @@ int rift_ctx_create(int device, RiftCtx** ctx) {
 void rift_ctx_destroy(RiftCtx* c) {
   if (!c) return;
   if (c->comm) { (void)rccl_api(nullptr).CommDestroy(c->comm); c->comm = nullptr; }
-  if (c->tick_scratch) (void)hipFree(c->tick_scratch);
-  if (c->ro_raw) (void)hipFree(c->ro_raw);
-  for (void* p : c->owned) (void)hipFree(p);
-  for (int i = 0; i < RIFT_DEFER_SLOTS; ++i) if (c->arenas[i]) (void)hipFree(c->arenas[i]);
-  if (c->l_S) (void)hipFree(c->l_S);
-  if (c->l_cnt) (void)hipFree(c->l_cnt);
-  if (c->l_dz) (void)hipFree(c->l_dz);
-  if (c->l_partial) (void)hipFree(c->l_partial);
-  if (c->l_sink) (void)hipFree(c->l_sink);
-  if (c->ego_w) (void)hipFree(c->ego_w);
-  if (c->ego_b) (void)hipFree(c->ego_b);
-  if (c->enc_idx) (void)hipFree(c->enc_idx);
-  if (c->cr_buf) { (void)hipFree(c->cr_buf); (void)hipFree(c->cr_part); }
-  if (c->clip_part) (void)hipFree(c->clip_part);
-  if (c->nonfinite) (void)hipFree(c->nonfinite);
-  for (int i = 0; i < RIFT_DEFER_SLOTS; ++i) if (c->rk_pub[i]) (void)hipFree(c->rk_pub[i]);
-  if (c->l0w_img) { (void)hipFree(c->l0w_img); (void)hipFree(c->l0w_par); }
-  if (c->l1w_img) { (void)hipFree(c->l1w_img); (void)hipFree(c->l1w_par); }
-  if (c->l2w_img) { (void)hipFree(c->l2w_img); (void)hipFree(c->l2w_par); }
-  if (c->encw_img) { (void)hipFree(c->encw_img); (void)hipFree(c->encw_par); }
-  if (c->decw_img) { (void)hipFree(c->decw_img); (void)hipFree(c->decw_par); }
-  for (int i = 0; i < 2; ++i) if (c->pew_img[i]) (void)hipFree(c->pew_img[i]);
-  for (int i = 0; i < 3; ++i) if (c->fow_img[i]) { (void)hipFree(c->fow_img[i]); (void)hipFree(c->fow_par[i]); }
-  if (c->ev_prep) (void)hipEventDestroy(c->ev_prep);
-  if (c->ev_join2) (void)hipEventDestroy(c->ev_join2);
-  if (c->side && c->side_owned) (void)hipStreamDestroy(c->side);
-  if (c->ev_fork) { (void)hipEventDestroy(c->ev_fork); (void)hipEventDestroy(c->ev_join); }
-  for (int i = 0; i < 4; ++i) { if (c->enc_wqkv[i]) (void)hipFree(c->enc_wqkv[i]); if (c->enc_bqkv[i]) (void)hipFree(c->enc_bqkv[i]); }
   delete c;
 }
 
@@ -1828,8 +1810,8 @@ static int pack_history_encoder(RiftCtx* c) {
     q.fn_g = fptr(c, HE + ".norm0.weight"); q.fn_b = fptr(c, HE + ".norm0.bias");
     q.w_ds = fptr(c, HE + ".levels.0.downsample.reduction.weight"); q.ds_g = fptr(c, HE + ".levels.0.downsample.norm.weight"); q.ds_b = fptr(c, HE + ".levels.0.downsample.norm.bias");
     if (!c->err.empty()) return RIFT_ERR_ARG;
-    if (!c->l0w_img) { HIPCHK(c, hipMalloc((void**)&c->l0w_img, (size_t)L0W_NFRAG * 1024)); HIPCHK(c, hipMalloc((void**)&c->l0w_par, (size_t)L0W_NPAR * 4)); }
-    l0w_pack(q, c->l0w_img, c->l0w_par, c->stream);
+    DEVCHK(c, c->l0w_img.reserve((size_t)L0W_NFRAG * 512)); DEVCHK(c, c->l0w_par.reserve(L0W_NPAR));
+    l0w_pack(q, c->l0w_img.get(), c->l0w_par.get(), c->stream);
   }
   {  // wave-private level-1 kernel (nat_l1w.h)
     NatL1WSrc q; memset(&q, 0, sizeof(q));
@@ -1837,16 +1819,16 @@ static int pack_history_encoder(RiftCtx* c) {
     q.fn_g = fptr(c, HE + ".norm1.weight"); q.fn_b = fptr(c, HE + ".norm1.bias");
     q.w_ds = fptr(c, HE + ".levels.1.downsample.reduction.weight"); q.ds_g = fptr(c, HE + ".levels.1.downsample.norm.weight"); q.ds_b = fptr(c, HE + ".levels.1.downsample.norm.bias");
     if (!c->err.empty()) return RIFT_ERR_ARG;
-    if (!c->l1w_img) { HIPCHK(c, hipMalloc((void**)&c->l1w_img, (size_t)L1W_NFRAG * 1024)); HIPCHK(c, hipMalloc((void**)&c->l1w_par, (size_t)L1W_NPAR * 4)); }
-    l1w_pack(q, c->l1w_img, c->l1w_par, c->stream);
+    DEVCHK(c, c->l1w_img.reserve((size_t)L1W_NFRAG * 512)); DEVCHK(c, c->l1w_par.reserve(L1W_NPAR));
+    l1w_pack(q, c->l1w_img.get(), c->l1w_par.get(), c->stream);
   }
   {  // wave-private level-2 kernel (nat_l2w.h)
     NatL2WSrc q; memset(&q, 0, sizeof(q));
     nat_blocks_src(c, q, 2);
     q.fn_g = fptr(c, HE + ".norm2.weight"); q.fn_b = fptr(c, HE + ".norm2.bias");
     if (!c->err.empty()) return RIFT_ERR_ARG;
-    if (!c->l2w_img) { HIPCHK(c, hipMalloc((void**)&c->l2w_img, (size_t)2 * L2W_BLK_FRAGS * 1024)); HIPCHK(c, hipMalloc((void**)&c->l2w_par, (size_t)L2W_NPAR * 4)); }
-    l2w_pack(q, c->l2w_img, c->l2w_par, c->stream);
+    DEVCHK(c, c->l2w_img.reserve((size_t)2 * L2W_BLK_FRAGS * 512)); DEVCHK(c, c->l2w_par.reserve(L2W_NPAR));
+    l2w_pack(q, c->l2w_img.get(), c->l2w_par.get(), c->stream);
   }
   {  // fpn_conv at the last step: taps 0,1 only -> [128][256]
     const Param* w = find(c, HE + ".fpn_conv.weight");
@@ -1876,8 +1858,8 @@ static int pack_streamed_images(RiftCtx* c) {
       q.dkv_w[i] = fptr(c, p + ".in_proj_weight"); q.dkv_b[i] = fptr(c, p + ".in_proj_bias");
     }
     if (!c->err.empty()) return RIFT_ERR_ARG;
-    if (!c->encw_img) { HIPCHK(c, hipMalloc((void**)&c->encw_img, (size_t)(4 * ENCW_LAYER_FRAGS + ENCW_TAIL_FRAGS) * 1024)); HIPCHK(c, hipMalloc((void**)&c->encw_par, (size_t)ENCW_NPAR * 4)); }
-    encw_pack(q, c->encw_img, c->encw_par, c->stream);
+    DEVCHK(c, c->encw_img.reserve((size_t)(4 * ENCW_LAYER_FRAGS + ENCW_TAIL_FRAGS) * 512)); DEVCHK(c, c->encw_par.reserve(ENCW_NPAR));
+    encw_pack(q, c->encw_img.get(), c->encw_par.get(), c->stream);
   }
   {  // wave-private Fourier embeddings (fo_w.h): weight streams + parameter blocks of the three embeddings of the fused launch
     const std::string emb[3] = {"pos_emb", "map_encoder.speed_limit_emb", PD + ".r_pos_emb"};
@@ -1893,8 +1875,8 @@ static int pack_streamed_images(RiftCtx* c) {
       q.og = fptr(c, emb[i] + ".to_out.0.weight"); q.ob = fptr(c, emb[i] + ".to_out.0.bias");
       q.wo = fptr(c, emb[i] + ".to_out.2.weight"); q.bo = fptr(c, emb[i] + ".to_out.2.bias"); q.freqs = fptr(c, emb[i] + ".freqs.weight");
       if (!c->err.empty()) return RIFT_ERR_ARG;
-      if (!c->fow_img[i]) { HIPCHK(c, hipMalloc((void**)&c->fow_img[i], (size_t)7 * 32 * 1024)); HIPCHK(c, hipMalloc((void**)&c->fow_par[i], (size_t)FOW_NPAR * 4)); }
-      fow_pack(q, c->fow_img[i], c->fow_par[i], c->stream);
+      DEVCHK(c, c->fow_img[i].reserve((size_t)7 * 32 * 512)); DEVCHK(c, c->fow_par[i].reserve(FOW_NPAR));
+      fow_pack(q, c->fow_img[i].get(), c->fow_par[i].get(), c->stream);
     }
   }
   {  // wave-private PointsEncoder pass B (pe_w.h): W1 | W2 | W3a streams of the two encoders
@@ -1904,8 +1886,8 @@ static int pack_streamed_images(RiftCtx* c) {
       PeWSrc q; q.Cin = cin[i];
       q.w1 = fptr(c, enc[i] + ".first_mlp.0.weight"); q.w2 = fptr(c, enc[i] + ".first_mlp.3.weight"); q.w3 = fptr(c, enc[i] + ".second_mlp.0.weight");
       if (!c->err.empty()) return RIFT_ERR_ARG;
-      if (!c->pew_img[i]) HIPCHK(c, hipMalloc((void**)&c->pew_img[i], (size_t)PEW_FRAGS * 1024));
-      pew_pack(q, c->pew_img[i], c->stream);
+      DEVCHK(c, c->pew_img[i].reserve((size_t)PEW_FRAGS * 512));
+      pew_pack(q, c->pew_img[i].get(), c->stream);
     }
   }
   {  // wave-private decoder kernel (dec_w.h): the layers' weight stream and parameter blocks
@@ -1924,19 +1906,22 @@ static int pack_streamed_images(RiftCtx* c) {
     }
     q.m_pos = fptr(c, PD + ".m_pos");
     if (!c->err.empty()) return RIFT_ERR_ARG;
-    if (!c->decw_img) { HIPCHK(c, hipMalloc((void**)&c->decw_img, (size_t)4 * DECW_LAYER_FRAGS * 1024)); HIPCHK(c, hipMalloc((void**)&c->decw_par, (size_t)4 * DECW_PAR_LAYER * 4)); }
-    decw_pack(q, c->decw_img, c->decw_par, c->stream);
+    DEVCHK(c, c->decw_img.reserve((size_t)4 * DECW_LAYER_FRAGS * 512)); DEVCHK(c, c->decw_par.reserve((size_t)4 * DECW_PAR_LAYER));
+    decw_pack(q, c->decw_img.get(), c->decw_par.get(), c->stream);
   }
   return RIFT_OK;
 }
+
+// what the entries that launch on the model's images answer while there is none (RIFT_ERR_STATE, ahead of any launch or allocation)
+static const std::string NOT_LOADED = ": no model is loaded (rift_model_load is missing, or the last one failed)";
 
 int rift_model_load(RiftCtx* c, const RiftTensorDesc* params, int n, void* stream) {
   if (!c || !params) return RIFT_ERR_ARG;
   c->err.clear();
   c->stream = (hipStream_t)stream;
   HIPCHK(c, hipSetDevice(c->device));
-  for (void* p : c->owned) (void)hipFree(p);
-  c->owned.clear(); c->pw.clear(); c->params.clear(); c->wconst.clear();
+  c->loaded = false;                    // (until this load has succeeded there is no model: the entries that launch refuse to run)
+  c->pw.clear(); c->params.clear(); c->wconst.clear();      // (frees the images and the weight-only products)
   c->dry_need = 0;                      // (the first forward on new weights sizes its arena again: it also computes the weight-only products)
   for (int i = 0; i < n; ++i) {
     Param p; p.data = params[i].data; p.numel = params[i].numel; p.ndim = params[i].ndim;
@@ -1948,13 +1933,13 @@ int rift_model_load(RiftCtx* c, const RiftTensorDesc* params, int n, void* strea
   TRY(pack_rows(c, EG + ".attn.q", EG + ".attn.in_proj_weight", EG + ".attn.in_proj_bias", 0, 128, 128));
   TRY(pack_rows(c, EG + ".attn.kv", EG + ".attn.in_proj_weight", EG + ".attn.in_proj_bias", 128, 256, 256));
   TRY(pack_linear(c, EG + ".attn.out_proj"));
-  if (!c->ego_w) { HIPCHK(c, hipMalloc((void**)&c->ego_w, 6 * 128 * 4)); HIPCHK(c, hipMalloc((void**)&c->ego_b, 6 * 128 * 4)); }
+  DEVCHK(c, c->ego_w.reserve(6 * 128)); DEVCHK(c, c->ego_b.reserve(6 * 128));
   for (int i = 0; i < 6; ++i) {
     const float* w = fptr(c, EG + ".linears." + std::to_string(i) + ".weight");
     const float* b = fptr(c, EG + ".linears." + std::to_string(i) + ".bias");
     if (!w || !b) return RIFT_ERR_ARG;
-    HIPCHK(c, hipMemcpyAsync(c->ego_w + i * 128, w, 128 * 4, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->ego_b + i * 128, b, 128 * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->ego_w.get() + i * 128, w, 128 * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->ego_b.get() + i * 128, b, 128 * 4, hipMemcpyDeviceToDevice, c->stream));
   }
   TRY(pack_points_encoder(c, "map_encoder.polygon_encoder"));
   TRY(pack_fourier(c, "map_encoder.speed_limit_emb", 1));
@@ -1973,16 +1958,16 @@ int rift_model_load(RiftCtx* c, const RiftTensorDesc* params, int n, void* strea
         const int head = 2 * ch + (seg < 4 ? (seg >> 1) : (seg - 4));
         for (int d = 0; d < 32; ++d) idx[ch * 192 + seg * 32 + d] = part * 128 + head * 32 + d;
       }
-    if (!c->enc_idx) HIPCHK(c, hipMalloc((void**)&c->enc_idx, sizeof(idx)));
-    HIPCHK(c, hipMemcpyAsync(c->enc_idx, idx, sizeof(idx), hipMemcpyHostToDevice, c->stream));
+    DEVCHK(c, c->enc_idx.reserve(384));
+    HIPCHK(c, hipMemcpyAsync(c->enc_idx.get(), idx, sizeof(idx), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));   // idx is a stack buffer
     for (int i = 0; i < 4; ++i) {
       const std::string p = "encoder_blocks." + std::to_string(i) + ".attn";
       const float* w = fptr(c, p + ".in_proj_weight"); const float* bsrc = fptr(c, p + ".in_proj_bias");
       if (!w || !bsrc) return RIFT_ERR_ARG;
-      if (!c->enc_wqkv[i]) { HIPCHK(c, hipMalloc((void**)&c->enc_wqkv[i], 384 * 128 * 2)); HIPCHK(c, hipMalloc((void**)&c->enc_bqkv[i], 384 * 4)); }
-      hipLaunchKernelGGL(pack_rows_indexed_kernel, dim3(cdiv(384 * 128, 256)), dim3(256), 0, c->stream, w, bsrc, (const int*)c->enc_idx,
-                         384, 128, c->enc_wqkv[i], c->enc_bqkv[i]);
+      DEVCHK(c, c->enc_wqkv[i].reserve(384 * 128)); DEVCHK(c, c->enc_bqkv[i].reserve(384));
+      hipLaunchKernelGGL(pack_rows_indexed_kernel, dim3(cdiv(384 * 128, 256)), dim3(256), 0, c->stream, w, bsrc, (const int*)c->enc_idx.get(),
+                         384, 128, c->enc_wqkv[i].get(), c->enc_bqkv[i].get());
     }
   }
   const char* ap[3] = {"loc_predictor", "yaw_predictor", "vel_predictor"};
@@ -2029,14 +2014,15 @@ int rift_model_load(RiftCtx* c, const RiftTensorDesc* params, int n, void* strea
 int rift_forward(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, int flags, uint32_t seed, void* stream) {
   if (!c || !B || !out) return RIFT_ERR_ARG;
   c->err.clear();
-  if (!c->loaded) { c->err = "rift_forward before rift_model_load"; return RIFT_ERR_STATE; }
+  if (!c->loaded) { c->err = "rift_forward before rift_model_load" + NOT_LOADED; return RIFT_ERR_STATE; }
   if (B->bs <= 0 || B->A <= 0 || B->Mp <= 0 || B->R <= 0 || B->S < 0 || B->T < 21) { c->err = "bad batch dims"; return RIFT_ERR_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
   c->stream = (hipStream_t)stream;
   // deferred-head forwards cycle through the arenas (the caller guarantees that the head / loss of the forward RIFT_DEFER_SLOTS calls back is
   // over, i.e. that this arena is free again); every other forward runs in arena 0
   c->parity = (flags & RIFT_F_DEFER_HEAD) ? (c->parity + 1) % RIFT_DEFER_SLOTS : 0;
-  c->arena = c->arenas[c->parity]; c->arena_cap = c->arena_caps[c->parity];
+  DevBuf<char>& slot = c->arenas[c->parity];
+  c->arena = slot.get(); c->arena_cap = slot.cap();
   // pass 1 (dry): size the activation arena; pass 2: launch.  The sizes depend on the batch dimensions, the flags and the data-parallel
   // descriptor only: a forward like the previous one skips pass 1 (it is half of the call's host time, which bounds a small-batch step)
   long long omask = 0;      // which outputs are wanted
@@ -2054,16 +2040,13 @@ int rift_forward(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
     memcpy(c->dry_key, dkey, sizeof(dkey)); c->dry_need = c->arena_off;
   }
   const size_t need = c->dry_need;
-  if (need > c->arena_cap) {
+  if (need > slot.cap()) {
     // (the whole device: with the deferred head and the prepare stream the arena's last readers sit on streams other than the caller's)
     HIPCHK(c, hipDeviceSynchronize());
-    if (c->arena) HIPCHK(c, hipFree(c->arena));
-    c->arena = nullptr; c->arena_cap = 0;
-    const size_t cap = need + (need >> 3);
-    HIPCHK(c, hipMalloc((void**)&c->arena, cap));
-    c->arena_cap = cap;
+    const int grown = slot.reserve(need, need + (need >> 3));
+    c->arena = slot.get(); c->arena_cap = slot.cap();      // (also when it failed: the view never outlives the block)
+    DEVCHK(c, grown);
   }
-  c->arenas[c->parity] = c->arena; c->arena_caps[c->parity] = c->arena_cap;
   c->dry = false; c->arena_off = 0; c->taps.clear();
   // diagnostic: RIFT_POISON_ARENA=<byte> fills the scratch arena before every forward (0xFF = NaN pattern), so that a kernel reading
   // scratch it never wrote shows up as NaN / as run-to-run differences instead of depending on what the memory held before
@@ -2086,6 +2069,7 @@ int rift_forward(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
 int rift_forward_head_back(RiftCtx* c, int back, void* stream) {
   if (!c || back < 0 || back >= RIFT_DEFER_SLOTS) return RIFT_ERR_ARG;
   c->err.clear();
+  if (!c->loaded) { c->err = "rift_forward_head without a RIFT_F_DEFER_HEAD forward" + NOT_LOADED; return RIFT_ERR_STATE; }
   const int slot = (c->parity - back + RIFT_DEFER_SLOTS) % RIFT_DEFER_SLOTS;
   if (!c->head[slot].valid) { c->err = "rift_forward_head without a RIFT_F_DEFER_HEAD forward"; return RIFT_ERR_STATE; }
   HIPCHK(c, hipSetDevice(c->device));
@@ -2109,32 +2093,22 @@ int rift_forward_head(RiftCtx* c, void* stream) { return abi::rift_forward_head_
 
 // scratch of pi_backward_kernel: dz per row and one 16897-float partial per workgroup of RIFT_PI_BWD_ROWS rows (grow-only)
 static int pi_backward_scratch(RiftCtx* c, int rows, int nwg) {
-  if ((size_t)rows > c->l_cap_rows) {
-    if (c->l_dz) (void)hipFree(c->l_dz);
-    c->l_dz = nullptr; c->l_cap_rows = 0;
-    HIPCHK(c, hipMalloc((void**)&c->l_dz, (size_t)rows * 4)); c->l_cap_rows = rows;
-  }
-  if ((size_t)nwg > c->l_cap_wg) {
-    if (c->l_partial) (void)hipFree(c->l_partial);
-    c->l_partial = nullptr; c->l_cap_wg = 0;
-    HIPCHK(c, hipMalloc((void**)&c->l_partial, (size_t)nwg * RIFT_PI_NPARAM * 4)); c->l_cap_wg = nwg;
-  }
+  DEVCHK(c, c->l_dz.reserve((size_t)rows));
+  DEVCHK(c, c->l_partial.reserve((size_t)nwg * RIFT_PI_NPARAM));
   return RIFT_OK;
 }
 
 int rift_loss_backward(RiftCtx* c, int kind, const RiftLossIn* in, const RiftLossOut* out, void* stream) {
   if (!c || !in || !out || !out->stats || !out->flat_grad_sum) return RIFT_ERR_ARG;
   c->err.clear();
+  if (!c->loaded) { c->err = "rift_loss_backward before rift_forward" + NOT_LOADED; return RIFT_ERR_STATE; }
   if (!c->last_qfinal) { c->err = "rift_loss_backward before rift_forward"; return RIFT_ERR_STATE; }
   HIPCHK(c, hipSetDevice(c->device));
   c->stream = (hipStream_t)stream; c->dry = false;
   const int bs = c->last_bs, R = c->last_R, M = 12, G = R * M, rows = bs * G;
   if (G > 64 * 16) { c->err = "group too large"; return RIFT_ERR_ARG; }
   const int nwg = cdiv(rows, RIFT_PI_BWD_ROWS);
-  if ((size_t)bs > c->l_cap_bs) {
-    if (c->l_S) { (void)hipFree(c->l_S); (void)hipFree(c->l_cnt); }
-    HIPCHK(c, hipMalloc((void**)&c->l_S, bs * 8)); HIPCHK(c, hipMalloc((void**)&c->l_cnt, bs * 8)); c->l_cap_bs = bs;
-  }
+  DEVCHK(c, c->l_S.reserve((size_t)bs)); DEVCHK(c, c->l_cnt.reserve((size_t)bs));
   TRY(pi_backward_scratch(c, rows, nwg));
   LossP p; memset(&p, 0, sizeof(p));
   p.kind = kind; p.bs = bs; p.G = G; p.M = M; p.prob = c->last_prob; p.r_kpm = c->last_rkpm;
@@ -2142,7 +2116,7 @@ int rift_loss_backward(RiftCtx* c, int kind, const RiftLossIn* in, const RiftLos
   p.valid = in->group_valid_mask; p.action_mode = (const long long*)in->action_mode;
   p.scal_a = kind == RIFT_LOSS_PPO ? in->advantage : in->returns; p.old_log_prob = in->old_log_prob;
   p.clip_eps = in->clip_epsilon; p.lambda_entropy = in->lambda_entropy;
-  p.S = c->l_S; p.cnt = c->l_cnt; p.dlogit = c->l_dz; p.argmax_rm = (long long*)out->argmax_rm;
+  p.S = c->l_S.get(); p.cnt = c->l_cnt.get(); p.dlogit = c->l_dz.get(); p.argmax_rm = (long long*)out->argmax_rm;
   if ((kind == RIFT_LOSS_RIFT || kind == RIFT_LOSS_GRPO) && (!p.old_logits || !p.adv64 || !p.valid)) { c->err = "missing loss inputs"; return RIFT_ERR_ARG; }
   if (kind == RIFT_LOSS_GRPO && !p.ref_logits) { c->err = "missing ref logits"; return RIFT_ERR_ARG; }
   if (kind == RIFT_LOSS_PPO && (!p.action_mode || !p.scal_a || !p.old_log_prob)) { c->err = "missing ppo inputs"; return RIFT_ERR_ARG; }
@@ -2154,10 +2128,10 @@ int rift_loss_backward(RiftCtx* c, int kind, const RiftLossIn* in, const RiftLos
   else launch(c, "loss_kernel", loss_kernel<16>, lgrid, lblock, 0, p);
   const std::string PH = "planning_decoder.pi_head.mlp.";
   launch(c, "pi_backward_kernel", pi_backward_kernel, dim3(nwg), dim3(256), 0, (const float*)c->last_qfinal, (const float*)c->last_hpi,
-         (const float*)c->l_dz, rows, fptr(c, PH + "1.weight"), fptr(c, PH + "1.bias"), fptr(c, PH + "3.weight"), 1e-5f,
-         c->l_partial);
-  launch(c, "loss_reduce_kernel", loss_reduce_kernel, dim3(cdiv(RIFT_PI_NPARAM, 256)), dim3(256), 0, (const float*)c->l_partial, nwg,
-         out->flat_grad_sum, (const double*)c->l_S, (const double*)c->l_cnt, bs, out->stats, out->exchange);
+         (const float*)c->l_dz.get(), rows, fptr(c, PH + "1.weight"), fptr(c, PH + "1.bias"), fptr(c, PH + "3.weight"), 1e-5f,
+         c->l_partial.get());
+  launch(c, "loss_reduce_kernel", loss_reduce_kernel, dim3(cdiv(RIFT_PI_NPARAM, 256)), dim3(256), 0, (const float*)c->l_partial.get(), nwg,
+         out->flat_grad_sum, (const double*)c->l_S.get(), (const double*)c->l_cnt.get(), bs, out->stats, out->exchange);
   HIPCHK(c, hipGetLastError());
   return RIFT_OK;
 }
@@ -2165,6 +2139,7 @@ int rift_loss_backward(RiftCtx* c, int kind, const RiftLossIn* in, const RiftLos
 int rift_head_backward(RiftCtx* c, const float* dlogits, int bs, int R, const RiftLossOut* out, int accumulate, void* stream) {
   if (!c || !dlogits || !out || !out->flat_grad_sum) return RIFT_ERR_ARG;
   c->err.clear();
+  if (!c->loaded) { c->err = "rift_head_backward before rift_forward" + NOT_LOADED; return RIFT_ERR_STATE; }
   if (!c->last_qfinal) { c->err = "rift_head_backward before rift_forward"; return RIFT_ERR_STATE; }
   if (bs != c->last_bs || R != c->last_R) {
     c->err = "rift_head_backward: dlogits of (" + std::to_string(bs) + ", " + std::to_string(R) + ", 12) against a forward of (" +
@@ -2175,15 +2150,15 @@ int rift_head_backward(RiftCtx* c, const float* dlogits, int bs, int R, const Ri
   c->stream = (hipStream_t)stream; c->dry = false;
   const int M = 12, rows = bs * R * M, nwg = cdiv(rows, RIFT_PI_BWD_ROWS);
   TRY(pi_backward_scratch(c, rows, nwg));
-  if (!c->l_sink) HIPCHK(c, hipMalloc((void**)&c->l_sink, 2 * sizeof(double)));
-  launch(c, "head_dz_kernel", head_dz_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, dlogits, (const uint8_t*)c->last_rkpm, rows, M, c->l_dz);
+  DEVCHK(c, c->l_sink.reserve(2));
+  launch(c, "head_dz_kernel", head_dz_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, dlogits, (const uint8_t*)c->last_rkpm, rows, M, c->l_dz.get());
   const std::string PH = "planning_decoder.pi_head.mlp.";
   launch(c, "pi_backward_kernel", pi_backward_kernel, dim3(nwg), dim3(256), 0, (const float*)c->last_qfinal, (const float*)c->last_hpi,
-         (const float*)c->l_dz, rows, fptr(c, PH + "1.weight"), fptr(c, PH + "1.bias"), fptr(c, PH + "3.weight"), 1e-5f,
-         c->l_partial);
+         (const float*)c->l_dz.get(), rows, fptr(c, PH + "1.weight"), fptr(c, PH + "1.bias"), fptr(c, PH + "3.weight"), 1e-5f,
+         c->l_partial.get());
   // (no objective: zero scenes, the two sums land in the sink)
-  launch(c, "loss_reduce_kernel", loss_reduce_kernel, dim3(cdiv(RIFT_PI_NPARAM, 256)), dim3(256), 0, (const float*)c->l_partial, nwg,
-         out->flat_grad_sum, (const double*)nullptr, (const double*)nullptr, 0, c->l_sink, (double*)nullptr);
+  launch(c, "loss_reduce_kernel", loss_reduce_kernel, dim3(cdiv(RIFT_PI_NPARAM, 256)), dim3(256), 0, (const float*)c->l_partial.get(), nwg,
+         out->flat_grad_sum, (const double*)nullptr, (const double*)nullptr, 0, c->l_sink.get(), (double*)nullptr);
   if (out->grad_w1 || out->grad_b1 || out->grad_ln_w || out->grad_ln_b || out->grad_w2 || out->grad_b2)
     launch(c, "head_scatter_kernel", head_scatter_kernel, dim3(cdiv(RIFT_PI_NPARAM, 256)), dim3(256), 0, (const float*)out->flat_grad_sum,
            out->grad_w1, out->grad_b1, out->grad_ln_w, out->grad_ln_b, out->grad_w2, out->grad_b2, accumulate);
@@ -2325,10 +2300,10 @@ int rift_check_finite(RiftCtx* c, void* stream) {
   if (!c) return RIFT_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   int flag = 0;
-  HIPCHK(c, hipMemcpyAsync(&flag, c->nonfinite, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(c, hipMemcpyAsync(&flag, c->nonfinite.get(), sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));
   if (!flag) return RIFT_OK;
-  HIPCHK(c, hipMemsetAsync(c->nonfinite, 0, sizeof(int), (hipStream_t)stream));
+  HIPCHK(c, hipMemsetAsync(c->nonfinite.get(), 0, sizeof(int), (hipStream_t)stream));
   c->err = (flag & 2) ? "the in-launch ranking of the history encoder's sequences gave up waiting for a predecessor (kernels.h: rank_scene_body): the forward's "
                         "results are invalid; non-finite flag raised"
                       : "non-finite decoder queries (the reference asserts torch.isfinite(q).all(), planning_decoder.py:175)";
@@ -2362,9 +2337,9 @@ int rift_clip_grad_norm(RiftCtx* c, float* const* grads, const int64_t* numels, 
   for (int i = 0; i < n; ++i) { L.g[i] = grads[i]; L.n[i] = numels[i]; tot += numels[i]; }
   L.count = n;
   const int nb = (int)std::min<long long>(64, (tot + 2047) / 2048);
-  if (!c->clip_part) HIPCHK(c, hipMalloc((void**)&c->clip_part, 64 * 8));
-  launch(c, "clip_norm_partial_kernel", clip_norm_partial_kernel, dim3(nb), dim3(256), 0, L, c->clip_part);
-  launch(c, "clip_scale_kernel", clip_scale_kernel, dim3(nb), dim3(256), 0, L, (const double*)c->clip_part, nb, max_norm, total_norm);
+  DEVCHK(c, c->clip_part.reserve(64));
+  launch(c, "clip_norm_partial_kernel", clip_norm_partial_kernel, dim3(nb), dim3(256), 0, L, c->clip_part.get());
+  launch(c, "clip_scale_kernel", clip_scale_kernel, dim3(nb), dim3(256), 0, L, (const double*)c->clip_part.get(), nb, max_norm, total_norm);
   HIPCHK(c, hipGetLastError());
   return RIFT_OK;
 }
@@ -2424,12 +2399,8 @@ int rift_update_tail(RiftCtx* c, const RiftLossOut* out, int accumulate, float m
 // ---- PPO critic ------------------------------------------------------------------------------------
 static int critic_scratch(RiftCtx* c, int n) {
   const size_t need = (size_t)((n + 15) / 16 * 16) * (128 + 4 * 256 + 1 + 2 * 128 + 2);
-  if (need > c->cr_cap) {
-    if (c->cr_buf) { (void)hipFree(c->cr_buf); (void)hipFree(c->cr_part); }
-    HIPCHK(c, hipMalloc((void**)&c->cr_buf, need * 4));
-    HIPCHK(c, hipMalloc((void**)&c->cr_part, (size_t)((n + 15) / 16) * 8));
-    c->cr_cap = need;
-  }
+  DEVCHK(c, c->cr_buf.reserve(need));
+  DEVCHK(c, c->cr_part.reserve((size_t)((n + 15) / 16)));
   return RIFT_OK;
 }
 
@@ -2461,8 +2432,8 @@ static int critic_backward_sums(RiftCtx* c, const RiftCritic* w, const float* st
   const int np = (n + 15) / 16 * 16, nwg = cdiv(n, 16);
   CriticRowsP p; memset(&p, 0, sizeof(p));
   p.w = critic_w(w); p.state = state; p.target = target; p.dvalue = dvalue; p.n = n;
-  p.sn = c->cr_buf; p.h1 = p.sn + (size_t)np * 128; p.h2 = p.h1 + (size_t)np * 256; p.dh1 = p.h2 + (size_t)np * 256;
-  p.dh2 = p.dh1 + (size_t)np * 256; p.dout = p.dh2 + (size_t)np * 256; p.sl1_part = c->cr_part;
+  p.sn = c->cr_buf.get(); p.h1 = p.sn + (size_t)np * 128; p.h2 = p.h1 + (size_t)np * 256; p.dh1 = p.h2 + (size_t)np * 256;
+  p.dh2 = p.dh1 + (size_t)np * 256; p.dout = p.dh2 + (size_t)np * 256; p.sl1_part = c->cr_part.get();
   p.gsa = p.dout + np; p.gss = p.gsa + (size_t)np * 128; p.gva = p.gss + (size_t)np * 128; p.gvs = p.gva + np;
   launch(c, "critic_rows_kernel", critic_rows_kernel, dim3(nwg), dim3(256), 0, p);
   launch(c, "critic_outer_sum_kernel", critic_outer_sum_kernel, dim3(cdiv(256 * 128, 256)), dim3(256), 0, (const float*)p.dh1, 256, (const float*)p.sn, 128, n, scale, flat);
@@ -2486,7 +2457,7 @@ int rift_critic_loss_backward(RiftCtx* c, const RiftCritic* w, const float* stat
   c->stream = (hipStream_t)stream; c->dry = false;
   // flat = -sum_rows d SmoothL1 / d theta
   TRY(critic_backward_sums(c, w, state, reward_sum, nullptr, n, -1.f, flat));
-  launch(c, "critic_stats_kernel", critic_stats_kernel, dim3(1), dim3(64), 0, (const double*)c->cr_part, cdiv(n, 16), stats);
+  launch(c, "critic_stats_kernel", critic_stats_kernel, dim3(1), dim3(64), 0, (const double*)c->cr_part.get(), cdiv(n, 16), stats);
   HIPCHK(c, hipGetLastError());
   return RIFT_OK;
 }
@@ -2564,15 +2535,14 @@ int rift_op_linear(RiftCtx* c, const float* X, int M, int K, const float* W, con
   const std::string key = "__op_linear__";
   // transient pack (test entry point; not on the hot path)
   TRY(pack(c, key, W, N, N, K, 0, 0, K, 0, 0, 0, bias));
-  PW w = c->pw[key];
+  const PW& w = c->pw[key];
   GemmP g = mk(X, K, M, w, Y, N);
   if (ln_w) { g.pro = PRO_LN; g.pg = ln_w; g.pb = ln_b; }
   g.act = act;
   gemm(c, g, w, fp32 != 0);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(w.bf); (void)hipFree(w.f32);
-  c->owned.pop_back(); c->owned.pop_back();
-  c->pw.erase(key);
+  const hipError_t done = hipStreamSynchronize(c->stream);
+  c->pw.erase(key);                     // (frees the transient images, whatever the wait answered)
+  HIPCHK(c, done);
   HIPCHK(c, hipGetLastError());
   return RIFT_OK;
 }
@@ -2587,7 +2557,7 @@ int rift_op_linear_bench(RiftCtx* c, const float* X, int M, int K, const float* 
   c->stream = (hipStream_t)stream; c->dry = false;
   const std::string key = "__op_linear_bench__";
   TRY(pack(c, key, W, N, N, K, 0, 0, K, 0, 0, 0, bias));
-  PW w = c->pw[key];
+  const PW& w = c->pw[key];
   GemmP g = mk(X, K, M, w, Y, N);
   if (ln_w) { g.pro = PRO_LN; g.pg = ln_w; g.pb = ln_b; }
   g.act = act;
@@ -2603,8 +2573,6 @@ int rift_op_linear_bench(RiftCtx* c, const float* X, int M, int K, const float* 
   HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
   if (ms_out) *ms_out = ms / reps;
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  (void)hipFree(w.bf); (void)hipFree(w.f32);
-  c->owned.pop_back(); c->owned.pop_back();
   c->pw.erase(key);
   return RIFT_OK;
 }
@@ -2709,13 +2677,10 @@ int rift_rollout(RiftCtx* c, const RiftRolloutIO* io, void* stream) {
   p.speed_buf = io->speed_buf; p.speed_ptr = (int*)io->speed_ptr; p.speed_len = (int*)io->speed_len;
   p.center = io->center; p.angle = io->angle; p.speed = io->speed; p.acc = io->acc; p.ang_vel = io->ang_vel; p.ang_acc = io->ang_acc;
   p.vertices = io->vertices; p.closest_index = (int*)io->closest_index; p.aim_idx = (int*)io->aim_idx;
-  if ((size_t)io->G * RIFT_RO_LEN * 4 > c->ro_cap) {          // the raw speed history between the two kernels (grown behind a device-wide wait)
-    if (c->ro_raw) { HIPCHK(c, hipDeviceSynchronize()); (void)hipFree(c->ro_raw); c->ro_raw = nullptr; c->ro_cap = 0; }
-    const size_t cap = std::max((size_t)io->G * 2, (size_t)256) * RIFT_RO_LEN * 4;
-    HIPCHK(c, hipMalloc((void**)&c->ro_raw, cap));
-    c->ro_cap = cap;
-  }
-  p.raw_speed = c->ro_raw;
+  const size_t ro_need = (size_t)io->G * RIFT_RO_LEN;          // the raw speed history between the two kernels (grown behind a device-wide wait)
+  if (ro_need > c->ro_raw.cap() && c->ro_raw.get()) HIPCHK(c, hipDeviceSynchronize());
+  DEVCHK(c, c->ro_raw.reserve(ro_need, std::max((size_t)io->G * 2, (size_t)256) * RIFT_RO_LEN));
+  p.raw_speed = c->ro_raw.get();
   if (!p.center || !p.angle || !p.speed || !p.acc || !p.ang_vel || !p.ang_acc || !p.vertices || !p.closest_index || !p.aim_idx) return RIFT_ERR_ARG;
   if (c->ro8) hipLaunchKernelGGL(rollout8_kernel, dim3(cdiv(io->G, 8)), dim3(64), (size_t)RIFT_RO_LDS_BYTES, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(rollout_kernel, dim3(cdiv(io->G, 64)), dim3(64), (size_t)RIFT_RO_LDS_BYTES, (hipStream_t)stream, p);
@@ -2751,11 +2716,8 @@ static int group_advantage_tick(RiftCtx* c, const float* trajectory, int Rb, int
                o_aa = take(G * TR * 4), o_vert = take(G * TR * 8 * 4), o_cl = take(G * 79 * 4), o_aim = take(G * 79 * 4), o_raw = take(G * TR * 4);
   const size_t o_ov = take((size_t)std::max(Nmax, 1) * Ts * 8 * 8), o_col = take(G * Ts), o_offr = take(G * TR), o_ret = take(G * 8);
   const size_t per = off, need = per * (size_t)std::min(K, RIFT_TICK_CHUNK);
-  if (need > c->tick_cap) {
-    if (c->tick_scratch) { HIPCHK(c, hipDeviceSynchronize()); (void)hipFree(c->tick_scratch); c->tick_scratch = nullptr; c->tick_cap = 0; }
-    HIPCHK(c, hipMalloc((void**)&c->tick_scratch, need * 2));
-    c->tick_cap = need * 2;
-  }
+  if (need > c->tick_scratch.cap() && c->tick_scratch.get()) HIPCHK(c, hipDeviceSynchronize());
+  DEVCHK(c, c->tick_scratch.reserve(need, need * 2));
   const hipStream_t st = (hipStream_t)stream;
   for (int k0 = 0; k0 < K; k0 += RIFT_TICK_CHUNK) {
     TickArr a; memset(&a, 0, sizeof(a));
@@ -2765,7 +2727,7 @@ static int group_advantage_tick(RiftCtx* c, const float* trajectory, int Rb, int
     int gmax = 0, nmax = 0;
     for (int j = 0; j < a.K; ++j) {
       const RiftTickCBV& v = cbvs[k0 + j];
-      char* S = c->tick_scratch + per * (size_t)j;
+      char* S = c->tick_scratch.get() + per * (size_t)j;
       TickK& d = a.d[j];
       d.traj = trajectory + (size_t)v.batch_index * Rb * M * Tfull * 6; d.G = v.R * M; d.Tfull = Tfull; d.Pmax = v.Pmax; d.N = v.n_actors; d.H = v.H; d.W = v.W;
       d.ref_pos = v.ref_pos; d.ref_ang = v.ref_angle; d.ref_len = (const int*)v.ref_len;

@@ -1,0 +1,165 @@
+"""The engine context's device memory over its lifetime: scratch that grows and is reused, weight images replaced by a reload, a reload
+that fails, and create / close cycles (csrc/devmem.h: DevBuf; tests/test_devmem_host.py runs the type's failure paths on the CPU).
+
+Default-size scenes with one to three reference lines: the allocation logic does not depend on the scene size.  Forwards run with
+no_drop=True, bn_update=False, so that two engines given the same input answer bit for bit; every comparison is torch.equal."""
+import pytest
+import torch
+
+from rift_amd import _ffi
+from rift_amd import synthetic as syn
+from tests import helpers as H
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+MISSING = "planning_decoder.pi_head.mlp.3.weight"
+_cache = {}
+
+
+def _to_dev(d):
+    return {k: _to_dev(v) if isinstance(v, dict) else (v.to(DEV) if torch.is_tensor(v) else v) for k, v in d.items()}
+
+
+def _batch(n):
+    if n not in _cache:
+        _cache[n] = _to_dev(syn.collate_scenes([syn.make_scene(7300 + 10 * n + i, r_min=1, r_max=3) for i in range(n)]))
+    return _cache[n]
+
+
+def _sd(perturbed=False):
+    """The test weights on the device (built once: an engine binds views onto them); perturbed: every floating tensor scaled by 1.05."""
+    if "sd" not in _cache:
+        _cache["sd"] = {k: v.to(DEV) for k, v in H.weights().items()}
+        _cache["sd2"] = {k: (v * 1.05 if v.is_floating_point() else v.clone()) for k, v in _cache["sd"].items()}
+    return _cache["sd2" if perturbed else "sd"]
+
+
+def _forward(eng, batch):
+    out = eng.forward(batch["cur_pluto_feature_torch"], no_drop=True, bn_update=False)
+    return [out["probability"].clone(), out["hidden"].clone()]
+
+
+def _step(eng, batch):
+    """forward + loss_backward("rift") + loss_finalize: [probability, hidden, stats, flat, loss, the six gradients]"""
+    res = _forward(eng, batch)
+    stats, flat, _ = eng.loss_backward("rift", batch)
+    grads = {k: torch.zeros_like(_sd()["planning_decoder.pi_head." + k]) for k in _ffi.PI_KEYS}
+    loss = eng.loss_finalize(stats, flat, grads)
+    return res + [stats.clone(), flat.clone(), loss.clone()] + [grads[k] for k in _ffi.PI_KEYS]
+
+
+def _critic(eng, n):
+    ci, csd = H.critic_inputs(n), _cache.setdefault("csd", {k: v.to(DEV) for k, v in H.critic_weights().items()})
+    state, dv = ci["state"].to(DEV), ci["advantage"].to(DEV)
+    return [eng.critic_forward(csd, state).clone(), eng.critic_backward(csd, state, dv).clone()]
+
+
+def _same(a, b):
+    assert len(a) == len(b)
+    for i, (x, y) in enumerate(zip(a, b)):
+        assert torch.equal(x, y), i
+
+
+def test_scratch_grows_and_is_reused_on_one_engine():
+    """One bf16 engine at 2, 5, 2 scenes (forward, loss, finalize; head_backward behind the 5-scene forward) and its critic at 3, 40, 3
+    rows: every result equals that of a fresh engine given the same input alone.  Each grow path of the arena, the loss scratch, the
+    pi_head backward scratch and the critic scratch runs once, and so does the reuse below capacity.  The growth of the ranking's
+    published words (rk_pub) needs a batch of more than 4096 scenes and is NOT exercised here."""
+    dz = torch.randn(5, 3, 12, generator=torch.Generator().manual_seed(5)).to(DEV)
+    eng = _ffi.Engine(DEV)
+    eng.load_state_dict(_sd())
+    got, got_head = [], None
+    for n in (2, 5, 2):
+        got.append(_step(eng, _batch(n)))
+        if n == 5:
+            dz = dz[:, :got[-1][0].shape[1]].contiguous()
+            got_head = eng.head_backward(dz).clone()
+    got_critic = [_critic(eng, n) for n in (3, 40, 3)]
+    torch.cuda.synchronize()
+    eng.close()
+    want = {}
+    for n, nc in ((2, 3), (5, 40)):
+        fresh = _ffi.Engine(DEV)
+        fresh.load_state_dict(_sd())
+        want[n] = _step(fresh, _batch(n))
+        if n == 5:
+            _same([got_head], [fresh.head_backward(dz).clone()])
+        want["c%d" % nc] = _critic(fresh, nc)
+        torch.cuda.synchronize()
+        fresh.close()
+    _same(got[0], want[2]); _same(got[1], want[5]); _same(got[2], want[2])
+    _same(got_critic[0], want["c3"]); _same(got_critic[1], want["c40"]); _same(got_critic[2], want["c3"])
+    assert not torch.equal(got[0][3], torch.zeros_like(got[0][3]))            # (the gradient sums are not trivially equal)
+
+
+def test_reload_replaces_the_images_and_the_weight_only_products():
+    eng = _ffi.Engine(DEV)
+    eng.load_state_dict(_sd())
+    out1 = _forward(eng, _batch(2))
+    eng.load_state_dict(_sd(perturbed=True))
+    out2 = _forward(eng, _batch(2))
+    assert not torch.equal(out1[0], out2[0]) and not torch.equal(out1[1], out2[1])
+    eng.load_state_dict(_sd())
+    _same(_forward(eng, _batch(2)), out1)
+    torch.cuda.synchronize()
+    eng.close()
+
+
+def test_failed_reload_is_refused_not_run():
+    """A load that fails leaves NO model: forward and loss_backward answer RIFT_ERR_STATE (-3) ahead of any launch instead of running on
+    the images the failed load freed; the next full load works as if nothing had happened."""
+    eng = _ffi.Engine(DEV)
+    eng.load_state_dict(_sd())
+    batch = _batch(2)
+    out1 = _forward(eng, batch)
+    with pytest.raises(RuntimeError, match="missing parameter"):
+        eng.load_state_dict({k: v for k, v in _sd().items() if k != MISSING})
+    with pytest.raises(RuntimeError, match=r"rift_forward failed \(-3\).*no model is loaded"):
+        eng.forward(batch["cur_pluto_feature_torch"], no_drop=True, bn_update=False)
+    with pytest.raises(RuntimeError, match=r"rift_loss_backward failed \(-3\).*no model is loaded"):
+        eng.loss_backward("rift", batch)
+    eng.load_state_dict(_sd())
+    _same(_forward(eng, batch), out1)
+    torch.cuda.synchronize()
+    eng.close()
+
+
+def test_nothing_accumulates_over_reloads_and_engine_lifetimes():
+    """Free device memory over six reload cycles on one engine and over six create / load / forward / loss / close cycles: after cycle 6
+    it is no lower than after cycle 1 by more than ONE footprint of an engine (free memory before Engine(...) minus free memory after
+    its first load and forward).  Derived, not measured: a leak of the image pool or of the arenas per cycle would lose five."""
+    batch, sds = _batch(2), (_sd(), _sd(perturbed=True))
+    warm = _ffi.Engine(DEV)                   # (the tensors, the library and torch's own blocks exist before the first reading)
+    warm.load_state_dict(sds[0])
+    _step(warm, batch)
+    torch.cuda.synchronize()
+    warm.close()
+
+    def free():
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info()[0]
+
+    free0 = free()
+    eng = _ffi.Engine(DEV)
+    eng.load_state_dict(sds[0])
+    _forward(eng, batch)
+    footprint = free0 - free()
+    assert footprint > 0
+    reloads = []
+    for i in range(6):
+        eng.load_state_dict(sds[(i + 1) % 2])
+        _forward(eng, batch)
+        reloads.append(free())
+    eng.close()
+    lives = []
+    for i in range(6):
+        e = _ffi.Engine(DEV)
+        e.load_state_dict(sds[0])
+        _step(e, batch)
+        torch.cuda.synchronize()
+        e.close()
+        lives.append(free())
+    print(f"lifetime: footprint {footprint} B; free-memory drift cycle 1 -> 6: reloads {reloads[0] - reloads[5]} B, "
+          f"create/close {lives[0] - lives[5]} B; after close vs before the first engine {free0 - lives[5]} B")
+    assert reloads[0] - reloads[5] <= footprint, (reloads, footprint)
+    assert lives[0] - lives[5] <= footprint, (lives, footprint)

@@ -262,6 +262,43 @@ int rift_loss_finalize(RiftCtx* ctx, const RiftLossOut* out, int accumulate, voi
  * custom_lightning.yaml:40-41).  total_norm: device float, may be NULL.  Not for PPO (the critic's gradients join the norm). */
 int rift_loss_finalize_clip(RiftCtx* ctx, const RiftLossOut* out, int accumulate, float max_norm, float* total_norm, void* stream);
 
+/* The settings of the two group objectives at run time.  rift_loss_backward compiles them in as the reference spells them
+ * (rift_trainer.py:165-170, grpo_trainer.py:178-182); rift_loss_backward_ex reads them from here.  With `params` RIFT and GRPO are ONE
+ * objective family and `kind` only names the set of defaults: per valid candidate j of a scene, with p / lp the softmax / log-softmax
+ * of the scene's logits (padded lines at -1e8, the lp of the ratio), ratio = exp(lp_j - lp_old_j), u = A_j ratio and
+ * c = A_j clamp(ratio, clip_low, clip_high),
+ *   objective_j = min(u, c)                                     -- then, for A_j < 0 and dual_clip != 0, max(., A_j dual_clip)
+ *               - kl_beta * ref_p_j (log ref_p_j - lp_j)        -- F.kl_div(log p, softmax(ref logits)), xlogy(0, 0) = 0
+ *               + entropy_coef * (-p_j lp_j)
+ * and stats = (sum_j objective_j, number of valid candidates).  Over a scene whose candidates are all valid the entropy terms sum to the
+ * scene's entropy H = -sum_j p_j log p_j; with a mask it is the masked part of that sum.  Its gradient on lp_j is -p_j (lp_j + 1), the
+ * expression of the PPO branch.  A term whose coefficient is 0 is not computed and its inputs are not read: ref_group_logits may be NULL
+ * when kl_beta == 0, for GRPO too.  RIFT_LOSS_GRPO with dual_clip = 3 and RIFT_LOSS_RIFT with kl_beta = 0.2 give the same bits.
+ * Arithmetic as in the compiled-in objectives: the clip bounds are compared and clamped in fp32, the floor and the KL term are formed in
+ * double, the KL gradient carries (float)kl_beta, the entropy term is the fp32 product widened to double. */
+typedef struct RiftObjectiveParams {
+  double clip_low, clip_high;  /* clamp(ratio, clip_low, clip_high); 0.8, 1.2 */
+  double dual_clip;            /* A < 0: objective = max(min(u, c), A * dual_clip); 0 = off.  RIFT 3.0, GRPO 0 */
+  double kl_beta;              /* RIFT 0, GRPO 0.2 */
+  double entropy_coef;         /* 0 */
+} RiftObjectiveParams;         /* 40 bytes */
+/* The defaults of `kind` (RIFT_LOSS_RIFT / RIFT_LOSS_GRPO; any other kind: RIFT_ERR_ARG, *out untouched).  No context, no device. */
+int rift_objective_params_default(int kind, RiftObjectiveParams* out);
+/* rift_loss_backward for kind RIFT / GRPO with the settings of `params`.  With rift_objective_params_default(kind) it writes the bits of
+ * rift_loss_backward into stats, flat_grad_sum and exchange, whether `terms` is given or not.
+ * terms: NULL, or device [8] f64 -- sums over the batch's valid candidates in a fixed order (the same bits from run to run; per-rank sums
+ * under data parallelism):
+ *   [0] sum of the surrogate min(u, c) after the dual clip        [3] candidates on the clamped side of min(u, c), which pass no gradient
+ *   [1] sum of the KL term, unweighted (0 when kl_beta == 0)          (those on the dual-clip floor not among them)
+ *   [2] sum of the entropy term, unweighted (0 when               [4] candidates on the dual-clip floor
+ *       entropy_coef == 0)                                        [5] valid candidates = stats[1]        [6], [7] written as 0
+ * so that stats[0] = terms[0] - kl_beta terms[1] + entropy_coef terms[2] up to fp64 reassociation.
+ * RIFT_ERR_ARG with a message in rift_last_error, decided on the host before any launch: params == NULL; a kind other than RIFT / GRPO
+ * (the other three have no settings beyond RiftLossIn); a field that is not finite; clip_low <= 0 or > 1; clip_high < 1; dual_clip != 0
+ * and <= 1; kl_beta < 0; entropy_coef < 0; kl_beta > 0 with in->ref_group_logits == NULL. */
+int rift_loss_backward_ex(RiftCtx* ctx, int kind, const RiftLossIn* in, const RiftObjectiveParams* params, const RiftLossOut* out,
+                          double* terms /* device [8] f64 or NULL */, void* stream);
+
 /* The vector-Jacobian product of planning_decoder.pi_head for an objective the CALLER wrote in PyTorch: what `loss.backward()` does through
  * MLPLayer (layers/mlp_layer.py:8-13) in the reference's LightningModule trainers, for any loss over `probability` (an entropy bonus on
  * get_rift_loss, another clip, a KL to a reference policy, a pairwise loss) -- rift_loss_backward covers the five compiled-in objectives only.

@@ -125,6 +125,32 @@ def eval_params(reward_model=None, gamma: float = 0.98, bbox_inflation_ratio: fl
     return p
 
 
+class RiftObjectiveParams(C.Structure):     # include/rift_hip.h: the settings of the RIFT / GRPO objective at run time (40 bytes)
+    _fields_ = [(n, C.c_double) for n in ("clip_low", "clip_high", "dual_clip", "kl_beta", "entropy_coef")]
+
+
+OBJECTIVE_KEYS = tuple(n for n, _ in RiftObjectiveParams._fields_)
+OBJECTIVE_KINDS = ("rift", "grpo")
+
+
+def objective_params(kind: str, **settings) -> RiftObjectiveParams:
+    """RiftObjectiveParams of kind 'rift' / 'grpo': the library's defaults of that kind (rift_objective_params_default) with `settings`
+    (clip_low, clip_high, dual_clip, kl_beta, entropy_coef) on top.  An unknown key or a kind without settings raises ValueError; what a
+    value may be (clip_low in (0, 1], ...) is the library's refusal, at the call that takes the struct."""
+    if kind not in OBJECTIVE_KINDS:
+        raise ValueError(f"objective settings exist for the kinds {list(OBJECTIVE_KINDS)}, not for {kind!r}")
+    unknown = sorted(set(settings) - set(OBJECTIVE_KEYS))
+    if unknown:
+        raise ValueError(f"objective: unknown key(s) {unknown}; known: {list(OBJECTIVE_KEYS)}")
+    p = RiftObjectiveParams()
+    rc = load_library().rift_objective_params_default(LOSS_KINDS[kind], C.byref(p))
+    if rc != 0:
+        raise RuntimeError(f"rift_objective_params_default failed ({rc})")
+    for k, v in settings.items():
+        setattr(p, k, float(v))
+    return p
+
+
 CONTROL_STATE = 44     # doubles per pid_state row of rift_control_tick: turn ring (20) | speed ring (20) | turn head, last | speed head, last
 OPERANDS = {"bf16": 0, "fp16": 1}       # RIFT_OPERANDS_* of include/rift_hip.h: the 16-bit MFMA operand format of a context's fused kernels
 EXPORTS = [
@@ -137,6 +163,7 @@ EXPORTS = [
     "rift_comm_unique_id", "rift_comm_init", "rift_comm_all_reduce", "rift_comm_destroy", "rift_group_advantage_tick",
     "rift_control_tick", "rift_head_backward", "rift_critic_backward",
     "rift_eval_params_default", "rift_rollout_return_ex", "rift_group_advantage_tick_ex",
+    "rift_objective_params_default", "rift_loss_backward_ex",
 ]
 CRITIC_NPARAM = 99331
 PI_KEYS = ("mlp.0.weight", "mlp.0.bias", "mlp.1.weight", "mlp.1.bias", "mlp.3.weight", "mlp.3.bias")       # flat order of PI_NPARAM
@@ -176,6 +203,8 @@ def load_library(variant: str = "") -> C.CDLL:
     lib.rift_forward_head.argtypes = [vp, vp]
     lib.rift_forward_head_back.argtypes = [vp, C.c_int, vp]
     lib.rift_loss_backward.argtypes = [vp, C.c_int, C.POINTER(RiftLossIn), C.POINTER(RiftLossOut), vp]
+    lib.rift_loss_backward_ex.argtypes = [vp, C.c_int, C.POINTER(RiftLossIn), C.POINTER(RiftObjectiveParams), C.POINTER(RiftLossOut), vp, vp]
+    lib.rift_objective_params_default.argtypes = [C.c_int, C.POINTER(RiftObjectiveParams)]
     lib.rift_loss_finalize.argtypes = [vp, C.POINTER(RiftLossOut), C.c_int, vp]
     lib.rift_head_backward.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(RiftLossOut), C.c_int, vp]
     lib.rift_critic_backward.argtypes = [vp, C.POINTER(RiftCritic), vp, vp, C.c_int, vp, vp]
@@ -541,10 +570,17 @@ class Engine:
         if rc != 0:
             self._check(rc, "rift_forward_head")
 
-    def loss_backward_raw(self, kind: int, li: RiftLossIn, lo: RiftLossOut):
-        rc = self.lib.rift_loss_backward(self.ctx, kind, C.byref(li), C.byref(lo), _stream())
+    def loss_backward_raw(self, kind: int, li: RiftLossIn, lo: RiftLossOut, params: Optional[RiftObjectiveParams] = None,
+                          terms: Optional[int] = None):
+        """rift_loss_backward; with `params` rift_loss_backward_ex (`terms`: the address of a device [8] f64 buffer, or None)."""
+        if params is None:
+            rc = self.lib.rift_loss_backward(self.ctx, kind, C.byref(li), C.byref(lo), _stream())
+            if rc != 0:
+                self._check(rc, "rift_loss_backward")
+            return
+        rc = self.lib.rift_loss_backward_ex(self.ctx, kind, C.byref(li), C.byref(params), C.byref(lo), terms, _stream())
         if rc != 0:
-            self._check(rc, "rift_loss_backward")
+            self._check(rc, "rift_loss_backward_ex")
 
     def loss_finalize_raw(self, lo: RiftLossOut, accumulate: int = 0):
         rc = self.lib.rift_loss_finalize(self.ctx, C.byref(lo), accumulate, _stream())
@@ -670,8 +706,16 @@ class Engine:
         return t
 
     # ---- loss + backward ---------------------------------------------------------------------
-    def loss_backward(self, kind: str, batch: Dict[str, torch.Tensor], clip_epsilon=0.2, lambda_entropy=0.01):
-        """Phase 1: per-rank sums.  Returns (stats[2] f64, flat_grad_sum[16897] f32, argmax_rm or None)."""
+    def loss_backward(self, kind: str, batch: Dict[str, torch.Tensor], clip_epsilon=0.2, lambda_entropy=0.01, objective=None,
+                      terms: bool = False):
+        """Phase 1: per-rank sums.  Returns (stats[2] f64, flat_grad_sum[16897] f32, argmax_rm or None).
+        objective (kinds 'rift' / 'grpo'): a dict of settings (objective_params' keys; {} = the kind's defaults) or a ready
+        RiftObjectiveParams -- the call is rift_loss_backward_ex; None: rift_loss_backward.  terms=True (with `objective`): the device
+        [8] f64 term sums of that call join the result as a fourth element."""
+        if terms and objective is None:
+            raise ValueError("loss_backward: terms=True needs objective= (rift_loss_backward has no term sums)")
+        if objective is not None and not isinstance(objective, RiftObjectiveParams):
+            objective = objective_params(kind, **objective)
         dev = self.device
         li = RiftLossIn()
         keep = []
@@ -700,6 +744,12 @@ class Engine:
         if kind in ("reinforce", "sft"):          # chosen (r, m): REINFORCE's argmax / SFT's target label
             argmax = torch.zeros(self._bs, 2, dtype=torch.int64, device=dev)
             lo.argmax_rm = argmax.data_ptr()
+        if objective is not None:
+            tsum = torch.zeros(8, dtype=torch.float64, device=dev) if terms else None
+            self._check(self.lib.rift_loss_backward_ex(self.ctx, LOSS_KINDS[kind], C.byref(li), C.byref(objective), C.byref(lo), _ptr(tsum), _stream()),
+                        "rift_loss_backward_ex")
+            self._keep_loss = keep
+            return (stats, flat, argmax, tsum) if terms else (stats, flat, argmax)
         self._check(self.lib.rift_loss_backward(self.ctx, LOSS_KINDS[kind], C.byref(li), C.byref(lo), _stream()),
                     "rift_loss_backward")
         self._keep_loss = keep

@@ -18,6 +18,7 @@
 #include "devmem.h"
 #include "adv.h"
 #include "eval_params.h"
+#include "objective_params.h"
 #include "gemm.h"
 #include "kernels.h"
 #include "loss.h"
@@ -100,6 +101,7 @@ struct RiftCtx {
   uint8_t* last_rkpm = nullptr; int last_bs = 0, last_R = 0;
   // loss scratch
   DevBuf<double> l_S, l_cnt; DevBuf<float> l_dz, l_partial;
+  DevBuf<double> l_T;      // [bs][LOSS_NTERM] per-scene term sums of rift_loss_backward_ex, reserved when its `terms` are asked for
   DevBuf<double> l_sink;   // [2] where loss_reduce_kernel's objective sums go when there is no objective (rift_head_backward)
   DevBuf<float> ego_w, ego_b;   // packed (6,128) linears of StateAttentionEncoder
   bool nat_fused = true; int gemm_dbg = 0;
@@ -2098,11 +2100,11 @@ static int pi_backward_scratch(RiftCtx* c, int rows, int nwg) {
   return RIFT_OK;
 }
 
-int rift_loss_backward(RiftCtx* c, int kind, const RiftLossIn* in, const RiftLossOut* out, void* stream) {
-  if (!c || !in || !out || !out->stats || !out->flat_grad_sum) return RIFT_ERR_ARG;
-  c->err.clear();
-  if (!c->loaded) { c->err = "rift_loss_backward before rift_forward" + NOT_LOADED; return RIFT_ERR_STATE; }
-  if (!c->last_qfinal) { c->err = "rift_loss_backward before rift_forward"; return RIFT_ERR_STATE; }
+// rift_loss_backward (ob == nullptr: the kernel with the reference's literals) and rift_loss_backward_ex (ob: its accepted settings)
+static int loss_backward_impl(RiftCtx* c, const char* who, int kind, const RiftLossIn* in, const RiftObjectiveParams* ob, const RiftLossOut* out,
+                              double* terms, void* stream) {
+  if (!c->loaded) { c->err = std::string(who) + " before rift_forward" + NOT_LOADED; return RIFT_ERR_STATE; }
+  if (!c->last_qfinal) { c->err = std::string(who) + " before rift_forward"; return RIFT_ERR_STATE; }
   HIPCHK(c, hipSetDevice(c->device));
   c->stream = (hipStream_t)stream; c->dry = false;
   const int bs = c->last_bs, R = c->last_R, M = 12, G = R * M, rows = bs * G;
@@ -2118,12 +2120,21 @@ int rift_loss_backward(RiftCtx* c, int kind, const RiftLossIn* in, const RiftLos
   p.clip_eps = in->clip_epsilon; p.lambda_entropy = in->lambda_entropy;
   p.S = c->l_S.get(); p.cnt = c->l_cnt.get(); p.dlogit = c->l_dz.get(); p.argmax_rm = (long long*)out->argmax_rm;
   if ((kind == RIFT_LOSS_RIFT || kind == RIFT_LOSS_GRPO) && (!p.old_logits || !p.adv64 || !p.valid)) { c->err = "missing loss inputs"; return RIFT_ERR_ARG; }
-  if (kind == RIFT_LOSS_GRPO && !p.ref_logits) { c->err = "missing ref logits"; return RIFT_ERR_ARG; }
+  if (kind == RIFT_LOSS_GRPO && !ob && !p.ref_logits) { c->err = "missing ref logits"; return RIFT_ERR_ARG; }
   if (kind == RIFT_LOSS_PPO && (!p.action_mode || !p.scal_a || !p.old_log_prob)) { c->err = "missing ppo inputs"; return RIFT_ERR_ARG; }
   if (kind == RIFT_LOSS_REINFORCE && !p.scal_a) { c->err = "missing returns"; return RIFT_ERR_ARG; }
   if (kind == RIFT_LOSS_SFT && !p.action_mode) { c->err = "missing teacher mode (action_mode)"; return RIFT_ERR_ARG; }
   const dim3 lgrid(cdiv(bs, 4)), lblock(256);
-  if (G <= 64 * 2) launch(c, "loss_kernel", loss_kernel<2>, lgrid, lblock, 0, p);
+  if (ob) {
+    if (terms) DEVCHK(c, c->l_T.reserve((size_t)bs * LOSS_NTERM));
+    p.clip_lo = (float)ob->clip_low; p.clip_hi = (float)ob->clip_high; p.kl_gw = (float)ob->kl_beta; p.ent_gw = (float)ob->entropy_coef;
+    p.dual_clip = ob->dual_clip; p.kl_beta = ob->kl_beta; p.ent_coef = ob->entropy_coef; p.T = terms ? c->l_T.get() : nullptr;
+    if (G <= 64 * 2) launch(c, "loss_kernel", loss_kernel<2, true>, lgrid, lblock, 0, p);
+    else if (G <= 64 * 4) launch(c, "loss_kernel", loss_kernel<4, true>, lgrid, lblock, 0, p);
+    else launch(c, "loss_kernel", loss_kernel<16, true>, lgrid, lblock, 0, p);
+    if (terms) launch(c, "loss_terms_kernel", loss_terms_kernel, dim3(1), dim3(64), 0, (const double*)c->l_T.get(), (const double*)c->l_cnt.get(), bs, terms);
+  }
+  else if (G <= 64 * 2) launch(c, "loss_kernel", loss_kernel<2>, lgrid, lblock, 0, p);
   else if (G <= 64 * 4) launch(c, "loss_kernel", loss_kernel<4>, lgrid, lblock, 0, p);
   else launch(c, "loss_kernel", loss_kernel<16>, lgrid, lblock, 0, p);
   const std::string PH = "planning_decoder.pi_head.mlp.";
@@ -2134,6 +2145,23 @@ int rift_loss_backward(RiftCtx* c, int kind, const RiftLossIn* in, const RiftLos
          out->flat_grad_sum, (const double*)c->l_S.get(), (const double*)c->l_cnt.get(), bs, out->stats, out->exchange);
   HIPCHK(c, hipGetLastError());
   return RIFT_OK;
+}
+
+int rift_loss_backward(RiftCtx* c, int kind, const RiftLossIn* in, const RiftLossOut* out, void* stream) {
+  if (!c || !in || !out || !out->stats || !out->flat_grad_sum) return RIFT_ERR_ARG;
+  c->err.clear();
+  return loss_backward_impl(c, "rift_loss_backward", kind, in, nullptr, out, nullptr, stream);
+}
+
+int rift_loss_backward_ex(RiftCtx* c, int kind, const RiftLossIn* in, const RiftObjectiveParams* params, const RiftLossOut* out, double* terms,
+                          void* stream) {
+  if (!c || !in || !out || !out->stats || !out->flat_grad_sum) return RIFT_ERR_ARG;
+  c->err.clear();
+  if (const char* why = rift_objective_params_refusal(kind, params, in->ref_group_logits != nullptr)) {
+    c->err = std::string("rift_loss_backward_ex: ") + why;
+    return RIFT_ERR_ARG;
+  }
+  return loss_backward_impl(c, "rift_loss_backward_ex", kind, in, params, out, terms, stream);
 }
 
 int rift_head_backward(RiftCtx* c, const float* dlogits, int bs, int R, const RiftLossOut* out, int accumulate, void* stream) {

@@ -51,10 +51,19 @@ struct LossP {
   double* cnt;                        // [bs] per-scene normaliser count
   float* dlogit;                      // [bs][G]  dS/dlogit
   long long* argmax_rm;               // [bs][2]  (REINFORCE) chosen (r, m), bit-exact integer output
+  // loss_kernel<MAXPL, true> only (rift_loss_backward_ex: RiftObjectiveParams, rift_hip.h), behind everything the compiled-in kernel reads
+  float clip_lo, clip_hi;             // (float)clip_low / clip_high: compared and clamped in fp32, like the literals 0.8f / 1.2f
+  float kl_gw, ent_gw;                // (float)kl_beta / entropy_coef: the weights on the gradient, like the literal 0.2f
+  double dual_clip, kl_beta, ent_coef;  // the floor and the two terms of the objective sum are formed in double; 0 = that term is off
+  double* T;                          // [bs][LOSS_NTERM] per-scene sums of rift_loss_backward_ex's `terms`, or null
 };
+enum { LOSS_NTERM = 5 };              // surrogate | KL | entropy | clamped without gradient | on the dual-clip floor
 
 // One 64-lane wave per scene (G <= 64*MAXPL candidates held in registers).
-template <int MAXPL>
+// RT = false: the settings of RIFT / GRPO are the literals of the reference (rift_loss_backward).  RT = true (RIFT / GRPO only): they are
+// read from LossP, the two kinds are one objective family -- dual clip, KL and entropy term each present when its coefficient is not 0 --
+// and at a kind's defaults every operation and its order are those of RT = false.
+template <int MAXPL, bool RT = false>
 __global__ void loss_kernel(LossP p) {
   const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -86,7 +95,79 @@ __global__ void loss_kernel(LossP p) {
 #pragma unroll
   for (int i = 0; i < MAXPL; ++i) gi[i] = 0.f;
 
-  if (p.kind == LOSS_RIFT || p.kind == LOSS_GRPO) {
+  if constexpr (RT) {
+    // No contraction in this block.  The compiled-in branch below forms every fp64 product of the objective rounded (its weighted KL term
+    // reaches the subtraction through a select, which keeps the compiler from fusing the two); here the term sits behind a run-time branch
+    // and would be fused into an FMA, one rounding fewer than the kernel it has to equal bit for bit.
+#pragma clang fp contract(off)
+    const bool want_kl = p.kl_beta != 0.0, want_dual = p.dual_clip != 0.0, want_ent = p.ent_coef != 0.0;
+    float zo[MAXPL], zr[MAXPL];
+    float mo = -INFINITY, mr = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < MAXPL; ++i) {
+      const int j = lane + i * 64;
+      zo[i] = -INFINITY; zr[i] = -INFINITY;
+      if (j < G) {
+        zo[i] = pad[i] ? -1e8f : p.old_logits[(size_t)b * G + j];
+        mo = fmaxf(mo, zo[i]);
+        if (want_kl) { zr[i] = pad[i] ? -1e8f : p.ref_logits[(size_t)b * G + j]; mr = fmaxf(mr, zr[i]); }
+      }
+    }
+    mo = wave_max(mo);
+    float so = 0.f, sr = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXPL; ++i) if (lane + i * 64 < G) so += expf(zo[i] - mo);
+    const float lseo = mo + logf(wave_sum(so));
+    float lser = 0.f;
+    if (want_kl) {
+      mr = wave_max(mr);
+#pragma unroll
+      for (int i = 0; i < MAXPL; ++i) if (lane + i * 64 < G) sr += expf(zr[i] - mr);
+      lser = mr + logf(wave_sum(sr));
+    }
+    double t_sur = 0.0, t_kl = 0.0, t_ent = 0.0, n_clamp = 0.0, n_floor = 0.0;
+#pragma unroll
+    for (int i = 0; i < MAXPL; ++i) {
+      const int j = lane + i * 64;
+      if (j >= G || !p.valid[(size_t)b * G + j]) continue;
+      const double A = p.adv64[(size_t)b * G + j];
+      const float ratio = expf(lp[i] - (zo[i] - lseo));
+      const double u = A * (double)ratio;
+      const double c = A * (double)fminf(fmaxf(ratio, p.clip_lo), p.clip_hi);
+      double obj = u < c ? u : c;
+      bool pass = (ratio >= p.clip_lo && ratio <= p.clip_hi) || (u < c);
+      bool floored = false;
+      if (want_dual && A < 0.0) {
+        const double lo = A * p.dual_clip;
+        if (obj < lo) { obj = lo; pass = false; floored = true; }
+      }
+      t_sur += obj;
+      if (floored) n_floor += 1.0; else if (!pass) n_clamp += 1.0;
+      if (want_kl) {
+        const float rp = expf(zr[i] - lser);
+        const double kl = rp > 0.f ? (double)(rp * (logf(rp) - lp[i])) : 0.0;
+        obj -= p.kl_beta * kl;
+        gi[i] += p.kl_gw * rp;
+        t_kl += kl;
+      }
+      if (pass) gi[i] += (float)(A * (double)ratio);
+      if (want_ent) {                                      // -p_j lp_j and its derivative on lp_j, -p_j (lp_j + 1): the PPO branch's expressions
+        const float pj = expf(lp[i]);
+        const double ent = -(double)(pj * lp[i]);
+        obj += p.ent_coef * ent;
+        gi[i] += -p.ent_gw * pj * (lp[i] + 1.f);
+        t_ent += ent;
+      }
+      S += obj; cnt += 1.0;
+    }
+    if (p.T) {                                             // (uniform over the wave: every lane takes part in the five reductions)
+      t_sur = wave_sum_d(t_sur); t_kl = wave_sum_d(t_kl); t_ent = wave_sum_d(t_ent); n_clamp = wave_sum_d(n_clamp); n_floor = wave_sum_d(n_floor);
+      if (lane == 0) {
+        double* t = p.T + (size_t)b * LOSS_NTERM;
+        t[0] = t_sur; t[1] = t_kl; t[2] = t_ent; t[3] = n_clamp; t[4] = n_floor;
+      }
+    }
+  } else if (p.kind == LOSS_RIFT || p.kind == LOSS_GRPO) {
     // old-policy log-softmax
     float zo[MAXPL], zr[MAXPL];
     float mo = -INFINITY, mr = -INFINITY;
@@ -201,8 +282,29 @@ __global__ void loss_kernel(LossP p) {
     const int j = lane + i * 64;
     if (j < G) p.dlogit[(size_t)b * G + j] = pad[i] ? 0.f : gi[i] - expf(lp[i]) * gs;
   }
-  if (p.kind == LOSS_RIFT || p.kind == LOSS_GRPO) { S = wave_sum_d(S); cnt = wave_sum_d(cnt); }
+  if (RT || p.kind == LOSS_RIFT || p.kind == LOSS_GRPO) { S = wave_sum_d(S); cnt = wave_sum_d(cnt); }
   if (lane == 0) { p.S[b] = S; p.cnt[b] = cnt; }
+}
+
+// terms[0..4] = sum_b T[b][k] in the order of loss_reduce_kernel's objective sums (lane-strided over the scenes, then the wave reduction:
+// the same bits from run to run), terms[5] = sum_b cnt[b], terms[6] = terms[7] = 0.  One wave.
+__global__ __launch_bounds__(64) void loss_terms_kernel(const double* __restrict__ T, const double* __restrict__ cnt, int bs,
+                                                        double* __restrict__ terms) {
+  double a[LOSS_NTERM + 1];
+#pragma unroll
+  for (int k = 0; k <= LOSS_NTERM; ++k) a[k] = 0.0;
+  for (int b = threadIdx.x; b < bs; b += 64) {
+#pragma unroll
+    for (int k = 0; k < LOSS_NTERM; ++k) a[k] += T[(size_t)b * LOSS_NTERM + k];
+    a[LOSS_NTERM] += cnt[b];
+  }
+#pragma unroll
+  for (int k = 0; k <= LOSS_NTERM; ++k) a[k] = wave_sum_d(a[k]);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k <= LOSS_NTERM; ++k) terms[k] = a[k];
+    terms[6] = 0.0; terms[7] = 0.0;
+  }
 }
 
 // SFT teacher label, the mode index (sft_trainer.py:186-199 with sft/utils.py:10-32 and pid_controller.py:108-125): every candidate's

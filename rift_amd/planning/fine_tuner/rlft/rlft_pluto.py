@@ -260,7 +260,7 @@ class RLFTPluto(PLUTO):
                               weight_decay=cfg["weight_decay"], epochs=cfg["epochs"], warmup_epochs=cfg["warmup_epochs"],
                               trainable_layers=tuple(cfg["trainable_layers"]), gradient_clip_val=cfg["gradient_clip_val"],
                               clip_epsilon=getattr(self, "clip_epsilon", 0.2), lambda_entropy=getattr(self, "lambda_entropy", 0.01),
-                              process_group=process_group, seed=int(e_i) + 1)
+                              process_group=process_group, seed=int(e_i) + 1, objective=getattr(self, "_objective", None))
         rank, world = trainer.rank, trainer.world
         eng = trainer.engine
         mark("trainer")
@@ -462,8 +462,13 @@ class _GroupRelativePluto(RLFTPluto):
     its valid reference lines (the "old policy" of the coming update) and the group-relative advantage of all R x 12 candidates."""
     EXTRA_COLUMNS = ('CBVs_actions_old_group_logits', 'CBVs_group_advantage')
     TRAJ_EVAL_KEYS = ('gamma', 'reward_model', 'reward_params', 'bbox_inflation_ratio', 'resolution', 'near_lane_change', 'breakdown')
+    OBJECTIVE_KEYS = ('clip_low', 'clip_high', 'dual_clip', 'kl_beta', 'entropy_coef')      # the fields of RiftObjectiveParams
+    GROUP_OBJECTIVE = True
 
     def __init__(self, config, logger):
+        # config['objective']: the settings of the update's objective at run time -- what the reference spells as literals in
+        # get_rift_loss / get_grpo_loss.  Handed to RLFTTrainer in train(); without the key every objective launch is the compiled-in one.
+        self._objective = self._read_objective(config.get('objective'))
         super().__init__(config, logger)
         self._traj_evaluator = None
         # config['traj_eval']: the reward model and the evaluator's settings at run time -- what the reference edits in
@@ -474,6 +479,20 @@ class _GroupRelativePluto(RLFTPluto):
         self._breakdown_reads = []
         self._fused_tick = bool(config.get('fused_tick', True))       # False: the per-CBV evaluator chain (the two are bit-identical, tested)
         self._tick_columns, self._tick_reads = {}, []
+
+    @classmethod
+    def _read_objective(cls, section):
+        """None without the section; else the settings as floats (the kind's defaults are filled in by the trainer: {} = the defaults)."""
+        if section is None:
+            return None
+        unknown = sorted(set(section) - set(cls.OBJECTIVE_KEYS))
+        if unknown:
+            raise ValueError(f"config['objective']: unknown key(s) {unknown}; known: {list(cls.OBJECTIVE_KEYS)}")
+        ob = {k: float(v) for k, v in section.items()}
+        if cls.kind == 'rift' and ob.get('kl_beta', 0.0) > 0:
+            raise ValueError("config['objective']['kl_beta'] > 0 on rift_pluto: its buffer records no reference logits.  grpo_pluto records "
+                             "them; with 'dual_clip': 3.0 it trains that objective (RIFT's dual clip plus the KL term)")
+        return ob
 
     @classmethod
     def _read_traj_eval(cls, section):

@@ -261,11 +261,18 @@ class RLFTTrainer:
     (SURVEY.md 8(e)): two inside the forward (BatchNorm sums of the PointsEncoders + the padding rows the r2r mask quirk reads, then
     the second BatchNorm; rift_set_dp) and one between backward and finalize (gradient sums, objective sum, valid count).
     `exchange` (callable(tensor) -> in-place sum over ranks) with `dp_rank` / `dp_world` replaces the process group's all-reduce
-    (tests drive several emulated ranks through one GPU with it)."""
+    (tests drive several emulated ranks through one GPU with it).
+
+    `objective` (kinds 'rift' / 'grpo'): a dict of run-time settings of the group objective -- clip_low, clip_high, dual_clip, kl_beta,
+    entropy_coef (_ffi.objective_params; {} = the kind's defaults) and optionally 'terms': True.  With it every objective launch of the
+    trainer (serial step, deferred tail, pipelined validation) is rift_loss_backward_ex, on the same streams and in the same place as
+    before; without it every call is rift_loss_backward.  'terms': `last_terms` is the device [8] f64 tensor of the latest such launch
+    (written on the stream that launch ran on: read it behind wait_update()).  The term sums are per-rank sums, so asking for them under
+    data parallelism raises; stats / flat_grad_sum / exchange are as before and the data-parallel step needs nothing else."""
 
     def __init__(self, model, kind: str = "rift", lr=1e-4, cl_lr_decay=0.9, weight_decay=1e-5, epochs=16,
                  warmup_epochs=3, trainable_layers=(PI_HEAD,), gradient_clip_val=0.5, process_group=None,
-                 clip_epsilon=0.2, lambda_entropy=0.01, seed: int = 0, exchange=None, dp_rank=None, dp_world=None):
+                 clip_epsilon=0.2, lambda_entropy=0.01, seed: int = 0, exchange=None, dp_rank=None, dp_world=None, objective=None):
         if kind == "rs":     # RS's objective (fine_tuner/sft/rs_pluto/rs_trainer.py:120-170) is REINFORCE's, line for line
             kind = "reinforce"
         if kind not in _ffi.LOSS_KINDS and kind != "rtr":
@@ -293,6 +300,16 @@ class RLFTTrainer:
         if exchange is None and process_group is not None:
             exchange = lambda t: torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.SUM, group=process_group)  # noqa: E731
         self.exchange = exchange             # None = single process
+        self.objective, self.last_terms = None, None
+        if objective is not None:
+            if kind not in _ffi.OBJECTIVE_KINDS:
+                raise ValueError(f"objective settings exist for the kinds {list(_ffi.OBJECTIVE_KINDS)}, not for {kind!r}")
+            settings = dict(objective)
+            want_terms = bool(settings.pop("terms", False))
+            if want_terms and (exchange is not None or self.world > 1):
+                raise ValueError("objective['terms'] under data parallelism: the term sums are per-rank sums and are not all-reduced")
+            self.objective = _ffi.objective_params(kind, **settings)
+            self._want_terms = want_terms
         self.dp_buf = None                   # exchange buffer of the forward (rift_set_dp), sized at the first step
         freeze_parameters(model, list(trainable_layers))
         self.optimizer = configure_optimizer(model, lr, weight_decay)
@@ -321,6 +338,9 @@ class RLFTTrainer:
         # exchange buffers of the DP path (see dp_all_reduce)
         self.flat = torch.zeros(_ffi.PI_NPARAM, dtype=torch.float32, device=dev)
         self.stats = torch.zeros(2, dtype=torch.float64, device=dev)
+        if self.objective is not None and self._want_terms:
+            self.last_terms = torch.zeros(8, dtype=torch.float64, device=dev)
+        self._terms_ptr = _ffi._ptr(self.last_terms)
         # the finalize kernel writes a training step's loss into its own slot of `loss_hist` (summed once per pop_mean_loss()): no
         # accumulate launch per step; validation writes the separate `loss_val`
         self.loss_hist = torch.zeros(self.LOSS_SLOTS, dtype=torch.float64, device=dev)
@@ -498,7 +518,7 @@ class RLFTTrainer:
             extras = dict(extras)
             extras["action_mode"] = eng.sft_teacher_mode(self._traj[0][:fb.bs], extras["teacher_infos"])
         self.set_loss_inputs(extras)
-        eng.loss_backward_raw(self.kind_id, self.li, self.lo)
+        eng.loss_backward_raw(self.kind_id, self.li, self.lo, self.objective, self._terms_ptr)
         if self.critic is not None:   # value loss half of get_ppo_loss (ppo_trainer.py:175-176,183)
             eng.critic_loss_backward_raw(self.critic_desc, extras["state"], extras["reward_sum"], self.stats, self.flat_c)
         if self.critic is not None and self.xchg is not None:
@@ -659,7 +679,7 @@ class RLFTTrainer:
                             if torch.is_tensor(t) and t.is_cuda:      # keep the caching allocator from recycling them under it
                                 t.record_stream(self._side)
                     self.set_loss_inputs(extras)
-                    self.engine.loss_backward_raw(self.kind_id, self.li, self.lo)
+                    self.engine.loss_backward_raw(self.kind_id, self.li, self.lo, self.objective, self._terms_ptr)
                     self._finalize_and_step(fused_clip)
                     self._ev_param.record(self._side)
                     self._ev_tail[slot].record(self._side)
@@ -837,7 +857,7 @@ class RLFTTrainer:
                         if torch.is_tensor(t) and t.is_cuda:
                             t.record_stream(self._side)
                 self.set_loss_inputs(extras)
-                self.engine.loss_backward_raw(self.kind_id, self.li, self.lo)
+                self.engine.loss_backward_raw(self.kind_id, self.li, self.lo, self.objective, self._terms_ptr)
                 self._exchange_and_finalize(False, None)
                 self._ev_param.record(self._side)
                 self._ev_tail[slot].record(self._side)

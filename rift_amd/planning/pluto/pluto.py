@@ -239,8 +239,11 @@ def paused_cyclic_gc(enabled: bool = True):
 class PLUTO(CBVBasePolicy):
     name = 'pluto'
     type = 'il'
+    GROUP_OBJECTIVE = False      # True on the policies whose update is the RIFT / GRPO group objective: they read config['objective']
 
     def __init__(self, config, logger):
+        if config.get('objective') is not None and not self.GROUP_OBJECTIVE:
+            raise ValueError(f"config['objective'] sets the RIFT / GRPO group objective (rift_pluto, grpo_pluto); {self.name} has no such settings")
         super().__init__(config, logger)
         self.logger = logger
         self.radius = config.get('obs', {}).get('radius', config.get('radius', 120))

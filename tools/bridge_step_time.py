@@ -2,6 +2,9 @@
 around `--steps` steps after `--warmup` warm-up steps each, legs alternated `--rounds` times.
 
   pipelined   RLFTTrainer.gather + training_step as bench.py runs it: device collate, deferred head, tail on the update stream
+  pipelined+objective   the same step with RLFTTrainer(objective=OBJECTIVE): the objective's settings read at run time
+              (rift_loss_backward_ex), every term switched on -- what a changed clip range, KL weight or entropy bonus costs on the
+              fixed-function path (profiles/NOTES_r16.md), next to the bridge leg, which was the only way to change one
   serial      the same fixed-function step on one stream: forward + rift_loss_backward + rift_update_tail on pre-gathered batches
   bridge      PlanningModel(differentiable_head=True).forward + the RIFT objective in PyTorch + loss.backward() (rift_head_backward) +
               torch clip_grad_norm_ + fused torch AdamW, on pre-staged device batches, one stream
@@ -22,6 +25,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 BATCH, NBATCH = 256, 4
+OBJECTIVE = {"clip_low": 0.7, "clip_high": 1.3, "dual_clip": 2.0, "kl_beta": 0.05, "entropy_coef": 0.5}
 
 
 def rift_objective(prob, r_pad, old_logits, adv, valid):
@@ -79,6 +83,13 @@ def main():
         fb, b = tr_p.gather(replay, idx[i % NBATCH])
         tr_p.training_step(fb, b)
 
+    # ---- pipelined, the objective's settings at run time (the synthetic scenes carry reference logits for the KL term)
+    tr_o = T.RLFTTrainer(model(), kind="rift", seed=1, objective=OBJECTIVE)
+
+    def step_objective(i):
+        fb, b = tr_o.gather(replay, idx[i % NBATCH])
+        tr_o.training_step(fb, b)
+
     # ---- serial (the switches are read when the trainer is built)
     os.environ["RIFT_OVERLAP"], os.environ["RIFT_PIPELINE"] = "0", "0"
     tr_s = T.RLFTTrainer(model(), kind="rift", seed=1)
@@ -111,7 +122,8 @@ def main():
         opt.step()
         opt.zero_grad(set_to_none=True)
 
-    legs = {"pipelined": (step_pipelined, tr_p.wait_update), "serial": (step_serial, tr_s.wait_update), "bridge": (step_bridge, lambda: None)}
+    legs = {"pipelined": (step_pipelined, tr_p.wait_update), "pipelined+objective": (step_objective, tr_o.wait_update),
+            "serial": (step_serial, tr_s.wait_update), "bridge": (step_bridge, lambda: None)}
     ms = {k: [] for k in legs}
     for r in range(args.rounds):
         for name, (step, drain) in legs.items():
@@ -127,11 +139,13 @@ def main():
             e1.record()
             torch.cuda.synchronize()
             ms[name].append(e0.elapsed_time(e1) / args.steps)
-            print(f"round {r} {name:10s} {ms[name][-1]:.4f} ms/step", file=sys.stderr, flush=True)
+            print(f"round {r} {name:19s} {ms[name][-1]:.4f} ms/step", file=sys.stderr, flush=True)
     res = {"batch": BATCH, "precision": args.precision, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
            "median_ms": {k: sorted(v)[len(v) // 2] for k, v in ms.items()}}
     res["bridge_minus_serial_ms"] = res["median_ms"]["bridge"] - res["median_ms"]["serial"]
     res["bridge_minus_pipelined_ms"] = res["median_ms"]["bridge"] - res["median_ms"]["pipelined"]
+    res["objective_over_pipelined"] = res["median_ms"]["pipelined+objective"] / res["median_ms"]["pipelined"]
+    res["bridge_over_objective"] = res["median_ms"]["bridge"] / res["median_ms"]["pipelined+objective"]
     line = json.dumps(res)
     print(line)
     if args.out:

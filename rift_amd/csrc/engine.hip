@@ -88,6 +88,8 @@ struct RiftCtx {
   // stream, and the caller's queue holds token assembly -> encoder of step k + 1 beside them.  All its operands live in the forward's
   // arena (four slots).  Which batch sizes: forward_impl's measured table, or bs <= RIFT_DEC_DEFER (0 = never).
   int dec_defer_max = -1; bool dec_split = true;   // (-1: the measured table in forward_impl; RIFT_DEC_DEFER=<n>: bs <= n)            // (RIFT_DEC_SPLIT=0: the deferred decoder as one launch)
+  int dec_layers = 4;               // (diagnostic, RIFT_DEC_LAYERS) 0 / 2: the non-deferred decoder stops after that many layers -- the `dec3` tap then holds q0 / the
+                                    // output of layer 1; 22: layers [0, 2) and [2, 4) of an eval forward as two launches; anything else: all four, one launch
   bool ro8 = true;                                         // candidate rollout with eight lanes per candidate (rollout.h; RIFT_RO8=0: one lane, the round-1 form)
   DevBuf<float> ro_raw;             // rift_rollout: the unsmoothed speed history handed from the closed-loop kernel to the kinematics kernel
   DevBuf<char> tick_scratch;      // rift_group_advantage_tick: per-CBV intermediates (reused CBV by CBV in stream order)
@@ -1444,7 +1446,8 @@ void decoder_layerwise(Fwd& f, float dp) {
   float* DQc = A_alloc<float>(c, (size_t)nQ * 128);
   float* DH = A_alloc<float>(c, (size_t)nQ * 512);
   float* KVm = A_alloc<float>(c, (size_t)nT * 256);
-  for (int i = 0; i < 4; ++i) {
+  const int n_layers = c->dec_layers == 0 || c->dec_layers == 2 ? c->dec_layers : 4;      // (RIFT_DEC_LAYERS)
+  for (int i = 0; i < n_layers; ++i) {
     const std::string p = PD + ".decoder_blocks." + std::to_string(i);
     // ---- r2r self attention over the R reference lines of each (scene, mode), with the mask quirk
     GemmP g = mk(f.Q, 128, nQ, c->pw[p + ".r2r_attn.qkv"], DQKV, 384);
@@ -1573,7 +1576,15 @@ int planning_decoder(Fwd& f) {
         launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });
         f.dec_later.l0 = 2; f.dec_later.rng_io = rng_io;
       }
-    } else launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });
+    } else if (c->dec_layers == 22 && dp == 0.f) {      // (RIFT_DEC_LAYERS=22: an eval forward's layers as two launches; the rows travel through Q as in the deferred split)
+      dq.l1 = 2;
+      launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });
+      dq.l0 = 2; dq.l1 = 4;
+      launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });
+    } else if (c->dec_layers == 2) {                    // (RIFT_DEC_LAYERS=2: `dec3` taps the output of layer 1)
+      dq.l1 = 2;
+      launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });
+    } else if (c->dec_layers != 0) launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });      // (RIFT_DEC_LAYERS=0: `dec3` taps q0)
   } else decoder_layerwise(f, dp);
   tap(c, "dec3", f.Q, (int64_t)nQ * 128);
   return RIFT_OK;
@@ -1739,6 +1750,7 @@ static void read_switches(RiftCtx* c) {
   env_flag("RIFT_NAT_ASIDE", &c->nat_aside);              // 0: the history chain on the caller's stream, not behind the preparation
   env_int("RIFT_DEC_DEFER", &c->dec_defer_max);           // <n>: the decoder goes with the deferred head for bs <= n (0: never; unset: the measured table)
   env_flag("RIFT_DEC_SPLIT", &c->dec_split);              // 0: the deferred decoder as one launch
+  env_int("RIFT_DEC_LAYERS", &c->dec_layers);             // (diagnostic) 0 / 2: the non-deferred decoder stops after that many layers and `dec3` taps that boundary; 22: an eval forward's layers as two launches
   env_flag("RIFT_RO8", &c->ro8);                          // 0: candidate rollout with one lane per candidate
   if (env_int("RIFT_POISON_LDS", &c->poison_lds, 0)) c->poison_lds &= 0xff;                // <byte>: every CU's LDS filled ahead of every launch
   if (env_int("RIFT_POISON_ARENA", &c->dg.poison_arena, 0)) c->dg.poison_arena &= 0xff;    // <byte>: the arena filled ahead of every forward

@@ -3,6 +3,8 @@
 The library holds TWO builds of the engine -- bf16 and fp16 MFMA operands (csrc/opfmt.h: -DRIFT_OP_F16=0/1, kernels in namespace
 rift_bf / rift_hf) -- behind one set of exported `rift_*` symbols (csrc/abi.cpp, generated from include/rift_hip.h by
 tools/gen/abi_trampolines.py): a context is created for one format and every call is routed to the build that owns it.
+What does not depend on the operand format is built ONCE per library (SHARED_UNITS: csrc/shared.hip -- objective and backward, AdamW and
+clipping, critic, advantages, rollout, ticks, collate, the device-memory hooks; namespace rift) and serves the contexts of both builds.
 """
 import glob
 import os
@@ -17,7 +19,7 @@ LIB = os.path.join(HERE, "librift_hip.so")
 LIB_STATS = os.path.join(HERE, "librift_hip_stats.so")     # diagnostic twin (build_stats): the bf16 build with the drop-decision counters of csrc/dropstats.h
 OBJ = os.path.join(HERE, "_obj")
 
-# Translation units of one engine build.  The wave-private streaming kernels are built with `-fno-honor-nans -mno-amdgpu-ieee`: no
+# Translation units of one engine build (compiled once per operand format; SHARED_UNITS below are compiled once per library).  The wave-private streaming kernels are built with `-fno-honor-nans -mno-amdgpu-ieee`: no
 # IEEE-mode canonicalisation (`v_max_f32 x, x, x` in front of every fmaxf on an MFMA result); they test no NaN themselves -- a NaN / Inf
 # in the residual stream is caught by the bit-pattern test of the policy-head kernels (rift_check_finite).
 # Spill rule (check_resources): a kernel with VGPR spills whose SGPR spills the backend parks in VGPR lanes was miscompiled by ROCm 7.2
@@ -27,6 +29,7 @@ OBJ = os.path.join(HERE, "_obj")
 FAST = ["-fno-honor-nans", "-mno-amdgpu-ieee"]
 SPILL_SAFE = ["-mllvm", "-amdgpu-spill-sgpr-to-vgpr=0"]
 UNITS = [("engine", []), ("dec_w", FAST), ("nat_l01w", FAST), ("nat_l2w", FAST), ("enc_w", FAST), ("pe_w", FAST), ("fo_w", FAST), ("enc112", FAST)]
+SHARED_UNITS = [("shared", [])]      # operand-format-free: no -DRIFT_OP_F16, one object per library (shared.o / shared_st.o / shared_<tag>.o)
 FORMATS = [("bf", 0), ("hf", 1)]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + os.environ.get("HIPCC_EXTRA", "").split()      # (HIPCC_EXTRA: diagnostic defines, e.g. -DRIFT_DEC_ARR=1)
 
@@ -57,6 +60,9 @@ def compile_commands(extra=(), stats=False, variant=None):
             if stats and unit in ("dec_w", "enc112"):      # the decision counters push the train-mode decoder and the 112-row encoder past 256 VGPRs: the diagnostic twin takes the safe spill path (spill rule above)
                 flags = flags + SPILL_SAFE
             cmds.append((o, [hipcc()] + COMMON + defs + [f"-DRIFT_OP_F16={f16}", "-c"] + flags + [os.path.join(CSRC, unit + ".hip"), "-o", o] + list(extra)))
+    for unit, flags in SHARED_UNITS:
+        o = os.path.join(OBJ, f"{unit}{sfx}.o")
+        cmds.append((o, [hipcc()] + COMMON + defs + ["-c"] + flags + [os.path.join(CSRC, unit + ".hip"), "-o", o] + list(extra)))
     o = os.path.join(OBJ, f"abi{sfx}.o")
     cmds.append((o, [hipcc()] + COMMON + (["-DRIFT_ABI_BF16_ONLY=1"] if stats else []) + ["-x", "hip", "-c", os.path.join(CSRC, "abi.cpp"), "-o", o] + list(extra)))
     return cmds
@@ -112,7 +118,8 @@ def build(force: bool = False, verbose: bool = True, jobs: int = 0, stats: bool 
             raise RuntimeError(f"{' '.join(cmd)}\n{r.stderr}")
         check_resources(r.stderr, "-amdgpu-spill-sgpr-to-vgpr=0" in cmd)
 
-    with ThreadPoolExecutor(max_workers=jobs or min(len(cmds), os.cpu_count() or 4)) as ex:
+    # (a command on a shared GPU host owns MAX_JOBS CPUs -- 16 unless set -- whatever cpu_count says)
+    with ThreadPoolExecutor(max_workers=jobs or min(len(cmds), int(os.environ.get("MAX_JOBS", 16)), os.cpu_count() or 4)) as ex:
         list(ex.map(run, cmds))
     link = [hipcc(), "--offload-arch=gfx950", "-shared"] + [o for o, _ in cmds] + ["-o", LIB]
     if verbose:

@@ -3,9 +3,9 @@
 // reductions, the dense-reward rollout return, and the replay-arena gather (collation).
 // All of them are latency / HBM bound scalar work -- no MFMA.
 #pragma once
-#include "common.h"
+#include "lanes.h"
 
-namespace RIFT_NS {
+namespace rift {
 
 // ---------------------------------------------------------------------------
 // Reverse affine scan  x_t = b_t + a_t * x_{t+1},  x_n = 0, in fp64, by ONE workgroup of 16 waves:
@@ -339,4 +339,4 @@ __global__ void collate_kernel(CollateP p, const int32_t* __restrict__ scene_idx
   }
 }
 
-}  // namespace RIFT_NS
+}  // namespace rift

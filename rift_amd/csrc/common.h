@@ -3,9 +3,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lanes.h"
 #include "opfmt.h"
 
 namespace RIFT_NS {
+
+using namespace rift;      // lanes.h: barrier, cross-lane reductions, RNG, finiteness test
 
 typedef __attribute__((ext_vector_type(8))) short h16x8;    // 8 operand words = 4 VGPRs (MFMA 16x16x32 A/B operand)
 typedef __attribute__((ext_vector_type(4))) float f32x4;    // MFMA 16x16 accumulator
@@ -119,23 +122,6 @@ __device__ __forceinline__ h16x8 fm_load(const unsigned short* W, int Kp, int n0
   return *reinterpret_cast<const h16x8*>(W + ((size_t)((n0 >> 4) * (Kp >> 5) + (k0 >> 5)) * 64 + lane) * 8);
 }
 
-// counter-based RNG for dropout / drop-path / state-dropout: one 32-bit hash per element
-// (two rounds of the lowbias32 integer finaliser over (seed, stream, element index); 32-bit multiplies only).
-__device__ __forceinline__ uint32_t hash32(uint32_t seed, uint32_t stream, uint32_t idx) {
-  uint32_t x = idx * 0x9E3779B1u + (seed ^ (stream * 0x85EBCA6Bu));
-  x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-  x += seed * 0xC2B2AE35u + stream;
-  x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-  return x;
-}
-// Element-wise dropout decisions: ONE lowbias32 round per counter and two 16-bit uniforms out of every hash (probability resolution
-// 2^-16); the decision is an integer compare against thr16 = p * 65536.  Four times cheaper per element than uniform01, which the
-// decoder kernel's dropout epilogues (attention weights, residual branches, FFN hidden layer) were paying 70 us a step for.
-__device__ __forceinline__ uint32_t hash1(uint32_t seed, uint32_t stream, uint32_t idx) {
-  uint32_t x = idx * 0x9E3779B1u + (seed ^ (stream * 0x85EBCA6Bu));
-  x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-  return x;
-}
 __device__ __forceinline__ uint32_t drop_thr16(float p) { return (uint32_t)(p * 65536.0f); }
 // keep / drop four consecutive elements whose first flat index is idx4 (a multiple of 4): scales v[] in place
 __device__ __forceinline__ void dropout4(float (&v)[4], uint32_t seed, uint32_t stream, uint32_t idx4, uint32_t thr16, float keep_scale) {
@@ -144,10 +130,6 @@ __device__ __forceinline__ void dropout4(float (&v)[4], uint32_t seed, uint32_t 
   v[1] = ((h0 >> 16) < thr16) ? 0.f : v[1] * keep_scale;
   v[2] = ((h1 & 0xffffu) < thr16) ? 0.f : v[2] * keep_scale;
   v[3] = ((h1 >> 16) < thr16) ? 0.f : v[3] * keep_scale;
-}
-
-__device__ __forceinline__ float uniform01(uint32_t seed, uint32_t stream, uint32_t idx) {
-  return (float)(hash32(seed, stream, idx) >> 8) * (1.0f / 16777216.0f);
 }
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
@@ -263,45 +245,6 @@ __device__ __forceinline__ uint2 gelu4_hid(const f32x4 a) {
   return u;
 }
 
-// Workgroup barrier for phases that hand data over through LDS only.  __syncthreads() makes hipcc drain EVERY outstanding memory
-// operation first (s_waitcnt vmcnt(0) lgkmcnt(0)), which ends the flight of the weight / parameter / next-tile loads these kernels
-// issue a phase ahead; here only the LDS counter is drained, so global loads stay in flight across the barrier until their first use.
-// Not for phases that exchange data through global memory.
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// Cross-lane sums.  __shfl_xor lowers to ds_bpermute_b32 (an LDS-crossbar round trip, ~100 cycles of dependent
-// latency per step); within a 16-lane row the same exchange is a DPP modifier on a VALU op (a few cycles):
-// quad_perm[1,0,3,2], quad_perm[2,3,0,1], row_half_mirror, row_mirror.
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float sum4(float v) { v += dpp_f<0xB1>(v); v += dpp_f<0x4E>(v); return v; }
-__device__ __forceinline__ float sum8(float v) { v = sum4(v); v += dpp_f<0x141>(v); return v; }
-__device__ __forceinline__ float sum16(float v) { v = sum8(v); v += dpp_f<0x140>(v); return v; }
-// Across the four 16-lane rows gfx950 has half-exchange instructions: v_permlane16_swap (odd rows of vdst <-> even rows of src)
-// and v_permlane32_swap (upper half of vdst <-> lower half of src).  With vdst = src = v the two results hold v[lane] and
-// v[lane ^ 16] (resp. v[lane ^ 32]) in some order in every lane, so a commutative combine of them is the xor exchange -- one
-// VALU-rate instruction instead of a ds_bpermute round trip.
-__device__ __forceinline__ float xadd16(float v) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float xadd32(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float xmax16(float v) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float xmax32(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float rows_sum(float v) { return xadd32(xadd16(v)); }   // over the 4 lanes {l, l^16, l^32, l^48}
 // Guard of the one-pass LayerNorm statistics (nat_l0w.h: l0w_layer_norm).  var = E[x^2] - mean^2 in fp32 loses log2(1 + mean^2 / var) of its 24
 // bits: nothing on the rows this model produces (|mean| of the order of the spread), but a row whose mean dwarfs its spread -- a
 // checkpoint with an outlier channel offset -- would get a variance of noise where torch's two-pass form is exact.  m2 = mean^2,
@@ -310,30 +253,6 @@ __device__ __forceinline__ float rows_sum(float v) { return xadd32(xadd16(v)); }
 // variance of that LayerNorm from the centred values instead.  Two instructions and a scalar branch per row tile on the fast path.
 __device__ __forceinline__ bool ln_row_cancels(float m2, float var1) { return m2 > 4096.0f * var1; }      // (per lane row; the caller ORs over its row tiles and ballots once)
 __device__ __forceinline__ bool ln_cancels(float m2, float var1) { return __builtin_amdgcn_ballot_w64(m2 > 4096.0f * var1) != 0ull; }
-__device__ __forceinline__ float rows_max(float v) { return xmax32(xmax16(v)); }
-__device__ __forceinline__ float sum32(float v) { v = sum16(v); return xadd16(v); }
-// sum over groups of LPR consecutive lanes (LPR = 8, 16, 32, 64), result in every lane of the group
-template <int LPR>
-__device__ __forceinline__ float group_sum(float v) {
-  if (LPR == 4) return sum4(v);
-  if (LPR == 8) return sum8(v);
-  if (LPR == 16) return sum16(v);
-  v = sum32(v);
-  if (LPR == 64) v = xadd32(v);
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) { return group_sum<64>(v); }
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // LayerNorm of one fp32 row of C = 8 * LPR columns held by LPR adjacent lanes (lr = lane % LPR; LPR = 4, 8, 16).  A lane owns columns
 // [4 lr, 4 lr + 4) and [C/2 + 4 lr, C/2 + 4 lr + 4): both 16-byte reads are then contiguous across the lanes of the row (a lane-stride of
 // 32 bytes would hit every LDS bank twice).  g0/b0 and g1/b1 are the scale / shift values of those two column groups:
@@ -404,11 +323,5 @@ __device__ __forceinline__ bool seq_live(int n, int c0, int c1, int c2, int seq)
   const int i = seq / 3, c = seq - 3 * i;
   return seq < n && i < (c == 0 ? c0 : c == 1 ? c1 : c2);
 }
-
-// Finiteness by bit pattern: a float is NaN / +-Inf iff its exponent field is all ones.  Integer compares, so the test also holds in the
-// translation units built with -fno-honor-nans (where x != x folds to false) -- used for the device flag behind the reference's
-// `assert torch.isfinite(q).all()` (planning_decoder.py:175).  exp_or accumulates the largest exponent field seen; nonfinite_exp tests it.
-__device__ __forceinline__ uint32_t exp_max(uint32_t acc, float v) { const uint32_t e = __float_as_uint(v) & 0x7f800000u; return acc > e ? acc : e; }
-__device__ __forceinline__ bool nonfinite_exp(uint32_t acc) { return acc == 0x7f800000u; }
 
 }  // namespace RIFT_NS

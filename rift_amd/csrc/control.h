@@ -1,4 +1,4 @@
-// The rollout tick's last step on the device (rift_control_tick, engine.hip): per CBV, keep the top-k candidates by logit, score them with
+// The rollout tick's last step on the device (rift_control_tick, shared.hip): per CBV, keep the top-k candidates by logit, score them with
 // a softmax over the kept logits, choose (the ref-free candidate joins last with score 0.25), move the chosen path into the CBV's frame and
 // step the waypoint PID -- what PLUTO._decide does on the host with trim_candidates + global_to_local (planning/pluto/inference.py;
 // reference pluto.py:142-279) and PIDController.control_pid (planning/pluto/controller/pid_controller.py; reference
@@ -10,9 +10,9 @@
 // One sum is not numpy's tree: the segment lengths behind the target speed are added in path order, which is what np.mean does below eight
 // segments (the default: 80 frames, interval 10, seven segments); from eight segments on numpy sums pairwise and the two agree to rounding.
 #pragma once
-#include "common.h"
+#include "lanes.h"
 
-namespace RIFT_NS {
+namespace rift {
 
 #define RIFT_CTL_CHUNK 16                        // CBVs per launch
 #define RIFT_CTL_STATE 44                        // doubles per pid_state row: turn ring [0,20) | speed ring [20,40) | turn head, last | speed head, last
@@ -140,4 +140,4 @@ __global__ __launch_bounds__(64) void control_tick_kernel(const CtlArr a) {
   o[6] = target; o[7] = bearing;
 }
 
-}  // namespace RIFT_NS
+}  // namespace rift

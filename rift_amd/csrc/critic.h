@@ -5,9 +5,9 @@
 // Backward is split so that every sum has a fixed order: a row kernel (16 rows per workgroup) produces the per-row deltas,
 // then each parameter gradient is a column / outer-product sum over the rows computed by exactly one thread.
 #pragma once
-#include "common.h"
+#include "lanes.h"
 
-namespace RIFT_NS {
+namespace rift {
 
 #define RIFT_CRITIC_IN 128
 #define RIFT_CRITIC_H 256
@@ -248,4 +248,4 @@ __global__ void critic_finalize_kernel(const float* __restrict__ flat, const dou
   if (dst) dst[o] = flat[i] * sc;
 }
 
-}  // namespace RIFT_NS
+}  // namespace rift

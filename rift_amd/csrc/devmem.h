@@ -3,7 +3,7 @@
 #include <cstddef>
 #include <utility>
 
-// The two hooks every allocation goes through.  The library defines them once (engine.hip: the HIP runtime's calls); the host test
+// The two hooks every allocation goes through.  The library defines them once (shared.hip: the HIP runtime's calls); the host test
 // (tests/test_devmem_host.py) defines counting fakes, so that the failure paths -- which cannot be provoked on a GPU -- run on the CPU.
 int rift_dev_alloc(void** p, size_t bytes);      // 0 on success (the library: the hipError_t)
 void rift_dev_free(void* p);

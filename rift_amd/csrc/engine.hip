@@ -14,14 +14,9 @@
 #include <dlfcn.h>
 #include <vector>
 
-#include "../../include/rift_hip.h"
-#include "devmem.h"
-#include "adv.h"
-#include "eval_params.h"
-#include "objective_params.h"
+#include "engine_ctx.h"
 #include "gemm.h"
 #include "kernels.h"
-#include "loss.h"
 #include "nat_l0w.h"
 #include "nat_l1w.h"
 #include "enc_fused.h"
@@ -33,15 +28,11 @@
 #include "fo_w.h"
 #include "pe_fused.h"
 #include "fourier_fused.h"
-#include "critic.h"
 #include "fpn_fused.h"
 #include "fwd_plan.h"
 #include "ego_fused.h"
 #include "heads_fused.h"
 #include "pi_fused.h"
-#include "rollout.h"
-#include "tick_multi.h"
-#include "control.h"
 
 #define ENC_NW 8
 
@@ -49,206 +40,8 @@ using namespace RIFT_NS;
 
 namespace {
 
-struct Param { void* data; int64_t numel; int ndim; int64_t shape[4]; };
-
-struct PWShape { int N = 0, K = 0, Kp = 0, Npad = 0; const float* bias = nullptr; };
-struct PW : PWShape {   // packed weight image of one linear map Y = X W^T (+ b); owns its images, lives in RiftCtx::pw and is handed on by reference
-  DevBuf<unsigned short> bf; DevBuf<float> f32;
-  DevBuf<unsigned short> hid;   // (fc2 weights of the fused encoder only) the same image in hidden-layer operand words (opfmt.h); pack_hid
-  DevBuf<float> own_bias;       // (pack_stacked_rows only) the stacked bias that `bias` points to
-};
-
-struct Tap { float* p; int64_t numel; };
-
-}  // namespace
-
-struct RiftCtx {
-  int opfmt = 0;                         // FIRST member (set by rift_ctx_create of the build): abi.cpp reads it to route a call to the build (bf16 / fp16 operands) that owns the context
-  int device = 0;
-  std::string err;
-  std::unordered_map<std::string, Param> params;
-  std::unordered_map<std::string, PW> pw;
-  struct WConst { DevBuf<float> p; bool ready = false; };
-  std::unordered_map<std::string, WConst> wconst;   // activations that depend on (frozen) weights only, computed once per model load
-  // activation arena (bump allocator, reset every forward).  A forward with RIFT_F_DEFER_HEAD alternates between two arenas, so that the
-  // policy head / loss / backward of step k (rift_forward_head, rift_loss_backward on another stream) read step k's activations while the
-  // frozen trunk of step k + 1 already writes its own.
-  char* arena = nullptr; size_t arena_cap = 0, arena_off = 0;      // (the current slot of `arenas`, as A_alloc reads it)
-  long long dry_key[11] = {}; size_t dry_need = 0;      // the arena size of the last sized forward and what it depended on
-  DevBuf<char> arenas[RIFT_DEFER_SLOTS]; int parity = 0;     // (parity: the arena of the current forward)
-  struct Head {   // what the policy head of a forward needs (pi_forward .. trajectory heads); kept per arena for the deferred form
-    bool valid = false, fp32 = false, need_traj = false;
-    float *Q = nullptr, *x0p = nullptr, *QF = nullptr, *Hpi = nullptr, *prob = nullptr, *traj = nullptr, *o3[3] = {nullptr, nullptr, nullptr}, *oT[3] = {nullptr, nullptr, nullptr};
-    uint8_t* r_kpm = nullptr; int bs = 0, R = 0, nQ = 0;
-    bool dec_pending = false; DecWP dec;      // the planning decoder deferred along with the head (small batches, see dec_defer_max)
-  } head[RIFT_DEFER_SLOTS];
-  // (round 4) Below a chip-filling batch a step is the LATENCY of token assembly -> encoder -> decoder on the caller's queue (one workgroup per
-  // scene whatever the batch) while most CUs idle.  Nothing behind the encoder belongs to the frozen trunk's critical path of the NEXT
-  // step, so with the head deferred the decoder goes with it: rift_forward_head_back launches decoder -> head on the caller's update
-  // stream, and the caller's queue holds token assembly -> encoder of step k + 1 beside them.  All its operands live in the forward's
-  // arena (four slots).  Which batch sizes: forward_impl's measured table, or bs <= RIFT_DEC_DEFER (0 = never).
-  int dec_defer_max = -1; bool dec_split = true;   // (-1: the measured table in forward_impl; RIFT_DEC_DEFER=<n>: bs <= n)            // (RIFT_DEC_SPLIT=0: the deferred decoder as one launch)
-  int dec_layers = 4;               // (diagnostic, RIFT_DEC_LAYERS) 0 / 2: the non-deferred decoder stops after that many layers -- the `dec3` tap then holds q0 / the
-                                    // output of layer 1; 22: layers [0, 2) and [2, 4) of an eval forward as two launches; anything else: all four, one launch
-  bool ro8 = true;                                         // candidate rollout with eight lanes per candidate (rollout.h; RIFT_RO8=0: one lane, the round-1 form)
-  DevBuf<float> ro_raw;             // rift_rollout: the unsmoothed speed history handed from the closed-loop kernel to the kinematics kernel
-  DevBuf<char> tick_scratch;      // rift_group_advantage_tick: per-CBV intermediates (reused CBV by CBV in stream order)
-  // (Measured and not kept: the deferred decoder on a third stream of the engine's own, so that decoder k would also run beside tail k - 1 --
-  // 0.21 -> 0.40 ms at 32 scenes, with 4 or 8 hardware queues; every stream beyond the four the step uses has made cross-queue waits slower.)
-  bool dry = false;
-  hipStream_t stream = nullptr;
-  std::unordered_map<std::string, Tap> taps;
-  // state of the last forward, consumed by rift_loss_backward
-  float* last_qfinal = nullptr; float* last_hpi = nullptr; float* last_prob = nullptr;
-  uint8_t* last_rkpm = nullptr; int last_bs = 0, last_R = 0;
-  // loss scratch
-  DevBuf<double> l_S, l_cnt; DevBuf<float> l_dz, l_partial;
-  DevBuf<double> l_T;      // [bs][LOSS_NTERM] per-scene term sums of rift_loss_backward_ex, reserved when its `terms` are asked for
-  DevBuf<double> l_sink;   // [2] where loss_reduce_kernel's objective sums go when there is no objective (rift_head_backward)
-  DevBuf<float> ego_w, ego_b;   // packed (6,128) linears of StateAttentionEncoder
-  bool nat_fused = true; int gemm_dbg = 0;
-  DevBuf<unsigned short> l0w_img; DevBuf<float> l0w_par;   // wave-private level-0 NAT kernel (nat_l0w.h)
-  DevBuf<unsigned short> encw_img; DevBuf<float> encw_par;   // weight stream / parameters of the dense-traffic scene encoder (enc_w.h)
-  DevBuf<unsigned short> l2w_img; DevBuf<float> l2w_par;   // wave-private, weight-streaming level-2 NAT kernel (nat_l2w.h)
-  DevBuf<unsigned short> l1w_img; DevBuf<float> l1w_par;   // wave-private level-1 NAT kernel (nat_l1w.h)
-  DevBuf<unsigned short> enc_wqkv[4];   // chunked (q|k|q|k|v|v) bf16 in_proj images
-  DevBuf<float> enc_bqkv[4];
-  DevBuf<int> enc_idx; bool enc_fused = true;
-  int poison_lds = -1;                   // RIFT_POISON_LDS diagnostic (see lds_poison_kernel)
-  // the per-call diagnostic switches of the environment, read ONCE when the context is made (nine getenv calls per forward were ~10 us of a
-  // call whose host time bounds a small-batch step): RIFT_{PE,PEW,NAT,ENC,DEC}_TS, RIFT_{PEW,DEC}_DBG, RIFT_POISON_ARENA
-  struct { std::string delay_label; long long delay_ticks = 0; int pe_ts = -1, pew_dbg = 0, pew_ts = 0, nat_ts = 0, enc_ts = 0, dec_ts = 0, dec_dbg = 0, poison_arena = -1; } dg;
-  hipEvent_t param_event = nullptr;      // rift_set_param_event: the trainable parameters are valid once this event has passed
-  bool dec_fused = true;
-  bool two_streams = true; bool nat_compact = true; bool pe_live = true; bool pe_pack = true;
-  hipStream_t prep_stream = nullptr; bool prep_set = false; hipEvent_t ev_prep = nullptr; int side_gate = 0;      // rift_set_prepare_stream
-  hipEvent_t ev_join2 = nullptr; bool nat_aside = true;      // (the history chain behind the preparation on the prepare stream: its join event)
-  hipStream_t side = nullptr; bool side_owned = false; hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // (RIFT_TWO_STREAMS=0 switches it off) the agent-history chain (NAT levels + FPN tail) on a second stream beside the map / reference-line chain
-  bool fo_w = true; DevBuf<unsigned short> fow_img[3]; DevBuf<float> fow_par[3];   // wave-private Fourier embeddings (fo_w.h): tokens, speed limits, reference-line positions
-  bool pe_w = true; DevBuf<unsigned short> pew_img[2];   // wave-private PointsEncoder pass B (pe_w.h): weight streams of the map / reference-line encoders
-  DevBuf<unsigned short> decw_img; DevBuf<float> decw_par;   // weight stream / parameter blocks of the decoder kernel (dec_w.h)
-  DevBuf<double> clip_part;
-  struct Dp { bool on = false; int off = 0, gbs = 0; double* xchg = nullptr; long long len = 0; RiftExchangeFn fn = nullptr; void* user = nullptr; } dp;   // rift_set_dp
-  DevBuf<int> nonfinite;            // device flag set by the policy-head kernels when the decoder output is not finite
-  // the in-launch ranking's published per-scene counts (kernels.h: rank_scene_body), one array per arena; they persist between launches
-  // (a word is valid when it carries the launch's epoch; zero at allocation, epochs start at 1)
-  // The look-back over these words relies on ONE preparation launch in flight per arena slot and on an epoch fixed on the host for each
-  // launch (prepare_inputs): a captured graph that replays the launch would replay a stale epoch, so that launch is never graph-replayed.
-  DevBuf<unsigned long long> rk_pub[RIFT_DEFER_SLOTS]; unsigned int rk_epoch[RIFT_DEFER_SLOTS] = {};
-  bool rank_fault = false;               // RIFT_RANK_FAULT=1 (diagnostic): the first scene block of the in-launch ranking never publishes its counts
-  bool no_skip = false;                  // RIFT_NO_SKIP=1: the scene encoder computes the branches DropPath drops and the decoder the padded reference lines' discarded
-                                         // sub-blocks, as until round 7 (the reference of tests/test_gpu_skip_discarded.py and the "before" leg of the A/B in one binary)
-  bool enc112 = true;                    // RIFT_ENC112=0: scenes of 97 .. 112 token slots on enc_w_kernel (rounds 3 - 5) instead of the fused kernel's 112-row layout
-  bool rank_in_prep = true;              // RIFT_RANK_IN_PREP=0: the ranking as its own launch behind the preparation (nat_rank_kernel, rounds 3 - 5)
-  void* comm = nullptr; int comm_rank = 0, comm_world = 1;      // library-owned RCCL communicator (rift_comm_init), or null
-  DevBuf<float> cr_buf; DevBuf<double> cr_part;   // PPO critic scratch (rows x 1153 floats)
-  bool pe_fused = true; bool fo_fused = true; int nat_grid = 256; bool fpn_fused = true; bool ego_fused = true; bool heads_fused = true; bool pi_fused = true;
-  bool loaded = false;
-  // optional per-launch HIP-event profiling (bench roofline leg; off on the timed path)
-  bool prof_on = false; double prof_flops = 0.0; bool prof_shapes = false;
-  std::set<std::string> prof_names;
-  std::vector<hipEvent_t> prof_pool; size_t prof_used = 0;
-  struct Rec { const char* label; hipEvent_t e0, e1; double flops; };
-  std::vector<Rec> prof_recs;
-  ~RiftCtx() {      // (the DevBuf members free the device memory)
-    if (ev_prep) (void)hipEventDestroy(ev_prep);
-    if (ev_join2) (void)hipEventDestroy(ev_join2);
-    if (side && side_owned) (void)hipStreamDestroy(side);
-    if (ev_fork) { (void)hipEventDestroy(ev_fork); (void)hipEventDestroy(ev_join); }
-  }
-};
-
-static void prof_events(RiftCtx* c, hipEvent_t* e0, hipEvent_t* e1) {
-  while (c->prof_pool.size() < c->prof_used + 2) { hipEvent_t e; (void)hipEventCreate(&e); c->prof_pool.push_back(e); }
-  *e0 = c->prof_pool[c->prof_used++]; *e1 = c->prof_pool[c->prof_used++];
-}
-static void prof_push(RiftCtx* c, const char* label, hipEvent_t e0, hipEvent_t e1, double flops) {
-  c->prof_recs.push_back(RiftCtx::Rec{label, e0, e1, flops});
-}
-
-#define HIPCHK(ctx, expr)                                                                 \
-  do {                                                                                    \
-    hipError_t e__ = (expr);                                                              \
-    if (e__ != hipSuccess) {                                                              \
-      (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                    \
-      return RIFT_ERR_HIP;                                                                \
-    }                                                                                     \
-  } while (0)
-#define DEVCHK(ctx, expr) HIPCHK(ctx, (hipError_t)(expr))      // DevBuf::reserve: the allocation hook hands the runtime's error through
-
-// devmem.h's hooks: every device allocation and release of the library (defined once: by the bf16 build, which every library holds)
-#if !RIFT_OP_F16
-__attribute__((visibility("hidden"))) int rift_dev_alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
-__attribute__((visibility("hidden"))) void rift_dev_free(void* p) { (void)hipFree(p); }
-#endif
-
-namespace {
-
-inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
-
-template <class T>
-T* A_alloc(RiftCtx* c, size_t n) {
-  size_t bytes = (n * sizeof(T) + 255) & ~(size_t)255;
-  char* p = c->dry ? nullptr : c->arena + c->arena_off;
-  c->arena_off += bytes;
-  return reinterpret_cast<T*>(p);
-}
-
-void tap(RiftCtx* c, const char* name, float* p, int64_t numel) {
-  if (!c->dry) c->taps[name] = Tap{p, numel};
-}
-
-// diagnostic (RIFT_POISON_LDS=<byte>): LDS keeps its contents between kernels, so a kernel that reads LDS it never wrote sees whatever
-// the previous kernel on that CU left there.  With the switch set every launch is preceded by a kernel that fills all 160 KB of every
-// CU's LDS with the byte (0xFF = NaN pattern): such a read then shows up in the parity tests instead of depending on history.
-__global__ __launch_bounds__(256) void lds_poison_kernel(unsigned int pattern) {
-  extern __shared__ unsigned int lds_all[];
-  for (int i = threadIdx.x; i < 160 * 1024 / 4; i += 256) lds_all[i] = pattern;
-  __syncthreads();
-  if (lds_all[threadIdx.x] != pattern) asm volatile("s_nop 0");      // keep the stores
-}
-
-// diagnostic (RIFT_DELAY=<launch label>:<microseconds>): one lane spins for that long on the stream right behind every launch of that
-// label -- the successors of the kernel start later, no CU is taken from anybody.  d(step time) / d(delay) is the kernel's share of the
-// step's critical path: ~1 on it, ~0 where the step pipeline has slack (tools/critical_path.py).
-__global__ void delay_kernel(long long ticks) {
-  const long long t0 = wall_clock64();
-  while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
-}
-inline void delay_behind(RiftCtx* c, const char* label) {
-  if (c->dg.delay_ticks > 0 && c->dg.delay_label == label) hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(1), 0, c->stream, c->dg.delay_ticks);
-}
-
-// the bookkeeping around one launch (the callable): LDS poison ahead of it, profiling events around it, the diagnostic delay behind it
-template <class F>
-void launch_call(RiftCtx* c, const char* label, F&& f) {
-  if (c->dry) return;
-  if (c->poison_lds >= 0) {
-    const unsigned int b = (unsigned int)c->poison_lds & 0xffu;
-    hipLaunchKernelGGL(lds_poison_kernel, dim3(2048), dim3(256), 160 * 1024, c->stream, b | (b << 8) | (b << 16) | (b << 24));
-  }
-  if (c->prof_on) {
-    hipEvent_t e0, e1;
-    prof_events(c, &e0, &e1);
-    (void)hipEventRecord(e0, c->stream);
-    f();
-    (void)hipEventRecord(e1, c->stream);
-    prof_push(c, label, e0, e1, c->prof_flops);
-    c->prof_flops = 0.0;
-    return;
-  }
-  f();
-  delay_behind(c, label);
-}
-
-template <class... KArgs, class... Args>
-void launch(RiftCtx* c, const char* label, void (*kern)(KArgs...), dim3 grid, dim3 block, size_t shmem, Args... args) {
-  if (grid.x == 0 || grid.y == 0) return;
-  launch_call(c, label, [&] { hipLaunchKernelGGL(kern, grid, block, shmem, c->stream, static_cast<KArgs>(args)...); });
-}
-
 template <class... KArgs>
-void launch_gemm(RiftCtx* c, const char* label, void (*kern)(KArgs...), dim3 grid, dim3 block, size_t shmem, const GemmP& g) {
+void launch_gemm(Ctx* c, const char* label, void (*kern)(KArgs...), dim3 grid, dim3 block, size_t shmem, const GemmP& g) {
   c->prof_flops = 2.0 * (double)g.M * (double)g.N * (double)g.K;
   if (c->prof_on && c->prof_shapes) {   // RIFT_PROF_SHAPES=1: one label per GEMM shape (interned)
     char tmp[160];
@@ -262,27 +55,16 @@ void launch_gemm(RiftCtx* c, const char* label, void (*kern)(KArgs...), dim3 gri
 // Weight-only products (mode embeddings through q_proj / m2m in-projection, the ego query projection): input
 // independent, so they are computed by the first forward after rift_model_load and kept (per precision mode).
 // Returns the buffer and whether the caller must fill it now.
-float* wconst_get(RiftCtx* c, const std::string& key, size_t n, bool fp32, bool* fill) {
-  RiftCtx::WConst& w = c->wconst[key + (fp32 ? "#32" : "#16")];
+float* wconst_get(Ctx* c, const std::string& key, size_t n, bool fp32, bool* fill) {
+  Ctx::WConst& w = c->wconst[key + (fp32 ? "#32" : "#16")];
   if (w.p.reserve(n) != 0) { *fill = false; return nullptr; }
   *fill = !w.ready && !c->dry;
   if (!c->dry) w.ready = true;
   return w.p.get();
 }
 
-const Param* find(RiftCtx* c, const std::string& name) {
-  auto it = c->params.find(name);
-  return it == c->params.end() ? nullptr : &it->second;
-}
-
-const float* fptr(RiftCtx* c, const std::string& name) {
-  const Param* p = find(c, name);
-  if (!p) { if (c->err.empty()) c->err = "missing parameter: " + name; return nullptr; }
-  return reinterpret_cast<const float*>(p->data);
-}
-
 // ---- weight packing -------------------------------------------------------------------
-int pack(RiftCtx* c, const std::string& key, const float* src, int n_src, int N, int K, int src_row_off,
+int pack(Ctx* c, const std::string& key, const float* src, int n_src, int N, int K, int src_row_off,
          int src_col_off, int src_ld, int conv_C, int tap_lo, int tap_n, const float* bias) {
   PW w;
   w.N = N; w.K = K; w.Kp = (K + 31) & ~31; w.Npad = (N + 15) & ~15; w.bias = bias;
@@ -299,7 +81,7 @@ int pack(RiftCtx* c, const std::string& key, const float* src, int n_src, int N,
 }
 
 // + the hidden-layer-operand image of an already packed weight (the fused scene encoder's fc2: its A rows are GELU outputs, common.h: gelu4_hid)
-int pack_hid(RiftCtx* c, const std::string& key) {
+int pack_hid(Ctx* c, const std::string& key) {
   PW& w = c->pw[key];
   const size_t cnt = (size_t)w.Npad * w.Kp;
   DEVCHK(c, w.hid.reserve(cnt));
@@ -307,7 +89,7 @@ int pack_hid(RiftCtx* c, const std::string& key) {
   return RIFT_OK;
 }
 
-int pack_linear(RiftCtx* c, const std::string& prefix) {   // nn.Linear
+int pack_linear(Ctx* c, const std::string& prefix) {   // nn.Linear
   const Param* w = find(c, prefix + ".weight");
   if (!w || w->ndim != 2) { c->err = "missing linear " + prefix; return RIFT_ERR_ARG; }
   const Param* b = find(c, prefix + ".bias");
@@ -315,7 +97,7 @@ int pack_linear(RiftCtx* c, const std::string& prefix) {   // nn.Linear
               (int)w->shape[1], 0, 0, 0, b ? (const float*)b->data : nullptr);
 }
 
-int pack_conv(RiftCtx* c, const std::string& prefix) {     // nn.Conv1d k=3 -> tap-major [N][3*C]
+int pack_conv(Ctx* c, const std::string& prefix) {     // nn.Conv1d k=3 -> tap-major [N][3*C]
   const Param* w = find(c, prefix + ".weight");
   if (!w || w->ndim != 3 || w->shape[2] != 3) { c->err = "missing conv " + prefix; return RIFT_ERR_ARG; }
   const Param* b = find(c, prefix + ".bias");
@@ -325,7 +107,7 @@ int pack_conv(RiftCtx* c, const std::string& prefix) {     // nn.Conv1d k=3 -> t
 }
 
 // rows [r0, r0+n_src) of an (R, K) matrix as a GEMM with N output columns (rows beyond n_src are zero)
-int pack_rows(RiftCtx* c, const std::string& key, const std::string& wname, const std::string& bname, int r0,
+int pack_rows(Ctx* c, const std::string& key, const std::string& wname, const std::string& bname, int r0,
               int n_src, int N) {
   const Param* w = find(c, wname);
   if (!w || w->ndim != 2) { c->err = "missing matrix " + wname; return RIFT_ERR_ARG; }
@@ -335,7 +117,7 @@ int pack_rows(RiftCtx* c, const std::string& key, const std::string& wname, cons
 }
 
 // columns [c0, c0+K) of a Linear weight (N, Ktot)
-int pack_cols(RiftCtx* c, const std::string& key, const std::string& prefix, int c0, int K, bool with_bias) {
+int pack_cols(Ctx* c, const std::string& key, const std::string& prefix, int c0, int K, bool with_bias) {
   const Param* w = find(c, prefix + ".weight");
   if (!w || w->ndim != 2) { c->err = "missing linear " + prefix; return RIFT_ERR_ARG; }
   const Param* b = with_bias ? find(c, prefix + ".bias") : nullptr;
@@ -343,10 +125,8 @@ int pack_cols(RiftCtx* c, const std::string& key, const std::string& prefix, int
               b ? (const float*)b->data : nullptr);
 }
 
-#define TRY(x) do { int rc__ = (x); if (rc__ != RIFT_OK) return rc__; } while (0)
-
 // rows [r0, r0+n) of `nsrc` (N_src, K) matrices stacked into one (nsrc*n, K) GEMM weight (+ stacked bias, engine-owned)
-int pack_stacked_rows(RiftCtx* c, const std::string& key, const std::vector<std::string>& wnames, const std::vector<std::string>& bnames,
+int pack_stacked_rows(Ctx* c, const std::string& key, const std::vector<std::string>& wnames, const std::vector<std::string>& bnames,
                       int r0, int n) {
   const Param* w0 = find(c, wnames[0]);
   if (!w0 || w0->ndim != 2) { c->err = "missing matrix " + wnames[0]; return RIFT_ERR_ARG; }
@@ -376,9 +156,9 @@ int pack_stacked_rows(RiftCtx* c, const std::string& key, const std::vector<std:
   return RIFT_OK;
 }
 
-int pack_mlp_layer(RiftCtx* c, const std::string& p) { TRY(pack_linear(c, p + ".mlp.0")); return pack_linear(c, p + ".mlp.3"); }
+int pack_mlp_layer(Ctx* c, const std::string& p) { TRY(pack_linear(c, p + ".mlp.0")); return pack_linear(c, p + ".mlp.3"); }
 
-int pack_fourier(RiftCtx* c, const std::string& p, int D) {
+int pack_fourier(Ctx* c, const std::string& p, int D) {
   for (int d = 0; d < D; ++d) {
     TRY(pack_linear(c, p + ".mlps." + std::to_string(d) + ".0"));
     TRY(pack_cols(c, p + ".mlps." + std::to_string(d) + ".0.lo", p + ".mlps." + std::to_string(d) + ".0", 0, 128, true));     // fused kernel:
@@ -388,7 +168,7 @@ int pack_fourier(RiftCtx* c, const std::string& p, int D) {
   return pack_linear(c, p + ".to_out.2");
 }
 
-int pack_points_encoder(RiftCtx* c, const std::string& p) {
+int pack_points_encoder(Ctx* c, const std::string& p) {
   TRY(pack_linear(c, p + ".first_mlp.0"));
   TRY(pack_linear(c, p + ".first_mlp.3"));
   TRY(pack_cols(c, p + ".second_mlp.0.feat", p + ".second_mlp.0", 0, 256, true));
@@ -396,7 +176,7 @@ int pack_points_encoder(RiftCtx* c, const std::string& p) {
   return pack_linear(c, p + ".second_mlp.3");
 }
 
-int pack_self_mha(RiftCtx* c, const std::string& p) {
+int pack_self_mha(Ctx* c, const std::string& p) {
   TRY(pack_rows(c, p + ".qkv", p + ".in_proj_weight", p + ".in_proj_bias", 0, 384, 384));
   return pack_linear(c, p + ".out_proj");
 }
@@ -416,7 +196,7 @@ GemmP mk(const float* X, int ldx, int M, const PWShape& w, float* Y, int ldy) {
 //   m2n6 : wave = 32 rows x  96 cols   -- 128 < N <= 192
 //   m4n4 : wave = 64 rows x  64 cols   -- N > 192, 256 columns per pass
 template <bool BF16>
-void gemm_launch(RiftCtx* c, GemmP g) {
+void gemm_launch(Ctx* c, GemmP g) {
   const size_t a_bytes = (((size_t)64 * (g.Kp + Prec<BF16>::PAD) * sizeof(typename Prec<BF16>::lds_t)) + 15) & ~(size_t)15;
   int variant;   // 0 m1n8, 1 m4n2, 2 m2n6, 3 m4n4
   if (g.N <= 128) variant = (g.Kp >= 128 && g.N > 32) ? 1 : 0;
@@ -437,14 +217,14 @@ void gemm_launch(RiftCtx* c, GemmP g) {
   }
 }
 
-void gemm(RiftCtx* c, GemmP g, const void* W, bool fp32) {      // W: the image of the precision (PW::f32 / PW::bf)
+void gemm(Ctx* c, GemmP g, const void* W, bool fp32) {      // W: the image of the precision (PW::f32 / PW::bf)
   if (g.M <= 0) return;
   // vectorised A staging needs 16-byte aligned rows: dense conv windows (C % 4 == 0) or ldx % 4 == 0, K % 4 == 0
   const bool conv = g.amode == AMODE_CONV3;
   const bool al = (((uintptr_t)g.X) & 15) == 0 && (g.K % 4 == 0) && (conv ? (g.cv_C % 4 == 0 && g.ldx == g.cv_C) : (g.ldx % 4 == 0)) &&
                   (g.pro == PRO_NONE || ((((uintptr_t)g.pg) | ((uintptr_t)g.pb)) & 15) == 0);
   const int KV = g.Kp / 4;
-  g.dbg = c->gemm_dbg;
+  g.dbg = c->sw.gemm_dbg;
   g.stage = !al ? 0 : (KV <= 8 ? 1 : KV <= 16 ? 2 : KV <= 32 ? 3 : KV <= 64 ? 4 : 5);
   g.evec = (g.N % 4 == 0) && (g.ldy % 4 == 0) && ((((uintptr_t)g.Y) & 15) == 0) &&
            (!g.bias || (((uintptr_t)g.bias) & 15) == 0) && (!g.gbias || (((uintptr_t)g.gbias) & 15) == 0) &&
@@ -453,12 +233,12 @@ void gemm(RiftCtx* c, GemmP g, const void* W, bool fp32) {      // W: the image 
   if (fp32) gemm_launch<false>(c, g);
   else gemm_launch<true>(c, g);
 }
-void gemm(RiftCtx* c, const GemmP& g, const PW& w, bool fp32) { gemm(c, g, fp32 ? (const void*)w.f32.get() : (const void*)w.bf.get(), fp32); }
+void gemm(Ctx* c, const GemmP& g, const PW& w, bool fp32) { gemm(c, g, fp32 ? (const void*)w.f32.get() : (const void*)w.bf.get(), fp32); }
 
-int set_lds_attrs(RiftCtx* c) {
+int set_lds_attrs(Ctx* c) {
   const int big = 160 * 1024;
 #define SETATTR(K) HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, big))
-  SETATTR(rollout_kernel);
+  HIPCHK(c, (hipError_t)shared_set_attributes());      // (rollout_kernel; shared.hip)
   SETATTR(enc_fused_kernel<ENC_NW>);
   HIPCHK(c, (hipError_t)enc112_set_attributes());
   HIPCHK(c, (hipError_t)decw_set_attributes());
@@ -491,35 +271,6 @@ int set_lds_attrs(RiftCtx* c) {
 }
 
 const std::string HE = "agent_encoder.history_encoder", PD = "planning_decoder";
-
-// per-forward context: the flags, the stream plan, the batch dimensions, and what one stage of forward_impl hands to the next
-struct Fwd {
-  RiftCtx* c; bool train, drop, fp32, need_traj, bn_update; uint32_t seed; uint32_t stream_id = 1;
-  uint32_t next_stream() { return stream_id++; }
-  // data parallel (rift_set_dp): xchg[0, kb) = quirk-mask slots of the global minibatch, xchg[kb, ...) = BatchNorm sums of the current point
-  bool dp = false, kpm_pending = false; int kb = 0; uint8_t* g_rkpm = nullptr;
-  uint8_t* r_tiles = nullptr;                        // tiles of every reference line up to its last valid point (prep_kernel), for pe_w_kernel's packed rounds
-  const RiftFeatureBatch* B = nullptr; const RiftOutputs* out = nullptr; int flags = 0;
-  StreamPlan plan; hipStream_t on[3] = {nullptr, nullptr, nullptr};      // (indexed by PlanStream)
-  int bs = 0, A = 0, Mp = 0, R = 0, S = 0, T = 0, N = 0, M = 12, nA = 0, nP = 0, nL = 0, nQ = 0, nT = 0;
-  DropStats ds = {};                                 // diagnostic build (dropstats.h): this forward's counters; all zero in the product library
-  // prepare_inputs
-  float *F9 = nullptr, *F10 = nullptr, *F6 = nullptr, *pos = nullptr, *r_pos = nullptr;
-  uint8_t *valid_agent = nullptr, *kpm = nullptr, *r_kpm = nullptr;
-  bool nat_compact = false; int *nat_aidx = nullptr, *nat_cnt = nullptr;      // the history encoder on the compacted sequences (nat_l0w.h ranks them)
-  const uint8_t* q_kpm = nullptr; int q_bs = 0, q_off = 0;                    // the r2r mask quirk's rows: this shard's, or the gathered global minibatch's
-  // history_encoder, ego_token, map_and_embeddings, assemble_tokens
-  float *nat_out = nullptr, *x_ego = nullptr, *poly = nullptr, *r_emb = nullptr, *speed_emb = nullptr, *PEtok = nullptr, *Q = nullptr, *X = nullptr;
-  bool pe_pair = false, fo3 = false, rpe_done = false;
-  // scene_encoder
-  float* ENC = nullptr;
-  unsigned short* enc_KT = nullptr;   // the decoder's cross-attention K | V^T operand fragments, written by the encoder kernel's tail
-  uint8_t* kpm_c = nullptr;           // the key padding of the compacted encoder rows (bs, 96): what the decoder masks those fragments with
-  float* enc_x0p = nullptr;           // cat_x_proj's ego-token half, written by the encoder kernel's tail
-  bool enc_wide = false;
-  // planning_decoder
-  bool dec_deferred = false; DecWP dec_later;
-};
 
 // RCCL through dlopen (rift_comm_*): the library has no link-time dependency on a communication library; an RCCL that is already in the
 // process (torch's) is reused so that one process does not run two of them.
@@ -557,7 +308,7 @@ static RcclApi& rccl_api(std::string* why) {
   if (why) *why = err;
   return api;
 }
-static int comm_sum_f64(RiftCtx* c, double* buf, long long count, hipStream_t stream) {
+static int comm_sum_f64(Ctx* c, double* buf, long long count, hipStream_t stream) {
   RcclApi& r = rccl_api(nullptr);
   if (!c->comm || !r.ok) return -1;
   return r.AllReduce(buf, buf, (size_t)count, /*ncclDouble*/ 8, /*ncclSum*/ 0, c->comm, stream);
@@ -566,7 +317,7 @@ static int comm_sum_f64(RiftCtx* c, double* buf, long long count, hipStream_t st
 // All-reduce xchg[kb, kb + n) over the ranks (BatchNorm sums); the first exchange of a forward also carries the mask slots [0, kb)
 // and is followed by their conversion into the gathered padding mask.  Dry (arena sizing) passes exchange nothing.
 void dp_exchange(Fwd& f, long long n) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   if (!f.dp) return;
   const bool with_kpm = f.kpm_pending;
   f.kpm_pending = false;
@@ -580,14 +331,14 @@ void dp_exchange(Fwd& f, long long n) {
 }
 
 void layernorm(Fwd& f, const float* X, int ldx, float* Y, int ldy, int rows, int C, const std::string& name, int relu = 0) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   launch(c, "layernorm_kernel", layernorm_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, X, ldx, Y, ldy, rows, C, fptr(c, name + ".weight"),
          fptr(c, name + ".bias"), 1e-5f, relu);
 }
 
 // FourierEmbedding (fourier_embedding.py:45-55): in (rows, D) -> out (rows, 128)
 FourierP fourier_desc(Fwd& f, const float* in, int in_ld, int rows, int D, const std::string& p, int wrap_dim, float* add_to) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   FourierP q; memset(&q, 0, sizeof(q));
   q.in = in; q.in_ld = in_ld; q.rows = rows; q.D = D; q.wrap_dim = wrap_dim; q.freqs = fptr(c, p + ".freqs.weight");
   for (int d = 0; d < D; ++d) {
@@ -606,8 +357,8 @@ FourierP fourier_desc(Fwd& f, const float* in, int in_ld, int rows, int D, const
 
 // add_to != nullptr: the embedding is added into that (rows, 128) buffer, which is returned
 float* fourier(Fwd& f, const float* in, int in_ld, int rows, int D, const std::string& p, int wrap_dim, float* add_to = nullptr) {
-  RiftCtx* c = f.c;
-  if (!f.fp32 && c->fo_fused && D <= 3) {
+  Ctx* c = f.c;
+  if (!f.fp32 && c->sw.fo_fused && D <= 3) {
     FourierP3 q3; memset(&q3, 0, sizeof(q3));
     q3.e[0] = fourier_desc(f, in, in_ld, rows, D, p, wrap_dim, add_to);
     q3.nblk[0] = cdiv(rows, FO_ROWS); q3.count = 1;
@@ -643,7 +394,7 @@ float* fourier(Fwd& f, const float* in, int in_ld, int rows, int D, const std::s
 // BatchNorm1d folded to an affine (scale, shift) for the next GEMM prologue.
 void batchnorm_affine(Fwd& f, const float* X, int rows, int C, const uint8_t* valid, const std::string& name,
                       float** scale, float** shift) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   *scale = A_alloc<float>(c, C); *shift = A_alloc<float>(c, C);
   const int rows_per_blk = 128;
   const int nblk = cdiv(rows, rows_per_blk);
@@ -665,7 +416,7 @@ void batchnorm_affine(Fwd& f, const float* X, int rows, int C, const uint8_t* va
 // The two PointsEncoders (map polygons 10 -> 128 with 20 points, reference lines 6 -> 128 with 120 points) in the fused
 // three-pass form (pe_fused.h), side by side: five launches for both (statistics, BN finalize, mid, BN finalize, out).
 static void pe_fill(Fwd& f, PeP& q, const float* F, int Cin, int groups, int n, const uint8_t* valid, const std::string& p) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   memset(&q, 0, sizeof(q));
   const int rows = groups * n;
   q.F = F; q.Cin = Cin; q.valid = valid; q.rows = rows; q.ntiles = cdiv(rows, 120);
@@ -682,10 +433,10 @@ static void pe_fill(Fwd& f, PeP& q, const float* F, int Cin, int groups, int n, 
   q.gp = A_alloc<float>(c, (size_t)groups * 256);
   q.out = A_alloc<float>(c, (size_t)groups * 128);
   q.do_stats = f.train ? 1 : 0;
-  { if (c->dg.pe_ts == n) { q.ts = A_alloc<long long>(c, 64); q.ts_tile = 0; tap(c, "pe_ts", (float*)q.ts, 128); } }
+  { if (c->sw.pe_ts == n) { q.ts = A_alloc<long long>(c, 64); q.ts_tile = 0; tap(c, "pe_ts", (float*)q.ts, 128); } }
 }
 
-static BnFinP bn_fin(RiftCtx* c, const PeP& q, const std::string& name, int C, const float* part, const float* sc, const float* sh,
+static BnFinP bn_fin(Ctx* c, const PeP& q, const std::string& name, int C, const float* part, const float* sc, const float* sh,
                      double* sums = nullptr, int sums_mode = 0) {
   BnFinP b; memset(&b, 0, sizeof(b));
   b.sums = sums; b.sums_mode = sums_mode;
@@ -698,16 +449,16 @@ static BnFinP bn_fin(RiftCtx* c, const PeP& q, const std::string& name, int C, c
 
 void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, const std::string& pm, const float* Fr, int gr,
                          const uint8_t* vr, const std::string& pr, float** out_m, float** out_r) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   PeP2 q;
   pe_fill(f, q.a, Fm, 10, gm, 20, vm, pm);
   pe_fill(f, q.b, Fr, 6, gr, 120, vr, pr);
   const int nt = q.a.ntiles + q.b.ntiles;
   const double rows = (double)q.a.rows + q.b.rows, groups = (double)gm + gr;
-  const bool stats_p = f.train && c->pe_w;          // persistent pass A: one partial per workgroup (pe_fused.h)
+  const bool stats_p = f.train && c->sw.pe_w;          // persistent pass A: one partial per workgroup (pe_fused.h)
   // reference lines packed at tile granularity (pe_fused.h: pe_pack_body): table + round count in device memory, built by one extra block
   // of pass A's launch (eval mode: a launch of its own)
-  const bool packb = c->pe_w && c->pe_pack && gr > 0 && f.r_tiles != nullptr;
+  const bool packb = c->sw.pe_w && c->sw.pe_pack && gr > 0 && f.r_tiles != nullptr;
   int* pk_tab = nullptr; int* pk_hdr = nullptr;
   PePackP pk; memset(&pk, 0, sizeof(pk));
   if (packb) {
@@ -718,7 +469,7 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
     if (!stats_p) { c->prof_flops = 0.0; launch(c, "pe_pack_lines_kernel", pe_pack_lines_kernel, dim3(1), dim3(256), (size_t)gr * 2 * sizeof(int), pk); }
   }
   if (stats_p) {
-    int g = std::min(nt, 4 * c->nat_grid);          // four 256-thread workgroups per CU
+    int g = std::min(nt, 4 * c->sw.nat_grid);          // four 256-thread workgroups per CU
     int ga = (int)(((long long)g * q.a.ntiles + nt / 2) / nt);
     if (q.a.ntiles > 0 && ga < 1) ga = 1;
     if (q.b.ntiles > 0 && ga > g - 1) ga = g - 1;
@@ -737,9 +488,9 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
   double* xs = dpx ? c->dp.xchg + f.kb : nullptr;
   // pass B's live rounds and workgroup split, from pass A's counts (pe_fused.h: PeLiveP): one extra block of the BatchNorm-1 finalize
   PeLiveP lv; memset(&lv, 0, sizeof(lv));
-  const bool live = stats_p && c->pe_live;
-  int pew_grid = std::max(c->nat_grid, 2), pew_ga = 0;      // (two sides: at one workgroup the split below leaves the polygons none -- RIFT_NAT_GRID=1)
-  if (c->pe_w) pew_split(cdiv(q.a.rows, PEW_ROUND_ROWS), cdiv(q.b.rows, PEW_ROUND_ROWS), &pew_grid, &pew_ga);
+  const bool live = stats_p && c->sw.pe_live;
+  int pew_grid = std::max(c->sw.nat_grid, 2), pew_ga = 0;      // (two sides: at one workgroup the split below leaves the polygons none -- RIFT_NAT_GRID=1)
+  if (c->sw.pe_w) pew_split(cdiv(q.a.rows, PEW_ROUND_ROWS), cdiv(q.b.rows, PEW_ROUND_ROWS), &pew_grid, &pew_ga);
   if (live || packb) {
     const PeP* sd[2] = {&q.a, &q.b};
     for (int i = 0; i < 2; ++i) {
@@ -763,7 +514,7 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
   }
   c->prof_flops = 2.0 * rows * (128.0 * 8 + 128.0 * 256 + (f.train ? 256.0 * 256 : 0.0)) + 2.0 * groups * 256.0 * 256;
   BnFinP fa, fb;
-  if (c->pe_w) {     // wave-private pass B: rounds of 240 rows, one statistics partial per workgroup
+  if (c->sw.pe_w) {     // wave-private pass B: rounds of 240 rows, one statistics partial per workgroup
     PeWP w; memset(&w, 0, sizeof(w));
     const PeP* src[2] = {&q.a, &q.b};
     PeWSide* dst[2] = {&w.a, &w.b};
@@ -773,7 +524,7 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
     for (int i = 0; i < 2; ++i) {
       const PeP& o = *src[i]; PeWSide& d = *dst[i];
       d.F = o.F; d.Cin = o.Cin; d.valid = o.valid; d.rows = o.rows; d.npts = npts[i]; d.nrounds = cdiv(o.rows, PEW_ROUND_ROWS);
-      d.img = c->pew_img[i].get(); d.w3b = o.w3b; d.b1 = o.b1; d.b2 = o.b2; d.b3 = o.b3; d.s1 = o.s1; d.t1 = o.t1;
+      d.img = c->img.pew_img[i].get(); d.w3b = o.w3b; d.b1 = o.b1; d.b2 = o.b2; d.b3 = o.b3; d.s1 = o.s1; d.t1 = o.t1;
       d.live = (live && !(i == 1 && packb)) ? lv.live[i] : nullptr;
       if (i == 1) { d.ptab = pk_tab; d.phdr = pk_hdr; }
       d.part2 = A_alloc<float>(c, (size_t)2 * 256 * std::max(nwg[i], 1)); d.cnt2 = A_alloc<int>(c, std::max(nwg[i], 1));
@@ -781,8 +532,8 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
     }
     w.ga = ga; w.hdr = lvblock ? lv.hdr : nullptr;
     w.do_stats = f.train ? 1 : 0;
-    w.dbg = c->dg.pew_dbg;
-    { if (c->dg.pew_ts) { w.ts = A_alloc<long long>(c, 128); tap(c, "pew_ts", (float*)w.ts, 256); } }
+    w.dbg = c->sw.pew_dbg;
+    { if (c->sw.pew_ts) { w.ts = A_alloc<long long>(c, 128); tap(c, "pew_ts", (float*)w.ts, 256); } }
     launch_call(c, "pe_w_kernel", [&] { pew_launch(w, grid, c->stream); });
     fa = bn_fin(c, q.a, pm + ".second_mlp.1", 256, w.a.part2, q.a.s2, q.a.t2, xs, 0); fa.cnt = w.a.cnt2; fa.nblk = nwg[0]; fa.nblk_dev = lvblock ? lv.hdr + 2 : nullptr;
     fb = bn_fin(c, q.b, pr + ".second_mlp.1", 256, w.b.part2, q.b.s2, q.b.t2, xs ? xs + 513 : nullptr, 0); fb.cnt = w.b.cnt2; fb.nblk = nwg[1]; fb.nblk_dev = lvblock ? lv.hdr + 3 : nullptr;
@@ -804,7 +555,7 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
 
 // PointsEncoder (embedding.py:271-296): F (groups*n, Cin) -> (groups, 128)
 float* points_encoder(Fwd& f, const float* F, int Cin, int groups, int n, const uint8_t* valid, const std::string& p) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   const int rows = groups * n;
   float* H1 = A_alloc<float>(c, (size_t)rows * 128);
   gemm(c, mk(F, Cin, rows, c->pw[p + ".first_mlp.0"], H1, 128), c->pw[p + ".first_mlp.0"], f.fp32);
@@ -836,7 +587,7 @@ float* points_encoder(Fwd& f, const float* F, int Cin, int groups, int n, const 
 }
 
 template <int NKT>
-void run_mha_mfma(RiftCtx* c, const MhaP& p) {
+void run_mha_mfma(Ctx* c, const MhaP& p) {
   const int nqt = (p.Lq + 15) / 16;
   const int waves = nqt < 4 ? nqt : 4;
   const size_t lds = (size_t)NKT * 16 * 40 * 2 + (size_t)32 * (NKT * 16 + 8) * 2 + NKT * 16;
@@ -844,7 +595,7 @@ void run_mha_mfma(RiftCtx* c, const MhaP& p) {
 }
 
 // bf16 mode: MFMA attention; fp32 mode (or unaligned / very long inputs): exact-fp32 VALU kernel
-void run_mha(RiftCtx* c, const MhaP& p, bool fp32) {
+void run_mha(Ctx* c, const MhaP& p, bool fp32) {
   const bool al = ((((uintptr_t)p.Q) | ((uintptr_t)p.K) | ((uintptr_t)p.V)) & 15) == 0 && p.ldq % 4 == 0 && p.ldkv % 4 == 0;
   if (!fp32 && al && p.Lk <= 192) {
     if (p.Lk <= 32) run_mha_mfma<2>(c, p);
@@ -858,7 +609,7 @@ void run_mha(RiftCtx* c, const MhaP& p, bool fp32) {
 
 // NAT block (embedding.py:196-202) on X (rows, C) in place
 void nat_layer(Fwd& f, float* X, int rows, int C, int H, int ksz, int L, const std::string& p, float droppath) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   float* QKV = A_alloc<float>(c, (size_t)rows * 3 * C);
   GemmP g = mk(X, C, rows, c->pw[p + ".attn.qkv"], QKV, 3 * C);
   g.pro = PRO_LN; g.pg = fptr(c, p + ".norm1.weight"); g.pb = fptr(c, p + ".norm1.bias");
@@ -884,7 +635,7 @@ void nat_layer(Fwd& f, float* X, int rows, int C, int H, int ksz, int L, const s
 // MLPLayer (mlp_layer.py:8-16): X (rows,128) -> out (rows, Nout) with hidden width Hd
 // three MLPLayer(128, 256, 160) heads -> interleaved (rows, 80, 6), one launch (heads_fused.h); bf16 mode
 void heads3_fused(Fwd& f, const float* X, int ldx, int rows, int g_per, int g_stride, int g_off, const std::string names[3], float* out) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   Heads3P q; memset(&q, 0, sizeof(q));
   q.X = X; q.ldx = ldx; q.rows = rows; q.gather_per = g_per; q.gather_stride = g_stride; q.gather_off = g_off; q.out = out;
   for (int i = 0; i < 3; ++i) {
@@ -897,7 +648,7 @@ void heads3_fused(Fwd& f, const float* X, int ldx, int rows, int g_per, int g_st
 }
 
 void mlp_layer(Fwd& f, const float* X, int ldx, int rows, const std::string& p, float* out, int ldo, bool fp32) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   const PW& w0 = c->pw[p + ".mlp.0"];
   float* T = A_alloc<float>(c, (size_t)rows * w0.N);
   gemm(c, mk(X, ldx, rows, w0, T, w0.N), w0, fp32);
@@ -918,13 +669,13 @@ __global__ void interleave_traj_kernel(const float* __restrict__ loc, const floa
 
 // The policy head of a forward: cat_x_proj -> pi_head (read LIVE: the only trainable parameters) -> masked logits, then the trajectory
 // heads on its q_final.  Launched on c->stream; leaves what rift_loss_backward consumes.
-int head_impl(RiftCtx* c, const RiftCtx::Head& h) {
+int head_impl(Ctx* c, const Ctx::Head& h) {
   const int nQ = h.nQ, R = h.R, M = 12;
   Fwd f; f.c = c; f.fp32 = h.fp32; f.need_traj = h.need_traj; f.train = f.drop = f.bn_update = false; f.seed = 0;
   // Everything before reads frozen, load-time-packed weights only; pi_head.* is read LIVE from here on.  A host that updates pi_head on
   // another stream (all-reduce + clip + AdamW of the previous step) hands over the event that marks the update's end.
-  if (c->param_event && !c->dry) HIPCHK(c, hipStreamWaitEvent(c->stream, c->param_event, 0));
-  if (!h.fp32 && c->pi_fused) {
+  if (c->st.param_event && !c->dry) HIPCHK(c, hipStreamWaitEvent(c->stream, c->st.param_event, 0));
+  if (!h.fp32 && c->sw.pi_fused) {
     // cat_x_proj (bf16) -> pi_head first Linear (exact fp32, live parameters) -> LayerNorm -> ReLU -> Linear -> masked logits: one launch
     PiFwdP q; memset(&q, 0, sizeof(q));
     q.Q = h.Q; q.rows = nQ; q.rows_per_scene = R * M;
@@ -947,7 +698,7 @@ int head_impl(RiftCtx* c, const RiftCtx::Head& h) {
            (const uint8_t*)h.r_kpm, 1e-5f, h.prob, c->nonfinite.get());
   }
   tap(c, "q_final", h.QF, (int64_t)nQ * 128);
-  if (h.need_traj && !h.fp32 && c->heads_fused) {
+  if (h.need_traj && !h.fp32 && c->sw.heads_fused) {
     const std::string nm3[3] = {PD + ".loc_head", PD + ".yaw_head", PD + ".vel_head"};
     heads3_fused(f, h.QF, 128, nQ, 0, 0, 0, nm3, h.traj);
   } else if (h.need_traj) {
@@ -974,7 +725,7 @@ int head_impl(RiftCtx* c, const RiftCtx::Head& h) {
 // ---- input-only preparation: one launch (prep_kernel) for the seven feature / mask / position builders
 // (on the plan's stream: the caller's prepare stream if there is one, rift_set_prepare_stream)
 int prepare_inputs(Fwd& f) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   const RiftFeatureBatch* B = f.B;
   const int bs = f.bs, A = f.A, Mp = f.Mp, S = f.S, T = f.T, nA = f.nA, nP = f.nP, nL = f.nL, nT = f.nT;
   (void)A_alloc<float>(c, 64);          // front padding: the level-0 NAT kernel's window loads start up to 9 floats before a sequence's first row
@@ -982,7 +733,7 @@ int prepare_inputs(Fwd& f) {
   f.valid_agent = A_alloc<uint8_t>(c, nA);
   // the fused history encoder runs on the sequences its output is read of -- valid agents other than the ego (agent_encoder.py:77-87) -- in
   // compacted order (nat_l0w.h ranks them); the layer-wise / fp32 path keeps all nA sequences
-  f.nat_compact = c->nat_compact && c->nat_fused && !f.fp32 && c->fpn_fused;
+  f.nat_compact = c->sw.nat_compact && c->sw.nat_fused && !f.fp32 && c->sw.fpn_fused;
   uint8_t* hist_agent = f.nat_compact ? A_alloc<uint8_t>(c, nA) : nullptr;
   f.nat_aidx = f.nat_compact ? A_alloc<int>(c, nA) : nullptr;
   f.nat_cnt = f.nat_compact ? A_alloc<int>(c, 4) : nullptr;
@@ -1007,21 +758,21 @@ int prepare_inputs(Fwd& f) {
   int tot = 0;
   for (int i = 0; i < 7; ++i) tot += q.nb[i];
   // (round 6) the ranking as the first bs blocks of this launch (kernels.h: rank_scene_body): no launch of its own on the history chain
-  const bool rank_in_prep = f.nat_compact && c->rank_in_prep && A <= 256;
+  const bool rank_in_prep = f.nat_compact && c->sw.rank_in_prep && A <= 256;
   if (rank_in_prep) {
     const int sl = c->parity;
-    DevBuf<unsigned long long>& pub = c->rk_pub[sl];
+    DevBuf<unsigned long long>& pub = c->slots[sl].rk_pub;
     bool fresh = false;                                // (a batch beyond the arrays of rift_ctx_create: a fresh zeroed array, epochs start over)
     if (pub.cap() < (size_t)bs) HIPCHK(c, hipDeviceSynchronize());      // nothing in flight reads the old array; and the zeros below are in place before ANY stream's launch
     DEVCHK(c, pub.reserve((size_t)bs, (size_t)std::max(2 * bs, 4096), &fresh));
     if (fresh) {
       HIPCHK(c, hipMemset(pub.get(), 0, pub.cap() * sizeof(unsigned long long)));
       HIPCHK(c, hipDeviceSynchronize());               // (hipMemset of device memory may return before the fill has run, and the preparation is launched on a non-blocking stream)
-      c->rk_epoch[sl] = 0;
+      c->slots[sl].rk_epoch = 0;
     }
-    q.nrk = bs; q.rk_pub = c->rk_pub[sl].get(); q.aidx = f.nat_aidx; q.cnt = f.nat_cnt; q.fail = c->nonfinite.get(); q.rk_fault = c->rank_fault ? 1 : 0;
-    if (!c->dry) { if (++c->rk_epoch[sl] == 0u) c->rk_epoch[sl] = 1u; }      // (epoch 0 = "never written")
-    q.rk_epoch = c->rk_epoch[sl];
+    q.nrk = bs; q.rk_pub = c->slots[sl].rk_pub.get(); q.aidx = f.nat_aidx; q.cnt = f.nat_cnt; q.fail = c->nonfinite.get(); q.rk_fault = c->sw.rank_fault ? 1 : 0;
+    if (!c->dry) { if (++c->slots[sl].rk_epoch == 0u) c->slots[sl].rk_epoch = 1u; }      // (epoch 0 = "never written")
+    q.rk_epoch = c->slots[sl].rk_epoch;
     q.hist_agent = nullptr;                            // (the scene blocks derive the marks themselves)
     tot += bs;
   }
@@ -1031,12 +782,12 @@ int prepare_inputs(Fwd& f) {
 }
 
 void dp_kpm_fill(Fwd& f) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   launch(c, "dp_kpm_fill_kernel", dp_kpm_fill_kernel, dim3(cdiv(f.kb, 256)), dim3(256), 0, (const uint8_t*)f.r_kpm, f.nL, c->dp.off * f.R, f.kb, c->dp.xchg);
 }
 
 int dp_mask_and_drop_counters(Fwd& f) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   const int bs = f.bs, R = f.R, nA = f.nA;
   // data parallel: the r2r mask quirk indexes padding rows of the GLOBAL minibatch -> gather them (slots in the exchange buffer; the
   // first BatchNorm exchange carries them, an eval forward exchanges them on their own before the decoder)
@@ -1071,15 +822,15 @@ int dp_mask_and_drop_counters(Fwd& f) {
 
 // ---- agent-history chain: the three NAT levels (one launch each, or layer-wise) and the FPN tail
 void history_encoder(Fwd& f) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   const int nA = f.nA;
   static const float dpr[6] = {0.f, 0.04f, 0.08f, 0.12f, 0.16f, 0.2f};   // linspace(0, 0.2, 6), embedding.py:30
-  const bool fused = c->nat_fused && !f.fp32;
+  const bool fused = c->sw.nat_fused && !f.fp32;
   static const int Ll[3] = {20, 10, 5}, Cl[3] = {32, 64, 128}, Hl[3] = {2, 4, 8}, Kl[3] = {3, 3, 5};
   float* Oc[3];   // LayerNorm(norm_i) of the last 3 steps of level i: all that out[:, :, -1] of the FPN depends on
   for (int i = 0; i < 3; ++i) Oc[i] = A_alloc<float>(c, (size_t)nA * 3 * Cl[i]);
   // the wave-private level kernels hand these rows to fpn_tail_kernel as bf16 (it rounds them to bf16 first thing anyway): same values, half the bytes
-  const bool oc_bf16 = fused && c->fpn_fused;
+  const bool oc_bf16 = fused && c->sw.fpn_fused;
   unsigned short* Ocb[3] = {nullptr, nullptr, nullptr};
   if (oc_bf16) for (int i = 0; i < 3; ++i) Ocb[i] = A_alloc<unsigned short>(c, (size_t)nA * 3 * Cl[i]);
   if (fused) {
@@ -1090,35 +841,35 @@ void history_encoder(Fwd& f) {
       if (lv == 0) {   // level 0 as wave-private, register-resident tiles (no workgroup barriers): nat_l0w.h
         NatL0WP q; memset(&q, 0, sizeof(q));
         q.aidx = f.nat_aidx; q.cnt = f.nat_cnt;
-        q.F9 = f.F9; q.nseq = nA; q.img = c->l0w_img.get(); q.par = c->l0w_par.get(); q.Oc = Oc[0]; q.Ocb = Ocb[0]; q.Xnext = Xin[1];
-        { if (c->dg.nat_ts == 1) { q.ts = A_alloc<long long>(c, 64); tap(c, "nat_ts", (float*)q.ts, 128); } }
+        q.F9 = f.F9; q.nseq = nA; q.img = c->img.l0w_img.get(); q.par = c->img.l0w_par.get(); q.Oc = Oc[0]; q.Ocb = Ocb[0]; q.Xnext = Xin[1];
+        { if (c->sw.nat_ts == 1) { q.ts = A_alloc<long long>(c, 64); tap(c, "nat_ts", (float*)q.ts, 128); } }
         q.droppath[0] = f.drop ? dpr[0] : 0.f; q.droppath[1] = f.drop ? dpr[1] : 0.f; q.seed = f.seed; q.stream = f.next_stream(); f.stream_id += 4;
         q.ds = f.ds;
         c->prof_flops = 2.0 * rows * (20.0 * C * C + 4.0 * ksz * C) + 2.0 * rows * 27 * 32 + (rows / 2) * 2.0 * 3 * C * 2 * C;
-        { const int g0 = std::min(cdiv(cdiv(nA, 4), L0W_NWV), c->nat_grid); launch_call(c, "nat_l0w_kernel", [&] { l0w_launch(q, g0, c->stream); }); }
+        { const int g0 = std::min(cdiv(cdiv(nA, 4), L0W_NWV), c->sw.nat_grid); launch_call(c, "nat_l0w_kernel", [&] { l0w_launch(q, g0, c->stream); }); }
         continue;
       }
       if (lv == 1) {   // level 1 likewise (weights swapped through LDS between the two layers): nat_l1w.h
         NatL1WP q; memset(&q, 0, sizeof(q));
         q.cnt = f.nat_cnt;
-        q.X = Xin[1]; q.nseq = nA; q.img = c->l1w_img.get(); q.par = c->l1w_par.get(); q.Oc = Oc[1]; q.Ocb = Ocb[1]; q.Xnext = Xin[2];
+        q.X = Xin[1]; q.nseq = nA; q.img = c->img.l1w_img.get(); q.par = c->img.l1w_par.get(); q.Oc = Oc[1]; q.Ocb = Ocb[1]; q.Xnext = Xin[2];
         q.droppath[0] = f.drop ? dpr[2] : 0.f; q.droppath[1] = f.drop ? dpr[3] : 0.f; q.seed = f.seed; q.stream = f.next_stream(); f.stream_id += 4;
         q.ds = f.ds;
         c->prof_flops = 2.0 * rows * (20.0 * C * C + 4.0 * ksz * C) + (rows / 2) * 2.0 * 3 * C * 2 * C;
-        { const int g1 = std::min(cdiv(cdiv(nA, 4), L1W_NWV), c->nat_grid); launch_call(c, "nat_l1w_kernel", [&] { l1w_launch(q, g1, c->stream); }); }
+        { const int g1 = std::min(cdiv(cdiv(nA, 4), L1W_NWV), c->sw.nat_grid); launch_call(c, "nat_l1w_kernel", [&] { l1w_launch(q, g1, c->stream); }); }
         continue;
       }
       {   // level 2: wave-private tiles of 3 agents, the two layers' weights streamed through LDS (nat_l2w.h)
         NatL2WP q; memset(&q, 0, sizeof(q));
         q.cnt = f.nat_cnt;
-        q.X = Xin[2]; q.nseq = nA; q.img = c->l2w_img.get(); q.par = c->l2w_par.get(); q.Oc = Oc[2]; q.Ocb = Ocb[2];
+        q.X = Xin[2]; q.nseq = nA; q.img = c->img.l2w_img.get(); q.par = c->img.l2w_par.get(); q.Oc = Oc[2]; q.Ocb = Ocb[2];
         q.droppath[0] = f.drop ? dpr[4] : 0.f; q.droppath[1] = f.drop ? dpr[5] : 0.f; q.seed = f.seed; q.stream = f.next_stream(); f.stream_id += 4;
         q.ds = f.ds;
-        { if (c->dg.nat_ts == 3) { q.ts = A_alloc<long long>(c, 64); tap(c, "nat_ts", (float*)q.ts, 128); } }
+        { if (c->sw.nat_ts == 3) { q.ts = A_alloc<long long>(c, 64); tap(c, "nat_ts", (float*)q.ts, 128); } }
         c->prof_flops = 2.0 * rows * (20.0 * C * C + 4.0 * ksz * C);
         // (round 6: up to one tile per workgroup -- a launch that does not fill the chip deals its tiles wave-major and waves without a tile skip
         // the arithmetic, so a small batch runs two or three waves on each of many CUs instead of eight on a few; nat_l2w.hip)
-        const int l2grid = std::min(cdiv(nA, 3), c->nat_grid);
+        const int l2grid = std::min(cdiv(nA, 3), c->sw.nat_grid);
         launch_call(c, "nat_l2w_kernel", [&] { l2w_launch(q, l2grid, c->stream); });
         continue;
       }
@@ -1173,7 +924,7 @@ void history_encoder(Fwd& f) {
   }
   // FPN restricted to what out[:, :, -1] depends on
   f.nat_out = A_alloc<float>(c, (size_t)nA * 128);
-  if (fused && c->fpn_fused) {
+  if (fused && c->sw.fpn_fused) {
     FpnP q; memset(&q, 0, sizeof(q));
     for (int i = 0; i < 3; ++i) {
       const PW& w = c->pw[HE + ".lateral_convs." + std::to_string(i)];
@@ -1202,7 +953,7 @@ void history_encoder(Fwd& f) {
 
 // ego state token (StateAttentionEncoder, agent_encoder.py:99-140)
 void ego_token(Fwd& f) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   const RiftFeatureBatch* B = f.B;
   const int bs = f.bs;
   const std::string EG = "agent_encoder.ego_state_emb";
@@ -1210,9 +961,9 @@ void ego_token(Fwd& f) {
   float* eq = wconst_get(c, "ego_q", 128, f.fp32, &fill_eq);
   if (fill_eq) gemm(c, mk(fptr(c, EG + ".query"), 128, 1, c->pw[EG + ".attn.q"], eq, 128), c->pw[EG + ".attn.q"], f.fp32);
   f.x_ego = A_alloc<float>(c, (size_t)bs * 128);
-  if (!f.fp32 && c->ego_fused) {
+  if (!f.fp32 && c->sw.ego_fused) {
     EgoP q; memset(&q, 0, sizeof(q));
-    q.cs = B->current_state; q.cs_ld = B->cs_ld; q.lw = c->ego_w.get(); q.lb = c->ego_b.get(); q.pos = fptr(c, EG + ".pos_embed");
+    q.cs = B->current_state; q.cs_ld = B->cs_ld; q.lw = c->img.ego_w.get(); q.lb = c->img.ego_b.get(); q.pos = fptr(c, EG + ".pos_embed");
     q.wkv = c->pw[EG + ".attn.kv"].bf.get(); q.bkv = c->pw[EG + ".attn.kv"].bias; q.q = eq;
     q.wo = c->pw[EG + ".attn.out_proj"].bf.get(); q.bo = c->pw[EG + ".attn.out_proj"].bias;
     q.out = f.x_ego; q.bs = bs; q.drop_p = f.drop ? 0.75f : 0.f; q.seed = f.seed; q.stream = f.drop ? f.next_stream() : 0;
@@ -1222,7 +973,7 @@ void ego_token(Fwd& f) {
   } else {
   float* E = A_alloc<float>(c, (size_t)bs * 6 * 128);
   launch(c, "ego_token_kernel", ego_token_kernel, dim3(cdiv((long long)bs * 6 * 128, 256)), dim3(256), 0, B->current_state, B->cs_ld,
-         (const float*)c->ego_w.get(), (const float*)c->ego_b.get(), fptr(c, EG + ".pos_embed"), bs, E);
+         (const float*)c->img.ego_w.get(), (const float*)c->img.ego_b.get(), fptr(c, EG + ".pos_embed"), bs, E);
   float* EKV = A_alloc<float>(c, (size_t)bs * 6 * 256);
   gemm(c, mk(E, 128, bs * 6, c->pw[EG + ".attn.kv"], EKV, 256), c->pw[EG + ".attn.kv"], f.fp32);
   uint8_t* edrop = nullptr;
@@ -1247,13 +998,13 @@ void ego_token(Fwd& f) {
 // decoder queries q0 = q_proj(cat[r_emb, m_emb]) (planning_decoder.py:149-154): they depend on the reference-line embedding only, so with the fused
 // embeddings done they are launched here, ahead of the join, and run beside the tail of the agent-history chain instead of between encoder and decoder
 int build_q0(Fwd& f) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   const int M = f.M, nL = f.nL, nQ = f.nQ;
   bool fill;
   float* Mb = wconst_get(c, "Mb", (size_t)M * 128, f.fp32, &fill);
   if (fill) gemm(c, mk(fptr(c, PD + ".m_emb"), 128, M, c->pw[PD + ".q_proj.m"], Mb, 128), c->pw[PD + ".q_proj.m"], f.fp32);
   f.Q = A_alloc<float>(c, (size_t)nQ * 128);
-  if (!f.fp32 && c->pi_fused) {
+  if (!f.fp32 && c->sw.pi_fused) {
     Q0P q; memset(&q, 0, sizeof(q));
     q.r_emb = f.r_emb; q.nL = nL; q.M = M; q.wr = c->pw[PD + ".q_proj.r"].bf.get(); q.br = c->pw[PD + ".q_proj.r"].bias;
     q.Mb = Mb; q.Q = f.Q;
@@ -1269,18 +1020,18 @@ int build_q0(Fwd& f) {
 
 // ---- map chain: both PointsEncoders, the three Fourier embeddings, the decoder queries
 int map_and_embeddings(Fwd& f) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   const RiftFeatureBatch* B = f.B;
   const int S = f.S, nP = f.nP, nL = f.nL, nT = f.nT;
   // map encoder (map_encoder.py:31-93)
   // reference-line features are input-only too: both PointsEncoders run side by side (fused path)
-  f.pe_pair = !f.fp32 && c->pe_fused;
+  f.pe_pair = !f.fp32 && c->sw.pe_fused;
   if (f.pe_pair) points_encoder_pair(f, f.F10, nP, B->map_valid_mask, "map_encoder.polygon_encoder", f.F6, nL, B->ref_valid_mask, PD + ".r_encoder", &f.poly, &f.r_emb);
   else f.poly = points_encoder(f, f.F10, 10, nP, 20, B->map_valid_mask, "map_encoder.polygon_encoder");
   tap(c, "poly_pe", f.poly, (int64_t)nP * 128);
   // the three Fourier embeddings (token positions, speed limits, reference-line positions) depend on inputs only: with both
   // PointsEncoders done they run as ONE launch, and the token kernels add the positional embedding on the way
-  f.fo3 = f.pe_pair && !f.fp32 && c->fo_fused && S == 0;
+  f.fo3 = f.pe_pair && !f.fp32 && c->sw.fo_fused && S == 0;
   if (f.fo3) {
     tap(c, "r_pe", f.r_emb, (int64_t)nL * 128);
     FourierP3 q3; memset(&q3, 0, sizeof(q3));
@@ -1289,12 +1040,12 @@ int map_and_embeddings(Fwd& f) {
     q3.e[2] = fourier_desc(f, f.r_pos, 3, nL, 3, PD + ".r_pos_emb", -1, f.r_emb);
     q3.nblk[0] = cdiv(nT, FO_ROWS); q3.nblk[1] = cdiv(nP, FO_ROWS); q3.nblk[2] = cdiv(nL, FO_ROWS); q3.count = 3;
     c->prof_flops = 2.0 * 128.0 * ((nT + nL) * (3 * 257.0 + 128.0) + nP * (257.0 + 128.0));
-    if (c->fo_w) {          // wave-private form: one 16-row tile per wave, 8 tiles per pass, the one-dimensional embedding two passes per workgroup
+    if (c->sw.fo_w) {          // wave-private form: one 16-row tile per wave, 8 tiles per pass, the one-dimensional embedding two passes per workgroup
       FoWP w; memset(&w, 0, sizeof(w));
       w.count = 3;
       for (int i = 0; i < 3; ++i) {
         const FourierP& o = q3.e[i]; FoWSide& d = w.e[i];
-        d.in = o.in; d.in_ld = o.in_ld; d.rows = o.rows; d.D = o.D; d.wrap_dim = o.wrap_dim; d.img = c->fow_img[i].get(); d.par = c->fow_par[i].get();
+        d.in = o.in; d.in_ld = o.in_ld; d.rows = o.rows; d.D = o.D; d.wrap_dim = o.wrap_dim; d.img = c->img.fow_img[i].get(); d.par = c->img.fow_par[i].get();
         d.Y = o.Y; d.accumulate = o.accumulate; d.rep = o.D == 1 ? 2 : 1; d.nwg = cdiv(cdiv(o.rows, 16), 8 * d.rep);
       }
       launch_call(c, "fo_w_kernel", [&] { fow_launch(w, c->stream); });
@@ -1310,7 +1061,7 @@ int map_and_embeddings(Fwd& f) {
 
 // ================= tokens =================
 void assemble_tokens(Fwd& f) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   const RiftFeatureBatch* B = f.B;
   const int bs = f.bs, A = f.A, Mp = f.Mp, S = f.S, N = f.N, nA = f.nA, nP = f.nP, nT = f.nT;
   f.X = A_alloc<float>(c, (size_t)nT * 128);
@@ -1333,14 +1084,14 @@ void assemble_tokens(Fwd& f) {
 
 // ================= encoder blocks (transformer.py:73-94) =================
 void scene_encoder(Fwd& f) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   const int bs = f.bs, R = f.R, N = f.N, nT = f.nT;
   static const float edpr[4] = {0.f, 0.2f / 3.f, 0.4f / 3.f, 0.2f};   // linspace(0, 0.2, 4), pluto_model.py:80-83
   f.ENC = A_alloc<float>(c, (size_t)nT * 128);
   // 97 .. 112 token slots (what train_cbv collates: 49 + 60 = 109): the fused kernel on its 112-row layout (enc_fused.h: EncLay<112>) when the
   // decoder's eight-key-tile variant consumes its K | V^T image; RIFT_ENC112=0 keeps those shapes on enc_w_kernel
-  f.enc_wide = N > 96 && N <= 112 && c->enc112 && c->dec_fused && R <= 8 && ENC_NW == 8;
-  if (c->enc_fused && !f.fp32 && (N <= 96 || f.enc_wide)) {
+  f.enc_wide = N > 96 && N <= 112 && c->sw.enc112 && c->sw.dec_fused && R <= 8 && ENC_NW == 8;
+  if (c->sw.enc_fused && !f.fp32 && (N <= 96 || f.enc_wide)) {
     EncFusedP ep; memset(&ep, 0, sizeof(ep));
     ep.X = f.X; ep.Y = f.ENC; ep.kpm = f.kpm; ep.bs = bs; ep.N = N; ep.seed = f.seed; ep.stream = f.next_stream(); f.stream_id += 8;
     for (int i = 0; i < 4; ++i) {
@@ -1348,17 +1099,17 @@ void scene_encoder(Fwd& f) {
       EncBlockW& w = ep.blk[i];
       w.ln1_g = fptr(c, p + ".norm1.weight"); w.ln1_b = fptr(c, p + ".norm1.bias");
       w.ln2_g = fptr(c, p + ".norm2.weight"); w.ln2_b = fptr(c, p + ".norm2.bias");
-      w.wqkv = c->enc_wqkv[i].get(); w.bqkv = c->enc_bqkv[i].get();
+      w.wqkv = c->img.enc_wqkv[i].get(); w.bqkv = c->img.enc_bqkv[i].get();
       w.wo = c->pw[p + ".attn.out_proj"].bf.get(); w.bo = c->pw[p + ".attn.out_proj"].bias;
       w.w1 = c->pw[p + ".mlp.fc1"].bf.get(); w.b1 = c->pw[p + ".mlp.fc1"].bias;
       w.w2 = c->pw[p + ".mlp.fc2"].hid.get(); w.b2 = c->pw[p + ".mlp.fc2"].bias;      // (hidden-layer operand words: pack_hid)
       w.droppath = f.drop ? edpr[i] : 0.f;
     }
     ep.norm_g = fptr(c, "norm.weight"); ep.norm_b = fptr(c, "norm.bias"); ep.nonfinite = c->nonfinite.get();
-    ep.ds = f.ds; ep.dbg = c->no_skip ? 1 : 0;
-    if (c->dg.enc_ts) { ep.ts = A_alloc<long long>(c, 256); tap(c, "enc_ts", (float*)ep.ts, 512); }
+    ep.ds = f.ds; ep.dbg = c->sw.no_skip ? 1 : 0;
+    if (c->sw.enc_ts) { ep.ts = A_alloc<long long>(c, 256); tap(c, "enc_ts", (float*)ep.ts, 512); }
     c->prof_flops = 4.0 * bs * N * (2.0 * 128 * 384 + 4.0 * N * 128 + 2.0 * 128 * 128 + 4.0 * 128 * 512);
-    if (c->dec_fused && R <= 8 && ENC_NW == 8) {   // the decoder kernel will run: emit its cross-attention K | V operand fragments here
+    if (c->sw.dec_fused && R <= 8 && ENC_NW == 8) {   // the decoder kernel will run: emit its cross-attention K | V operand fragments here
       f.enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * (f.enc_wide ? 96 : DECW_KV_FRAGS) * 512);      // (wide: the dense per-head image, dec_kv.h)
       ep.wkv = c->pw["planning_decoder.kv_all"].bf.get(); ep.bkv = c->pw["planning_decoder.kv_all"].bias;
       ep.KT = f.enc_KT;
@@ -1369,12 +1120,12 @@ void scene_encoder(Fwd& f) {
     }
     if (f.enc_wide) launch_call(c, "enc_fused112_kernel", [&] { enc112_launch(ep, c->stream); });
     else launch(c, "enc_fused_kernel", enc_fused_kernel<ENC_NW>, dim3(bs), dim3(64 * ENC_NW), (size_t)RIFT_ENC_LDS_BYTES, ep);
-  } else if (c->enc_fused && !f.fp32 && N <= 192) {   // dense-traffic shapes: the wave-private, weight-streaming encoder (two passes per layer)
+  } else if (c->sw.enc_fused && !f.fp32 && N <= 192) {   // dense-traffic shapes: the wave-private, weight-streaming encoder (two passes per layer)
     EncWP eq; memset(&eq, 0, sizeof(eq));
     eq.X = f.X; eq.Y = f.ENC; eq.kpm = f.kpm; eq.bs = bs; eq.N = N; eq.seed = f.seed; eq.stream = f.next_stream(); f.stream_id += 8;
     eq.KVs = A_alloc<unsigned short>(c, (size_t)bs * 96 * 512);
-    eq.img = c->encw_img.get(); eq.par = c->encw_par.get(); eq.nonfinite = c->nonfinite.get();
-    if (c->dec_fused && R <= 16) { f.enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * 96 * 512); eq.DKV = f.enc_KT; }   // the decoder's (dense-variant) operands
+    eq.img = c->img.encw_img.get(); eq.par = c->img.encw_par.get(); eq.nonfinite = c->nonfinite.get();
+    if (c->sw.dec_fused && R <= 16) { f.enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * 96 * 512); eq.DKV = f.enc_KT; }   // the decoder's (dense-variant) operands
     for (int i = 0; i < 4; ++i) eq.droppath[i] = f.drop ? edpr[i] : 0.f;
     eq.ds = f.ds;
     c->prof_flops = 4.0 * bs * N * (2.0 * 128 * 384 + 4.0 * N * 128 + 2.0 * 128 * 128 + 4.0 * 128 * 512);
@@ -1413,12 +1164,12 @@ void scene_encoder(Fwd& f) {
 
 // ================= agent predictor (agent_predictor.py:17-29) =================
 void agent_predictor(Fwd& f) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   const RiftOutputs* out = f.out;
   const int bs = f.bs, A = f.A, N = f.N;
   if (f.need_traj && out->prediction && A > 1) {
     const int rows = bs * (A - 1);
-    if (!f.fp32 && c->heads_fused) {
+    if (!f.fp32 && c->sw.heads_fused) {
       const std::string nm3[3] = {"agent_predictor.loc_predictor", "agent_predictor.yaw_predictor", "agent_predictor.vel_predictor"};
       heads3_fused(f, f.ENC, 128, rows, A - 1, N, 1, nm3, out->prediction);
     } else {
@@ -1439,14 +1190,14 @@ void agent_predictor(Fwd& f) {
 
 // the four decoder blocks as GEMM / attention launches (fp32 mode, RIFT_DEC_UNFUSED=1, shapes outside the fused kernel's)
 void decoder_layerwise(Fwd& f, float dp) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   const int bs = f.bs, R = f.R, N = f.N, M = f.M, nL = f.nL, nQ = f.nQ, nT = f.nT;
   float* DQKV = A_alloc<float>(c, (size_t)nQ * 384);
   float* DAO = A_alloc<float>(c, (size_t)nQ * 128);
   float* DQc = A_alloc<float>(c, (size_t)nQ * 128);
   float* DH = A_alloc<float>(c, (size_t)nQ * 512);
   float* KVm = A_alloc<float>(c, (size_t)nT * 256);
-  const int n_layers = c->dec_layers == 0 || c->dec_layers == 2 ? c->dec_layers : 4;      // (RIFT_DEC_LAYERS)
+  const int n_layers = c->sw.dec_layers == 0 || c->sw.dec_layers == 2 ? c->sw.dec_layers : 4;      // (RIFT_DEC_LAYERS)
   for (int i = 0; i < n_layers; ++i) {
     const std::string p = PD + ".decoder_blocks." + std::to_string(i);
     // ---- r2r self attention over the R reference lines of each (scene, mode), with the mask quirk
@@ -1519,7 +1270,7 @@ void decoder_layerwise(Fwd& f, float dp) {
 
 // ================= planning decoder (planning_decoder.py:135-188) =================
 int planning_decoder(Fwd& f) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   const RiftFeatureBatch* B = f.B;
   const int flags = f.flags;
   const int bs = f.bs, R = f.R, N = f.N, M = f.M, nL = f.nL, nQ = f.nQ;
@@ -1536,22 +1287,22 @@ int planning_decoder(Fwd& f) {
   dp_exchange(f, 0);                      // (eval forward under data parallelism: the mask slots have not travelled yet)
   const float dp = f.drop ? 0.1f : 0.f;   // pluto_model.py:35,93
   const bool dec_dense = (R > 8 || N > 96) && R <= 16 && N <= 192;      // dense-traffic shapes: the kernel's round-of-eight-tiles variant
-  if (c->dec_fused && !f.fp32 && dec_dense && !f.enc_KT) {   // its K | V^T operand fragments from the (layer-wise) encoder's output
+  if (c->sw.dec_fused && !f.fp32 && dec_dense && !f.enc_KT) {   // its K | V^T operand fragments from the (layer-wise) encoder's output
     f.enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * 96 * 512);
     DecKvP kq; memset(&kq, 0, sizeof(kq));
     kq.ENC = f.ENC; kq.bs = bs; kq.N = N; kq.wkv = c->pw[PD + ".kv_all"].bf.get(); kq.bkv = c->pw[PD + ".kv_all"].bias; kq.KV = f.enc_KT;
     c->prof_flops = 2.0 * bs * N * 128.0 * 1024;
     launch(c, "dec_kv_frag_kernel", dec_kv_frag_kernel, dim3(bs), dim3(512), (size_t)DEC_KV_LDS, kq);
   }
-  if (c->dec_fused && !f.fp32 && ((R <= 8 && N <= 96) || dec_dense) && f.enc_KT) {
+  if (c->sw.dec_fused && !f.fp32 && ((R <= 8 && N <= 96) || dec_dense) && f.enc_KT) {
     DecWP dq; memset(&dq, 0, sizeof(dq));
     dq.Q = f.Q; dq.kpm = f.kpm; dq.r_kpm = f.r_kpm; dq.q_kpm = f.q_kpm; dq.q_bs = f.q_bs; dq.q_off = f.q_off; dq.bs = bs; dq.N = N; dq.R = R; dq.dropout = dp; dq.seed = f.seed;
     if (f.kpm_c) { dq.kpm = f.kpm_c; dq.N = f.enc_wide ? 112 : 96; dq.compact = 1; }      // (the encoder compacted its rows: its own key padding, valid keys a prefix)
     dq.stream = f.next_stream(); f.stream_id += 64;
-    dq.KV = f.enc_KT; dq.img = c->decw_img.get(); dq.par = c->decw_par.get(); dq.nonfinite = c->nonfinite.get();
+    dq.KV = f.enc_KT; dq.img = c->img.decw_img.get(); dq.par = c->img.decw_par.get(); dq.nonfinite = c->nonfinite.get();
     dq.ds = f.ds;
-    if (c->dg.dec_ts) { dq.ts = A_alloc<long long>(c, 1024); tap(c, "dec_ts", (float*)dq.ts, 2048); }      // [0, 128): boundaries of wave 0; [128 + 112 w, ...): arrivals of wave w
-    dq.dbg = c->dg.dec_dbg | (c->no_skip ? 64 : 0);
+    if (c->sw.dec_ts) { dq.ts = A_alloc<long long>(c, 1024); tap(c, "dec_ts", (float*)dq.ts, 2048); }      // [0, 128): boundaries of wave 0; [128 + 112 w, ...): arrivals of wave w
+    dq.dbg = c->sw.dec_dbg | (c->sw.no_skip ? 64 : 0);
     dq.prob_only = f.need_traj ? 0 : 1;      // no trajectory heads: the policy head and the objectives mask the rows of padded reference lines, nobody else reads them
     c->prof_flops = 4.0 * bs * (R * M) * (2.0 * 128 * (384 + 128) * 2 + 2.0 * 128 * 128 * 2 + 4.0 * 128 * 512 + 4.0 * 128 * (N + R + M));
     // (with the trajectory heads on, the tail behind the decoder is longer and the caller's queue carries the prediction head too: measured
@@ -1560,14 +1311,14 @@ int planning_decoder(Fwd& f) {
     // Which batches: measured per size (profiles/r04_batch_sweep.txt; ms per step with / without): 32 0.18 / 0.23, 64 0.21 / 0.24, 80 0.253 / 0.264, 88 0.259 / 0.254,
     // 96 0.315 / 0.300, 104 0.325 / 0.321, 112 0.338 / 0.359, 128 0.368 / 0.381, 160 0.433 / 0.440, 192 0.503 / 0.520, 256 0.656 / 0.65 -- a win except between 84 and 108
     // scenes and at a chip-filling batch.  RIFT_DEC_DEFER=<n> replaces the table by bs <= n (0: never).
-    const bool dec_size_ok = c->dec_defer_max >= 0 ? bs <= c->dec_defer_max : (f.need_traj ? bs <= 128 : (bs <= 84 || (bs >= 108 && bs <= 192)));
+    const bool dec_size_ok = c->sw.dec_defer_max >= 0 ? bs <= c->sw.dec_defer_max : (f.need_traj ? bs <= 128 : (bs <= 84 || (bs >= 108 && bs <= 192)));
     const bool dec_may_defer = (flags & RIFT_F_DEFER_HEAD) && dec_size_ok && !c->prof_on;      // (the same in the sizing pass)
     // ... and split: layers 0 - 1 here, behind the encoder, layers 2 - 3 in front of the deferred head -- token assembly + encoder + half a decoder
     // on the caller's queue against half a decoder + tail on the update stream (9 + 88 + 55 against 55 + 80 us at 32 scenes) instead of 97 against
     // 190.  The dropout streams of the second launch carry on from the states the first one leaves (rng_io): the draws are a single launch's.
     // Measured (ms per step, split / one launch): 64 scenes 0.217 / 0.229, 32 scenes 0.20 - 0.21 / 0.20 - 0.21 (the host issues a 32-scene step in 0.15 - 0.2 ms: it
     // bounds that one now); with the trajectory heads on the caller's queue carries the prediction head as well and the split LOSES (0.30 / 0.26 at 64): off there.
-    uint32_t* rng_io = (dec_may_defer && c->dec_split && !f.need_traj) ? A_alloc<uint32_t>(c, (size_t)bs * 512 * 4) : nullptr;
+    uint32_t* rng_io = (dec_may_defer && c->sw.dec_split && !f.need_traj) ? A_alloc<uint32_t>(c, (size_t)bs * 512 * 4) : nullptr;
     f.dec_deferred = dec_may_defer && !c->dry && !dq.ts;
     if (f.dec_deferred) {
       f.dec_later = dq;
@@ -1576,15 +1327,15 @@ int planning_decoder(Fwd& f) {
         launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });
         f.dec_later.l0 = 2; f.dec_later.rng_io = rng_io;
       }
-    } else if (c->dec_layers == 22 && dp == 0.f) {      // (RIFT_DEC_LAYERS=22: an eval forward's layers as two launches; the rows travel through Q as in the deferred split)
+    } else if (c->sw.dec_layers == 22 && dp == 0.f) {      // (RIFT_DEC_LAYERS=22: an eval forward's layers as two launches; the rows travel through Q as in the deferred split)
       dq.l1 = 2;
       launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });
       dq.l0 = 2; dq.l1 = 4;
       launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });
-    } else if (c->dec_layers == 2) {                    // (RIFT_DEC_LAYERS=2: `dec3` taps the output of layer 1)
+    } else if (c->sw.dec_layers == 2) {                    // (RIFT_DEC_LAYERS=2: `dec3` taps the output of layer 1)
       dq.l1 = 2;
       launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });
-    } else if (c->dec_layers != 0) launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });      // (RIFT_DEC_LAYERS=0: `dec3` taps q0)
+    } else if (c->sw.dec_layers != 0) launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });      // (RIFT_DEC_LAYERS=0: `dec3` taps q0)
   } else decoder_layerwise(f, dp);
   tap(c, "dec3", f.Q, (int64_t)nQ * 128);
   return RIFT_OK;
@@ -1592,7 +1343,7 @@ int planning_decoder(Fwd& f) {
 
 // ================= policy head, hidden_proj / ref_free_decoder =================
 int policy_and_ego_heads(Fwd& f) {
-  RiftCtx* c = f.c;
+  Ctx* c = f.c;
   const RiftOutputs* out = f.out;
   const int flags = f.flags;
   const int bs = f.bs, R = f.R, N = f.N, nQ = f.nQ;
@@ -1605,19 +1356,19 @@ int policy_and_ego_heads(Fwd& f) {
   // ---- the policy head (and the trajectory heads that read its q_final): right here, or -- RIFT_F_DEFER_HEAD -- later through
   // rift_forward_head on a stream of the caller's choice, so that it (and the loss / backward / update behind it) runs beside the next
   // forward's frozen trunk
-  RiftCtx::Head hs;
+  Ctx::Head hs;
   hs.valid = true; hs.fp32 = f.fp32; hs.need_traj = f.need_traj && out->trajectory != nullptr; hs.Q = f.Q; hs.x0p = x0p; hs.r_kpm = f.r_kpm;
   hs.bs = bs; hs.R = R; hs.nQ = nQ; hs.traj = out->trajectory;
   hs.QF = A_alloc<float>(c, (size_t)nQ * 128);
   hs.Hpi = A_alloc<float>(c, (size_t)nQ * 128);
   hs.prob = out->probability ? out->probability : A_alloc<float>(c, nQ);
-  if (hs.need_traj && (f.fp32 || !c->heads_fused))      // layer-wise trajectory heads: their buffers come out of this forward's arena
+  if (hs.need_traj && (f.fp32 || !c->sw.heads_fused))      // layer-wise trajectory heads: their buffers come out of this forward's arena
     for (int i = 0; i < 3; ++i) { hs.oT[i] = A_alloc<float>(c, (size_t)nQ * 256); hs.o3[i] = A_alloc<float>(c, (size_t)nQ * 160); }
   hs.dec_pending = f.dec_deferred; hs.dec = f.dec_later;
-  if (flags & RIFT_F_DEFER_HEAD) { if (!c->dry) c->head[c->parity] = hs; }
+  if (flags & RIFT_F_DEFER_HEAD) { if (!c->dry) c->slots[c->parity].head = hs; }
   else TRY(head_impl(c, hs));
   // hidden_proj / ref_free_decoder on the ego token (pluto_model.py:173-180)
-  if (!f.fp32 && c->heads_fused && (out->hidden || (f.need_traj && out->ref_free_trajectory))) {      // one launch (heads_fused.h: ego_heads_kernel)
+  if (!f.fp32 && c->sw.heads_fused && (out->hidden || (f.need_traj && out->ref_free_trajectory))) {      // one launch (heads_fused.h: ego_heads_kernel)
     const PW &h0 = c->pw["hidden_proj.0"], &h2 = c->pw["hidden_proj.2"], &r0 = c->pw["ref_free_decoder.mlp.0"], &r3 = c->pw["ref_free_decoder.mlp.3"];
     EgoHeadsP q; memset(&q, 0, sizeof(q));
     q.X = f.ENC; q.ldx = N * 128; q.rows = bs;
@@ -1643,24 +1394,24 @@ int policy_and_ego_heads(Fwd& f) {
 }
 
 // The streams and events the plan needs, made on first use.
-int plan_resources(RiftCtx* c, const StreamPlan& p) {
-  if (p.prefetched && !c->ev_prep) HIPCHK(c, hipEventCreateWithFlags(&c->ev_prep, hipEventDisableTiming));
-  if (p.forked && !c->side) { HIPCHK(c, hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking)); c->side_owned = true; }
-  if (p.forked && !c->ev_fork) { HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming)); HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming)); }
-  if (p.nat_aside && !c->ev_join2) HIPCHK(c, hipEventCreateWithFlags(&c->ev_join2, hipEventDisableTiming));
+int plan_resources(Ctx* c, const StreamPlan& p) {
+  if (p.prefetched && !c->st.ev_prep) HIPCHK(c, hipEventCreateWithFlags(&c->st.ev_prep, hipEventDisableTiming));
+  if (p.forked && !c->st.side) { HIPCHK(c, hipStreamCreateWithFlags(&c->st.side, hipStreamNonBlocking)); c->st.side_owned = true; }
+  if (p.forked && !c->st.ev_fork) { HIPCHK(c, hipEventCreateWithFlags(&c->st.ev_fork, hipEventDisableTiming)); HIPCHK(c, hipEventCreateWithFlags(&c->st.ev_join, hipEventDisableTiming)); }
+  if (p.nat_aside && !c->st.ev_join2) HIPCHK(c, hipEventCreateWithFlags(&c->st.ev_join2, hipEventDisableTiming));
   return RIFT_OK;
 }
 
-StreamPlan plan_of(const RiftCtx* c, bool fp32, int bs) {
+StreamPlan plan_of(const Ctx* c, bool fp32, int bs) {
   PlanIn in;
-  in.two_streams = c->two_streams; in.nat_fused = c->nat_fused; in.nat_aside = c->nat_aside; in.side_gate = c->side_gate;
-  in.fp32 = fp32; in.prof_on = c->prof_on; in.dry = c->dry; in.prep_set = c->prep_set; in.dp_on = c->dp.on; in.bs = bs;
+  in.two_streams = c->sw.two_streams; in.nat_fused = c->sw.nat_fused; in.nat_aside = c->sw.nat_aside; in.side_gate = c->sw.side_gate;
+  in.fp32 = fp32; in.prof_on = c->prof_on; in.dry = c->dry; in.prep_set = c->st.prep_set; in.dp_on = c->dp.on; in.bs = bs;
   return plan_streams(in);
 }
 
 // One forward on c->stream (the caller's), in the arena of c->parity; with c->dry set, the sizing pass: the same code, no launch.  The
 // stages switch c->stream by the plan (fwd_plan.h) and an early error return leaves it switched: rift_forward restores it.
-int forward_impl(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, int flags, uint32_t seed) {
+int forward_impl(Ctx* c, const RiftFeatureBatch* B, const RiftOutputs* out, int flags, uint32_t seed) {
   Fwd f;
   f.c = c; f.train = (flags & RIFT_F_TRAIN) != 0; f.drop = f.train && !(flags & RIFT_F_NO_DROP);
   f.fp32 = (flags & RIFT_F_FP32) != 0; f.need_traj = (flags & RIFT_F_NEED_TRAJ) != 0;
@@ -1671,23 +1422,23 @@ int forward_impl(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
   f.nA = f.bs * f.A; f.nP = f.bs * f.Mp; f.nL = f.bs * f.R; f.nQ = f.nL * f.M; f.nT = f.bs * f.N;
   const StreamPlan& p = f.plan = plan_of(c, f.fp32, f.bs);
   TRY(plan_resources(c, p));
-  f.on[ON_CALLER] = c->stream; f.on[ON_PREPARE] = c->prep_stream; f.on[ON_SIDE] = c->side;
+  f.on[ON_CALLER] = c->stream; f.on[ON_PREPARE] = c->st.prep_stream; f.on[ON_SIDE] = c->st.side;
 
   c->stream = f.on[p.prep_on];
   TRY(prepare_inputs(f));
   c->stream = f.on[ON_CALLER];
-  if (p.prefetched) HIPCHK(c, hipEventRecord(c->ev_prep, f.on[ON_PREPARE]));
-  if (p.main_waits_prep) HIPCHK(c, hipStreamWaitEvent(f.on[ON_CALLER], c->ev_prep, 0));
+  if (p.prefetched) HIPCHK(c, hipEventRecord(c->st.ev_prep, f.on[ON_PREPARE]));
+  if (p.main_waits_prep) HIPCHK(c, hipStreamWaitEvent(f.on[ON_CALLER], c->st.ev_prep, 0));
   TRY(dp_mask_and_drop_counters(f));
-  if (p.side_waits_prep) HIPCHK(c, hipStreamWaitEvent(f.on[ON_SIDE], c->ev_prep, 0));
+  if (p.side_waits_prep) HIPCHK(c, hipStreamWaitEvent(f.on[ON_SIDE], c->st.ev_prep, 0));
   if (p.fork_from_main) {
-    HIPCHK(c, hipEventRecord(c->ev_fork, f.on[ON_CALLER]));
-    HIPCHK(c, hipStreamWaitEvent(f.on[ON_SIDE], c->ev_fork, 0));
+    HIPCHK(c, hipEventRecord(c->st.ev_fork, f.on[ON_CALLER]));
+    HIPCHK(c, hipStreamWaitEvent(f.on[ON_SIDE], c->st.ev_fork, 0));
   }
 
   c->stream = f.on[p.history_on];
   history_encoder(f);
-  if (p.nat_aside) HIPCHK(c, hipEventRecord(c->ev_join2, f.on[ON_PREPARE]));
+  if (p.nat_aside) HIPCHK(c, hipEventRecord(c->st.ev_join2, f.on[ON_PREPARE]));
 
   c->stream = f.on[p.dp_fill_on];
   if (p.dp_fill_late) dp_kpm_fill(f);      // (behind the previous forward's exchanges)
@@ -1696,12 +1447,12 @@ int forward_impl(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
   TRY(map_and_embeddings(f));
 
   // join: the agent tokens need both chains
-  if (p.join_once) HIPCHK(c, hipStreamWaitEvent(f.on[ON_SIDE], c->ev_join2, 0));
+  if (p.join_once) HIPCHK(c, hipStreamWaitEvent(f.on[ON_SIDE], c->st.ev_join2, 0));
   if (p.forked) {
-    HIPCHK(c, hipEventRecord(c->ev_join, f.on[ON_SIDE]));
-    HIPCHK(c, hipStreamWaitEvent(f.on[ON_CALLER], c->ev_join, 0));
+    HIPCHK(c, hipEventRecord(c->st.ev_join, f.on[ON_SIDE]));
+    HIPCHK(c, hipStreamWaitEvent(f.on[ON_CALLER], c->st.ev_join, 0));
   }
-  if (p.nat_aside && !p.join_once) HIPCHK(c, hipStreamWaitEvent(f.on[ON_CALLER], c->ev_join2, 0));
+  if (p.nat_aside && !p.join_once) HIPCHK(c, hipStreamWaitEvent(f.on[ON_CALLER], c->st.ev_join2, 0));
 
   c->stream = f.on[ON_CALLER];
   assemble_tokens(f);
@@ -1725,57 +1476,57 @@ static bool env_is(const char* name, char ch) { const char* ev = getenv(name); r
 static void env_flag(const char* name, bool* v) { const char* ev = getenv(name); if (ev) *v = atoi(ev) != 0; }
 static bool env_int(const char* name, int* v, int base = 10) { const char* ev = getenv(name); if (ev) *v = (int)strtol(ev, nullptr, base); return ev != nullptr; }
 
-static void read_switches(RiftCtx* c) {
-  c->nat_fused = !env_is("RIFT_NAT_UNFUSED", '1');        // 1: the history encoder's NAT levels layer-wise (GEMM / attention launches)
-  c->dec_fused = !env_is("RIFT_DEC_UNFUSED", '1');        // 1: the planning decoder layer-wise
-  c->enc_fused = !env_is("RIFT_ENC_UNFUSED", '1');        // 1: the scene encoder layer-wise
-  c->pe_fused = !env_is("RIFT_PE_UNFUSED", '1');          // 1: the PointsEncoders layer-wise, one after the other
-  c->fpn_fused = !env_is("RIFT_FPN_UNFUSED", '1');        // 1: the FPN tail as lateral GEMMs + merge
-  c->ego_fused = !env_is("RIFT_EGO_UNFUSED", '1');        // 1: the ego state token as five launches
-  c->heads_fused = !env_is("RIFT_HEADS_UNFUSED", '1');    // 1: trajectory / prediction / ego heads as MLPLayer GEMMs
-  c->pi_fused = !env_is("RIFT_PI_UNFUSED", '1');          // 1: cat_x_proj -> pi_head and the decoder queries as separate launches
-  c->fo_fused = !env_is("RIFT_FOURIER_UNFUSED", '1');     // 1: the Fourier embeddings layer-wise
-  c->pe_w = !env_is("RIFT_PE_W", '0');                    // 0: PointsEncoder pass B as the workgroup-tiled pe_mid_kernel
-  c->fo_w = !env_is("RIFT_FO_W", '0');                    // 0: the three Fourier embeddings through fourier_fused_kernel
-  c->two_streams = !env_is("RIFT_TWO_STREAMS", '0');      // 0: history and map chains one after the other on the caller's stream
-  { int g = 0; env_int("RIFT_NAT_GRID", &g); if (g > 0) c->nat_grid = g; }      // workgroups of the persistent launches (default 256: one per CU)
-  env_flag("RIFT_NAT_COMPACT", &c->nat_compact);          // 0: the history encoder on all agent slots, not the compacted valid ones
-  env_flag("RIFT_PE_LIVE", &c->pe_live);                  // 0: pass B over all rounds instead of the live ones of pass A's counts
-  env_flag("RIFT_PE_PACK", &c->pe_pack);                  // 0: reference lines of pass B in two-line rounds instead of packed valid-prefix tiles
-  env_flag("RIFT_RANK_IN_PREP", &c->rank_in_prep);        // 0: the ranking as its own launch behind the preparation (nat_rank_kernel)
-  env_flag("RIFT_NO_SKIP", &c->no_skip);                  // 1: compute, then discard (dropped encoder branches, padded reference lines of the decoder)
-  env_flag("RIFT_ENC112", &c->enc112);                    // 0: scenes of 97 .. 112 token slots on enc_w_kernel
-  env_flag("RIFT_RANK_FAULT", &c->rank_fault);            // 1 (diagnostic): the first scene block of the in-launch ranking never publishes
-  env_int("RIFT_SIDE_GATE", &c->side_gate);               // 1: both front chains behind the caller's queue (fwd_plan.h)
-  env_flag("RIFT_NAT_ASIDE", &c->nat_aside);              // 0: the history chain on the caller's stream, not behind the preparation
-  env_int("RIFT_DEC_DEFER", &c->dec_defer_max);           // <n>: the decoder goes with the deferred head for bs <= n (0: never; unset: the measured table)
-  env_flag("RIFT_DEC_SPLIT", &c->dec_split);              // 0: the deferred decoder as one launch
-  env_int("RIFT_DEC_LAYERS", &c->dec_layers);             // (diagnostic) 0 / 2: the non-deferred decoder stops after that many layers and `dec3` taps that boundary; 22: an eval forward's layers as two launches
+static void read_switches(Ctx* c) {
+  c->sw.nat_fused = !env_is("RIFT_NAT_UNFUSED", '1');        // 1: the history encoder's NAT levels layer-wise (GEMM / attention launches)
+  c->sw.dec_fused = !env_is("RIFT_DEC_UNFUSED", '1');        // 1: the planning decoder layer-wise
+  c->sw.enc_fused = !env_is("RIFT_ENC_UNFUSED", '1');        // 1: the scene encoder layer-wise
+  c->sw.pe_fused = !env_is("RIFT_PE_UNFUSED", '1');          // 1: the PointsEncoders layer-wise, one after the other
+  c->sw.fpn_fused = !env_is("RIFT_FPN_UNFUSED", '1');        // 1: the FPN tail as lateral GEMMs + merge
+  c->sw.ego_fused = !env_is("RIFT_EGO_UNFUSED", '1');        // 1: the ego state token as five launches
+  c->sw.heads_fused = !env_is("RIFT_HEADS_UNFUSED", '1');    // 1: trajectory / prediction / ego heads as MLPLayer GEMMs
+  c->sw.pi_fused = !env_is("RIFT_PI_UNFUSED", '1');          // 1: cat_x_proj -> pi_head and the decoder queries as separate launches
+  c->sw.fo_fused = !env_is("RIFT_FOURIER_UNFUSED", '1');     // 1: the Fourier embeddings layer-wise
+  c->sw.pe_w = !env_is("RIFT_PE_W", '0');                    // 0: PointsEncoder pass B as the workgroup-tiled pe_mid_kernel
+  c->sw.fo_w = !env_is("RIFT_FO_W", '0');                    // 0: the three Fourier embeddings through fourier_fused_kernel
+  c->sw.two_streams = !env_is("RIFT_TWO_STREAMS", '0');      // 0: history and map chains one after the other on the caller's stream
+  { int g = 0; env_int("RIFT_NAT_GRID", &g); if (g > 0) c->sw.nat_grid = g; }      // workgroups of the persistent launches (default 256: one per CU)
+  env_flag("RIFT_NAT_COMPACT", &c->sw.nat_compact);          // 0: the history encoder on all agent slots, not the compacted valid ones
+  env_flag("RIFT_PE_LIVE", &c->sw.pe_live);                  // 0: pass B over all rounds instead of the live ones of pass A's counts
+  env_flag("RIFT_PE_PACK", &c->sw.pe_pack);                  // 0: reference lines of pass B in two-line rounds instead of packed valid-prefix tiles
+  env_flag("RIFT_RANK_IN_PREP", &c->sw.rank_in_prep);        // 0: the ranking as its own launch behind the preparation (nat_rank_kernel)
+  env_flag("RIFT_NO_SKIP", &c->sw.no_skip);                  // 1: compute, then discard (dropped encoder branches, padded reference lines of the decoder)
+  env_flag("RIFT_ENC112", &c->sw.enc112);                    // 0: scenes of 97 .. 112 token slots on enc_w_kernel
+  env_flag("RIFT_RANK_FAULT", &c->sw.rank_fault);            // 1 (diagnostic): the first scene block of the in-launch ranking never publishes
+  env_int("RIFT_SIDE_GATE", &c->sw.side_gate);               // 1: both front chains behind the caller's queue (fwd_plan.h)
+  env_flag("RIFT_NAT_ASIDE", &c->sw.nat_aside);              // 0: the history chain on the caller's stream, not behind the preparation
+  env_int("RIFT_DEC_DEFER", &c->sw.dec_defer_max);           // <n>: the decoder goes with the deferred head for bs <= n (0: never; unset: the measured table)
+  env_flag("RIFT_DEC_SPLIT", &c->sw.dec_split);              // 0: the deferred decoder as one launch
+  env_int("RIFT_DEC_LAYERS", &c->sw.dec_layers);             // (diagnostic) 0 / 2: the non-deferred decoder stops after that many layers and `dec3` taps that boundary; 22: an eval forward's layers as two launches
   env_flag("RIFT_RO8", &c->ro8);                          // 0: candidate rollout with one lane per candidate
   if (env_int("RIFT_POISON_LDS", &c->poison_lds, 0)) c->poison_lds &= 0xff;                // <byte>: every CU's LDS filled ahead of every launch
-  if (env_int("RIFT_POISON_ARENA", &c->dg.poison_arena, 0)) c->dg.poison_arena &= 0xff;    // <byte>: the arena filled ahead of every forward
+  if (env_int("RIFT_POISON_ARENA", &c->sw.poison_arena, 0)) c->sw.poison_arena &= 0xff;    // <byte>: the arena filled ahead of every forward
   { const char* ev = getenv("RIFT_DELAY"); const char* col = ev ? strrchr(ev, ':') : nullptr;      // <launch label>:<us> (wall_clock64: 100 MHz)
     if (col) { c->dg.delay_label.assign(ev, col - ev); c->dg.delay_ticks = (long long)(atof(col + 1) * 100.0); } }
-  env_int("RIFT_PE_TS", &c->dg.pe_ts);                    // the *_TS taps: phase timestamps of one workgroup
-  c->dg.pew_ts = env_is("RIFT_PEW_TS", '1');
-  env_int("RIFT_NAT_TS", &c->dg.nat_ts);
-  c->dg.enc_ts = getenv("RIFT_ENC_TS") != nullptr;
-  c->dg.dec_ts = getenv("RIFT_DEC_TS") != nullptr;
-  env_int("RIFT_PEW_DBG", &c->dg.pew_dbg);                // the *_DBG words: handed to the kernel as they are
-  env_int("RIFT_DEC_DBG", &c->dg.dec_dbg);
-  env_int("RIFT_GEMM_DBG", &c->gemm_dbg);
+  env_int("RIFT_PE_TS", &c->sw.pe_ts);                    // the *_TS taps: phase timestamps of one workgroup
+  c->sw.pew_ts = env_is("RIFT_PEW_TS", '1');
+  env_int("RIFT_NAT_TS", &c->sw.nat_ts);
+  c->sw.enc_ts = getenv("RIFT_ENC_TS") != nullptr;
+  c->sw.dec_ts = getenv("RIFT_DEC_TS") != nullptr;
+  env_int("RIFT_PEW_DBG", &c->sw.pew_dbg);                // the *_DBG words: handed to the kernel as they are
+  env_int("RIFT_DEC_DBG", &c->sw.dec_dbg);
+  env_int("RIFT_GEMM_DBG", &c->sw.gemm_dbg);
 }
 
 int rift_ctx_create(int device, RiftCtx** ctx) {
   if (!ctx) return RIFT_ERR_ARG;
-  RiftCtx* c = new RiftCtx();
+  Ctx* c = new Ctx();
   c->opfmt = RIFT_OP_F16;
   c->device = device;
   if (hipSetDevice(device) != hipSuccess) { delete c; return RIFT_ERR_HIP; }
   read_switches(c);
   if (c->nonfinite.reserve(1) != 0 || hipMemset(c->nonfinite.get(), 0, sizeof(int)) != hipSuccess) { delete c; return RIFT_ERR_HIP; }
   for (int i = 0; i < RIFT_DEFER_SLOTS; ++i) {      // the in-launch ranking's published counts (kernels.h: rank_scene_body): zero = "never written"
-    if (c->rk_pub[i].reserve(4096) != 0 || hipMemset(c->rk_pub[i].get(), 0, 4096 * sizeof(unsigned long long)) != hipSuccess) { delete c; return RIFT_ERR_HIP; }
+    if (c->slots[i].rk_pub.reserve(4096) != 0 || hipMemset(c->slots[i].rk_pub.get(), 0, 4096 * sizeof(unsigned long long)) != hipSuccess) { delete c; return RIFT_ERR_HIP; }
   }
   if (hipDeviceSynchronize() != hipSuccess) { delete c; return RIFT_ERR_HIP; }      // (the zeros are in place before any stream launches a kernel that reads them)
   int rc = set_lds_attrs(c);
@@ -1784,17 +1535,18 @@ int rift_ctx_create(int device, RiftCtx** ctx) {
   return RIFT_OK;
 }
 
-void rift_ctx_destroy(RiftCtx* c) {
+void rift_ctx_destroy(RiftCtx* h) {      // (this build's entry: its own context type's destructor runs)
+  Ctx* c = static_cast<Ctx*>(h);
   if (!c) return;
   if (c->comm) { (void)rccl_api(nullptr).CommDestroy(c->comm); c->comm = nullptr; }
   delete c;
 }
 
-const char* rift_last_error(RiftCtx* c) { return c ? c->err.c_str() : "null context"; }
+const char* rift_last_error(RiftCtx* h) { return h ? h->err.c_str() : "null context"; }
 
 // the parameters of the two NAT blocks of level lv, for the packers of the wave-private level kernels (NatL0WSrc / NatL1WSrc / NatL2WSrc)
 template <class Src>
-static void nat_blocks_src(RiftCtx* c, Src& q, int lv) {
+static void nat_blocks_src(Ctx* c, Src& q, int lv) {
   for (int b = 0; b < 2; ++b) {
     const std::string p = HE + ".levels." + std::to_string(lv) + ".blocks." + std::to_string(b);
     auto& k = q.blk[b];
@@ -1806,7 +1558,7 @@ static void nat_blocks_src(RiftCtx* c, Src& q, int lv) {
 }
 
 // rift_model_load: the history encoder's GEMM images and the weight streams of its wave-private level kernels
-static int pack_history_encoder(RiftCtx* c) {
+static int pack_history_encoder(Ctx* c) {
   TRY(pack_conv(c, HE + ".embed.proj"));
   for (int lv = 0; lv < 3; ++lv) {
     for (int b = 0; b < 2; ++b) {
@@ -1824,8 +1576,8 @@ static int pack_history_encoder(RiftCtx* c) {
     q.fn_g = fptr(c, HE + ".norm0.weight"); q.fn_b = fptr(c, HE + ".norm0.bias");
     q.w_ds = fptr(c, HE + ".levels.0.downsample.reduction.weight"); q.ds_g = fptr(c, HE + ".levels.0.downsample.norm.weight"); q.ds_b = fptr(c, HE + ".levels.0.downsample.norm.bias");
     if (!c->err.empty()) return RIFT_ERR_ARG;
-    DEVCHK(c, c->l0w_img.reserve((size_t)L0W_NFRAG * 512)); DEVCHK(c, c->l0w_par.reserve(L0W_NPAR));
-    l0w_pack(q, c->l0w_img.get(), c->l0w_par.get(), c->stream);
+    DEVCHK(c, c->img.l0w_img.reserve((size_t)L0W_NFRAG * 512)); DEVCHK(c, c->img.l0w_par.reserve(L0W_NPAR));
+    l0w_pack(q, c->img.l0w_img.get(), c->img.l0w_par.get(), c->stream);
   }
   {  // wave-private level-1 kernel (nat_l1w.h)
     NatL1WSrc q; memset(&q, 0, sizeof(q));
@@ -1833,16 +1585,16 @@ static int pack_history_encoder(RiftCtx* c) {
     q.fn_g = fptr(c, HE + ".norm1.weight"); q.fn_b = fptr(c, HE + ".norm1.bias");
     q.w_ds = fptr(c, HE + ".levels.1.downsample.reduction.weight"); q.ds_g = fptr(c, HE + ".levels.1.downsample.norm.weight"); q.ds_b = fptr(c, HE + ".levels.1.downsample.norm.bias");
     if (!c->err.empty()) return RIFT_ERR_ARG;
-    DEVCHK(c, c->l1w_img.reserve((size_t)L1W_NFRAG * 512)); DEVCHK(c, c->l1w_par.reserve(L1W_NPAR));
-    l1w_pack(q, c->l1w_img.get(), c->l1w_par.get(), c->stream);
+    DEVCHK(c, c->img.l1w_img.reserve((size_t)L1W_NFRAG * 512)); DEVCHK(c, c->img.l1w_par.reserve(L1W_NPAR));
+    l1w_pack(q, c->img.l1w_img.get(), c->img.l1w_par.get(), c->stream);
   }
   {  // wave-private level-2 kernel (nat_l2w.h)
     NatL2WSrc q; memset(&q, 0, sizeof(q));
     nat_blocks_src(c, q, 2);
     q.fn_g = fptr(c, HE + ".norm2.weight"); q.fn_b = fptr(c, HE + ".norm2.bias");
     if (!c->err.empty()) return RIFT_ERR_ARG;
-    DEVCHK(c, c->l2w_img.reserve((size_t)2 * L2W_BLK_FRAGS * 512)); DEVCHK(c, c->l2w_par.reserve(L2W_NPAR));
-    l2w_pack(q, c->l2w_img.get(), c->l2w_par.get(), c->stream);
+    DEVCHK(c, c->img.l2w_img.reserve((size_t)2 * L2W_BLK_FRAGS * 512)); DEVCHK(c, c->img.l2w_par.reserve(L2W_NPAR));
+    l2w_pack(q, c->img.l2w_img.get(), c->img.l2w_par.get(), c->stream);
   }
   {  // fpn_conv at the last step: taps 0,1 only -> [128][256]
     const Param* w = find(c, HE + ".fpn_conv.weight");
@@ -1854,7 +1606,7 @@ static int pack_history_encoder(RiftCtx* c) {
 }
 
 // rift_model_load: the weight streams / parameter blocks of the wave-private encoder, Fourier, PointsEncoder and decoder kernels
-static int pack_streamed_images(RiftCtx* c) {
+static int pack_streamed_images(Ctx* c) {
   {  // dense-traffic scene encoder (enc_w.h)
     EncWSrc q; memset(&q, 0, sizeof(q));
     for (int i = 0; i < 4; ++i) {
@@ -1872,8 +1624,8 @@ static int pack_streamed_images(RiftCtx* c) {
       q.dkv_w[i] = fptr(c, p + ".in_proj_weight"); q.dkv_b[i] = fptr(c, p + ".in_proj_bias");
     }
     if (!c->err.empty()) return RIFT_ERR_ARG;
-    DEVCHK(c, c->encw_img.reserve((size_t)(4 * ENCW_LAYER_FRAGS + ENCW_TAIL_FRAGS) * 512)); DEVCHK(c, c->encw_par.reserve(ENCW_NPAR));
-    encw_pack(q, c->encw_img.get(), c->encw_par.get(), c->stream);
+    DEVCHK(c, c->img.encw_img.reserve((size_t)(4 * ENCW_LAYER_FRAGS + ENCW_TAIL_FRAGS) * 512)); DEVCHK(c, c->img.encw_par.reserve(ENCW_NPAR));
+    encw_pack(q, c->img.encw_img.get(), c->img.encw_par.get(), c->stream);
   }
   {  // wave-private Fourier embeddings (fo_w.h): weight streams + parameter blocks of the three embeddings of the fused launch
     const std::string emb[3] = {"pos_emb", "map_encoder.speed_limit_emb", PD + ".r_pos_emb"};
@@ -1889,8 +1641,8 @@ static int pack_streamed_images(RiftCtx* c) {
       q.og = fptr(c, emb[i] + ".to_out.0.weight"); q.ob = fptr(c, emb[i] + ".to_out.0.bias");
       q.wo = fptr(c, emb[i] + ".to_out.2.weight"); q.bo = fptr(c, emb[i] + ".to_out.2.bias"); q.freqs = fptr(c, emb[i] + ".freqs.weight");
       if (!c->err.empty()) return RIFT_ERR_ARG;
-      DEVCHK(c, c->fow_img[i].reserve((size_t)7 * 32 * 512)); DEVCHK(c, c->fow_par[i].reserve(FOW_NPAR));
-      fow_pack(q, c->fow_img[i].get(), c->fow_par[i].get(), c->stream);
+      DEVCHK(c, c->img.fow_img[i].reserve((size_t)7 * 32 * 512)); DEVCHK(c, c->img.fow_par[i].reserve(FOW_NPAR));
+      fow_pack(q, c->img.fow_img[i].get(), c->img.fow_par[i].get(), c->stream);
     }
   }
   {  // wave-private PointsEncoder pass B (pe_w.h): W1 | W2 | W3a streams of the two encoders
@@ -1900,8 +1652,8 @@ static int pack_streamed_images(RiftCtx* c) {
       PeWSrc q; q.Cin = cin[i];
       q.w1 = fptr(c, enc[i] + ".first_mlp.0.weight"); q.w2 = fptr(c, enc[i] + ".first_mlp.3.weight"); q.w3 = fptr(c, enc[i] + ".second_mlp.0.weight");
       if (!c->err.empty()) return RIFT_ERR_ARG;
-      DEVCHK(c, c->pew_img[i].reserve((size_t)PEW_FRAGS * 512));
-      pew_pack(q, c->pew_img[i].get(), c->stream);
+      DEVCHK(c, c->img.pew_img[i].reserve((size_t)PEW_FRAGS * 512));
+      pew_pack(q, c->img.pew_img[i].get(), c->stream);
     }
   }
   {  // wave-private decoder kernel (dec_w.h): the layers' weight stream and parameter blocks
@@ -1920,16 +1672,14 @@ static int pack_streamed_images(RiftCtx* c) {
     }
     q.m_pos = fptr(c, PD + ".m_pos");
     if (!c->err.empty()) return RIFT_ERR_ARG;
-    DEVCHK(c, c->decw_img.reserve((size_t)4 * DECW_LAYER_FRAGS * 512)); DEVCHK(c, c->decw_par.reserve((size_t)4 * DECW_PAR_LAYER));
-    decw_pack(q, c->decw_img.get(), c->decw_par.get(), c->stream);
+    DEVCHK(c, c->img.decw_img.reserve((size_t)4 * DECW_LAYER_FRAGS * 512)); DEVCHK(c, c->img.decw_par.reserve((size_t)4 * DECW_PAR_LAYER));
+    decw_pack(q, c->img.decw_img.get(), c->img.decw_par.get(), c->stream);
   }
   return RIFT_OK;
 }
 
-// what the entries that launch on the model's images answer while there is none (RIFT_ERR_STATE, ahead of any launch or allocation)
-static const std::string NOT_LOADED = ": no model is loaded (rift_model_load is missing, or the last one failed)";
-
-int rift_model_load(RiftCtx* c, const RiftTensorDesc* params, int n, void* stream) {
+int rift_model_load(RiftCtx* h, const RiftTensorDesc* params, int n, void* stream) {
+  Ctx* c = static_cast<Ctx*>(h);
   if (!c || !params) return RIFT_ERR_ARG;
   c->err.clear();
   c->stream = (hipStream_t)stream;
@@ -1947,13 +1697,13 @@ int rift_model_load(RiftCtx* c, const RiftTensorDesc* params, int n, void* strea
   TRY(pack_rows(c, EG + ".attn.q", EG + ".attn.in_proj_weight", EG + ".attn.in_proj_bias", 0, 128, 128));
   TRY(pack_rows(c, EG + ".attn.kv", EG + ".attn.in_proj_weight", EG + ".attn.in_proj_bias", 128, 256, 256));
   TRY(pack_linear(c, EG + ".attn.out_proj"));
-  DEVCHK(c, c->ego_w.reserve(6 * 128)); DEVCHK(c, c->ego_b.reserve(6 * 128));
+  DEVCHK(c, c->img.ego_w.reserve(6 * 128)); DEVCHK(c, c->img.ego_b.reserve(6 * 128));
   for (int i = 0; i < 6; ++i) {
     const float* w = fptr(c, EG + ".linears." + std::to_string(i) + ".weight");
     const float* b = fptr(c, EG + ".linears." + std::to_string(i) + ".bias");
     if (!w || !b) return RIFT_ERR_ARG;
-    HIPCHK(c, hipMemcpyAsync(c->ego_w.get() + i * 128, w, 128 * 4, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->ego_b.get() + i * 128, b, 128 * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->img.ego_w.get() + i * 128, w, 128 * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->img.ego_b.get() + i * 128, b, 128 * 4, hipMemcpyDeviceToDevice, c->stream));
   }
   TRY(pack_points_encoder(c, "map_encoder.polygon_encoder"));
   TRY(pack_fourier(c, "map_encoder.speed_limit_emb", 1));
@@ -1972,16 +1722,16 @@ int rift_model_load(RiftCtx* c, const RiftTensorDesc* params, int n, void* strea
         const int head = 2 * ch + (seg < 4 ? (seg >> 1) : (seg - 4));
         for (int d = 0; d < 32; ++d) idx[ch * 192 + seg * 32 + d] = part * 128 + head * 32 + d;
       }
-    DEVCHK(c, c->enc_idx.reserve(384));
-    HIPCHK(c, hipMemcpyAsync(c->enc_idx.get(), idx, sizeof(idx), hipMemcpyHostToDevice, c->stream));
+    DEVCHK(c, c->img.enc_idx.reserve(384));
+    HIPCHK(c, hipMemcpyAsync(c->img.enc_idx.get(), idx, sizeof(idx), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));   // idx is a stack buffer
     for (int i = 0; i < 4; ++i) {
       const std::string p = "encoder_blocks." + std::to_string(i) + ".attn";
       const float* w = fptr(c, p + ".in_proj_weight"); const float* bsrc = fptr(c, p + ".in_proj_bias");
       if (!w || !bsrc) return RIFT_ERR_ARG;
-      DEVCHK(c, c->enc_wqkv[i].reserve(384 * 128)); DEVCHK(c, c->enc_bqkv[i].reserve(384));
-      hipLaunchKernelGGL(pack_rows_indexed_kernel, dim3(cdiv(384 * 128, 256)), dim3(256), 0, c->stream, w, bsrc, (const int*)c->enc_idx.get(),
-                         384, 128, c->enc_wqkv[i].get(), c->enc_bqkv[i].get());
+      DEVCHK(c, c->img.enc_wqkv[i].reserve(384 * 128)); DEVCHK(c, c->img.enc_bqkv[i].reserve(384));
+      hipLaunchKernelGGL(pack_rows_indexed_kernel, dim3(cdiv(384 * 128, 256)), dim3(256), 0, c->stream, w, bsrc, (const int*)c->img.enc_idx.get(),
+                         384, 128, c->img.enc_wqkv[i].get(), c->img.enc_bqkv[i].get());
     }
   }
   const char* ap[3] = {"loc_predictor", "yaw_predictor", "vel_predictor"};
@@ -2025,7 +1775,8 @@ int rift_model_load(RiftCtx* c, const RiftTensorDesc* params, int n, void* strea
   return RIFT_OK;
 }
 
-int rift_forward(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, int flags, uint32_t seed, void* stream) {
+int rift_forward(RiftCtx* h, const RiftFeatureBatch* B, const RiftOutputs* out, int flags, uint32_t seed, void* stream) {
+  Ctx* c = static_cast<Ctx*>(h);
   if (!c || !B || !out) return RIFT_ERR_ARG;
   c->err.clear();
   if (!c->loaded) { c->err = "rift_forward before rift_model_load" + NOT_LOADED; return RIFT_ERR_STATE; }
@@ -2035,7 +1786,7 @@ int rift_forward(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
   // deferred-head forwards cycle through the arenas (the caller guarantees that the head / loss of the forward RIFT_DEFER_SLOTS calls back is
   // over, i.e. that this arena is free again); every other forward runs in arena 0
   c->parity = (flags & RIFT_F_DEFER_HEAD) ? (c->parity + 1) % RIFT_DEFER_SLOTS : 0;
-  DevBuf<char>& slot = c->arenas[c->parity];
+  DevBuf<char>& slot = c->slots[c->parity].arena;
   c->arena = slot.get(); c->arena_cap = slot.cap();
   // pass 1 (dry): size the activation arena; pass 2: launch.  The sizes depend on the batch dimensions, the flags and the data-parallel
   // descriptor only: a forward like the previous one skips pass 1 (it is half of the call's host time, which bounds a small-batch step)
@@ -2065,7 +1816,7 @@ int rift_forward(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
   // diagnostic: RIFT_POISON_ARENA=<byte> fills the scratch arena before every forward (0xFF = NaN pattern), so that a kernel reading
   // scratch it never wrote shows up as NaN / as run-to-run differences instead of depending on what the memory held before
   // (on the prepare stream if the preparation runs there: every other stream of the forward waits for the preparation)
-  if (c->dg.poison_arena >= 0 && c->arena) { HIPCHK(c, hipMemsetAsync(c->arena, c->dg.poison_arena, c->arena_cap, plan_of(c, (flags & RIFT_F_FP32) != 0, B->bs).prefetched ? c->prep_stream : c->stream)); }
+  if (c->sw.poison_arena >= 0 && c->arena) { HIPCHK(c, hipMemsetAsync(c->arena, c->sw.poison_arena, c->arena_cap, plan_of(c, (flags & RIFT_F_FP32) != 0, B->bs).prefetched ? c->st.prep_stream : c->stream)); }
   rc = forward_impl(c, B, out, flags, seed);
   c->stream = (hipStream_t)stream;
   if (rc != RIFT_OK) return rc;
@@ -2080,22 +1831,23 @@ int rift_forward(RiftCtx* c, const RiftFeatureBatch* B, const RiftOutputs* out, 
   return RIFT_OK;
 }
 
-int rift_forward_head_back(RiftCtx* c, int back, void* stream) {
+int rift_forward_head_back(RiftCtx* h, int back, void* stream) {
+  Ctx* c = static_cast<Ctx*>(h);
   if (!c || back < 0 || back >= RIFT_DEFER_SLOTS) return RIFT_ERR_ARG;
   c->err.clear();
   if (!c->loaded) { c->err = "rift_forward_head without a RIFT_F_DEFER_HEAD forward" + NOT_LOADED; return RIFT_ERR_STATE; }
   const int slot = (c->parity - back + RIFT_DEFER_SLOTS) % RIFT_DEFER_SLOTS;
-  if (!c->head[slot].valid) { c->err = "rift_forward_head without a RIFT_F_DEFER_HEAD forward"; return RIFT_ERR_STATE; }
+  if (!c->slots[slot].head.valid) { c->err = "rift_forward_head without a RIFT_F_DEFER_HEAD forward"; return RIFT_ERR_STATE; }
   HIPCHK(c, hipSetDevice(c->device));
   const hipStream_t trunk_stream = c->stream;
   c->stream = (hipStream_t)stream; c->dry = false;
-  if (c->head[slot].dec_pending) {          // (the forward left its planning decoder to this call: dec_defer_max)
-    const DecWP dq = c->head[slot].dec;
+  if (c->slots[slot].head.dec_pending) {          // (the forward left its planning decoder to this call: dec_defer_max)
+    const DecWP dq = c->slots[slot].head.dec;
     launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });
-    c->head[slot].dec_pending = false;
+    c->slots[slot].head.dec_pending = false;
   }
-  const int rc = head_impl(c, c->head[slot]);
-  c->head[slot].valid = false;
+  const int rc = head_impl(c, c->slots[slot].head);
+  c->slots[slot].head.valid = false;
   c->stream = trunk_stream;
   if (rc != RIFT_OK) return rc;
   if (!c->err.empty()) return RIFT_ERR_ARG;
@@ -2103,170 +1855,12 @@ int rift_forward_head_back(RiftCtx* c, int back, void* stream) {
   return RIFT_OK;
 }
 
-int rift_forward_head(RiftCtx* c, void* stream) { return abi::rift_forward_head_back(c, 0, stream); }
+int rift_forward_head(RiftCtx* h, void* stream) { return abi::rift_forward_head_back(h, 0, stream); }
 
-// scratch of pi_backward_kernel: dz per row and one 16897-float partial per workgroup of RIFT_PI_BWD_ROWS rows (grow-only)
-static int pi_backward_scratch(RiftCtx* c, int rows, int nwg) {
-  DEVCHK(c, c->l_dz.reserve((size_t)rows));
-  DEVCHK(c, c->l_partial.reserve((size_t)nwg * RIFT_PI_NPARAM));
-  return RIFT_OK;
-}
-
-// rift_loss_backward (ob == nullptr: the kernel with the reference's literals) and rift_loss_backward_ex (ob: its accepted settings)
-static int loss_backward_impl(RiftCtx* c, const char* who, int kind, const RiftLossIn* in, const RiftObjectiveParams* ob, const RiftLossOut* out,
-                              double* terms, void* stream) {
-  if (!c->loaded) { c->err = std::string(who) + " before rift_forward" + NOT_LOADED; return RIFT_ERR_STATE; }
-  if (!c->last_qfinal) { c->err = std::string(who) + " before rift_forward"; return RIFT_ERR_STATE; }
-  HIPCHK(c, hipSetDevice(c->device));
-  c->stream = (hipStream_t)stream; c->dry = false;
-  const int bs = c->last_bs, R = c->last_R, M = 12, G = R * M, rows = bs * G;
-  if (G > 64 * 16) { c->err = "group too large"; return RIFT_ERR_ARG; }
-  const int nwg = cdiv(rows, RIFT_PI_BWD_ROWS);
-  DEVCHK(c, c->l_S.reserve((size_t)bs)); DEVCHK(c, c->l_cnt.reserve((size_t)bs));
-  TRY(pi_backward_scratch(c, rows, nwg));
-  LossP p; memset(&p, 0, sizeof(p));
-  p.kind = kind; p.bs = bs; p.G = G; p.M = M; p.prob = c->last_prob; p.r_kpm = c->last_rkpm;
-  p.old_logits = in->old_group_logits; p.ref_logits = in->ref_group_logits; p.adv64 = in->group_advantage;
-  p.valid = in->group_valid_mask; p.action_mode = (const long long*)in->action_mode;
-  p.scal_a = kind == RIFT_LOSS_PPO ? in->advantage : in->returns; p.old_log_prob = in->old_log_prob;
-  p.clip_eps = in->clip_epsilon; p.lambda_entropy = in->lambda_entropy;
-  p.S = c->l_S.get(); p.cnt = c->l_cnt.get(); p.dlogit = c->l_dz.get(); p.argmax_rm = (long long*)out->argmax_rm;
-  if ((kind == RIFT_LOSS_RIFT || kind == RIFT_LOSS_GRPO) && (!p.old_logits || !p.adv64 || !p.valid)) { c->err = "missing loss inputs"; return RIFT_ERR_ARG; }
-  if (kind == RIFT_LOSS_GRPO && !ob && !p.ref_logits) { c->err = "missing ref logits"; return RIFT_ERR_ARG; }
-  if (kind == RIFT_LOSS_PPO && (!p.action_mode || !p.scal_a || !p.old_log_prob)) { c->err = "missing ppo inputs"; return RIFT_ERR_ARG; }
-  if (kind == RIFT_LOSS_REINFORCE && !p.scal_a) { c->err = "missing returns"; return RIFT_ERR_ARG; }
-  if (kind == RIFT_LOSS_SFT && !p.action_mode) { c->err = "missing teacher mode (action_mode)"; return RIFT_ERR_ARG; }
-  const dim3 lgrid(cdiv(bs, 4)), lblock(256);
-  if (ob) {
-    if (terms) DEVCHK(c, c->l_T.reserve((size_t)bs * LOSS_NTERM));
-    p.clip_lo = (float)ob->clip_low; p.clip_hi = (float)ob->clip_high; p.kl_gw = (float)ob->kl_beta; p.ent_gw = (float)ob->entropy_coef;
-    p.dual_clip = ob->dual_clip; p.kl_beta = ob->kl_beta; p.ent_coef = ob->entropy_coef; p.T = terms ? c->l_T.get() : nullptr;
-    if (G <= 64 * 2) launch(c, "loss_kernel", loss_kernel<2, true>, lgrid, lblock, 0, p);
-    else if (G <= 64 * 4) launch(c, "loss_kernel", loss_kernel<4, true>, lgrid, lblock, 0, p);
-    else launch(c, "loss_kernel", loss_kernel<16, true>, lgrid, lblock, 0, p);
-    if (terms) launch(c, "loss_terms_kernel", loss_terms_kernel, dim3(1), dim3(64), 0, (const double*)c->l_T.get(), (const double*)c->l_cnt.get(), bs, terms);
-  }
-  else if (G <= 64 * 2) launch(c, "loss_kernel", loss_kernel<2>, lgrid, lblock, 0, p);
-  else if (G <= 64 * 4) launch(c, "loss_kernel", loss_kernel<4>, lgrid, lblock, 0, p);
-  else launch(c, "loss_kernel", loss_kernel<16>, lgrid, lblock, 0, p);
-  const std::string PH = "planning_decoder.pi_head.mlp.";
-  launch(c, "pi_backward_kernel", pi_backward_kernel, dim3(nwg), dim3(256), 0, (const float*)c->last_qfinal, (const float*)c->last_hpi,
-         (const float*)c->l_dz.get(), rows, fptr(c, PH + "1.weight"), fptr(c, PH + "1.bias"), fptr(c, PH + "3.weight"), 1e-5f,
-         c->l_partial.get());
-  launch(c, "loss_reduce_kernel", loss_reduce_kernel, dim3(cdiv(RIFT_PI_NPARAM, 256)), dim3(256), 0, (const float*)c->l_partial.get(), nwg,
-         out->flat_grad_sum, (const double*)c->l_S.get(), (const double*)c->l_cnt.get(), bs, out->stats, out->exchange);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-int rift_loss_backward(RiftCtx* c, int kind, const RiftLossIn* in, const RiftLossOut* out, void* stream) {
-  if (!c || !in || !out || !out->stats || !out->flat_grad_sum) return RIFT_ERR_ARG;
-  c->err.clear();
-  return loss_backward_impl(c, "rift_loss_backward", kind, in, nullptr, out, nullptr, stream);
-}
-
-int rift_loss_backward_ex(RiftCtx* c, int kind, const RiftLossIn* in, const RiftObjectiveParams* params, const RiftLossOut* out, double* terms,
-                          void* stream) {
-  if (!c || !in || !out || !out->stats || !out->flat_grad_sum) return RIFT_ERR_ARG;
-  c->err.clear();
-  if (const char* why = rift_objective_params_refusal(kind, params, in->ref_group_logits != nullptr)) {
-    c->err = std::string("rift_loss_backward_ex: ") + why;
-    return RIFT_ERR_ARG;
-  }
-  return loss_backward_impl(c, "rift_loss_backward_ex", kind, in, params, out, terms, stream);
-}
-
-int rift_head_backward(RiftCtx* c, const float* dlogits, int bs, int R, const RiftLossOut* out, int accumulate, void* stream) {
-  if (!c || !dlogits || !out || !out->flat_grad_sum) return RIFT_ERR_ARG;
-  c->err.clear();
-  if (!c->loaded) { c->err = "rift_head_backward before rift_forward" + NOT_LOADED; return RIFT_ERR_STATE; }
-  if (!c->last_qfinal) { c->err = "rift_head_backward before rift_forward"; return RIFT_ERR_STATE; }
-  if (bs != c->last_bs || R != c->last_R) {
-    c->err = "rift_head_backward: dlogits of (" + std::to_string(bs) + ", " + std::to_string(R) + ", 12) against a forward of (" +
-             std::to_string(c->last_bs) + ", " + std::to_string(c->last_R) + ", 12)";
-    return RIFT_ERR_ARG;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  c->stream = (hipStream_t)stream; c->dry = false;
-  const int M = 12, rows = bs * R * M, nwg = cdiv(rows, RIFT_PI_BWD_ROWS);
-  TRY(pi_backward_scratch(c, rows, nwg));
-  DEVCHK(c, c->l_sink.reserve(2));
-  launch(c, "head_dz_kernel", head_dz_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, dlogits, (const uint8_t*)c->last_rkpm, rows, M, c->l_dz.get());
-  const std::string PH = "planning_decoder.pi_head.mlp.";
-  launch(c, "pi_backward_kernel", pi_backward_kernel, dim3(nwg), dim3(256), 0, (const float*)c->last_qfinal, (const float*)c->last_hpi,
-         (const float*)c->l_dz.get(), rows, fptr(c, PH + "1.weight"), fptr(c, PH + "1.bias"), fptr(c, PH + "3.weight"), 1e-5f,
-         c->l_partial.get());
-  // (no objective: zero scenes, the two sums land in the sink)
-  launch(c, "loss_reduce_kernel", loss_reduce_kernel, dim3(cdiv(RIFT_PI_NPARAM, 256)), dim3(256), 0, (const float*)c->l_partial.get(), nwg,
-         out->flat_grad_sum, (const double*)nullptr, (const double*)nullptr, 0, c->l_sink.get(), (double*)nullptr);
-  if (out->grad_w1 || out->grad_b1 || out->grad_ln_w || out->grad_ln_b || out->grad_w2 || out->grad_b2)
-    launch(c, "head_scatter_kernel", head_scatter_kernel, dim3(cdiv(RIFT_PI_NPARAM, 256)), dim3(256), 0, (const float*)out->flat_grad_sum,
-           out->grad_w1, out->grad_b1, out->grad_ln_w, out->grad_ln_b, out->grad_w2, out->grad_b2, accumulate);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-int rift_loss_finalize(RiftCtx* c, const RiftLossOut* out, int accumulate, void* stream) {
-  if (!c || !out || !out->stats || !out->flat_grad_sum) return RIFT_ERR_ARG;
-  c->stream = (hipStream_t)stream; c->dry = false;
-  launch(c, "loss_finalize_kernel", loss_finalize_kernel, dim3(cdiv(RIFT_PI_NPARAM, 256)), dim3(256), 0, (const float*)out->flat_grad_sum,
-         (const double*)out->stats, out->grad_w1, out->grad_b1, out->grad_ln_w, out->grad_ln_b, out->grad_w2, out->grad_b2,
-         out->loss, accumulate, (const double*)out->exchange, out->stats);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-int rift_other_vehicle_rollout(RiftCtx* c, const double* actions, const double* speed, const double* location, const double* yaw_deg,
-                               const double* extent, int N, int T, int near_lane_change, double bbox_inflation_ratio, double* vertices,
-                               void* stream) {
-  if (!c || N < 0 || T <= 0) return RIFT_ERR_ARG;
-  if (N == 0) return RIFT_OK;
-  if (!actions || !speed || !location || !yaw_deg || !extent || !vertices) return RIFT_ERR_ARG;
-  c->err.clear();
-  HIPCHK(c, hipSetDevice(c->device));
-  hipLaunchKernelGGL(other_vehicle_rollout_kernel, dim3(cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, actions, speed, location, yaw_deg, extent,
-                     N, T, near_lane_change, bbox_inflation_ratio, vertices);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-int rift_collision_matrix(RiftCtx* c, const float* center_vertices, int G, int Tc, const double* other_vertices, int N, int Ts,
-                          uint8_t* collision, void* stream) {
-  if (!c || G <= 0 || Ts <= 0 || Tc < Ts || N < 0 || !center_vertices || !collision || (N > 0 && !other_vertices)) return RIFT_ERR_ARG;
-  c->err.clear();
-  HIPCHK(c, hipSetDevice(c->device));
-  hipLaunchKernelGGL(collision_matrix_kernel, dim3(cdiv((long long)G * Ts, 256)), dim3(256), 0, (hipStream_t)stream, center_vertices, G, Tc,
-                     other_vertices, N, Ts, collision);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-int rift_off_road_matrix(RiftCtx* c, const float* rollout_center, int n_points, const uint8_t* off_road_mask, int H, int W,
-                         double origin_x, double origin_y, double heading, double res_x, double res_y, double off_x, double off_y,
-                         uint8_t* off_road, void* stream) {
-  if (!c || n_points <= 0 || H <= 0 || W <= 0 || !rollout_center || !off_road_mask || !off_road || res_x == 0.0 || res_y == 0.0) return RIFT_ERR_ARG;
-  c->err.clear();
-  HIPCHK(c, hipSetDevice(c->device));
-  hipLaunchKernelGGL(off_road_kernel, dim3(cdiv(n_points, 256)), dim3(256), 0, (hipStream_t)stream, rollout_center, n_points, off_road_mask,
-                     H, W, origin_x, origin_y, std::cos(heading), std::sin(heading), res_x, res_y, off_x, off_y, off_road);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-int rift_sft_teacher_mode(RiftCtx* c, const float* trajectory, const float* teacher_infos, int bs, int R, int M, int T, int frame_rate,
-                          int64_t* mode_rm, void* stream) {
-  if (!c || !trajectory || !teacher_infos || !mode_rm || bs <= 0 || R <= 0 || M <= 0 || T <= 0 || frame_rate <= 0) return RIFT_ERR_ARG;
-  c->err.clear();
-  HIPCHK(c, hipSetDevice(c->device));
-  hipLaunchKernelGGL(sft_teacher_mode_kernel, dim3(bs), dim3(64), 0, (hipStream_t)stream, trajectory, teacher_infos, bs, R * M, M, T, frame_rate,
-                     (long long*)mode_rm);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-int rift_set_dp(RiftCtx* c, const RiftDp* dp) {
+int rift_set_dp(RiftCtx* h, const RiftDp* dp) {
+  Ctx* c = static_cast<Ctx*>(h);
   if (!c) return RIFT_ERR_ARG;
-  if (!dp || dp->global_bs <= 0) { c->dp = RiftCtx::Dp(); return RIFT_OK; }
+  if (!dp || dp->global_bs <= 0) { c->dp = Ctx::Dp(); return RIFT_OK; }
   if (!dp->xchg || dp->scene_offset < 0 || dp->xchg_len <= 0) { c->err = "rift_set_dp: bad descriptor"; return RIFT_ERR_ARG; }
   if (!dp->exchange && !c->comm) { c->err = "rift_set_dp: no exchange callback and no library communicator (rift_comm_init)"; return RIFT_ERR_ARG; }
   c->dp.on = true; c->dp.off = dp->scene_offset; c->dp.gbs = dp->global_bs; c->dp.xchg = dp->xchg; c->dp.len = dp->xchg_len;
@@ -2274,7 +1868,8 @@ int rift_set_dp(RiftCtx* c, const RiftDp* dp) {
   return RIFT_OK;
 }
 
-int rift_comm_unique_id(RiftCtx* c, void* unique_id_out) {
+int rift_comm_unique_id(RiftCtx* h, void* unique_id_out) {
+  Ctx* c = static_cast<Ctx*>(h);
   if (!c || !unique_id_out) return RIFT_ERR_ARG;
   std::string why;
   RcclApi& r = rccl_api(&why);
@@ -2286,7 +1881,8 @@ int rift_comm_unique_id(RiftCtx* c, void* unique_id_out) {
   return RIFT_OK;
 }
 
-int rift_comm_init(RiftCtx* c, const void* unique_id, int rank, int world) {
+int rift_comm_init(RiftCtx* h, const void* unique_id, int rank, int world) {
+  Ctx* c = static_cast<Ctx*>(h);
   if (!c || !unique_id || world < 1 || rank < 0 || rank >= world) return RIFT_ERR_ARG;
   if (c->comm) { c->err = "rift_comm_init: the context has a communicator already (rift_comm_destroy first)"; return RIFT_ERR_STATE; }
   std::string why;
@@ -2302,7 +1898,8 @@ int rift_comm_init(RiftCtx* c, const void* unique_id, int rank, int world) {
   return RIFT_OK;
 }
 
-int rift_comm_all_reduce(RiftCtx* c, double* buf, int64_t count, void* stream) {
+int rift_comm_all_reduce(RiftCtx* h, double* buf, int64_t count, void* stream) {
+  Ctx* c = static_cast<Ctx*>(h);
   if (!c || !buf || count <= 0) return RIFT_ERR_ARG;
   if (!c->comm) { c->err = "rift_comm_all_reduce before rift_comm_init"; return RIFT_ERR_STATE; }
   HIPCHK(c, hipSetDevice(c->device));
@@ -2311,32 +1908,36 @@ int rift_comm_all_reduce(RiftCtx* c, double* buf, int64_t count, void* stream) {
   return RIFT_OK;
 }
 
-int rift_comm_destroy(RiftCtx* c) {
+int rift_comm_destroy(RiftCtx* h) {
+  Ctx* c = static_cast<Ctx*>(h);
   if (!c) return RIFT_ERR_ARG;
   if (c->comm) {
-    if (c->dp.on && !c->dp.fn) c->dp = RiftCtx::Dp();      // (forwards must not reach for a communicator that is gone)
+    if (c->dp.on && !c->dp.fn) c->dp = Ctx::Dp();      // (forwards must not reach for a communicator that is gone)
     (void)rccl_api(nullptr).CommDestroy(c->comm);
     c->comm = nullptr; c->comm_world = 1; c->comm_rank = 0;
   }
   return RIFT_OK;
 }
 
-int rift_set_prepare_stream(RiftCtx* c, void* prepare_stream) {
+int rift_set_prepare_stream(RiftCtx* h, void* prepare_stream) {
+  Ctx* c = static_cast<Ctx*>(h);
   if (!c) return RIFT_ERR_ARG;
-  c->prep_stream = (hipStream_t)prepare_stream; c->prep_set = prepare_stream != nullptr;
+  c->st.prep_stream = (hipStream_t)prepare_stream; c->st.prep_set = prepare_stream != nullptr;
   return RIFT_OK;
 }
 
-int rift_set_side_stream(RiftCtx* c, void* side_stream) {
+int rift_set_side_stream(RiftCtx* h, void* side_stream) {
+  Ctx* c = static_cast<Ctx*>(h);
   if (!c) return RIFT_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  if (c->side && c->side_owned) { HIPCHK(c, hipStreamSynchronize(c->side)); (void)hipStreamDestroy(c->side); }
-  else if (c->side) HIPCHK(c, hipStreamSynchronize(c->side));
-  c->side = (hipStream_t)side_stream; c->side_owned = false;
+  if (c->st.side && c->st.side_owned) { HIPCHK(c, hipStreamSynchronize(c->st.side)); (void)hipStreamDestroy(c->st.side); }
+  else if (c->st.side) HIPCHK(c, hipStreamSynchronize(c->st.side));
+  c->st.side = (hipStream_t)side_stream; c->st.side_owned = false;
   return RIFT_OK;
 }
 
-int rift_check_finite(RiftCtx* c, void* stream) {
+int rift_check_finite(RiftCtx* h, void* stream) {
+  Ctx* c = static_cast<Ctx*>(h);
   if (!c) return RIFT_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   int flag = 0;
@@ -2350,179 +1951,15 @@ int rift_check_finite(RiftCtx* c, void* stream) {
   return RIFT_ERR_NONFINITE;
 }
 
-int rift_set_param_event(RiftCtx* c, void* event) {
+int rift_set_param_event(RiftCtx* h, void* event) {
+  Ctx* c = static_cast<Ctx*>(h);
   if (!c) return RIFT_ERR_ARG;
-  c->param_event = (hipEvent_t)event;
+  c->st.param_event = (hipEvent_t)event;
   return RIFT_OK;
 }
 
-int rift_loss_finalize_clip(RiftCtx* c, const RiftLossOut* out, int accumulate, float max_norm, float* total_norm, void* stream) {
-  if (!c || !out || !out->stats || !out->flat_grad_sum || !(max_norm > 0.f)) return RIFT_ERR_ARG;
-  if (!out->grad_w1 || !out->grad_b1 || !out->grad_ln_w || !out->grad_ln_b || !out->grad_w2 || !out->grad_b2) return RIFT_ERR_ARG;
-  c->stream = (hipStream_t)stream; c->dry = false;
-  launch(c, "loss_finalize_clip_kernel", loss_finalize_clip_kernel, dim3(1), dim3(1024), 0, (const float*)out->flat_grad_sum,
-         (const double*)out->stats, out->grad_w1, out->grad_b1, out->grad_ln_w, out->grad_ln_b, out->grad_w2, out->grad_b2,
-         out->loss, accumulate, (const double*)out->exchange, out->stats, max_norm, total_norm);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-int rift_clip_grad_norm(RiftCtx* c, float* const* grads, const int64_t* numels, int n, float max_norm, float* total_norm, void* stream) {
-  if (!c || !grads || !numels || n <= 0 || n > 16) return RIFT_ERR_ARG;
-  c->err.clear();
-  HIPCHK(c, hipSetDevice(c->device));
-  c->stream = (hipStream_t)stream; c->dry = false;
-  ClipList L; memset(&L, 0, sizeof(L));
-  long long tot = 0;
-  for (int i = 0; i < n; ++i) { L.g[i] = grads[i]; L.n[i] = numels[i]; tot += numels[i]; }
-  L.count = n;
-  const int nb = (int)std::min<long long>(64, (tot + 2047) / 2048);
-  DEVCHK(c, c->clip_part.reserve(64));
-  launch(c, "clip_norm_partial_kernel", clip_norm_partial_kernel, dim3(nb), dim3(256), 0, L, c->clip_part.get());
-  launch(c, "clip_scale_kernel", clip_scale_kernel, dim3(nb), dim3(256), 0, L, (const double*)c->clip_part.get(), nb, max_norm, total_norm);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-int rift_adamw_step(RiftCtx* c, int n, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
-                    float* const* steps, const int64_t* numels, const double* lr, const double* weight_decay, double step_new,
-                    double beta1, double beta2, double eps, void* stream) {
-  if (!c || n <= 0 || n > 16 || !params || !grads || !exp_avg || !exp_avg_sq || !steps || !numels || !lr || !weight_decay) return RIFT_ERR_ARG;
-  if (!(step_new >= 1.0)) return RIFT_ERR_ARG;
-  c->err.clear();
-  HIPCHK(c, hipSetDevice(c->device));
-  c->stream = (hipStream_t)stream; c->dry = false;
-  AdamList L; memset(&L, 0, sizeof(L));
-  const double bc1 = 1.0 - std::pow(beta1, step_new), bc2 = 1.0 - std::pow(beta2, step_new);
-  long long tot = 0;
-  for (int i = 0; i < n; ++i) {
-    if (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i] || !steps[i] || numels[i] <= 0) return RIFT_ERR_ARG;
-    L.p[i] = params[i]; L.g[i] = grads[i]; L.m[i] = exp_avg[i]; L.v[i] = exp_avg_sq[i]; L.step[i] = steps[i];
-    L.n[i] = numels[i]; L.step_size[i] = (float)(lr[i] / bc1); L.decay[i] = (float)(1.0 - lr[i] * weight_decay[i]); L.step_new[i] = (float)step_new;
-    tot += numels[i];
-  }
-  L.count = n; L.beta1 = (float)beta1; L.beta2 = (float)beta2; L.omb1 = (float)(1.0 - beta1); L.omb2 = (float)(1.0 - beta2);
-  L.bc2_sqrt = (float)std::sqrt(bc2); L.eps = (float)eps;
-  const int nb = (int)std::min<long long>(256, (tot + 255) / 256);
-  launch(c, "adamw_kernel", adamw_kernel, dim3(nb), dim3(256), 0, L);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-int rift_update_tail(RiftCtx* c, const RiftLossOut* out, int accumulate, float max_norm, float* total_norm, int n, float* const* params,
-                     const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, float* const* steps, const double* lr,
-                     const double* weight_decay, double step_new, double beta1, double beta2, double eps, void* stream) {
-  if (!c || !out || !out->stats || !out->flat_grad_sum || !(max_norm > 0.f) || n != 6) return RIFT_ERR_ARG;
-  if (!params || !grads || !exp_avg || !exp_avg_sq || !steps || !lr || !weight_decay || !(step_new >= 1.0)) return RIFT_ERR_ARG;
-  float* const gseg[6] = {out->grad_w1, out->grad_b1, out->grad_ln_w, out->grad_ln_b, out->grad_w2, out->grad_b2};
-  c->err.clear();
-  HIPCHK(c, hipSetDevice(c->device));
-  c->stream = (hipStream_t)stream; c->dry = false;
-  TailAdam A; memset(&A, 0, sizeof(A));
-  const double bc1 = 1.0 - std::pow(beta1, step_new), bc2 = 1.0 - std::pow(beta2, step_new);
-  for (int sgi = 0; sgi < 6; ++sgi) {
-    int j = -1;
-    for (int t = 0; t < 6; ++t) if (gseg[sgi] && grads[t] == gseg[sgi]) j = t;
-    if (j < 0 || !params[j] || !exp_avg[j] || !exp_avg_sq[j] || !steps[j]) { c->err = "rift_update_tail: the AdamW list does not hold the six pi_head gradient tensors"; return RIFT_ERR_ARG; }
-    A.p[sgi] = params[j]; A.m[sgi] = exp_avg[j]; A.v[sgi] = exp_avg_sq[j]; A.step[sgi] = steps[j];
-    A.step_size[sgi] = (float)(lr[j] / bc1); A.decay[sgi] = (float)(1.0 - lr[j] * weight_decay[j]);
-  }
-  A.step_new = (float)step_new; A.beta2 = (float)beta2; A.omb1 = (float)(1.0 - beta1); A.omb2 = (float)(1.0 - beta2);
-  A.bc2_sqrt = (float)std::sqrt(bc2); A.eps = (float)eps;
-  launch(c, "update_tail_kernel", update_tail_kernel, dim3(1), dim3(1024), 0, (const float*)out->flat_grad_sum, (const double*)out->stats,
-         out->grad_w1, out->grad_b1, out->grad_ln_w, out->grad_ln_b, out->grad_w2, out->grad_b2, out->loss, accumulate,
-         (const double*)out->exchange, out->stats, max_norm, total_norm, A);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-// ---- PPO critic ------------------------------------------------------------------------------------
-static int critic_scratch(RiftCtx* c, int n) {
-  const size_t need = (size_t)((n + 15) / 16 * 16) * (128 + 4 * 256 + 1 + 2 * 128 + 2);
-  DEVCHK(c, c->cr_buf.reserve(need));
-  DEVCHK(c, c->cr_part.reserve((size_t)((n + 15) / 16)));
-  return RIFT_OK;
-}
-
-static CriticW critic_w(const RiftCritic* w) {
-  CriticW q;
-  q.w0 = w->w0; q.b0 = w->b0; q.w1 = w->w1; q.b1 = w->b1; q.w2 = w->w2; q.b2 = w->b2;
-  q.savg = w->state_avg; q.sstd = w->state_std; q.vavg = w->value_avg; q.vstd = w->value_std;
-  return q;
-}
-
-int rift_critic_forward(RiftCtx* c, const RiftCritic* w, const float* state, int n, float* value, void* stream) {
-  if (!c || !w || !state || !value || n < 0) return RIFT_ERR_ARG;
-  c->err.clear();
-  HIPCHK(c, hipSetDevice(c->device));
-  c->stream = (hipStream_t)stream; c->dry = false;
-  if (n == 0) return RIFT_OK;
-  CriticRowsP p; memset(&p, 0, sizeof(p));
-  p.w = critic_w(w); p.state = state; p.n = n; p.value = value;
-  launch(c, "critic_rows_kernel", critic_rows_kernel, dim3(cdiv(n, 16)), dim3(256), 0, p);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-// The critic's backward for n rows: forward recomputed by critic_rows_kernel, whose per-row output delta is the SmoothL1 derivative against
-// `target` or the caller's `dvalue`; then flat = scale * sum_rows delta_row * d value_row / d theta -- one thread per parameter, rows summed in order
-static int critic_backward_sums(RiftCtx* c, const RiftCritic* w, const float* state, const float* target, const float* dvalue, int n, float scale,
-                                float* flat) {
-  TRY(critic_scratch(c, n));
-  const int np = (n + 15) / 16 * 16, nwg = cdiv(n, 16);
-  CriticRowsP p; memset(&p, 0, sizeof(p));
-  p.w = critic_w(w); p.state = state; p.target = target; p.dvalue = dvalue; p.n = n;
-  p.sn = c->cr_buf.get(); p.h1 = p.sn + (size_t)np * 128; p.h2 = p.h1 + (size_t)np * 256; p.dh1 = p.h2 + (size_t)np * 256;
-  p.dh2 = p.dh1 + (size_t)np * 256; p.dout = p.dh2 + (size_t)np * 256; p.sl1_part = c->cr_part.get();
-  p.gsa = p.dout + np; p.gss = p.gsa + (size_t)np * 128; p.gva = p.gss + (size_t)np * 128; p.gvs = p.gva + np;
-  launch(c, "critic_rows_kernel", critic_rows_kernel, dim3(nwg), dim3(256), 0, p);
-  launch(c, "critic_outer_sum_kernel", critic_outer_sum_kernel, dim3(cdiv(256 * 128, 256)), dim3(256), 0, (const float*)p.dh1, 256, (const float*)p.sn, 128, n, scale, flat);
-  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(256), 0, (const float*)p.dh1, 256, n, scale, flat + RIFT_CRITIC_OFF_B0);
-  launch(c, "critic_outer_sum_kernel", critic_outer_sum_kernel, dim3(cdiv(256 * 256, 256)), dim3(256), 0, (const float*)p.dh2, 256, (const float*)p.h1, 256, n, scale, flat + RIFT_CRITIC_OFF_W1);
-  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(256), 0, (const float*)p.dh2, 256, n, scale, flat + RIFT_CRITIC_OFF_B1);
-  launch(c, "critic_outer_sum_kernel", critic_outer_sum_kernel, dim3(1), dim3(256), 0, (const float*)p.dout, 1, (const float*)p.h2, 256, n, scale, flat + RIFT_CRITIC_OFF_W2);
-  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(64), 0, (const float*)p.dout, 1, n, scale, flat + RIFT_CRITIC_OFF_B2);
-  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(128), 0, (const float*)p.gsa, 128, n, scale, flat + RIFT_CRITIC_OFF_SAVG);
-  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(128), 0, (const float*)p.gss, 128, n, scale, flat + RIFT_CRITIC_OFF_SSTD);
-  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(64), 0, (const float*)p.gva, 1, n, scale, flat + RIFT_CRITIC_OFF_VAVG);
-  launch(c, "critic_col_sum_kernel", critic_col_sum_kernel, dim3(1), dim3(64), 0, (const float*)p.gvs, 1, n, scale, flat + RIFT_CRITIC_OFF_VSTD);
-  return RIFT_OK;
-}
-
-int rift_critic_loss_backward(RiftCtx* c, const RiftCritic* w, const float* state, const float* reward_sum, int n, double* stats,
-                              float* flat, void* stream) {
-  if (!c || !w || !state || !reward_sum || !stats || !flat || n <= 0) return RIFT_ERR_ARG;
-  c->err.clear();
-  HIPCHK(c, hipSetDevice(c->device));
-  c->stream = (hipStream_t)stream; c->dry = false;
-  // flat = -sum_rows d SmoothL1 / d theta
-  TRY(critic_backward_sums(c, w, state, reward_sum, nullptr, n, -1.f, flat));
-  launch(c, "critic_stats_kernel", critic_stats_kernel, dim3(1), dim3(64), 0, (const double*)c->cr_part.get(), cdiv(n, 16), stats);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-int rift_critic_backward(RiftCtx* c, const RiftCritic* w, const float* state, const float* dvalue, int n, float* flat, void* stream) {
-  if (!c || !w || !state || !dvalue || !flat || n <= 0) return RIFT_ERR_ARG;
-  c->err.clear();
-  HIPCHK(c, hipSetDevice(c->device));
-  c->stream = (hipStream_t)stream; c->dry = false;
-  TRY(critic_backward_sums(c, w, state, nullptr, dvalue, n, 1.f, flat));
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-int rift_critic_finalize(RiftCtx* c, const float* flat, const double* stats, float* g_w0, float* g_b0, float* g_w1, float* g_b1,
-                         float* g_w2, float* g_b2, float* g_savg, float* g_sstd, float* g_vavg, float* g_vstd, void* stream) {
-  if (!c || !flat || !stats) return RIFT_ERR_ARG;
-  c->stream = (hipStream_t)stream; c->dry = false;
-  launch(c, "critic_finalize_kernel", critic_finalize_kernel, dim3(cdiv(RIFT_CRITIC_NPARAM, 256)), dim3(256), 0, flat, stats, g_w0, g_b0,
-         g_w1, g_b1, g_w2, g_b2, g_savg, g_sstd, g_vavg, g_vstd);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-int rift_prof_enable(RiftCtx* c, int on) {
+int rift_prof_enable(RiftCtx* h, int on) {
+  Ctx* c = static_cast<Ctx*>(h);
   if (!c) return RIFT_ERR_ARG;
   c->prof_on = on != 0;
   c->dry_need = 0;                      // the next forward sizes its arena again
@@ -2533,7 +1970,8 @@ int rift_prof_enable(RiftCtx* c, int on) {
 }
 
 // JSON: {"label": {"count": n, "ms": total_ms, "flops": total_flops}, ...}; synchronises the device.
-int rift_prof_report(RiftCtx* c, char* buf, int buflen) {
+int rift_prof_report(RiftCtx* h, char* buf, int buflen) {
+  Ctx* c = static_cast<Ctx*>(h);
   if (!c || !buf || buflen <= 0) return RIFT_ERR_ARG;
   HIPCHK(c, hipDeviceSynchronize());
   struct Agg { long n = 0; double ms = 0, fl = 0; };
@@ -2556,7 +1994,8 @@ int rift_prof_report(RiftCtx* c, char* buf, int buflen) {
   return RIFT_OK;
 }
 
-int rift_tap(RiftCtx* c, const char* name, float* dst, int64_t* numel, void* stream) {
+int rift_tap(RiftCtx* h, const char* name, float* dst, int64_t* numel, void* stream) {
+  Ctx* c = static_cast<Ctx*>(h);
   if (!c || !name) return RIFT_ERR_ARG;
   auto it = c->taps.find(name);
   if (it == c->taps.end()) { c->err = std::string("unknown tap ") + name; return RIFT_ERR_ARG; }
@@ -2566,8 +2005,9 @@ int rift_tap(RiftCtx* c, const char* name, float* dst, int64_t* numel, void* str
   return RIFT_OK;
 }
 
-int rift_op_linear(RiftCtx* c, const float* X, int M, int K, const float* W, const float* bias, int N,
+int rift_op_linear(RiftCtx* h, const float* X, int M, int K, const float* W, const float* bias, int N,
                    const float* ln_w, const float* ln_b, int act, int fp32, float* Y, void* stream) {
+  Ctx* c = static_cast<Ctx*>(h);
   if (!c || !X || !W || !Y || K > 512) return RIFT_ERR_ARG;
   c->err.clear();
   HIPCHK(c, hipSetDevice(c->device));
@@ -2588,9 +2028,10 @@ int rift_op_linear(RiftCtx* c, const float* X, int M, int K, const float* W, con
 }
 
 // Diagnostic: pack once, launch the GEMM `reps` times back to back, return the average milliseconds per launch.
-int rift_op_linear_bench(RiftCtx* c, const float* X, int M, int K, const float* W, const float* bias, int N,
+int rift_op_linear_bench(RiftCtx* h, const float* X, int M, int K, const float* W, const float* bias, int N,
                          const float* ln_w, const float* ln_b, int act, const float* residual, float* Y, int reps,
                          float* ms_out, void* stream) {
+  Ctx* c = static_cast<Ctx*>(h);
   if (!c || !X || !W || !Y || K > 512 || reps <= 0) return RIFT_ERR_ARG;
   c->err.clear();
   HIPCHK(c, hipSetDevice(c->device));
@@ -2614,301 +2055,6 @@ int rift_op_linear_bench(RiftCtx* c, const float* X, int M, int K, const float* 
   if (ms_out) *ms_out = ms / reps;
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   c->pw.erase(key);
-  return RIFT_OK;
-}
-
-// An empty buffer is a valid (no-op) input of the three scans below, as it is for the reference's loops.
-int rift_gae(RiftCtx* c, const double* rewards, const float* undones, const float* values, const float* next_values,
-             const float* unterminated, float gamma, float lambda_, int n, float* advantages, void* stream) {
-  if (!c || n < 0) return RIFT_ERR_ARG;
-  if (n == 0) return RIFT_OK;
-  GaeCoef k{rewards, undones, values, next_values, unterminated, gamma, lambda_};
-  hipLaunchKernelGGL((affine_scan_reverse_kernel<GaeCoef, float>), dim3(1), dim3(RIFT_SCAN_THREADS), 0, (hipStream_t)stream, k, n, advantages);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-int rift_discounted_return(RiftCtx* c, const double* rewards, const float* dones, double gamma, int n, double* returns,
-                           void* stream) {
-  if (!c || n < 0) return RIFT_ERR_ARG;
-  if (n == 0) return RIFT_OK;
-  ReturnCoef k{rewards, dones, gamma};
-  hipLaunchKernelGGL((affine_scan_reverse_kernel<ReturnCoef, double>), dim3(1), dim3(RIFT_SCAN_THREADS), 0, (hipStream_t)stream, k, n, returns);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-int rift_normalize_advantage(RiftCtx* c, float* x, int n, void* stream) {
-  if (!c || n < 0) return RIFT_ERR_ARG;
-  if (n == 0) return RIFT_OK;
-  hipLaunchKernelGGL(normalize_unbiased_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, x, n);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-int rift_group_advantage(RiftCtx* c, const double* returns, int n_groups, int G, double* advantage, void* stream) {
-  if (!c || n_groups <= 0 || G <= 0) return RIFT_ERR_ARG;
-  hipLaunchKernelGGL(group_zscore_kernel, dim3(cdiv(n_groups, 4)), dim3(256), 0, (hipStream_t)stream, returns, n_groups, G, advantage);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-// The reward half of RiftEvalParams as the kernels take it (adv.h)
-static RewardP reward_of(const RiftEvalParams& e) {
-  return RewardP{e.alpha_collision, e.alpha_boundary, e.alpha_comfort, e.alpha_l_align, e.alpha_vel_align, e.alpha_l_center, e.alpha_center_bias,
-                 e.alpha_velocity, e.alpha_timestep, e.reward_model == RIFT_REWARD_SPARSE ? 1 : 0};
-}
-
-int rift_eval_params_default(RiftCtx* c, RiftEvalParams* out) {
-  if (!c || !out) return RIFT_ERR_ARG;
-  rift_eval_params_set_default(out);
-  return RIFT_OK;
-}
-
-template <bool TERMS, class RP>
-static void launch_rollout_return(const float* delta_dis, const float* delta_angle, const float* speed, const float* acc, const float* ang_vel,
-                                  const float* ang_acc, const uint8_t* collision, int collision_ld, const uint8_t* off_road, int off_road_ld,
-                                  int G, int Ts, double gamma, const RP& rp, double* returns, double* terms, void* stream) {
-  hipLaunchKernelGGL((rollout_return_kernel<TERMS, RP>), dim3(cdiv(G, 4)), dim3(256), 0, (hipStream_t)stream, delta_dis, delta_angle, speed,
-                     acc, ang_vel, ang_acc, collision, collision_ld, off_road, off_road_ld, G, Ts, gamma, rp, returns, Ts, terms);
-}
-
-int rift_rollout_return(RiftCtx* c, const float* delta_dis, const float* delta_angle, const float* speed, const float* acc,
-                        const float* ang_vel, const float* ang_acc, const uint8_t* collision, int collision_ld,
-                        const uint8_t* off_road, int off_road_ld, int G, int Ts, double gamma, double* returns, void* stream) {
-  if (!c || G <= 0 || Ts <= 0) return RIFT_ERR_ARG;
-  launch_rollout_return<false>(delta_dis, delta_angle, speed, acc, ang_vel, ang_acc, collision, collision_ld, off_road, off_road_ld, G, Ts, gamma,
-                               RewardDefaults(), returns, nullptr, stream);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-int rift_rollout_return_ex(RiftCtx* c, const float* delta_dis, const float* delta_angle, const float* speed, const float* acc,
-                           const float* ang_vel, const float* ang_acc, const uint8_t* collision, int collision_ld,
-                           const uint8_t* off_road, int off_road_ld, int G, int Ts, const RiftEvalParams* params, double* returns,
-                           double* terms, void* stream) {
-  if (!c) return RIFT_ERR_ARG;
-  if (const char* why = rift_eval_params_refusal(params)) { c->err = std::string("rift_rollout_return_ex: ") + why; return RIFT_ERR_ARG; }
-  if (G <= 0 || Ts <= 0 || !returns) { c->err = "rift_rollout_return_ex: G <= 0, Ts <= 0 or returns == NULL"; return RIFT_ERR_ARG; }
-  const RewardP rp = reward_of(*params);
-  const double g = params->gamma;
-#define RIFT_RR(TERMS, RP) launch_rollout_return<TERMS>(delta_dis, delta_angle, speed, acc, ang_vel, ang_acc, collision, collision_ld, off_road, off_road_ld, G, Ts, g, RP, returns, terms, stream)
-  if (reward_is_default(rp)) { if (terms) RIFT_RR(true, RewardDefaults()); else RIFT_RR(false, RewardDefaults()); }      // the default weights: the old entry's instance
-  else { if (terms) RIFT_RR(true, rp); else RIFT_RR(false, rp); }
-#undef RIFT_RR
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-int rift_ref_line_info(RiftCtx* c, const float* traj, int G, int Tfull, int Ts, int M, const float* ref_pos, const float* ref_ang,
-                       const int32_t* ref_len, int Pmax, float* delta_dis, float* delta_angle, int32_t* closest_idx, void* stream) {
-  if (!c || !traj || !ref_pos || !ref_ang || !ref_len || G <= 0 || Ts <= 0 || M <= 0) return RIFT_ERR_ARG;
-  hipLaunchKernelGGL(ref_line_info_kernel, dim3(cdiv((long long)G * Ts, 128)), dim3(128), 0, (hipStream_t)stream, traj, G, Tfull, Ts, M,
-                     ref_pos, ref_ang, (const int*)ref_len, Pmax, delta_dis, delta_angle, (int*)closest_idx);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-int rift_rollout(RiftCtx* c, const RiftRolloutIO* io, void* stream) {
-  if (!c || !io || !io->trajectories || !io->center_state || io->G <= 0 || io->Tfull < 40 || io->G_per_group <= 0) return RIFT_ERR_ARG;
-  RolloutP p; memset(&p, 0, sizeof(p));
-  p.traj = io->trajectories; p.G = io->G; p.Tfull = io->Tfull; p.Gper = io->G_per_group; p.state = io->center_state;
-  p.turn_buf = io->turn_buf; p.turn_ptr = (int*)io->turn_ptr; p.turn_len = (int*)io->turn_len;
-  p.speed_buf = io->speed_buf; p.speed_ptr = (int*)io->speed_ptr; p.speed_len = (int*)io->speed_len;
-  p.center = io->center; p.angle = io->angle; p.speed = io->speed; p.acc = io->acc; p.ang_vel = io->ang_vel; p.ang_acc = io->ang_acc;
-  p.vertices = io->vertices; p.closest_index = (int*)io->closest_index; p.aim_idx = (int*)io->aim_idx;
-  const size_t ro_need = (size_t)io->G * RIFT_RO_LEN;          // the raw speed history between the two kernels (grown behind a device-wide wait)
-  if (ro_need > c->ro_raw.cap() && c->ro_raw.get()) HIPCHK(c, hipDeviceSynchronize());
-  DEVCHK(c, c->ro_raw.reserve(ro_need, std::max((size_t)io->G * 2, (size_t)256) * RIFT_RO_LEN));
-  p.raw_speed = c->ro_raw.get();
-  if (!p.center || !p.angle || !p.speed || !p.acc || !p.ang_vel || !p.ang_acc || !p.vertices || !p.closest_index || !p.aim_idx) return RIFT_ERR_ARG;
-  if (c->ro8) hipLaunchKernelGGL(rollout8_kernel, dim3(cdiv(io->G, 8)), dim3(64), (size_t)RIFT_RO_LDS_BYTES, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(rollout_kernel, dim3(cdiv(io->G, 64)), dim3(64), (size_t)RIFT_RO_LDS_BYTES, (hipStream_t)stream, p);
-  hipLaunchKernelGGL(rollout_kinematics_kernel, dim3(cdiv(io->G * RIFT_RO_LEN, 256)), dim3(256), 0, (hipStream_t)stream, p);
-  HIPCHK(c, hipGetLastError());
-  return RIFT_OK;
-}
-
-// One rollout tick's group advantages (rift_hip.h).  Everything but the candidate rollouts is independent between the CBVs: one launch per
-// stage serves a chunk of up to RIFT_TICK_CHUNK of them (tick_multi.h) -- reference-line deviations and neighbour forecasts first, then the
-// rollouts CBV by CBV in list order (the shared PID state), then kinematics, flags, returns and z-scores: K + 7 launches instead of 9 K.
-// (own_offset: the pixel offset of a CBV comes from its own raster -- the _ex entry; else 200, 200 whatever the raster)
-static int group_advantage_tick(RiftCtx* c, const float* trajectory, int Rb, int Tfull, const RiftTickCBV* cbvs, int K,
-                                float* turn_buf, int32_t* turn_ptr, int32_t* turn_len, float* speed_buf, int32_t* speed_ptr, int32_t* speed_len,
-                                const RiftEvalParams& ev, bool own_offset, double* advantage, double* returns, double* terms, void* stream) {
-  if (!c || !trajectory || !cbvs || K <= 0 || Rb <= 0 || Tfull < 80 || !advantage || !turn_buf || !turn_ptr || !turn_len || !speed_buf || !speed_ptr || !speed_len) return RIFT_ERR_ARG;
-  c->err.clear();
-  HIPCHK(c, hipSetDevice(c->device));
-  constexpr int M = 12, Ts = 40, TR = RIFT_RO_LEN;
-  int Gmax = 0, Nmax = 0;
-  for (int k = 0; k < K; ++k) {
-    const RiftTickCBV& v = cbvs[k];
-    if (v.R <= 0 || v.R > Rb || v.batch_index < 0 || v.Pmax <= 0 || v.n_actors < 0 || !v.center_state || !v.ref_pos || !v.ref_angle || !v.ref_len ||
-        (v.n_actors > 0 && !v.actors) || (v.off_road_mask && (v.H <= 0 || v.W <= 0))) { c->err = "rift_group_advantage_tick: bad entry"; return RIFT_ERR_ARG; }
-    Gmax = std::max(Gmax, v.R * M); Nmax = std::max(Nmax, v.n_actors);
-  }
-  // per-CBV scratch (bytes, 256-aligned pieces), one set per CBV of a chunk
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-  const size_t G = (size_t)Gmax;
-  const size_t o_dd = take(G * Ts * 4), o_da = take(G * Ts * 4), o_ci = take(G * Ts * 4);
-  const size_t o_center = take(G * TR * 2 * 4), o_angle = take(G * TR * 4), o_speed = take(G * TR * 4), o_acc = take(G * TR * 4), o_av = take(G * TR * 4),
-               o_aa = take(G * TR * 4), o_vert = take(G * TR * 8 * 4), o_cl = take(G * 79 * 4), o_aim = take(G * 79 * 4), o_raw = take(G * TR * 4);
-  const size_t o_ov = take((size_t)std::max(Nmax, 1) * Ts * 8 * 8), o_col = take(G * Ts), o_offr = take(G * TR), o_ret = take(G * 8);
-  const size_t per = off, need = per * (size_t)std::min(K, RIFT_TICK_CHUNK);
-  if (need > c->tick_scratch.cap() && c->tick_scratch.get()) HIPCHK(c, hipDeviceSynchronize());
-  DEVCHK(c, c->tick_scratch.reserve(need, need * 2));
-  const hipStream_t st = (hipStream_t)stream;
-  for (int k0 = 0; k0 < K; k0 += RIFT_TICK_CHUNK) {
-    TickArr a; memset(&a, 0, sizeof(a));
-    a.K = std::min(RIFT_TICK_CHUNK, K - k0); a.gamma = ev.gamma; a.near_lane_change = ev.near_lane_change ? 1 : 0; a.inflation = ev.bbox_inflation_ratio;
-    a.res = (double)(float)ev.resolution;                       // resolution_hw is a float32 array in the reference (traj_evaluator.py:102)
-    a.reward = reward_of(ev); a.reward_default = reward_is_default(a.reward) ? 1 : 0;
-    int gmax = 0, nmax = 0;
-    for (int j = 0; j < a.K; ++j) {
-      const RiftTickCBV& v = cbvs[k0 + j];
-      char* S = c->tick_scratch.get() + per * (size_t)j;
-      TickK& d = a.d[j];
-      d.traj = trajectory + (size_t)v.batch_index * Rb * M * Tfull * 6; d.G = v.R * M; d.Tfull = Tfull; d.Pmax = v.Pmax; d.N = v.n_actors; d.H = v.H; d.W = v.W;
-      d.ref_pos = v.ref_pos; d.ref_ang = v.ref_angle; d.ref_len = (const int*)v.ref_len;
-      d.dd = (float*)(S + o_dd); d.da = (float*)(S + o_da); d.ci = (int*)(S + o_ci);
-      d.actors = v.actors; d.ov = (double*)(S + o_ov);
-      RolloutP& p = d.ro;
-      p.traj = d.traj; p.G = d.G; p.Tfull = Tfull; p.Gper = d.G; p.state = v.center_state;
-      p.turn_buf = turn_buf; p.turn_ptr = (int*)turn_ptr; p.turn_len = (int*)turn_len; p.speed_buf = speed_buf; p.speed_ptr = (int*)speed_ptr; p.speed_len = (int*)speed_len;
-      p.center = (float*)(S + o_center); p.angle = (float*)(S + o_angle); p.speed = (float*)(S + o_speed); p.acc = (float*)(S + o_acc);
-      p.ang_vel = (float*)(S + o_av); p.ang_acc = (float*)(S + o_aa); p.vertices = (float*)(S + o_vert);
-      p.closest_index = (int*)(S + o_cl); p.aim_idx = (int*)(S + o_aim); p.raw_speed = (float*)(S + o_raw);
-      d.mask = v.off_road_mask; d.ox = v.pose[0]; d.oy = v.pose[1]; d.ch = std::cos(v.pose[2]); d.sh = std::sin(v.pose[2]);
-      d.off_x = own_offset ? (double)(float)(v.H / 2.0) : 200.0; d.off_y = own_offset ? (double)(float)(v.W / 2.0) : 200.0;   // x gets H / 2: the reference's quirk (rift_hip.h)
-      d.col = (uint8_t*)(S + o_col); d.offr = (uint8_t*)(S + o_offr);
-      d.ret = returns ? returns + (size_t)(k0 + j) * Rb * M : (double*)(S + o_ret);       // straight to the caller's tensor when asked for
-      d.terms = terms ? terms + (size_t)(k0 + j) * Rb * M * 8 : nullptr;
-      d.adv = advantage + (size_t)(k0 + j) * Rb * M;
-      gmax = std::max(gmax, d.G); nmax = std::max(nmax, d.N);
-    }
-    const dim3 gy((unsigned)1, (unsigned)a.K);
-    hipLaunchKernelGGL(tick_multi_kernel<0>, dim3(cdiv(gmax * Ts, 128), a.K), dim3(128), 0, st, a);
-    if (nmax > 0) hipLaunchKernelGGL(tick_multi_kernel<1>, dim3(cdiv(nmax, 64), a.K), dim3(64), 0, st, a);
-    for (int j = 0; j < a.K; ++j) {
-      if (c->ro8) hipLaunchKernelGGL(rollout8_kernel, dim3(cdiv(a.d[j].G, 8)), dim3(64), (size_t)RIFT_RO_LDS_BYTES, st, a.d[j].ro);
-      else hipLaunchKernelGGL(rollout_kernel, dim3(cdiv(a.d[j].G, 64)), dim3(64), (size_t)RIFT_RO_LDS_BYTES, st, a.d[j].ro);
-    }
-    hipLaunchKernelGGL(tick_multi_kernel<2>, dim3(cdiv(gmax * TR, 256), a.K), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(tick_multi_kernel<3>, dim3(cdiv(gmax * Ts, 256), a.K), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(tick_multi_kernel<4>, dim3(cdiv(gmax * TR, 256), a.K), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(tick_multi_kernel<5>, dim3(cdiv(gmax, 4), a.K), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(tick_multi_kernel<6>, dim3(1, a.K), dim3(256), 0, st, a);
-    (void)gy;
-    HIPCHK(c, hipGetLastError());
-  }
-  return RIFT_OK;
-}
-
-int rift_group_advantage_tick(RiftCtx* c, const float* trajectory, int Rb, int Tfull, const RiftTickCBV* cbvs, int K,
-                              float* turn_buf, int32_t* turn_ptr, int32_t* turn_len, float* speed_buf, int32_t* speed_ptr, int32_t* speed_len,
-                              double gamma, double* advantage, void* stream) {
-  RiftEvalParams ev;
-  rift_eval_params_set_default(&ev);
-  ev.gamma = gamma;
-  return group_advantage_tick(c, trajectory, Rb, Tfull, cbvs, K, turn_buf, turn_ptr, turn_len, speed_buf, speed_ptr, speed_len, ev, false,
-                              advantage, nullptr, nullptr, stream);
-}
-
-int rift_group_advantage_tick_ex(RiftCtx* c, const float* trajectory, int Rb, int Tfull, const RiftTickCBV* cbvs, int K,
-                                 float* turn_buf, int32_t* turn_ptr, int32_t* turn_len, float* speed_buf, int32_t* speed_ptr, int32_t* speed_len,
-                                 const RiftEvalParams* params, double* advantage, double* returns, double* terms, void* stream) {
-  if (!c) return RIFT_ERR_ARG;
-  if (const char* why = rift_eval_params_refusal(params)) { c->err = std::string("rift_group_advantage_tick_ex: ") + why; return RIFT_ERR_ARG; }
-  return group_advantage_tick(c, trajectory, Rb, Tfull, cbvs, K, turn_buf, turn_ptr, turn_len, speed_buf, speed_ptr, speed_len, *params, true,
-                              advantage, returns, terms, stream);
-}
-
-// One rollout tick's decisions (rift_hip.h): every refusal is decided here, on the host, before anything is launched; then one wave per CBV
-// (control.h), RIFT_CTL_CHUNK descriptors per launch.  The logits of a row are held MAXPL per lane: dispatched as loss_kernel<MAXPL> is.
-int rift_control_tick(RiftCtx* c, const float* trajectory, const float* probability, const float* ref_free_trajectory, int Rb, int Tfull,
-                      const RiftControlCBV* cbvs, int K, int topk, int sample_interval, double* pid_state, int n_slots, double* decision,
-                      void* stream) {
-  if (!c) return RIFT_ERR_ARG;
-  auto refuse = [&](const char* why) { c->err = std::string("rift_control_tick: ") + why; return (int)RIFT_ERR_ARG; };
-  if (K < 0) return refuse("K < 0");
-  if (Rb < 1) return refuse("Rb < 1");
-  const long long G = (long long)Rb * 12;
-  if (topk < 1 || topk > G) return refuse("topk outside [1, Rb * 12]");
-  if (sample_interval < 1) return refuse("sample_interval < 1");
-  if (Tfull < 2 * (long long)sample_interval) return refuse("Tfull < 2 * sample_interval (the thinned path needs two points)");
-  if (G > 64 * 16) return refuse("Rb * 12 above 1024 candidates (16 logits per lane)");
-  if (n_slots < 0) return refuse("n_slots < 0");
-  if (K > 0 && (!trajectory || !probability || !cbvs || !pid_state || !decision)) return refuse("null pointer");
-  std::vector<int> slots((size_t)K);
-  for (int k = 0; k < K; ++k) {
-    if (cbvs[k].batch_index < 0) return refuse("batch_index < 0");
-    if (cbvs[k].slot < 0 || cbvs[k].slot >= n_slots) return refuse("slot outside [0, n_slots)");
-    slots[(size_t)k] = cbvs[k].slot;
-  }
-  std::sort(slots.begin(), slots.end());
-  if (std::adjacent_find(slots.begin(), slots.end()) != slots.end()) return refuse("two CBVs with the same slot");
-  c->err.clear();
-  if (K == 0) return RIFT_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  const hipStream_t st = (hipStream_t)stream;
-  for (int k0 = 0; k0 < K; k0 += RIFT_CTL_CHUNK) {
-    CtlArr a; memset(&a, 0, sizeof(a));
-    a.K = std::min(RIFT_CTL_CHUNK, K - k0); a.G = (int)G; a.Tfull = Tfull; a.topk = topk; a.interval = sample_interval;
-    for (int j = 0; j < a.K; ++j) {
-      const RiftControlCBV& v = cbvs[k0 + j];
-      CtlK& d = a.d[j];
-      d.traj = trajectory + (size_t)v.batch_index * (size_t)G * Tfull * 6;
-      d.prob = probability + (size_t)v.batch_index * (size_t)G;
-      d.rf = ref_free_trajectory ? ref_free_trajectory + (size_t)v.batch_index * Tfull * 4 : nullptr;
-      d.state = pid_state + (size_t)v.slot * RIFT_CTL_STATE;
-      d.dec = decision + (size_t)(k0 + j) * 8;
-      d.ox = v.x; d.oy = v.y; d.ch = std::cos(v.heading); d.sh = std::sin(v.heading); d.speed = v.speed;
-    }
-    if (G <= 64 * 2) hipLaunchKernelGGL(control_tick_kernel<2>, dim3(a.K), dim3(64), 0, st, a);
-    else if (G <= 64 * 4) hipLaunchKernelGGL(control_tick_kernel<4>, dim3(a.K), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(control_tick_kernel<16>, dim3(a.K), dim3(64), 0, st, a);
-    HIPCHK(c, hipGetLastError());
-  }
-  return RIFT_OK;
-}
-
-int rift_collate(RiftCtx* c, const RiftReplayArena* ar, const int32_t* scene_idx, int bs, int R_out,
-                 const RiftFeatureBatch* ob, float* out_old_logits, float* out_ref_logits, double* out_advantage,
-                 uint8_t* out_valid_mask, void* stream) {
-  if (!c || !ar || !scene_idx || !ob || bs <= 0 || R_out <= 0 || R_out > ar->Rcap) return RIFT_ERR_ARG;
-  // the arena's rows are stored padded to its capacities (ar->A, Mp, Rcap, S); the batch is padded to the dimensions of `ob`, which
-  // may be smaller (a host arena that grows by doubling keeps capacities above the largest stored scene): every ragged dimension
-  // leads its per-scene block, so the crop is a prefix copy
-  if (ob->A > ar->A || ob->Mp > ar->Mp || ob->S > ar->S || ob->A <= 0 || ob->T != ar->T) return RIFT_ERR_ARG;
-  const RiftFeatureBatch& s = ar->scenes;
-  const int A = ar->A, Mp = ar->Mp, Rc = ar->Rcap, S = ar->S, T = ar->T;
-  const int oA = ob->A, oMp = ob->Mp, oS = ob->S;
-  CollateP p; memset(&p, 0, sizeof(p));
-  int k = 0;
-  auto add = [&](const void* src, void* dst, long long src_bytes, long long dst_bytes) {
-    if (!src || !dst || dst_bytes <= 0) return;
-    p.src[k] = (const unsigned char*)src; p.dst[k] = (unsigned char*)dst; p.src_bytes[k] = (int)src_bytes; p.dst_bytes[k] = (int)dst_bytes; ++k;
-  };
-#define FIX(field, n_src, n_dst, per) add(s.field, (void*)ob->field, (long long)(n_src) * (per), (long long)(n_dst) * (per))
-  FIX(agent_position, A, oA, T * 8); FIX(agent_heading, A, oA, T * 4); FIX(agent_velocity, A, oA, T * 8);
-  FIX(agent_shape, A, oA, T * 8); FIX(agent_category, A, oA, 1); FIX(agent_valid_mask, A, oA, T);
-  FIX(map_point_position, Mp, oMp, 3 * 20 * 8); FIX(map_point_vector, Mp, oMp, 3 * 20 * 8);
-  FIX(map_point_orientation, Mp, oMp, 3 * 20 * 4); FIX(map_polygon_center, Mp, oMp, 12);
-  FIX(map_polygon_type, Mp, oMp, 1); FIX(map_polygon_on_route, Mp, oMp, 1); FIX(map_polygon_tl_status, Mp, oMp, 1);
-  FIX(map_polygon_has_speed_limit, Mp, oMp, 1); FIX(map_polygon_speed_limit, Mp, oMp, 4); FIX(map_valid_mask, Mp, oMp, 20);
-  FIX(static_position, S, oS, 8); FIX(static_heading, S, oS, 4); FIX(static_shape, S, oS, 8);
-  FIX(static_category, S, oS, 1); FIX(static_valid_mask, S, oS, 1); FIX(current_state, 1, 1, ar->cs_ld * 4);
-#undef FIX
-#define RAG(srcp, dstp, per_line) add((srcp), (void*)(dstp), (long long)Rc * (per_line), (long long)R_out * (per_line))
-  RAG(s.ref_position, ob->ref_position, 120 * 8); RAG(s.ref_vector, ob->ref_vector, 120 * 8);
-  RAG(s.ref_orientation, ob->ref_orientation, 120 * 4); RAG(s.ref_valid_mask, ob->ref_valid_mask, 120);
-  RAG(ar->old_group_logits, out_old_logits, 12 * 4); RAG(ar->ref_group_logits, out_ref_logits, 12 * 4);
-  RAG(ar->group_advantage, out_advantage, 12 * 8); RAG(ar->group_valid_mask, out_valid_mask, 12);
-#undef RAG
-  p.nt = k;
-  hipLaunchKernelGGL(collate_kernel, dim3(bs, k), dim3(256), 0, (hipStream_t)stream, p, scene_idx);
-  HIPCHK(c, hipGetLastError());
   return RIFT_OK;
 }
 

@@ -3,37 +3,11 @@
 // Row softmax / LayerNorm reductions are wavefront shuffles; objective sums are fp64
 // (the reference promotes fp64 advantage x fp32 ratio, rift_trainer.py:160-178).
 #pragma once
-#include "common.h"
+#include "lanes.h"
 
-namespace RIFT_NS {
+namespace rift {
 
 enum { LOSS_RIFT = 0, LOSS_GRPO = 1, LOSS_PPO = 2, LOSS_REINFORCE = 3, LOSS_SFT = 4 };
-
-// pi_head tail (mlp_layer.py:8-13 after the first Linear): per row  LN(128) -> ReLU -> dot(w2) + b2.
-// One wave per row.  Writes raw logits and the -1e6-masked `probability` (pluto_model.py:203).
-__global__ void pi_tail_kernel(const float* __restrict__ Hpi /*[rows][128]*/, int rows, int M,
-                               const float* __restrict__ g, const float* __restrict__ be,
-                               const float* __restrict__ w2, const float* __restrict__ b2,
-                               const uint8_t* __restrict__ r_kpm /*[rows/M]*/, float eps,
-                               float* __restrict__ prob /*[rows]*/, int* __restrict__ nonfinite) {
-  const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  const float h0 = Hpi[(size_t)row * 128 + lane], h1 = Hpi[(size_t)row * 128 + 64 + lane];
-  const float mean = wave_sum(h0 + h1) * (1.f / 128.f);
-  const float d0 = h0 - mean, d1 = h1 - mean;
-  const float rstd = rsqrtf(wave_sum(d0 * d0 + d1 * d1) * (1.f / 128.f) + eps);
-  const float a0 = fmaxf(d0 * rstd * g[lane] + be[lane], 0.f);
-  const float a1 = fmaxf(d1 * rstd * g[lane + 64] + be[lane + 64], 0.f);
-  const float z = wave_sum(a0 * w2[lane] + a1 * w2[lane + 64]) + b2[0];
-  // a NaN / Inf in the decoder queries (the reference's assert, planning_decoder.py:175) reaches this hidden row; test the row itself
-  // (x * 0 is NaN for NaN and +-Inf) -- the ReLU's fmaxf would swallow a NaN before it reached the logit
-  const float bad = wave_sum(h0 * 0.f + h1 * 0.f);
-  if (lane == 0) {
-    prob[row] = r_kpm[row / M] ? -1e6f : z;
-    if (nonfinite && bad != 0.f) atomicOr(nonfinite, 1);
-  }
-}
 
 struct LossP {
   int kind, bs, G, M;                 // G = R*M candidates per scene
@@ -714,4 +688,4 @@ __global__ __launch_bounds__(1024) void update_tail_kernel(const float* __restri
   }
 }
 
-}  // namespace RIFT_NS
+}  // namespace rift

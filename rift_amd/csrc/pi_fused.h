@@ -11,6 +11,32 @@
 
 namespace RIFT_NS {
 
+// pi_head tail (mlp_layer.py:8-13 after the first Linear): per row  LN(128) -> ReLU -> dot(w2) + b2.
+// One wave per row.  Writes raw logits and the -1e6-masked `probability` (pluto_model.py:203).
+__global__ void pi_tail_kernel(const float* __restrict__ Hpi /*[rows][128]*/, int rows, int M,
+                               const float* __restrict__ g, const float* __restrict__ be,
+                               const float* __restrict__ w2, const float* __restrict__ b2,
+                               const uint8_t* __restrict__ r_kpm /*[rows/M]*/, float eps,
+                               float* __restrict__ prob /*[rows]*/, int* __restrict__ nonfinite) {
+  const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const float h0 = Hpi[(size_t)row * 128 + lane], h1 = Hpi[(size_t)row * 128 + 64 + lane];
+  const float mean = wave_sum(h0 + h1) * (1.f / 128.f);
+  const float d0 = h0 - mean, d1 = h1 - mean;
+  const float rstd = rsqrtf(wave_sum(d0 * d0 + d1 * d1) * (1.f / 128.f) + eps);
+  const float a0 = fmaxf(d0 * rstd * g[lane] + be[lane], 0.f);
+  const float a1 = fmaxf(d1 * rstd * g[lane + 64] + be[lane + 64], 0.f);
+  const float z = wave_sum(a0 * w2[lane] + a1 * w2[lane + 64]) + b2[0];
+  // a NaN / Inf in the decoder queries (the reference's assert, planning_decoder.py:175) reaches this hidden row; test the row itself
+  // (x * 0 is NaN for NaN and +-Inf) -- the ReLU's fmaxf would swallow a NaN before it reached the logit
+  const float bad = wave_sum(h0 * 0.f + h1 * 0.f);
+  if (lane == 0) {
+    prob[row] = r_kpm[row / M] ? -1e6f : z;
+    if (nonfinite && bad != 0.f) atomicOr(nonfinite, 1);
+  }
+}
+
 struct PiFwdP {
   const float* Q; int rows, rows_per_scene;      // (rows, 128) decoder output
   const unsigned short* wq; const float* bq;     // cat_x_proj columns 0:128, fragment-major bf16 [128][128], and the bias

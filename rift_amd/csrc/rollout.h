@@ -6,9 +6,9 @@
 // wavefronts; the smoothed kinematics and box corners of the 80 frames are a second kernel, one thread per
 // (candidate, frame).  Replaces 79 x ~40 tiny torch launches per CBV per tick.
 #pragma once
-#include "common.h"
+#include "lanes.h"
 
-namespace RIFT_NS {
+namespace rift {
 
 // ---- reference-line deviation: one thread per (candidate, frame), ragged reference lines ----
 __device__ __forceinline__ void ref_line_info_body(const float* __restrict__ traj /*(G,Tfull,6)*/, int G, int Tfull, int Ts, int M,
@@ -340,4 +340,4 @@ __device__ __forceinline__ void rollout_kinematics_body(const RolloutP& p) {
 }
 __global__ __launch_bounds__(256) void rollout_kinematics_kernel(RolloutP p) { rollout_kinematics_body(p); }
 
-}  // namespace RIFT_NS
+}  // namespace rift

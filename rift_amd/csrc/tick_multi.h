@@ -1,4 +1,4 @@
-// The rollout tick's per-CBV kernels with the CBV as a second grid dimension (rift_group_advantage_tick, engine.hip): everything of the
+// The rollout tick's per-CBV kernels with the CBV as a second grid dimension (rift_group_advantage_tick, shared.hip): everything of the
 // evaluation chain except the candidate rollout itself is independent between the CBVs of a tick, so one launch per STAGE serves all of
 // them -- reference-line deviations and neighbour forecasts ahead of the rollouts, kinematics / collision / off-road flags, returns and
 // z-scores behind them.  The rollouts stay one launch per CBV: CBV k + 1 starts from the PID state CBV k leaves (the reference shares one
@@ -7,7 +7,7 @@
 #include "adv.h"
 #include "rollout.h"
 
-namespace RIFT_NS {
+namespace rift {
 
 #define RIFT_TICK_CHUNK 8                        // CBVs per launch (the descriptors travel as kernel arguments)
 
@@ -58,4 +58,4 @@ __global__ void tick_multi_kernel(const TickArr a) {
   if (STAGE == 6) group_zscore_body(d.ret, 1, d.G, d.adv);
 }
 
-}  // namespace RIFT_NS
+}  // namespace rift

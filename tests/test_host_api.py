@@ -61,6 +61,57 @@ def test_trampolines_are_generated_from_the_header():
     assert lib.rift_ctx_create_ex(0, 7, ctypes.byref(ctx)) == -1
 
 
+def test_format_free_entries_are_defined_once_and_the_context_types_cannot_collide():
+    """The objects of the library (csrc/shared.hip is compiled once, csrc/engine.hip once per operand format), read with nm:
+    (a) the two engine builds define no common symbol of a context type -- each build's context is a type of its own namespace, so no
+        destructor or member function of one can be linked in place of the other's;
+    (b) every operand-format-free entry (tools/gen/abi_trampolines.py: FORMAT_FREE) is defined in shared.o and in neither engine object;
+    (c) the device-memory hooks are defined in shared.o only;
+    (d) the library exports the `rift_*` symbols of tests/golden/exported_symbols.txt (the functions include/rift_hip.h declares, by the
+        generator's own parse, and one table per engine build), no more and no fewer."""
+    import importlib.util
+    import shutil
+    import subprocess
+    from rift_amd import build
+    build.build()
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    nm = shutil.which("llvm-nm") or next((p for p in ("/opt/rocm/llvm/bin/llvm-nm", "/opt/rocm/lib/llvm/bin/llvm-nm") if os.path.exists(p)), None) \
+        or shutil.which("nm")
+    if nm is None:
+        pytest.skip("no llvm-nm / nm")
+    objs = {n: os.path.join(build.OBJ, n + ".o") for n in ("engine_bf", "engine_hf", "shared")}
+    if not all(os.path.exists(p) for p in objs.values()):          # (a library that was up to date, its objects cleaned away)
+        build.build(force=True)
+
+    def defined(path, flags=("-C",), kinds="TWV"):
+        out = subprocess.check_output([nm, "--defined-only", *flags, path], text=True)
+        return {line.split(None, 2)[2] for line in out.splitlines() if len(line.split(None, 2)) == 3 and line.split(None, 2)[1] in kinds}
+
+    sym = {n: defined(p) for n, p in objs.items()}
+    # (a)
+    both = {s for s in sym["engine_bf"] & sym["engine_hf"] if "RiftCtx::" in s or "Ctx::~" in s}
+    assert not both, both
+    assert any(s.startswith("rift_bf::Ctx::~Ctx") for s in sym["engine_bf"]) and any(s.startswith("rift_hf::Ctx::~Ctx") for s in sym["engine_hf"])
+    # (b), (c)
+    spec = importlib.util.spec_from_file_location("abi_trampolines", os.path.join(repo, "tools", "gen", "abi_trampolines.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    assert len(gen.FORMAT_FREE) == 29 and not set(gen.FORMAT_FREE) & set(gen.SPECIAL) and not set(gen.FORMAT_FREE) & set(gen.NO_CTX)
+
+    def names(symbols):          # "rift::abi::rift_gae(RiftCtx*, ...)" -> "rift_gae"
+        return {s.split("(")[0].split("::")[-1] for s in symbols if "::abi::rift_" in s.split("(")[0]} | {s.split("(")[0] for s in symbols if s.startswith("rift_dev_")}
+    for name in gen.FORMAT_FREE + ("rift_dev_alloc", "rift_dev_free"):
+        assert name in names(sym["shared"]), f"{name} is not defined in shared.o"
+        assert name not in names(sym["engine_bf"]) and name not in names(sym["engine_hf"]), f"{name} is defined in an engine build"
+    assert all(s.split("(")[0].startswith("rift::abi::") for s in sym["shared"] if "::abi::rift_" in s.split("(")[0])
+    # (d)
+    exported = {s for s in defined(build.LIB, ("-D",), "TWVRDB") if re.fullmatch(r"rift_[a-z0-9_]+", s)}      # (mangled names: C symbols only)
+    golden = set(open(os.path.join(repo, "tests", "golden", "exported_symbols.txt")).read().split())
+    declared = {name for _, name, _ in gen.declarations(open(gen.HEADER).read())}
+    assert golden == declared | {"rift_vtable_bf16", "rift_vtable_fp16"}
+    assert exported == golden, (sorted(exported - golden), sorted(golden - exported))
+
+
 def test_bench_kernel_labels_resolve_in_the_committed_counter_tables():
     """bench.py's roofline object reads HBM traffic and MFMA counters of the dominant kernel from the newest committed PMC passes
     (profiles/rNN_pmc_*): every kernel the newest committed bench line lists must resolve there, so that a renamed kernel shows up here

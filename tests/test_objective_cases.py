@@ -43,7 +43,7 @@ def test_batches_have_the_shapes_the_kernel_dispatches_on(forwards):
     for name in NAMES:
         r_pad, prob, _, _ = forwards[name, "model"]
         bs, R, M = prob.shape
-        maxpl = 2 if R * M <= 128 else (4 if R * M <= 256 else 16)              # engine.hip rift_loss_backward
+        maxpl = 2 if R * M <= 128 else (4 if R * M <= 256 else 16)              # shared.hip rift_loss_backward
         assert (bs, R * M, maxpl) == want[name]
         assert tuple((~r_pad).sum(1).tolist()) == O.BATCHES[name]
         assert bool((prob[r_pad] == -1e6).all()) and bool(torch.isfinite(prob).all())

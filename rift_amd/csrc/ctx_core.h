@@ -32,7 +32,8 @@ struct RiftCtxCore {
   std::vector<Rec> prof_recs;
   int poison_lds = -1;                   // RIFT_POISON_LDS diagnostic (see lds_poison_kernel)
   struct { std::string delay_label; long long delay_ticks = 0; } dg;      // RIFT_DELAY diagnostic (see delay_kernel)
-  std::unordered_map<std::string, rift::Param> params;
+  std::unordered_map<std::string, rift::Param> params;      // written by rift_model_load only
+  struct PiHead { const float *w0 = nullptr, *b0 = nullptr, *ln_g = nullptr, *ln_b = nullptr, *w3 = nullptr, *b3 = nullptr; } pi;   // planning_decoder.pi_head.mlp.{0,1,3}: the trainable tensors, read LIVE through these pointers (resolved at load)
   bool loaded = false;
   // state of the last forward, consumed by rift_loss_backward
   float* last_qfinal = nullptr; float* last_hpi = nullptr; float* last_prob = nullptr;

@@ -55,8 +55,8 @@ void launch_gemm(Ctx* c, const char* label, void (*kern)(KArgs...), dim3 grid, d
 // Weight-only products (mode embeddings through q_proj / m2m in-projection, the ego query projection): input
 // independent, so they are computed by the first forward after rift_model_load and kept (per precision mode).
 // Returns the buffer and whether the caller must fill it now.
-float* wconst_get(Ctx* c, const std::string& key, size_t n, bool fp32, bool* fill) {
-  Ctx::WConst& w = c->wconst[key + (fp32 ? "#32" : "#16")];
+float* wconst_get(Ctx* c, Ctx::WConst& slot, size_t n, bool fp32, bool* fill) {
+  Ctx::WConst::V& w = slot.v[fp32 ? 0 : 1];
   if (w.p.reserve(n) != 0) { *fill = false; return nullptr; }
   *fill = !w.ready && !c->dry;
   if (!c->dry) w.ready = true;
@@ -330,37 +330,39 @@ void dp_exchange(Fwd& f, long long n) {
   if (with_kpm) launch(c, "dp_kpm_read_kernel", dp_kpm_read_kernel, dim3(cdiv(f.kb, 256)), dim3(256), 0, (const double*)c->dp.xchg, f.kb, f.g_rkpm);
 }
 
-void layernorm(Fwd& f, const float* X, int ldx, float* Y, int ldy, int rows, int C, const std::string& name, int relu = 0) {
+void layernorm(Fwd& f, const float* X, int ldx, float* Y, int ldy, int rows, int C, const LayerNormW& ln, int relu = 0) {
   Ctx* c = f.c;
-  launch(c, "layernorm_kernel", layernorm_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, X, ldx, Y, ldy, rows, C, fptr(c, name + ".weight"),
-         fptr(c, name + ".bias"), 1e-5f, relu);
+  launch(c, "layernorm_kernel", layernorm_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, X, ldx, Y, ldy, rows, C, ln.g,
+         ln.b, 1e-5f, relu);
 }
 
 // FourierEmbedding (fourier_embedding.py:45-55): in (rows, D) -> out (rows, 128)
-FourierP fourier_desc(Fwd& f, const float* in, int in_ld, int rows, int D, const std::string& p, int wrap_dim, float* add_to) {
+FourierP fourier_desc(Fwd& f, const float* in, int in_ld, int rows, const FourierW& p, int wrap_dim, float* add_to) {
   Ctx* c = f.c;
+  const int D = p.D;
   FourierP q; memset(&q, 0, sizeof(q));
-  q.in = in; q.in_ld = in_ld; q.rows = rows; q.D = D; q.wrap_dim = wrap_dim; q.freqs = fptr(c, p + ".freqs.weight");
+  q.in = in; q.in_ld = in_ld; q.rows = rows; q.D = D; q.wrap_dim = wrap_dim; q.freqs = p.freqs;
   for (int d = 0; d < D; ++d) {
-    const std::string m = p + ".mlps." + std::to_string(d);
-    const PW &lo = c->pw[m + ".0.lo"], &last = c->pw[m + ".0.last"], &w3 = c->pw[m + ".3"];
+    const FourierW::Dim& m = p.mlps[d];
+    const PW &lo = *m.lo, &last = *m.last, &w3 = *m.l3;
     q.w0[d] = lo.bf.get(); q.b0[d] = lo.bias; q.wl[d] = last.f32.get(); q.wl_ld = last.Kp;
-    q.lng[d] = fptr(c, m + ".1.weight"); q.lnb[d] = fptr(c, m + ".1.bias");
+    q.lng[d] = m.ln.g; q.lnb[d] = m.ln.b;
     q.w3[d] = w3.bf.get(); q.b3[d] = w3.bias;
   }
-  q.og = fptr(c, p + ".to_out.0.weight"); q.ob = fptr(c, p + ".to_out.0.bias");
-  q.wo = c->pw[p + ".to_out.2"].bf.get(); q.bo = c->pw[p + ".to_out.2"].bias;
+  q.og = p.out_ln.g; q.ob = p.out_ln.b;
+  q.wo = p.out->bf.get(); q.bo = p.out->bias;
   q.Y = add_to ? add_to : A_alloc<float>(c, (size_t)rows * 128);
   q.accumulate = add_to ? 1 : 0;
   return q;
 }
 
 // add_to != nullptr: the embedding is added into that (rows, 128) buffer, which is returned
-float* fourier(Fwd& f, const float* in, int in_ld, int rows, int D, const std::string& p, int wrap_dim, float* add_to = nullptr) {
+float* fourier(Fwd& f, const float* in, int in_ld, int rows, const FourierW& p, int wrap_dim, float* add_to = nullptr) {
   Ctx* c = f.c;
+  const int D = p.D;
   if (!f.fp32 && c->sw.fo_fused && D <= 3) {
     FourierP3 q3; memset(&q3, 0, sizeof(q3));
-    q3.e[0] = fourier_desc(f, in, in_ld, rows, D, p, wrap_dim, add_to);
+    q3.e[0] = fourier_desc(f, in, in_ld, rows, p, wrap_dim, add_to);
     q3.nblk[0] = cdiv(rows, FO_ROWS); q3.count = 1;
     c->prof_flops = 2.0 * rows * 128.0 * (D * (129.0 + 128.0) + 128.0);
     launch(c, "fourier_fused_kernel", fourier_fused_kernel, dim3(q3.nblk[0]), dim3(256), (size_t)FO_LDS, q3);
@@ -368,22 +370,22 @@ float* fourier(Fwd& f, const float* in, int in_ld, int rows, int D, const std::s
   }
   float* FF = A_alloc<float>(c, (size_t)D * rows * 129);
   launch(c, "fourier_feature_kernel", fourier_feature_kernel, dim3(cdiv((long long)D * rows * 65, 256)), dim3(256), 0, in, in_ld, rows, D,
-         fptr(c, p + ".freqs.weight"), wrap_dim, FF);
+         p.freqs, wrap_dim, FF);
   float* T1 = A_alloc<float>(c, (size_t)rows * 128);
   float* acc = A_alloc<float>(c, (size_t)rows * 128);
   for (int d = 0; d < D; ++d) {
-    const std::string m = p + ".mlps." + std::to_string(d);
-    GemmP g = mk(FF + (size_t)d * rows * 129, 129, rows, c->pw[m + ".0"], T1, 128);
-    gemm(c, g, c->pw[m + ".0"], f.fp32);
-    GemmP g2 = mk(T1, 128, rows, c->pw[m + ".3"], acc, 128);
-    g2.pro = PRO_LN; g2.pg = fptr(c, m + ".1.weight"); g2.pb = fptr(c, m + ".1.bias"); g2.pro_relu = 1;
+    const FourierW::Dim& m = p.mlps[d];
+    GemmP g = mk(FF + (size_t)d * rows * 129, 129, rows, *m.l0, T1, 128);
+    gemm(c, g, *m.l0, f.fp32);
+    GemmP g2 = mk(T1, 128, rows, *m.l3, acc, 128);
+    g2.pro = PRO_LN; g2.pg = m.ln.g; g2.pb = m.ln.b; g2.pro_relu = 1;
     if (d > 0) { g2.residual = acc; g2.ldr = 128; }
-    gemm(c, g2, c->pw[m + ".3"], f.fp32);
+    gemm(c, g2, *m.l3, f.fp32);
   }
   float* out = A_alloc<float>(c, (size_t)rows * 128);
-  GemmP g3 = mk(acc, 128, rows, c->pw[p + ".to_out.2"], out, 128);
-  g3.pro = PRO_LN; g3.pg = fptr(c, p + ".to_out.0.weight"); g3.pb = fptr(c, p + ".to_out.0.bias"); g3.pro_relu = 1;
-  gemm(c, g3, c->pw[p + ".to_out.2"], f.fp32);
+  GemmP g3 = mk(acc, 128, rows, *p.out, out, 128);
+  g3.pro = PRO_LN; g3.pg = p.out_ln.g; g3.pb = p.out_ln.b; g3.pro_relu = 1;
+  gemm(c, g3, *p.out, f.fp32);
   if (add_to) {
     launch(c, "add_inplace_kernel", add_inplace_kernel, dim3(cdiv((long long)rows * 128, 256)), dim3(256), 0, add_to, (const float*)out, (size_t)rows * 128);
     return add_to;
@@ -392,7 +394,7 @@ float* fourier(Fwd& f, const float* in, int in_ld, int rows, int D, const std::s
 }
 
 // BatchNorm1d folded to an affine (scale, shift) for the next GEMM prologue.
-void batchnorm_affine(Fwd& f, const float* X, int rows, int C, const uint8_t* valid, const std::string& name,
+void batchnorm_affine(Fwd& f, const float* X, int rows, int C, const uint8_t* valid, const BatchNormW& bn,
                       float** scale, float** shift) {
   Ctx* c = f.c;
   *scale = A_alloc<float>(c, C); *shift = A_alloc<float>(c, C);
@@ -401,13 +403,12 @@ void batchnorm_affine(Fwd& f, const float* X, int rows, int C, const uint8_t* va
   double* part = A_alloc<double>(c, (size_t)nblk * 2 * C);
   int* cnt = A_alloc<int>(c, nblk);
   if (f.train) launch(c, "bn_partial_kernel", bn_partial_kernel, dim3(nblk), dim3(C), 0, X, C, rows, C, valid, part, cnt, rows_per_blk);
-  const Param* nb = find(c, name + ".num_batches_tracked");
   const bool dpx = f.dp && f.train;      // data parallel: batch statistics over the GLOBAL minibatch (sums all-reduced between two launches)
   double* sums = dpx ? c->dp.xchg + f.kb : nullptr;
   for (int mode = dpx ? 1 : 0; mode <= (dpx ? 2 : 0); ++mode) {
     launch(c, "bn_finalize_kernel", bn_finalize_kernel, dim3(cdiv(C, 4)), dim3(256), 0, (const double*)part, (const int*)cnt, nblk, C,
-           fptr(c, name + ".weight"), fptr(c, name + ".bias"), (float*)fptr(c, name + ".running_mean"),
-           (float*)fptr(c, name + ".running_var"), nb ? (long long*)nb->data : (long long*)nullptr, f.train ? 1 : 0,
+           bn.g, bn.b, bn.mean,
+           bn.var, bn.num_batches, f.train ? 1 : 0,
            f.bn_update ? 1 : 0, 1e-5f, *scale, *shift, sums, mode);
     if (mode == 1) dp_exchange(f, 2 * C + 1);
   }
@@ -415,13 +416,12 @@ void batchnorm_affine(Fwd& f, const float* X, int rows, int C, const uint8_t* va
 
 // The two PointsEncoders (map polygons 10 -> 128 with 20 points, reference lines 6 -> 128 with 120 points) in the fused
 // three-pass form (pe_fused.h), side by side: five launches for both (statistics, BN finalize, mid, BN finalize, out).
-static void pe_fill(Fwd& f, PeP& q, const float* F, int Cin, int groups, int n, const uint8_t* valid, const std::string& p) {
+static void pe_fill(Fwd& f, PeP& q, const float* F, int Cin, int groups, int n, const uint8_t* valid, const PointsEncoderW& p) {
   Ctx* c = f.c;
   memset(&q, 0, sizeof(q));
   const int rows = groups * n;
   q.F = F; q.Cin = Cin; q.valid = valid; q.rows = rows; q.ntiles = cdiv(rows, 120);
-  const PW &w1 = c->pw[p + ".first_mlp.0"], &w2 = c->pw[p + ".first_mlp.3"], &w3a = c->pw[p + ".second_mlp.0.feat"],
-           &w3b = c->pw[p + ".second_mlp.0.pool"], &w4 = c->pw[p + ".second_mlp.3"];
+  const PW &w1 = *p.first0, &w2 = *p.first3, &w3a = *p.feat, &w3b = *p.pool, &w4 = *p.second3;
   q.w1 = w1.bf.get(); q.w2 = w2.bf.get(); q.w3a = w3a.bf.get();
   q.w3b = w3b.bf.get(); q.w4 = w4.bf.get();
   q.b1 = w1.bias; q.b2 = w2.bias; q.b3 = w3a.bias; q.b4 = w4.bias;
@@ -436,19 +436,18 @@ static void pe_fill(Fwd& f, PeP& q, const float* F, int Cin, int groups, int n, 
   { if (c->sw.pe_ts == n) { q.ts = A_alloc<long long>(c, 64); q.ts_tile = 0; tap(c, "pe_ts", (float*)q.ts, 128); } }
 }
 
-static BnFinP bn_fin(Ctx* c, const PeP& q, const std::string& name, int C, const float* part, const float* sc, const float* sh,
+static BnFinP bn_fin(const PeP& q, const BatchNormW& bn, int C, const float* part, const float* sc, const float* sh,
                      double* sums = nullptr, int sums_mode = 0) {
   BnFinP b; memset(&b, 0, sizeof(b));
   b.sums = sums; b.sums_mode = sums_mode;
-  const Param* nb = find(c, name + ".num_batches_tracked");
-  b.part = part; b.cnt = q.cnt; b.nblk = q.ntiles; b.C = C; b.gamma = fptr(c, name + ".weight"); b.beta = fptr(c, name + ".bias");
-  b.running_mean = (float*)fptr(c, name + ".running_mean"); b.running_var = (float*)fptr(c, name + ".running_var");
-  b.num_batches = nb ? (long long*)nb->data : nullptr; b.scale = (float*)sc; b.shift = (float*)sh;
+  b.part = part; b.cnt = q.cnt; b.nblk = q.ntiles; b.C = C; b.gamma = bn.g; b.beta = bn.b;
+  b.running_mean = bn.mean; b.running_var = bn.var;
+  b.num_batches = bn.num_batches; b.scale = (float*)sc; b.shift = (float*)sh;
   return b;
 }
 
-void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, const std::string& pm, const float* Fr, int gr,
-                         const uint8_t* vr, const std::string& pr, float** out_m, float** out_r) {
+void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, const PointsEncoderW& pm, const float* Fr, int gr,
+                         const uint8_t* vr, const PointsEncoderW& pr, float** out_m, float** out_r) {
   Ctx* c = f.c;
   PeP2 q;
   pe_fill(f, q.a, Fm, 10, gm, 20, vm, pm);
@@ -503,8 +502,8 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
   }
   const bool lvblock = live || packb;       // the extra block of the BatchNorm-1 finalize launch
   for (int mode = dpx ? 1 : 0; mode <= (dpx ? 2 : 0); ++mode) {
-    BnFinP f1a = bn_fin(c, q.a, pm + ".first_mlp.1", 128, q.a.part1, q.a.s1, q.a.t1, xs, mode);
-    BnFinP f1b = bn_fin(c, q.b, pr + ".first_mlp.1", 128, q.b.part1, q.b.s1, q.b.t1, xs ? xs + 257 : nullptr, mode);
+    BnFinP f1a = bn_fin(q.a, pm.bn1, 128, q.a.part1, q.a.s1, q.a.t1, xs, mode);
+    BnFinP f1b = bn_fin(q.b, pr.bn1, 128, q.b.part1, q.b.s1, q.b.t1, xs ? xs + 257 : nullptr, mode);
     if (stats_p) { f1a.part = q.a.part1w; f1a.cnt = q.a.cnt1w; f1a.nblk = q.a.nwg1; f1b.part = q.b.part1w; f1b.cnt = q.b.cnt1w; f1b.nblk = q.b.nwg1; }
     const bool with_lv = lvblock && mode == (dpx ? 2 : 0);
     PeLiveP none; memset(&none, 0, sizeof(none));
@@ -535,12 +534,12 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
     w.dbg = c->sw.pew_dbg;
     { if (c->sw.pew_ts) { w.ts = A_alloc<long long>(c, 128); tap(c, "pew_ts", (float*)w.ts, 256); } }
     launch_call(c, "pe_w_kernel", [&] { pew_launch(w, grid, c->stream); });
-    fa = bn_fin(c, q.a, pm + ".second_mlp.1", 256, w.a.part2, q.a.s2, q.a.t2, xs, 0); fa.cnt = w.a.cnt2; fa.nblk = nwg[0]; fa.nblk_dev = lvblock ? lv.hdr + 2 : nullptr;
-    fb = bn_fin(c, q.b, pr + ".second_mlp.1", 256, w.b.part2, q.b.s2, q.b.t2, xs ? xs + 513 : nullptr, 0); fb.cnt = w.b.cnt2; fb.nblk = nwg[1]; fb.nblk_dev = lvblock ? lv.hdr + 3 : nullptr;
+    fa = bn_fin(q.a, pm.bn2, 256, w.a.part2, q.a.s2, q.a.t2, xs, 0); fa.cnt = w.a.cnt2; fa.nblk = nwg[0]; fa.nblk_dev = lvblock ? lv.hdr + 2 : nullptr;
+    fb = bn_fin(q.b, pr.bn2, 256, w.b.part2, q.b.s2, q.b.t2, xs ? xs + 513 : nullptr, 0); fb.cnt = w.b.cnt2; fb.nblk = nwg[1]; fb.nblk_dev = lvblock ? lv.hdr + 3 : nullptr;
   } else {
     launch(c, "pe_mid_kernel", pe_mid_kernel, dim3(nt), dim3(512), (size_t)PE_MID_LDS, q);
-    fa = bn_fin(c, q.a, pm + ".second_mlp.1", 256, q.a.part2, q.a.s2, q.a.t2, xs, 0);
-    fb = bn_fin(c, q.b, pr + ".second_mlp.1", 256, q.b.part2, q.b.s2, q.b.t2, xs ? xs + 513 : nullptr, 0);
+    fa = bn_fin(q.a, pm.bn2, 256, q.a.part2, q.a.s2, q.a.t2, xs, 0);
+    fb = bn_fin(q.b, pr.bn2, 256, q.b.part2, q.b.s2, q.b.t2, xs ? xs + 513 : nullptr, 0);
   }
   for (int mode = dpx ? 1 : 0; mode <= (dpx ? 2 : 0); ++mode) {
     fa.sums_mode = mode; fb.sums_mode = mode;
@@ -554,32 +553,32 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
 }
 
 // PointsEncoder (embedding.py:271-296): F (groups*n, Cin) -> (groups, 128)
-float* points_encoder(Fwd& f, const float* F, int Cin, int groups, int n, const uint8_t* valid, const std::string& p) {
+float* points_encoder(Fwd& f, const float* F, int Cin, int groups, int n, const uint8_t* valid, const PointsEncoderW& p) {
   Ctx* c = f.c;
   const int rows = groups * n;
   float* H1 = A_alloc<float>(c, (size_t)rows * 128);
-  gemm(c, mk(F, Cin, rows, c->pw[p + ".first_mlp.0"], H1, 128), c->pw[p + ".first_mlp.0"], f.fp32);
+  gemm(c, mk(F, Cin, rows, *p.first0, H1, 128), *p.first0, f.fp32);
   float *s1, *t1;
-  batchnorm_affine(f, H1, rows, 128, valid, p + ".first_mlp.1", &s1, &t1);
+  batchnorm_affine(f, H1, rows, 128, valid, p.bn1, &s1, &t1);
   float* F256 = A_alloc<float>(c, (size_t)rows * 256);
-  GemmP g = mk(H1, 128, rows, c->pw[p + ".first_mlp.3"], F256, 256);
+  GemmP g = mk(H1, 128, rows, *p.first3, F256, 256);
   g.pro = PRO_AFFINE; g.pg = s1; g.pb = t1; g.pro_relu = 1;
-  gemm(c, g, c->pw[p + ".first_mlp.3"], f.fp32);
+  gemm(c, g, *p.first3, f.fp32);
   float* pooled = A_alloc<float>(c, (size_t)groups * 256);
   launch(c, "masked_maxpool_kernel", masked_maxpool_kernel, dim3(cdiv((long long)groups * 256, 256)), dim3(256), 0, (const float*)F256, 256, groups, n, 256,
          valid, pooled);
   float* G1 = A_alloc<float>(c, (size_t)groups * 256);
-  gemm(c, mk(pooled, 256, groups, c->pw[p + ".second_mlp.0.pool"], G1, 256), c->pw[p + ".second_mlp.0.pool"], f.fp32);
+  gemm(c, mk(pooled, 256, groups, *p.pool, G1, 256), *p.pool, f.fp32);
   float* H2 = A_alloc<float>(c, (size_t)rows * 256);
-  GemmP g2 = mk(F256, 256, rows, c->pw[p + ".second_mlp.0.feat"], H2, 256);
+  GemmP g2 = mk(F256, 256, rows, *p.feat, H2, 256);
   g2.gbias = G1; g2.gb_div = n; g2.gb_mod = 0;
-  gemm(c, g2, c->pw[p + ".second_mlp.0.feat"], f.fp32);
+  gemm(c, g2, *p.feat, f.fp32);
   float *s2, *t2;
-  batchnorm_affine(f, H2, rows, 256, valid, p + ".second_mlp.1", &s2, &t2);
+  batchnorm_affine(f, H2, rows, 256, valid, p.bn2, &s2, &t2);
   float* O = A_alloc<float>(c, (size_t)rows * 128);
-  GemmP g3 = mk(H2, 256, rows, c->pw[p + ".second_mlp.3"], O, 128);
+  GemmP g3 = mk(H2, 256, rows, *p.second3, O, 128);
   g3.pro = PRO_AFFINE; g3.pg = s2; g3.pb = t2; g3.pro_relu = 1;
-  gemm(c, g3, c->pw[p + ".second_mlp.3"], f.fp32);
+  gemm(c, g3, *p.second3, f.fp32);
   float* out = A_alloc<float>(c, (size_t)groups * 128);
   launch(c, "masked_maxpool_kernel", masked_maxpool_kernel, dim3(cdiv((long long)groups * 128, 256)), dim3(256), 0, (const float*)O, 128, groups, n, 128,
          valid, out);
@@ -608,53 +607,53 @@ void run_mha(Ctx* c, const MhaP& p, bool fp32) {
 }
 
 // NAT block (embedding.py:196-202) on X (rows, C) in place
-void nat_layer(Fwd& f, float* X, int rows, int C, int H, int ksz, int L, const std::string& p, float droppath) {
+void nat_layer(Fwd& f, float* X, int rows, int C, int H, int ksz, int L, const NatBlockW& p, float droppath) {
   Ctx* c = f.c;
   float* QKV = A_alloc<float>(c, (size_t)rows * 3 * C);
-  GemmP g = mk(X, C, rows, c->pw[p + ".attn.qkv"], QKV, 3 * C);
-  g.pro = PRO_LN; g.pg = fptr(c, p + ".norm1.weight"); g.pb = fptr(c, p + ".norm1.bias");
-  gemm(c, g, c->pw[p + ".attn.qkv"], f.fp32);
+  GemmP g = mk(X, C, rows, *p.qkv, QKV, 3 * C);
+  g.pro = PRO_LN; g.pg = p.norm1.g; g.pb = p.norm1.b;
+  gemm(c, g, *p.qkv, f.fp32);
   float* AO = A_alloc<float>(c, (size_t)rows * C);
   const int nthreads = rows * H;
-  if (ksz == 3) launch(c, "nat_attention_kernel", nat_attention_kernel<3>, dim3(cdiv(nthreads, 256)), dim3(256), 0, (const float*)QKV, fptr(c, p + ".attn.rpb"), rows / L, L, H, AO);
-  else launch(c, "nat_attention_kernel", nat_attention_kernel<5>, dim3(cdiv(nthreads, 256)), dim3(256), 0, (const float*)QKV, fptr(c, p + ".attn.rpb"), rows / L, L, H, AO);
-  GemmP g2 = mk(AO, C, rows, c->pw[p + ".attn.proj"], X, C);
+  if (ksz == 3) launch(c, "nat_attention_kernel", nat_attention_kernel<3>, dim3(cdiv(nthreads, 256)), dim3(256), 0, (const float*)QKV, p.rpb, rows / L, L, H, AO);
+  else launch(c, "nat_attention_kernel", nat_attention_kernel<5>, dim3(cdiv(nthreads, 256)), dim3(256), 0, (const float*)QKV, p.rpb, rows / L, L, H, AO);
+  GemmP g2 = mk(AO, C, rows, *p.proj, X, C);
   g2.residual = X; g2.ldr = C;
   if (f.drop && droppath > 0.f) { g2.droppath_p = droppath; g2.dp_div = L; g2.seed = f.seed; g2.stream = f.next_stream(); }
-  gemm(c, g2, c->pw[p + ".attn.proj"], f.fp32);
+  gemm(c, g2, *p.proj, f.fp32);
   float* Hh = A_alloc<float>(c, (size_t)rows * 3 * C);
-  GemmP g3 = mk(X, C, rows, c->pw[p + ".mlp.fc1"], Hh, 3 * C);
-  g3.pro = PRO_LN; g3.pg = fptr(c, p + ".norm2.weight"); g3.pb = fptr(c, p + ".norm2.bias"); g3.act = ACT_GELU;
-  gemm(c, g3, c->pw[p + ".mlp.fc1"], f.fp32);
-  GemmP g4 = mk(Hh, 3 * C, rows, c->pw[p + ".mlp.fc2"], X, C);
+  GemmP g3 = mk(X, C, rows, *p.fc1, Hh, 3 * C);
+  g3.pro = PRO_LN; g3.pg = p.norm2.g; g3.pb = p.norm2.b; g3.act = ACT_GELU;
+  gemm(c, g3, *p.fc1, f.fp32);
+  GemmP g4 = mk(Hh, 3 * C, rows, *p.fc2, X, C);
   g4.residual = X; g4.ldr = C;
   if (f.drop && droppath > 0.f) { g4.droppath_p = droppath; g4.dp_div = L; g4.seed = f.seed; g4.stream = f.next_stream(); }
-  gemm(c, g4, c->pw[p + ".mlp.fc2"], f.fp32);
+  gemm(c, g4, *p.fc2, f.fp32);
 }
 
 // MLPLayer (mlp_layer.py:8-16): X (rows,128) -> out (rows, Nout) with hidden width Hd
 // three MLPLayer(128, 256, 160) heads -> interleaved (rows, 80, 6), one launch (heads_fused.h); bf16 mode
-void heads3_fused(Fwd& f, const float* X, int ldx, int rows, int g_per, int g_stride, int g_off, const std::string names[3], float* out) {
+void heads3_fused(Fwd& f, const float* X, int ldx, int rows, int g_per, int g_stride, int g_off, const MLPLayerW heads[3], float* out) {
   Ctx* c = f.c;
   Heads3P q; memset(&q, 0, sizeof(q));
   q.X = X; q.ldx = ldx; q.rows = rows; q.gather_per = g_per; q.gather_stride = g_stride; q.gather_off = g_off; q.out = out;
   for (int i = 0; i < 3; ++i) {
-    const PW &w1 = c->pw[names[i] + ".mlp.0"], &w2 = c->pw[names[i] + ".mlp.3"];
+    const PW &w1 = *heads[i].l0, &w2 = *heads[i].l3;
     q.w1[i] = w1.bf.get(); q.b1[i] = w1.bias; q.w2[i] = w2.bf.get(); q.b2[i] = w2.bias;
-    q.lng[i] = fptr(c, names[i] + ".mlp.1.weight"); q.lnb[i] = fptr(c, names[i] + ".mlp.1.bias");
+    q.lng[i] = heads[i].ln.g; q.lnb[i] = heads[i].ln.b;
   }
   c->prof_flops = 3.0 * 2.0 * rows * (128.0 * 256 + 256.0 * 160);
   launch(c, "heads3_fused_kernel", heads3_fused_kernel, dim3(24 * cdiv(cdiv(rows, HD_ROWS), 8)), dim3(512), (size_t)HD_LDS, q);      // (groups of 8 tiles x 3 heads: heads_fused.h)
 }
 
-void mlp_layer(Fwd& f, const float* X, int ldx, int rows, const std::string& p, float* out, int ldo, bool fp32) {
+void mlp_layer(Fwd& f, const float* X, int ldx, int rows, const MLPLayerW& p, float* out, int ldo, bool fp32) {
   Ctx* c = f.c;
-  const PW& w0 = c->pw[p + ".mlp.0"];
+  const PW& w0 = *p.l0;
   float* T = A_alloc<float>(c, (size_t)rows * w0.N);
   gemm(c, mk(X, ldx, rows, w0, T, w0.N), w0, fp32);
-  const PW& w3 = c->pw[p + ".mlp.3"];
+  const PW& w3 = *p.l3;
   GemmP g = mk(T, w0.N, rows, w3, out, ldo);
-  g.pro = PRO_LN; g.pg = fptr(c, p + ".mlp.1.weight"); g.pb = fptr(c, p + ".mlp.1.bias"); g.pro_relu = 1;
+  g.pro = PRO_LN; g.pg = p.ln.g; g.pb = p.ln.b; g.pro_relu = 1;
   gemm(c, g, w3, fp32);
 }
 
@@ -679,37 +678,35 @@ int head_impl(Ctx* c, const Ctx::Head& h) {
     // cat_x_proj (bf16) -> pi_head first Linear (exact fp32, live parameters) -> LayerNorm -> ReLU -> Linear -> masked logits: one launch
     PiFwdP q; memset(&q, 0, sizeof(q));
     q.Q = h.Q; q.rows = nQ; q.rows_per_scene = R * M;
-    q.wq = c->pw[PD + ".cat_x_proj.q"].bf.get(); q.bq = c->pw[PD + ".cat_x_proj.q"].bias; q.x0p = h.x0p;
-    q.w1 = fptr(c, PD + ".pi_head.mlp.0.weight"); q.b1 = fptr(c, PD + ".pi_head.mlp.0.bias");
-    q.lng = fptr(c, PD + ".pi_head.mlp.1.weight"); q.lnb = fptr(c, PD + ".pi_head.mlp.1.bias");
-    q.w2 = fptr(c, PD + ".pi_head.mlp.3.weight"); q.b2 = fptr(c, PD + ".pi_head.mlp.3.bias");
+    q.wq = c->m.dec.cat_x_proj_q->bf.get(); q.bq = c->m.dec.cat_x_proj_q->bias; q.x0p = h.x0p;
+    q.w1 = c->pi.w0; q.b1 = c->pi.b0;
+    q.lng = c->pi.ln_g; q.lnb = c->pi.ln_b;
+    q.w2 = c->pi.w3; q.b2 = c->pi.b3;
     q.r_kpm = h.r_kpm; q.M = M; q.eps = 1e-5f; q.QF = h.QF; q.Hpi = h.Hpi; q.prob = h.prob; q.nonfinite = c->nonfinite.get();
     c->prof_flops = 2.0 * nQ * (2.0 * 128 * 128 + 128);
     launch(c, "pi_forward_kernel", pi_forward_kernel, dim3(cdiv(nQ, PI_ROWS)), dim3(512), (size_t)PI_LDS, q);
   } else {
-    GemmP g = mk(h.Q, 128, nQ, c->pw[PD + ".cat_x_proj.q"], h.QF, 128);
+    GemmP g = mk(h.Q, 128, nQ, *c->m.dec.cat_x_proj_q, h.QF, 128);
     g.gbias = h.x0p; g.gb_div = R * M; g.gb_mod = 0;
-    gemm(c, g, c->pw[PD + ".cat_x_proj.q"], h.fp32);
+    gemm(c, g, *c->m.dec.cat_x_proj_q, h.fp32);
     // pi head: first Linear straight from the live (trainable) fp32 parameters, exact-fp32 MFMA
-    PWShape w; w.N = 128; w.K = 128; w.Kp = 128; w.Npad = 128; w.bias = fptr(c, PD + ".pi_head.mlp.0.bias");
-    gemm(c, mk(h.QF, 128, nQ, w, h.Hpi, 128), (const void*)fptr(c, PD + ".pi_head.mlp.0.weight"), true);
-    launch(c, "pi_tail_kernel", pi_tail_kernel, dim3(cdiv(nQ, 4)), dim3(256), 0, (const float*)h.Hpi, nQ, M, fptr(c, PD + ".pi_head.mlp.1.weight"),
-           fptr(c, PD + ".pi_head.mlp.1.bias"), fptr(c, PD + ".pi_head.mlp.3.weight"), fptr(c, PD + ".pi_head.mlp.3.bias"),
+    PWShape w; w.N = 128; w.K = 128; w.Kp = 128; w.Npad = 128; w.bias = c->pi.b0;
+    gemm(c, mk(h.QF, 128, nQ, w, h.Hpi, 128), (const void*)c->pi.w0, true);
+    launch(c, "pi_tail_kernel", pi_tail_kernel, dim3(cdiv(nQ, 4)), dim3(256), 0, (const float*)h.Hpi, nQ, M, c->pi.ln_g,
+           c->pi.ln_b, c->pi.w3, c->pi.b3,
            (const uint8_t*)h.r_kpm, 1e-5f, h.prob, c->nonfinite.get());
   }
   tap(c, "q_final", h.QF, (int64_t)nQ * 128);
   if (h.need_traj && !h.fp32 && c->sw.heads_fused) {
-    const std::string nm3[3] = {PD + ".loc_head", PD + ".yaw_head", PD + ".vel_head"};
-    heads3_fused(f, h.QF, 128, nQ, 0, 0, 0, nm3, h.traj);
+    heads3_fused(f, h.QF, 128, nQ, 0, 0, 0, c->m.dec.head, h.traj);
   } else if (h.need_traj) {
-    const char* nm[3] = {"loc_head", "yaw_head", "vel_head"};
     for (int i = 0; i < 3; ++i) {      // MLPLayer(128, 256, 160) as in mlp_layer(), on the buffers the trunk reserved
-      const PW& w0 = c->pw[PD + "." + nm[i] + ".mlp.0"];
-      const PW& w3 = c->pw[PD + "." + nm[i] + ".mlp.3"];
+      const PW& w0 = *c->m.dec.head[i].l0;
+      const PW& w3 = *c->m.dec.head[i].l3;
       float* T = h.oT[i];
       gemm(c, mk(h.QF, 128, nQ, w0, T, w0.N), w0, h.fp32);
       GemmP g = mk(T, w0.N, nQ, w3, h.o3[i], 160);
-      g.pro = PRO_LN; g.pg = fptr(c, PD + "." + nm[i] + ".mlp.1.weight"); g.pb = fptr(c, PD + "." + nm[i] + ".mlp.1.bias"); g.pro_relu = 1;
+      g.pro = PRO_LN; g.pg = c->m.dec.head[i].ln.g; g.pb = c->m.dec.head[i].ln.b; g.pro_relu = 1;
       gemm(c, g, w3, h.fp32);
     }
     launch(c, "interleave_traj_kernel", interleave_traj_kernel, dim3(cdiv((long long)nQ * 480, 256)), dim3(256), 0, (const float*)h.o3[0], (const float*)h.o3[1],
@@ -823,6 +820,7 @@ int dp_mask_and_drop_counters(Fwd& f) {
 // ---- agent-history chain: the three NAT levels (one launch each, or layer-wise) and the FPN tail
 void history_encoder(Fwd& f) {
   Ctx* c = f.c;
+  const auto& he = c->m.agent;
   const int nA = f.nA;
   static const float dpr[6] = {0.f, 0.04f, 0.08f, 0.12f, 0.16f, 0.2f};   // linspace(0, 0.2, 6), embedding.py:30
   const bool fused = c->sw.nat_fused && !f.fp32;
@@ -879,31 +877,31 @@ void history_encoder(Fwd& f) {
   } else {
     float* X0 = A_alloc<float>(c, (size_t)nA * 20 * 32);
     {
-      GemmP g = mk(f.F9, 9, nA * 20, c->pw[HE + ".embed.proj"], X0, 32);
+      GemmP g = mk(f.F9, 9, nA * 20, *he.embed_proj, X0, 32);
       g.amode = AMODE_CONV3; g.cv_C = 9; g.cv_Lin = 20; g.cv_nout = 20; g.cv_t0 = 0; g.cv_stride = 1;
-      gemm(c, g, c->pw[HE + ".embed.proj"], f.fp32);
+      gemm(c, g, *he.embed_proj, f.fp32);
     }
     auto nat_level = [&](float* Xl, int lv, int rows, int C, int H, int ksz, int L) {
-      nat_layer(f, Xl, rows, C, H, ksz, L, HE + ".levels." + std::to_string(lv) + ".blocks.0", dpr[2 * lv]);
-      nat_layer(f, Xl, rows, C, H, ksz, L, HE + ".levels." + std::to_string(lv) + ".blocks.1", dpr[2 * lv + 1]);
+      nat_layer(f, Xl, rows, C, H, ksz, L, he.levels[lv].blocks[0], dpr[2 * lv]);
+      nat_layer(f, Xl, rows, C, H, ksz, L, he.levels[lv].blocks[1], dpr[2 * lv + 1]);
     };
     nat_level(X0, 0, nA * 20, 32, 2, 3, 20);
     float* X1 = A_alloc<float>(c, (size_t)nA * 10 * 64);
     {
-      GemmP g = mk(X0, 32, nA * 10, c->pw[HE + ".levels.0.downsample.reduction"], X1, 64);
+      GemmP g = mk(X0, 32, nA * 10, *he.levels[0].reduction, X1, 64);
       g.amode = AMODE_CONV3; g.cv_C = 32; g.cv_Lin = 20; g.cv_nout = 10; g.cv_t0 = 0; g.cv_stride = 2;
-      gemm(c, g, c->pw[HE + ".levels.0.downsample.reduction"], f.fp32);
-      layernorm(f, X1, 64, X1, 64, nA * 10, 64, HE + ".levels.0.downsample.norm");
+      gemm(c, g, *he.levels[0].reduction, f.fp32);
+      layernorm(f, X1, 64, X1, 64, nA * 10, 64, he.levels[0].ds_norm);
     }
     nat_level(X1, 1, nA * 10, 64, 4, 3, 10);
     // level outputs are the PRE-downsample activations (NATBlock returns (downsample(x), x)); X0/X1 are
     // still needed below, so the downsample writes new buffers.
     float* X2 = A_alloc<float>(c, (size_t)nA * 5 * 128);
     {
-      GemmP g = mk(X1, 64, nA * 5, c->pw[HE + ".levels.1.downsample.reduction"], X2, 128);
+      GemmP g = mk(X1, 64, nA * 5, *he.levels[1].reduction, X2, 128);
       g.amode = AMODE_CONV3; g.cv_C = 64; g.cv_Lin = 10; g.cv_nout = 5; g.cv_t0 = 0; g.cv_stride = 2;
-      gemm(c, g, c->pw[HE + ".levels.1.downsample.reduction"], f.fp32);
-      layernorm(f, X2, 128, X2, 128, nA * 5, 128, HE + ".levels.1.downsample.norm");
+      gemm(c, g, *he.levels[1].reduction, f.fp32);
+      layernorm(f, X2, 128, X2, 128, nA * 5, 128, he.levels[1].ds_norm);
     }
     nat_level(X2, 2, nA * 5, 128, 8, 5, 5);
     tap(c, "nat_level2", X2, (int64_t)nA * 5 * 128);
@@ -912,25 +910,25 @@ void history_encoder(Fwd& f) {
       for (int j = 0; j < 3; ++j)   // rows (a, j) <- level rows (a*L + L-3 + j): 3 strided LN calls
         launch(c, "layernorm_kernel", layernorm_kernel, dim3(cdiv(nA, 4)), dim3(256), 0, (const float*)(Xl[i] + (size_t)(Ll[i] - 3 + j) * Cl[i]),
                Ll[i] * Cl[i], Oc[i] + (size_t)j * Cl[i], 3 * Cl[i], nA, Cl[i],
-               fptr(c, HE + ".norm" + std::to_string(i) + ".weight"), fptr(c, HE + ".norm" + std::to_string(i) + ".bias"),
+               he.levels[i].norm.g, he.levels[i].norm.b,
                1e-5f, 0);
   }
   // the FPN inputs (LayerNorm of the last three steps of level i): as the 16-bit operand words the fused tail receives (two per float of
   // the tap, in the launch's compacted order), else fp32 rows of all nA slots
+  static const char* const oc_tap[3] = {"nat_oc0", "nat_oc1", "nat_oc2"};
   for (int i = 0; i < 3; ++i) {
-    const std::string nm = "nat_oc" + std::to_string(i);
-    if (oc_bf16) tap(c, nm.c_str(), (float*)Ocb[i], (int64_t)nA * 3 * Cl[i] / 2);
-    else tap(c, nm.c_str(), Oc[i], (int64_t)nA * 3 * Cl[i]);
+    if (oc_bf16) tap(c, oc_tap[i], (float*)Ocb[i], (int64_t)nA * 3 * Cl[i] / 2);
+    else tap(c, oc_tap[i], Oc[i], (int64_t)nA * 3 * Cl[i]);
   }
   // FPN restricted to what out[:, :, -1] depends on
   f.nat_out = A_alloc<float>(c, (size_t)nA * 128);
   if (fused && c->sw.fpn_fused) {
     FpnP q; memset(&q, 0, sizeof(q));
     for (int i = 0; i < 3; ++i) {
-      const PW& w = c->pw[HE + ".lateral_convs." + std::to_string(i)];
+      const PW& w = *he.levels[i].lateral;
       q.oc[i] = Oc[i]; q.ocb[i] = Ocb[i]; q.wl[i] = w.bf.get(); q.bl[i] = w.bias;
     }
-    q.wf = c->pw[HE + ".fpn_conv.last"].bf.get(); q.bf_ = c->pw[HE + ".fpn_conv.last"].bias;
+    q.wf = he.fpn_last->bf.get(); q.bf_ = he.fpn_last->bias;
     q.out = f.nat_out; q.nA = nA; q.cnt = fused ? f.nat_cnt : nullptr; q.aidx = fused ? f.nat_aidx : nullptr;
     c->prof_flops = 2.0 * nA * (2.0 * 128 * (96 + 192 + 384) + 256.0 * 128);
     launch(c, "fpn_tail_kernel", fpn_tail_kernel, dim3(cdiv(nA, FPN_AG)), dim3(512), (size_t)FPN_LDS, q);
@@ -938,15 +936,15 @@ void history_encoder(Fwd& f) {
     float* lat[3];
     for (int i = 0; i < 3; ++i) {
       lat[i] = A_alloc<float>(c, (size_t)nA * 2 * 128);
-      const std::string lc = HE + ".lateral_convs." + std::to_string(i);
-      GemmP g = mk(Oc[i], Cl[i], nA * 2, c->pw[lc], lat[i], 128);
+      const PW& lc = *he.levels[i].lateral;
+      GemmP g = mk(Oc[i], Cl[i], nA * 2, lc, lat[i], 128);
       g.amode = AMODE_CONV3; g.cv_C = Cl[i]; g.cv_Lin = 3; g.cv_nout = 2; g.cv_t0 = 1; g.cv_stride = 1;
-      gemm(c, g, c->pw[lc], f.fp32);
+      gemm(c, g, lc, f.fp32);
     }
     float* Z = A_alloc<float>(c, (size_t)nA * 256);
     launch(c, "fpn_merge_kernel", fpn_merge_kernel, dim3(cdiv((long long)nA * 128, 256)), dim3(256), 0, (const float*)lat[0], (const float*)lat[1],
            (const float*)lat[2], nA, Z);
-    gemm(c, mk(Z, 256, nA, c->pw[HE + ".fpn_conv.last"], f.nat_out, 128), c->pw[HE + ".fpn_conv.last"], f.fp32);
+    gemm(c, mk(Z, 256, nA, *he.fpn_last, f.nat_out, 128), *he.fpn_last, f.fp32);
   }
   tap(c, "nat_out", f.nat_out, (int64_t)nA * 128);
 }
@@ -956,16 +954,16 @@ void ego_token(Fwd& f) {
   Ctx* c = f.c;
   const RiftFeatureBatch* B = f.B;
   const int bs = f.bs;
-  const std::string EG = "agent_encoder.ego_state_emb";
+  const auto& eg = c->m.agent.ego;
   bool fill_eq;
-  float* eq = wconst_get(c, "ego_q", 128, f.fp32, &fill_eq);
-  if (fill_eq) gemm(c, mk(fptr(c, EG + ".query"), 128, 1, c->pw[EG + ".attn.q"], eq, 128), c->pw[EG + ".attn.q"], f.fp32);
+  float* eq = wconst_get(c, c->wc.ego_q, 128, f.fp32, &fill_eq);
+  if (fill_eq) gemm(c, mk(eg.query, 128, 1, *eg.q, eq, 128), *eg.q, f.fp32);
   f.x_ego = A_alloc<float>(c, (size_t)bs * 128);
   if (!f.fp32 && c->sw.ego_fused) {
     EgoP q; memset(&q, 0, sizeof(q));
-    q.cs = B->current_state; q.cs_ld = B->cs_ld; q.lw = c->img.ego_w.get(); q.lb = c->img.ego_b.get(); q.pos = fptr(c, EG + ".pos_embed");
-    q.wkv = c->pw[EG + ".attn.kv"].bf.get(); q.bkv = c->pw[EG + ".attn.kv"].bias; q.q = eq;
-    q.wo = c->pw[EG + ".attn.out_proj"].bf.get(); q.bo = c->pw[EG + ".attn.out_proj"].bias;
+    q.cs = B->current_state; q.cs_ld = B->cs_ld; q.lw = c->img.ego_w.get(); q.lb = c->img.ego_b.get(); q.pos = eg.pos_embed;
+    q.wkv = eg.kv->bf.get(); q.bkv = eg.kv->bias; q.q = eq;
+    q.wo = eg.out_proj->bf.get(); q.bo = eg.out_proj->bias;
     q.out = f.x_ego; q.bs = bs; q.drop_p = f.drop ? 0.75f : 0.f; q.seed = f.seed; q.stream = f.drop ? f.next_stream() : 0;
     q.ds = f.ds;
     c->prof_flops = 2.0 * bs * (6.0 * 128 * 256 + 128.0 * 128);
@@ -973,9 +971,9 @@ void ego_token(Fwd& f) {
   } else {
   float* E = A_alloc<float>(c, (size_t)bs * 6 * 128);
   launch(c, "ego_token_kernel", ego_token_kernel, dim3(cdiv((long long)bs * 6 * 128, 256)), dim3(256), 0, B->current_state, B->cs_ld,
-         (const float*)c->img.ego_w.get(), (const float*)c->img.ego_b.get(), fptr(c, EG + ".pos_embed"), bs, E);
+         (const float*)c->img.ego_w.get(), (const float*)c->img.ego_b.get(), eg.pos_embed, bs, E);
   float* EKV = A_alloc<float>(c, (size_t)bs * 6 * 256);
-  gemm(c, mk(E, 128, bs * 6, c->pw[EG + ".attn.kv"], EKV, 256), c->pw[EG + ".attn.kv"], f.fp32);
+  gemm(c, mk(E, 128, bs * 6, *eg.kv, EKV, 256), *eg.kv, f.fp32);
   uint8_t* edrop = nullptr;
   if (f.drop) {
     edrop = A_alloc<uint8_t>(c, (size_t)bs * 6);
@@ -990,7 +988,7 @@ void ego_token(Fwd& f) {
     p.o_outer = 1; p.o_inner = 0; p.o_stride = 0; p.mask = edrop; p.mask_quirk = 0; p.mask_mod = 1;
     run_mha(c, p, f.fp32);
   }
-  gemm(c, mk(EAO, 128, bs, c->pw[EG + ".attn.out_proj"], f.x_ego, 128), c->pw[EG + ".attn.out_proj"], f.fp32);
+  gemm(c, mk(EAO, 128, bs, *eg.out_proj, f.x_ego, 128), *eg.out_proj, f.fp32);
   }
   tap(c, "x_ego", f.x_ego, (int64_t)bs * 128);
 }
@@ -999,20 +997,21 @@ void ego_token(Fwd& f) {
 // embeddings done they are launched here, ahead of the join, and run beside the tail of the agent-history chain instead of between encoder and decoder
 int build_q0(Fwd& f) {
   Ctx* c = f.c;
+  const auto& pd = c->m.dec;
   const int M = f.M, nL = f.nL, nQ = f.nQ;
   bool fill;
-  float* Mb = wconst_get(c, "Mb", (size_t)M * 128, f.fp32, &fill);
-  if (fill) gemm(c, mk(fptr(c, PD + ".m_emb"), 128, M, c->pw[PD + ".q_proj.m"], Mb, 128), c->pw[PD + ".q_proj.m"], f.fp32);
+  float* Mb = wconst_get(c, c->wc.Mb, (size_t)M * 128, f.fp32, &fill);
+  if (fill) gemm(c, mk(pd.m_emb, 128, M, *pd.q_proj_m, Mb, 128), *pd.q_proj_m, f.fp32);
   f.Q = A_alloc<float>(c, (size_t)nQ * 128);
   if (!f.fp32 && c->sw.pi_fused) {
     Q0P q; memset(&q, 0, sizeof(q));
-    q.r_emb = f.r_emb; q.nL = nL; q.M = M; q.wr = c->pw[PD + ".q_proj.r"].bf.get(); q.br = c->pw[PD + ".q_proj.r"].bias;
+    q.r_emb = f.r_emb; q.nL = nL; q.M = M; q.wr = pd.q_proj_r->bf.get(); q.br = pd.q_proj_r->bias;
     q.Mb = Mb; q.Q = f.Q;
     c->prof_flops = 2.0 * nL * 128.0 * 128;
     launch(c, "q0_fused_kernel", q0_fused_kernel, dim3(cdiv(nL, 16)), dim3(256), 0, q);
   } else {
     float* Ra = A_alloc<float>(c, (size_t)nL * 128);
-    gemm(c, mk(f.r_emb, 128, nL, c->pw[PD + ".q_proj.r"], Ra, 128), c->pw[PD + ".q_proj.r"], f.fp32);
+    gemm(c, mk(f.r_emb, 128, nL, *pd.q_proj_r, Ra, 128), *pd.q_proj_r, f.fp32);
     launch(c, "build_q0_kernel", build_q0_kernel, dim3(cdiv((long long)nQ * 128, 256)), dim3(256), 0, (const float*)Ra, (const float*)Mb, nL, M, f.Q);
   }
   return RIFT_OK;
@@ -1026,8 +1025,8 @@ int map_and_embeddings(Fwd& f) {
   // map encoder (map_encoder.py:31-93)
   // reference-line features are input-only too: both PointsEncoders run side by side (fused path)
   f.pe_pair = !f.fp32 && c->sw.pe_fused;
-  if (f.pe_pair) points_encoder_pair(f, f.F10, nP, B->map_valid_mask, "map_encoder.polygon_encoder", f.F6, nL, B->ref_valid_mask, PD + ".r_encoder", &f.poly, &f.r_emb);
-  else f.poly = points_encoder(f, f.F10, 10, nP, 20, B->map_valid_mask, "map_encoder.polygon_encoder");
+  if (f.pe_pair) points_encoder_pair(f, f.F10, nP, B->map_valid_mask, c->m.map.polygon_encoder, f.F6, nL, B->ref_valid_mask, c->m.dec.r_encoder, &f.poly, &f.r_emb);
+  else f.poly = points_encoder(f, f.F10, 10, nP, 20, B->map_valid_mask, c->m.map.polygon_encoder);
   tap(c, "poly_pe", f.poly, (int64_t)nP * 128);
   // the three Fourier embeddings (token positions, speed limits, reference-line positions) depend on inputs only: with both
   // PointsEncoders done they run as ONE launch, and the token kernels add the positional embedding on the way
@@ -1035,9 +1034,9 @@ int map_and_embeddings(Fwd& f) {
   if (f.fo3) {
     tap(c, "r_pe", f.r_emb, (int64_t)nL * 128);
     FourierP3 q3; memset(&q3, 0, sizeof(q3));
-    q3.e[0] = fourier_desc(f, f.pos, 3, nT, 3, "pos_emb", 2, nullptr);
-    q3.e[1] = fourier_desc(f, B->map_polygon_speed_limit, 1, nP, 1, "map_encoder.speed_limit_emb", -1, nullptr);
-    q3.e[2] = fourier_desc(f, f.r_pos, 3, nL, 3, PD + ".r_pos_emb", -1, f.r_emb);
+    q3.e[0] = fourier_desc(f, f.pos, 3, nT, c->m.pos_emb, 2, nullptr);
+    q3.e[1] = fourier_desc(f, B->map_polygon_speed_limit, 1, nP, c->m.map.speed_limit_emb, -1, nullptr);
+    q3.e[2] = fourier_desc(f, f.r_pos, 3, nL, c->m.dec.r_pos_emb, -1, f.r_emb);
     q3.nblk[0] = cdiv(nT, FO_ROWS); q3.nblk[1] = cdiv(nP, FO_ROWS); q3.nblk[2] = cdiv(nL, FO_ROWS); q3.count = 3;
     c->prof_flops = 2.0 * 128.0 * ((nT + nL) * (3 * 257.0 + 128.0) + nP * (257.0 + 128.0));
     if (c->sw.fo_w) {          // wave-private form: one 16-row tile per wave, 8 tiles per pass, the one-dimensional embedding two passes per workgroup
@@ -1053,7 +1052,7 @@ int map_and_embeddings(Fwd& f) {
     launch(c, "fourier_fused_kernel", fourier_fused_kernel, dim3(q3.nblk[0] + q3.nblk[1] + q3.nblk[2]), dim3(256), (size_t)FO_LDS, q3);
     f.PEtok = q3.e[0].Y; f.speed_emb = q3.e[1].Y; f.rpe_done = true;
   } else {
-    f.speed_emb = fourier(f, B->map_polygon_speed_limit, 1, nP, 1, "map_encoder.speed_limit_emb", -1);
+    f.speed_emb = fourier(f, B->map_polygon_speed_limit, 1, nP, c->m.map.speed_limit_emb, -1);
   }
   if (f.plan.forked && f.rpe_done) TRY(build_q0(f));      // ahead of the join
   return RIFT_OK;
@@ -1066,19 +1065,19 @@ void assemble_tokens(Fwd& f) {
   const int bs = f.bs, A = f.A, Mp = f.Mp, S = f.S, N = f.N, nA = f.nA, nP = f.nP, nT = f.nT;
   f.X = A_alloc<float>(c, (size_t)nT * 128);
   TokenP q; memset(&q, 0, sizeof(q));
-  q.nat = f.nat_out; q.x_ego = f.x_ego; q.valid_agent = (const uint8_t*)f.valid_agent; q.category = B->agent_category; q.a_type_emb = fptr(c, "agent_encoder.type_emb.weight");
+  q.nat = f.nat_out; q.x_ego = f.x_ego; q.valid_agent = (const uint8_t*)f.valid_agent; q.category = B->agent_category; q.a_type_emb = c->m.agent.type_emb;
   q.pooled = f.poly; q.ptype = B->map_polygon_type; q.on_route = B->map_polygon_on_route; q.tl = B->map_polygon_tl_status; q.has_sl = B->map_polygon_has_speed_limit;
-  q.speed_emb = f.speed_emb; q.p_type_emb = fptr(c, "map_encoder.type_emb.weight"); q.route_emb = fptr(c, "map_encoder.on_route_emb.weight");
-  q.tl_emb = fptr(c, "map_encoder.traffic_light_emb.weight"); q.unk_emb = fptr(c, "map_encoder.unknown_speed_emb.weight");
+  q.speed_emb = f.speed_emb; q.p_type_emb = c->m.map.type_emb; q.route_emb = c->m.map.on_route_emb;
+  q.tl_emb = c->m.map.traffic_light_emb; q.unk_emb = c->m.map.unknown_speed_emb;
   q.bs = bs; q.A = A; q.Mp = Mp; q.N = N; q.X = f.X; q.pe = f.PEtok;
   q.nblk_a = cdiv((long long)nA * 32, 256);
   launch(c, "token_kernel", token_kernel, dim3(q.nblk_a + cdiv((long long)nP * 32, 256)), dim3(256), 0, q);
   if (S > 0) {
-    float* semb = fourier(f, B->static_shape, 2, bs * S, 2, "static_objects_encoder.obj_encoder", -1);
+    float* semb = fourier(f, B->static_shape, 2, bs * S, c->m.stat.obj_encoder, -1);
     launch(c, "static_token_kernel", static_token_kernel, dim3(cdiv((long long)bs * S * 128, 256)), dim3(256), 0, (const float*)semb, B->static_category,
-           B->static_valid_mask, fptr(c, "static_objects_encoder.type_emb.weight"), bs, A, Mp, S, N, f.X);
+           B->static_valid_mask, c->m.stat.type_emb, bs, A, Mp, S, N, f.X);
   }
-  if (!f.fo3) fourier(f, f.pos, 3, nT, 3, "pos_emb", 2, f.X);
+  if (!f.fo3) fourier(f, f.pos, 3, nT, c->m.pos_emb, 2, f.X);
   tap(c, "x_tokens", f.X, (int64_t)nT * 128);
 }
 
@@ -1095,27 +1094,27 @@ void scene_encoder(Fwd& f) {
     EncFusedP ep; memset(&ep, 0, sizeof(ep));
     ep.X = f.X; ep.Y = f.ENC; ep.kpm = f.kpm; ep.bs = bs; ep.N = N; ep.seed = f.seed; ep.stream = f.next_stream(); f.stream_id += 8;
     for (int i = 0; i < 4; ++i) {
-      const std::string p = "encoder_blocks." + std::to_string(i);
+      const SceneBlockW& p = c->m.encoder_blocks[i];
       EncBlockW& w = ep.blk[i];
-      w.ln1_g = fptr(c, p + ".norm1.weight"); w.ln1_b = fptr(c, p + ".norm1.bias");
-      w.ln2_g = fptr(c, p + ".norm2.weight"); w.ln2_b = fptr(c, p + ".norm2.bias");
+      w.ln1_g = p.norm1.g; w.ln1_b = p.norm1.b;
+      w.ln2_g = p.norm2.g; w.ln2_b = p.norm2.b;
       w.wqkv = c->img.enc_wqkv[i].get(); w.bqkv = c->img.enc_bqkv[i].get();
-      w.wo = c->pw[p + ".attn.out_proj"].bf.get(); w.bo = c->pw[p + ".attn.out_proj"].bias;
-      w.w1 = c->pw[p + ".mlp.fc1"].bf.get(); w.b1 = c->pw[p + ".mlp.fc1"].bias;
-      w.w2 = c->pw[p + ".mlp.fc2"].hid.get(); w.b2 = c->pw[p + ".mlp.fc2"].bias;      // (hidden-layer operand words: pack_hid)
+      w.wo = p.out_proj->bf.get(); w.bo = p.out_proj->bias;
+      w.w1 = p.fc1->bf.get(); w.b1 = p.fc1->bias;
+      w.w2 = p.fc2->hid.get(); w.b2 = p.fc2->bias;      // (hidden-layer operand words: pack_hid)
       w.droppath = f.drop ? edpr[i] : 0.f;
     }
-    ep.norm_g = fptr(c, "norm.weight"); ep.norm_b = fptr(c, "norm.bias"); ep.nonfinite = c->nonfinite.get();
+    ep.norm_g = c->m.norm.g; ep.norm_b = c->m.norm.b; ep.nonfinite = c->nonfinite.get();
     ep.ds = f.ds; ep.dbg = c->sw.no_skip ? 1 : 0;
     if (c->sw.enc_ts) { ep.ts = A_alloc<long long>(c, 256); tap(c, "enc_ts", (float*)ep.ts, 512); }
     c->prof_flops = 4.0 * bs * N * (2.0 * 128 * 384 + 4.0 * N * 128 + 2.0 * 128 * 128 + 4.0 * 128 * 512);
     if (c->sw.dec_fused && R <= 8 && ENC_NW == 8) {   // the decoder kernel will run: emit its cross-attention K | V operand fragments here
       f.enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * (f.enc_wide ? 96 : DECW_KV_FRAGS) * 512);      // (wide: the dense per-head image, dec_kv.h)
-      ep.wkv = c->pw["planning_decoder.kv_all"].bf.get(); ep.bkv = c->pw["planning_decoder.kv_all"].bias;
+      ep.wkv = c->m.dec.kv_all->bf.get(); ep.bkv = c->m.dec.kv_all->bias;
       ep.KT = f.enc_KT;
       f.kpm_c = A_alloc<uint8_t>(c, (size_t)bs * (f.enc_wide ? 112 : 96)); ep.kpm_c = f.kpm_c;
       f.enc_x0p = A_alloc<float>(c, (size_t)bs * 128);
-      ep.wx0 = c->pw["planning_decoder.cat_x_proj.x"].bf.get(); ep.x0p = f.enc_x0p;
+      ep.wx0 = c->m.dec.cat_x_proj_x->bf.get(); ep.x0p = f.enc_x0p;
       c->prof_flops += 2.0 * bs * N * 128.0 * 1024;
     }
     if (f.enc_wide) launch_call(c, "enc_fused112_kernel", [&] { enc112_launch(ep, c->stream); });
@@ -1135,29 +1134,29 @@ void scene_encoder(Fwd& f) {
   float* AO = A_alloc<float>(c, (size_t)nT * 128);
   float* H512 = A_alloc<float>(c, (size_t)nT * 512);
   for (int i = 0; i < 4; ++i) {
-    const std::string p = "encoder_blocks." + std::to_string(i);
-    GemmP g = mk(f.X, 128, nT, c->pw[p + ".attn.qkv"], QKV, 384);
-    g.pro = PRO_LN; g.pg = fptr(c, p + ".norm1.weight"); g.pb = fptr(c, p + ".norm1.bias");
-    gemm(c, g, c->pw[p + ".attn.qkv"], f.fp32);
+    const SceneBlockW& p = c->m.encoder_blocks[i];
+    GemmP g = mk(f.X, 128, nT, *p.qkv, QKV, 384);
+    g.pro = PRO_LN; g.pg = p.norm1.g; g.pb = p.norm1.b;
+    gemm(c, g, *p.qkv, f.fp32);
     MhaP m; memset(&m, 0, sizeof(m));
     m.Q = QKV; m.ldq = 384; m.K = QKV + 128; m.V = QKV + 256; m.ldkv = 384; m.O = AO; m.ldo = 128;
     m.nb_outer = bs; m.nb_inner = 1; m.H = 4; m.Lq = N; m.Lk = N;
     m.q_outer = N; m.q_stride = 1; m.kv_outer = N; m.kv_stride = 1; m.o_outer = N; m.o_stride = 1;
     m.mask = f.kpm; m.mask_mod = 1;
     run_mha(c, m, f.fp32);
-    GemmP g2 = mk(AO, 128, nT, c->pw[p + ".attn.out_proj"], f.X, 128);
+    GemmP g2 = mk(AO, 128, nT, *p.out_proj, f.X, 128);
     g2.residual = f.X; g2.ldr = 128;
     if (f.drop && edpr[i] > 0.f) { g2.droppath_p = edpr[i]; g2.dp_div = N; g2.seed = f.seed; g2.stream = f.next_stream(); }
-    gemm(c, g2, c->pw[p + ".attn.out_proj"], f.fp32);
-    GemmP g3 = mk(f.X, 128, nT, c->pw[p + ".mlp.fc1"], H512, 512);
-    g3.pro = PRO_LN; g3.pg = fptr(c, p + ".norm2.weight"); g3.pb = fptr(c, p + ".norm2.bias"); g3.act = ACT_GELU;
-    gemm(c, g3, c->pw[p + ".mlp.fc1"], f.fp32);
-    GemmP g4 = mk(H512, 512, nT, c->pw[p + ".mlp.fc2"], f.X, 128);
+    gemm(c, g2, *p.out_proj, f.fp32);
+    GemmP g3 = mk(f.X, 128, nT, *p.fc1, H512, 512);
+    g3.pro = PRO_LN; g3.pg = p.norm2.g; g3.pb = p.norm2.b; g3.act = ACT_GELU;
+    gemm(c, g3, *p.fc1, f.fp32);
+    GemmP g4 = mk(H512, 512, nT, *p.fc2, f.X, 128);
     g4.residual = f.X; g4.ldr = 128;
     if (f.drop && edpr[i] > 0.f) { g4.droppath_p = edpr[i]; g4.dp_div = N; g4.seed = f.seed; g4.stream = f.next_stream(); }
-    gemm(c, g4, c->pw[p + ".mlp.fc2"], f.fp32);
+    gemm(c, g4, *p.fc2, f.fp32);
   }
-  layernorm(f, f.X, 128, f.ENC, 128, nT, 128, "norm");
+  layernorm(f, f.X, 128, f.ENC, 128, nT, 128, c->m.norm);
   }
   tap(c, "enc_out", f.ENC, (int64_t)nT * 128);
 }
@@ -1170,17 +1169,15 @@ void agent_predictor(Fwd& f) {
   if (f.need_traj && out->prediction && A > 1) {
     const int rows = bs * (A - 1);
     if (!f.fp32 && c->sw.heads_fused) {
-      const std::string nm3[3] = {"agent_predictor.loc_predictor", "agent_predictor.yaw_predictor", "agent_predictor.vel_predictor"};
-      heads3_fused(f, f.ENC, 128, rows, A - 1, N, 1, nm3, out->prediction);
+      heads3_fused(f, f.ENC, 128, rows, A - 1, N, 1, c->m.predictor, out->prediction);
     } else {
     float* Xa = A_alloc<float>(c, (size_t)rows * 128);
     launch(c, "gather_rows_kernel", gather_rows_kernel, dim3(cdiv((long long)rows * 128, 256)), dim3(256), 0, (const float*)f.ENC, 128, Xa, 128, rows, 128,
            A - 1, N, 1);
     float* o3[3];
-    const char* nm[3] = {"loc_predictor", "yaw_predictor", "vel_predictor"};
     for (int i = 0; i < 3; ++i) {
       o3[i] = A_alloc<float>(c, (size_t)rows * 160);
-      mlp_layer(f, Xa, 128, rows, std::string("agent_predictor.") + nm[i], o3[i], 160, f.fp32);
+      mlp_layer(f, Xa, 128, rows, c->m.predictor[i], o3[i], 160, f.fp32);
     }
     launch(c, "interleave_traj_kernel", interleave_traj_kernel, dim3(cdiv((long long)rows * 480, 256)), dim3(256), 0, (const float*)o3[0], (const float*)o3[1],
            (const float*)o3[2], rows, out->prediction);
@@ -1199,11 +1196,11 @@ void decoder_layerwise(Fwd& f, float dp) {
   float* KVm = A_alloc<float>(c, (size_t)nT * 256);
   const int n_layers = c->sw.dec_layers == 0 || c->sw.dec_layers == 2 ? c->sw.dec_layers : 4;      // (RIFT_DEC_LAYERS)
   for (int i = 0; i < n_layers; ++i) {
-    const std::string p = PD + ".decoder_blocks." + std::to_string(i);
+    const DecoderBlockW& p = c->m.dec.decoder_blocks[i];
     // ---- r2r self attention over the R reference lines of each (scene, mode), with the mask quirk
-    GemmP g = mk(f.Q, 128, nQ, c->pw[p + ".r2r_attn.qkv"], DQKV, 384);
-    g.pro = PRO_LN; g.pg = fptr(c, p + ".norm1.weight"); g.pb = fptr(c, p + ".norm1.bias");
-    gemm(c, g, c->pw[p + ".r2r_attn.qkv"], f.fp32);
+    GemmP g = mk(f.Q, 128, nQ, *p.r2r_qkv, DQKV, 384);
+    g.pro = PRO_LN; g.pg = p.norm[0].g; g.pb = p.norm[0].b;
+    gemm(c, g, *p.r2r_qkv, f.fp32);
     {
       MhaP m; memset(&m, 0, sizeof(m));
       m.Q = DQKV; m.ldq = 384; m.K = DQKV + 128; m.V = DQKV + 256; m.ldkv = 384; m.O = DAO; m.ldo = 128;
@@ -1214,18 +1211,18 @@ void decoder_layerwise(Fwd& f, float dp) {
       if (dp > 0.f) { m.dropout_p = dp; m.seed = f.seed; m.stream = f.next_stream(); }
       run_mha(c, m, f.fp32);
     }
-    GemmP g2 = mk(DAO, 128, nQ, c->pw[p + ".r2r_attn.out_proj"], f.Q, 128);
+    GemmP g2 = mk(DAO, 128, nQ, *p.r2r_out, f.Q, 128);
     g2.residual = f.Q; g2.ldr = 128;
     if (dp > 0.f) { g2.dropout_p = dp; g2.seed = f.seed; g2.stream = f.next_stream(); }
-    gemm(c, g2, c->pw[p + ".r2r_attn.out_proj"], f.fp32);
+    gemm(c, g2, *p.r2r_out, f.fp32);
     // ---- m2m self attention over the 12 modes: q = k = (h + m_pos) W + b, v = h W + b
     bool fill_mp;
-    float* MP = wconst_get(c, p + ".mp", (size_t)M * 384, f.fp32, &fill_mp);
-    if (fill_mp) gemm(c, mk(fptr(c, PD + ".m_pos"), 128, M, c->pw[p + ".m2m_attn.qk0"], MP, 384), c->pw[p + ".m2m_attn.qk0"], f.fp32);
-    GemmP g3 = mk(f.Q, 128, nQ, c->pw[p + ".m2m_attn.qkv"], DQKV, 384);
-    g3.pro = PRO_LN; g3.pg = fptr(c, p + ".norm2.weight"); g3.pb = fptr(c, p + ".norm2.bias");
+    float* MP = wconst_get(c, c->wc.mp[i], (size_t)M * 384, f.fp32, &fill_mp);
+    if (fill_mp) gemm(c, mk(c->m.dec.m_pos, 128, M, *p.m2m_qk0, MP, 384), *p.m2m_qk0, f.fp32);
+    GemmP g3 = mk(f.Q, 128, nQ, *p.m2m_qkv, DQKV, 384);
+    g3.pro = PRO_LN; g3.pg = p.norm[1].g; g3.pb = p.norm[1].b;
     g3.gbias = MP; g3.gb_div = 1; g3.gb_mod = M;
-    gemm(c, g3, c->pw[p + ".m2m_attn.qkv"], f.fp32);
+    gemm(c, g3, *p.m2m_qkv, f.fp32);
     {
       MhaP m; memset(&m, 0, sizeof(m));
       m.Q = DQKV; m.ldq = 384; m.K = DQKV + 128; m.V = DQKV + 256; m.ldkv = 384; m.O = DAO; m.ldo = 128;
@@ -1234,15 +1231,15 @@ void decoder_layerwise(Fwd& f, float dp) {
       if (dp > 0.f) { m.dropout_p = dp; m.seed = f.seed; m.stream = f.next_stream(); }
       run_mha(c, m, f.fp32);
     }
-    GemmP g4 = mk(DAO, 128, nQ, c->pw[p + ".m2m_attn.out_proj"], f.Q, 128);
+    GemmP g4 = mk(DAO, 128, nQ, *p.m2m_out, f.Q, 128);
     g4.residual = f.Q; g4.ldr = 128; g4.rowzero = f.r_kpm; g4.rz_div = M;   // rows of padded ref lines become 0 (:65-72)
     if (dp > 0.f) { g4.dropout_p = dp; g4.seed = f.seed; g4.stream = f.next_stream(); }
-    gemm(c, g4, c->pw[p + ".m2m_attn.out_proj"], f.fp32);
+    gemm(c, g4, *p.m2m_out, f.fp32);
     // ---- cross attention: R*12 queries per scene against the encoder tokens
-    GemmP g5 = mk(f.Q, 128, nQ, c->pw[p + ".cross_attn.q"], DQc, 128);
-    g5.pro = PRO_LN; g5.pg = fptr(c, p + ".norm3.weight"); g5.pb = fptr(c, p + ".norm3.bias");
-    gemm(c, g5, c->pw[p + ".cross_attn.q"], f.fp32);
-    gemm(c, mk(f.ENC, 128, nT, c->pw[p + ".cross_attn.kv"], KVm, 256), c->pw[p + ".cross_attn.kv"], f.fp32);
+    GemmP g5 = mk(f.Q, 128, nQ, *p.cross_q, DQc, 128);
+    g5.pro = PRO_LN; g5.pg = p.norm[2].g; g5.pb = p.norm[2].b;
+    gemm(c, g5, *p.cross_q, f.fp32);
+    gemm(c, mk(f.ENC, 128, nT, *p.cross_kv, KVm, 256), *p.cross_kv, f.fp32);
     {
       MhaP m; memset(&m, 0, sizeof(m));
       m.Q = DQc; m.ldq = 128; m.K = KVm; m.V = KVm + 128; m.ldkv = 256; m.O = DAO; m.ldo = 128;
@@ -1252,19 +1249,19 @@ void decoder_layerwise(Fwd& f, float dp) {
       if (dp > 0.f) { m.dropout_p = dp; m.seed = f.seed; m.stream = f.next_stream(); }
       run_mha(c, m, f.fp32);
     }
-    GemmP g6 = mk(DAO, 128, nQ, c->pw[p + ".cross_attn.out_proj"], f.Q, 128);
+    GemmP g6 = mk(DAO, 128, nQ, *p.cross_out, f.Q, 128);
     g6.residual = f.Q; g6.ldr = 128;
     if (dp > 0.f) { g6.dropout_p = dp; g6.seed = f.seed; g6.stream = f.next_stream(); }
-    gemm(c, g6, c->pw[p + ".cross_attn.out_proj"], f.fp32);
+    gemm(c, g6, *p.cross_out, f.fp32);
     // ---- FFN
-    GemmP g7 = mk(f.Q, 128, nQ, c->pw[p + ".ffn.0"], DH, 512);
-    g7.pro = PRO_LN; g7.pg = fptr(c, p + ".norm4.weight"); g7.pb = fptr(c, p + ".norm4.bias"); g7.act = ACT_RELU;
+    GemmP g7 = mk(f.Q, 128, nQ, *p.ffn0, DH, 512);
+    g7.pro = PRO_LN; g7.pg = p.norm[3].g; g7.pb = p.norm[3].b; g7.act = ACT_RELU;
     if (dp > 0.f) { g7.dropout_p = dp; g7.seed = f.seed; g7.stream = f.next_stream(); }
-    gemm(c, g7, c->pw[p + ".ffn.0"], f.fp32);
-    GemmP g8 = mk(DH, 512, nQ, c->pw[p + ".ffn.3"], f.Q, 128);
+    gemm(c, g7, *p.ffn0, f.fp32);
+    GemmP g8 = mk(DH, 512, nQ, *p.ffn3, f.Q, 128);
     g8.residual = f.Q; g8.ldr = 128;
     if (dp > 0.f) { g8.dropout_p = dp; g8.seed = f.seed; g8.stream = f.next_stream(); }
-    gemm(c, g8, c->pw[p + ".ffn.3"], f.fp32);
+    gemm(c, g8, *p.ffn3, f.fp32);
   }
 }
 
@@ -1274,10 +1271,10 @@ int planning_decoder(Fwd& f) {
   const RiftFeatureBatch* B = f.B;
   const int flags = f.flags;
   const int bs = f.bs, R = f.R, N = f.N, M = f.M, nL = f.nL, nQ = f.nQ;
-  if (!f.pe_pair) f.r_emb = points_encoder(f, f.F6, 6, nL, 120, B->ref_valid_mask, PD + ".r_encoder");
+  if (!f.pe_pair) f.r_emb = points_encoder(f, f.F6, 6, nL, 120, B->ref_valid_mask, c->m.dec.r_encoder);
   if (!f.rpe_done) {
     tap(c, "r_pe", f.r_emb, (int64_t)nL * 128);
-    fourier(f, f.r_pos, 3, nL, 3, PD + ".r_pos_emb", -1, f.r_emb);
+    fourier(f, f.r_pos, 3, nL, c->m.dec.r_pos_emb, -1, f.r_emb);
   }
   tap(c, "r_emb", f.r_emb, (int64_t)nL * 128);
   if (!f.Q) TRY(build_q0(f));
@@ -1290,7 +1287,7 @@ int planning_decoder(Fwd& f) {
   if (c->sw.dec_fused && !f.fp32 && dec_dense && !f.enc_KT) {   // its K | V^T operand fragments from the (layer-wise) encoder's output
     f.enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * 96 * 512);
     DecKvP kq; memset(&kq, 0, sizeof(kq));
-    kq.ENC = f.ENC; kq.bs = bs; kq.N = N; kq.wkv = c->pw[PD + ".kv_all"].bf.get(); kq.bkv = c->pw[PD + ".kv_all"].bias; kq.KV = f.enc_KT;
+    kq.ENC = f.ENC; kq.bs = bs; kq.N = N; kq.wkv = c->m.dec.kv_all->bf.get(); kq.bkv = c->m.dec.kv_all->bias; kq.KV = f.enc_KT;
     c->prof_flops = 2.0 * bs * N * 128.0 * 1024;
     launch(c, "dec_kv_frag_kernel", dec_kv_frag_kernel, dim3(bs), dim3(512), (size_t)DEC_KV_LDS, kq);
   }
@@ -1351,7 +1348,7 @@ int policy_and_ego_heads(Fwd& f) {
   float* x0p = f.enc_x0p;
   if (!x0p) {
     x0p = A_alloc<float>(c, (size_t)bs * 128);
-    gemm(c, mk(f.ENC, N * 128, bs, c->pw[PD + ".cat_x_proj.x"], x0p, 128), c->pw[PD + ".cat_x_proj.x"], f.fp32);
+    gemm(c, mk(f.ENC, N * 128, bs, *c->m.dec.cat_x_proj_x, x0p, 128), *c->m.dec.cat_x_proj_x, f.fp32);
   }
   // ---- the policy head (and the trajectory heads that read its q_final): right here, or -- RIFT_F_DEFER_HEAD -- later through
   // rift_forward_head on a stream of the caller's choice, so that it (and the loss / backward / update behind it) runs beside the next
@@ -1369,12 +1366,12 @@ int policy_and_ego_heads(Fwd& f) {
   else TRY(head_impl(c, hs));
   // hidden_proj / ref_free_decoder on the ego token (pluto_model.py:173-180)
   if (!f.fp32 && c->sw.heads_fused && (out->hidden || (f.need_traj && out->ref_free_trajectory))) {      // one launch (heads_fused.h: ego_heads_kernel)
-    const PW &h0 = c->pw["hidden_proj.0"], &h2 = c->pw["hidden_proj.2"], &r0 = c->pw["ref_free_decoder.mlp.0"], &r3 = c->pw["ref_free_decoder.mlp.3"];
+    const PW &h0 = *c->m.hidden_proj0, &h2 = *c->m.hidden_proj2, &r0 = *c->m.ref_free_decoder.l0, &r3 = *c->m.ref_free_decoder.l3;
     EgoHeadsP q; memset(&q, 0, sizeof(q));
     q.X = f.ENC; q.ldx = N * 128; q.rows = bs;
     q.wh0 = h0.bf.get(); q.wh2 = h2.bf.get(); q.wr0 = r0.bf.get(); q.wr3 = r3.bf.get();
     q.bh0 = h0.bias; q.bh2 = h2.bias; q.br0 = r0.bias; q.br3 = r3.bias;
-    q.lng = fptr(c, "ref_free_decoder.mlp.1.weight"); q.lnb = fptr(c, "ref_free_decoder.mlp.1.bias");
+    q.lng = c->m.ref_free_decoder.ln.g; q.lnb = c->m.ref_free_decoder.ln.b;
     q.hidden = out->hidden; q.ref = (f.need_traj && out->ref_free_trajectory) ? out->ref_free_trajectory : nullptr;
     c->prof_flops = 2.0 * bs * (2.0 * 128 * 128 + 128.0 * 256 + 256.0 * 320);
     launch(c, "ego_heads_kernel", ego_heads_kernel, dim3(cdiv(bs, 16)), dim3(256), 0, q);
@@ -1382,13 +1379,13 @@ int policy_and_ego_heads(Fwd& f) {
   }
   if (out->hidden) {
     float* Th = A_alloc<float>(c, (size_t)bs * 128);
-    GemmP g = mk(f.ENC, N * 128, bs, c->pw["hidden_proj.0"], Th, 128);
+    GemmP g = mk(f.ENC, N * 128, bs, *c->m.hidden_proj0, Th, 128);
     g.act = ACT_RELU;
-    gemm(c, g, c->pw["hidden_proj.0"], f.fp32);
-    gemm(c, mk(Th, 128, bs, c->pw["hidden_proj.2"], out->hidden, 128), c->pw["hidden_proj.2"], f.fp32);
+    gemm(c, g, *c->m.hidden_proj0, f.fp32);
+    gemm(c, mk(Th, 128, bs, *c->m.hidden_proj2, out->hidden, 128), *c->m.hidden_proj2, f.fp32);
   }
   if (f.need_traj && out->ref_free_trajectory)
-    mlp_layer(f, f.ENC, N * 128, bs, "ref_free_decoder", out->ref_free_trajectory, 320, f.fp32);
+    mlp_layer(f, f.ENC, N * 128, bs, c->m.ref_free_decoder, out->ref_free_trajectory, 320, f.fp32);
 
   return RIFT_OK;
 }
@@ -1678,6 +1675,93 @@ static int pack_streamed_images(Ctx* c) {
   return RIFT_OK;
 }
 
+// rift_model_load, last step: every operand of the forward, looked up ONCE (model.h) -- behind the packers, the only place where a parameter
+// name is spelt.  Both lookups are strict: a name that matches nothing fails the load with "missing parameter: <name>" (the first one)
+// instead of reaching a launch as a null pointer; only a BatchNorm's num_batches_tracked is optional.  The PW pointers are the addresses
+// of nodes of c->pw: an unordered_map never moves its nodes, so they survive rehashing and the insert / erase of rift_op_linear's
+// transient key; pw.clear() at the top of the next load ends them, and the table is reset there with it.
+static int resolve_model(Ctx* c) {
+  auto W = [&](const std::string& key) -> const PW* {
+    auto it = c->pw.find(key);
+    if (it != c->pw.end()) return &it->second;
+    if (c->err.empty()) c->err = "missing parameter: " + key;
+    return nullptr;
+  };
+  auto P = [&](const std::string& name) { return fptr(c, name); };
+  auto ln = [&](const std::string& p) { return LayerNormW{P(p + ".weight"), P(p + ".bias")}; };
+  auto bn = [&](const std::string& p) {
+    const Param* nb = find(c, p + ".num_batches_tracked");
+    return BatchNormW{P(p + ".weight"), P(p + ".bias"), (float*)P(p + ".running_mean"), (float*)P(p + ".running_var"), nb ? (long long*)nb->data : nullptr};
+  };
+  auto mlp = [&](const std::string& p) { return MLPLayerW{W(p + ".mlp.0"), W(p + ".mlp.3"), ln(p + ".mlp.1")}; };
+  auto fourier = [&](const std::string& p, int D) {
+    FourierW f; f.D = D; f.freqs = P(p + ".freqs.weight");
+    for (int d = 0; d < D; ++d) {
+      const std::string m = p + ".mlps." + std::to_string(d);
+      f.mlps[d] = {W(m + ".0"), W(m + ".0.lo"), W(m + ".0.last"), W(m + ".3"), ln(m + ".1")};
+    }
+    f.out_ln = ln(p + ".to_out.0"); f.out = W(p + ".to_out.2");
+    return f;
+  };
+  auto points = [&](const std::string& p) {
+    return PointsEncoderW{W(p + ".first_mlp.0"), W(p + ".first_mlp.3"), W(p + ".second_mlp.0.feat"), W(p + ".second_mlp.0.pool"), W(p + ".second_mlp.3"),
+                          bn(p + ".first_mlp.1"), bn(p + ".second_mlp.1")};
+  };
+  Model& m = c->m;
+  m.agent.embed_proj = W(HE + ".embed.proj");
+  for (int lv = 0; lv < 3; ++lv) {
+    const std::string l = HE + ".levels." + std::to_string(lv), n = std::to_string(lv);
+    NatLevelW& k = m.agent.levels[lv];
+    for (int b = 0; b < 2; ++b) {
+      const std::string p = l + ".blocks." + std::to_string(b);
+      k.blocks[b] = {ln(p + ".norm1"), ln(p + ".norm2"), W(p + ".attn.qkv"), W(p + ".attn.proj"), W(p + ".mlp.fc1"), W(p + ".mlp.fc2"), P(p + ".attn.rpb")};
+    }
+    k.norm = ln(HE + ".norm" + n);
+    if (lv < 2) { k.reduction = W(l + ".downsample.reduction"); k.ds_norm = ln(l + ".downsample.norm"); }
+    k.lateral = W(HE + ".lateral_convs." + n);
+  }
+  m.agent.fpn_last = W(HE + ".fpn_conv.last");
+  m.agent.type_emb = P("agent_encoder.type_emb.weight");
+  const std::string EG = "agent_encoder.ego_state_emb";
+  m.agent.ego = {P(EG + ".query"), P(EG + ".pos_embed"), W(EG + ".attn.q"), W(EG + ".attn.kv"), W(EG + ".attn.out_proj")};
+  m.map.polygon_encoder = points("map_encoder.polygon_encoder");
+  m.map.speed_limit_emb = fourier("map_encoder.speed_limit_emb", 1);
+  m.map.type_emb = P("map_encoder.type_emb.weight"); m.map.on_route_emb = P("map_encoder.on_route_emb.weight");
+  m.map.traffic_light_emb = P("map_encoder.traffic_light_emb.weight"); m.map.unknown_speed_emb = P("map_encoder.unknown_speed_emb.weight");
+  m.stat.obj_encoder = fourier("static_objects_encoder.obj_encoder", 2);
+  m.stat.type_emb = P("static_objects_encoder.type_emb.weight");
+  m.pos_emb = fourier("pos_emb", 3);
+  for (int i = 0; i < 4; ++i) {
+    const std::string p = "encoder_blocks." + std::to_string(i);
+    m.encoder_blocks[i] = {ln(p + ".norm1"), ln(p + ".norm2"), W(p + ".attn.qkv"), W(p + ".attn.out_proj"), W(p + ".mlp.fc1"), W(p + ".mlp.fc2")};
+  }
+  m.norm = ln("norm");
+  const char* three[3] = {"loc", "yaw", "vel"};
+  for (int i = 0; i < 3; ++i) {
+    m.predictor[i] = mlp(std::string("agent_predictor.") + three[i] + "_predictor");
+    m.dec.head[i] = mlp(PD + "." + three[i] + "_head");
+  }
+  m.dec.r_encoder = points(PD + ".r_encoder");
+  m.dec.r_pos_emb = fourier(PD + ".r_pos_emb", 3);
+  m.dec.q_proj_r = W(PD + ".q_proj.r"); m.dec.q_proj_m = W(PD + ".q_proj.m");
+  m.dec.m_emb = P(PD + ".m_emb"); m.dec.m_pos = P(PD + ".m_pos");
+  for (int i = 0; i < 4; ++i) {
+    const std::string p = PD + ".decoder_blocks." + std::to_string(i);
+    DecoderBlockW& k = m.dec.decoder_blocks[i];
+    for (int j = 0; j < 4; ++j) k.norm[j] = ln(p + ".norm" + std::to_string(j + 1));
+    k.r2r_qkv = W(p + ".r2r_attn.qkv"); k.r2r_out = W(p + ".r2r_attn.out_proj");
+    k.m2m_qkv = W(p + ".m2m_attn.qkv"); k.m2m_qk0 = W(p + ".m2m_attn.qk0"); k.m2m_out = W(p + ".m2m_attn.out_proj");
+    k.cross_q = W(p + ".cross_attn.q"); k.cross_kv = W(p + ".cross_attn.kv"); k.cross_out = W(p + ".cross_attn.out_proj");
+    k.ffn0 = W(p + ".ffn.0"); k.ffn3 = W(p + ".ffn.3");
+  }
+  m.dec.kv_all = W(PD + ".kv_all"); m.dec.cat_x_proj_q = W(PD + ".cat_x_proj.q"); m.dec.cat_x_proj_x = W(PD + ".cat_x_proj.x");
+  m.hidden_proj0 = W("hidden_proj.0"); m.hidden_proj2 = W("hidden_proj.2");
+  m.ref_free_decoder = mlp("ref_free_decoder");
+  const std::string PH = PD + ".pi_head.mlp.";      // (the trainable tensors: the head and both backward entries of shared.hip read them live through these pointers)
+  c->pi = {P(PH + "0.weight"), P(PH + "0.bias"), P(PH + "1.weight"), P(PH + "1.bias"), P(PH + "3.weight"), P(PH + "3.bias")};
+  return c->err.empty() ? RIFT_OK : RIFT_ERR_ARG;
+}
+
 int rift_model_load(RiftCtx* h, const RiftTensorDesc* params, int n, void* stream) {
   Ctx* c = static_cast<Ctx*>(h);
   if (!c || !params) return RIFT_ERR_ARG;
@@ -1685,7 +1769,7 @@ int rift_model_load(RiftCtx* h, const RiftTensorDesc* params, int n, void* strea
   c->stream = (hipStream_t)stream;
   HIPCHK(c, hipSetDevice(c->device));
   c->loaded = false;                    // (until this load has succeeded there is no model: the entries that launch refuse to run)
-  c->pw.clear(); c->params.clear(); c->wconst.clear();      // (frees the images and the weight-only products)
+  c->pw.clear(); c->params.clear(); c->m = Model(); c->pi = RiftCtxCore::PiHead(); c->wc = Ctx::WeightOnly();      // (frees the images and the weight-only products; the table pointed into both maps)
   c->dry_need = 0;                      // (the first forward on new weights sizes its arena again: it also computes the weight-only products)
   for (int i = 0; i < n; ++i) {
     Param p; p.data = params[i].data; p.numel = params[i].numel; p.ndim = params[i].ndim;
@@ -1765,11 +1849,7 @@ int rift_model_load(RiftCtx* h, const RiftTensorDesc* params, int n, void* strea
   for (int i = 0; i < 3; ++i) TRY(pack_mlp_layer(c, PD + "." + hd[i]));
   TRY(pack_linear(c, "hidden_proj.0")); TRY(pack_linear(c, "hidden_proj.2"));
   TRY(pack_mlp_layer(c, "ref_free_decoder"));
-  // required unpacked tensors: fail early and loudly
-  const char* need[] = {"norm.weight", "agent_encoder.type_emb.weight", "map_encoder.type_emb.weight",
-                        "planning_decoder.m_emb", "planning_decoder.m_pos", "planning_decoder.pi_head.mlp.0.weight",
-                        "planning_decoder.pi_head.mlp.3.weight", "agent_encoder.ego_state_emb.query"};
-  for (const char* nme : need) if (!fptr(c, nme)) return RIFT_ERR_ARG;
+  TRY(resolve_model(c));      // (every tensor the forward reads: a missing one fails the load here)
   HIPCHK(c, hipGetLastError());
   c->loaded = true;
   return RIFT_OK;
@@ -1823,7 +1903,9 @@ int rift_forward(RiftCtx* h, const RiftFeatureBatch* B, const RiftOutputs* out, 
   if (!c->err.empty()) return RIFT_ERR_ARG;
   if (c->arena_off > c->arena_cap) {     // the launch pass allocated more than the sizing pass it was matched with: kernels were given scratch beyond the arena
     c->dry_need = 0;
-    c->err = "activation arena overrun: the forward allocated " + std::to_string(c->arena_off) + " B of a " + std::to_string(c->arena_cap) + " B arena (stale sizing pass)";
+    char msg[160];
+    snprintf(msg, sizeof(msg), "activation arena overrun: the forward allocated %zu B of a %zu B arena (stale sizing pass)", c->arena_off, c->arena_cap);
+    c->err = msg;
     (void)hipDeviceSynchronize();
     return RIFT_ERR_STATE;
   }

@@ -1,27 +1,22 @@
 // The context of one engine build (included by engine.hip inside the build: one type per MFMA operand format) and the per-forward context.
 #pragma once
-#include "launch.h"
+#include "model.h"
 #include "dec_w.h"
 #include "dropstats.h"
 #include "fwd_plan.h"
 
 namespace RIFT_NS {
 
-struct PWShape { int N = 0, K = 0, Kp = 0, Npad = 0; const float* bias = nullptr; };
-struct PW : PWShape {   // packed weight image of one linear map Y = X W^T (+ b); owns its images, lives in Ctx::pw and is handed on by reference
-  DevBuf<unsigned short> bf; DevBuf<float> f32;
-  DevBuf<unsigned short> hid;   // (fc2 weights of the fused encoder only) the same image in hidden-layer operand words (opfmt.h); pack_hid
-  DevBuf<float> own_bias;       // (pack_stacked_rows only) the stacked bias that `bias` points to
-};
-
 struct Tap { float* p; int64_t numel; };
 
 // The context of this build: the model side on top of the format-free core (ctx_core.h).  One type per operand format (rift_bf::Ctx,
 // rift_hf::Ctx); the entries of this build's table cast the C handle down once at the top.
 struct Ctx : RiftCtx {
-  std::unordered_map<std::string, PW> pw;
-  struct WConst { DevBuf<float> p; bool ready = false; };
-  std::unordered_map<std::string, WConst> wconst;   // activations that depend on (frozen) weights only, computed once per model load
+  std::unordered_map<std::string, PW> pw;      // the packed images by name: written by rift_model_load (and the transient key of rift_op_linear) only
+  Model m;                                     // the forward's operands, resolved from `pw` and `params` once per load (model.h)
+  // activations that depend on (frozen) weights only, computed once per model load, each for the fp32 and the 16-bit mode
+  struct WConst { struct V { DevBuf<float> p; bool ready = false; } v[2]; };
+  struct WeightOnly { WConst ego_q, Mb, mp[4]; } wc;      // the ego query through attn.q, m_emb through q_proj.m, m_pos through the layers' m2m qk0
   // activation arena (bump allocator, reset every forward).  A forward with RIFT_F_DEFER_HEAD alternates between the arenas of `slots`, so
   // that the policy head / loss / backward of step k (rift_forward_head, rift_loss_backward on another stream) read step k's activations
   // while the frozen trunk of step k + 1 already writes its own.

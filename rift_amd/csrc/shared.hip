@@ -82,9 +82,8 @@ static int loss_backward_impl(RiftCtx* c, const char* who, int kind, const RiftL
   else if (G <= 64 * 2) launch(c, "loss_kernel", loss_kernel<2>, lgrid, lblock, 0, p);
   else if (G <= 64 * 4) launch(c, "loss_kernel", loss_kernel<4>, lgrid, lblock, 0, p);
   else launch(c, "loss_kernel", loss_kernel<16>, lgrid, lblock, 0, p);
-  const std::string PH = "planning_decoder.pi_head.mlp.";
   launch(c, "pi_backward_kernel", pi_backward_kernel, dim3(nwg), dim3(256), 0, (const float*)c->last_qfinal, (const float*)c->last_hpi,
-         (const float*)c->l_dz.get(), rows, fptr(c, PH + "1.weight"), fptr(c, PH + "1.bias"), fptr(c, PH + "3.weight"), 1e-5f,
+         (const float*)c->l_dz.get(), rows, c->pi.ln_g, c->pi.ln_b, c->pi.w3, 1e-5f,
          c->l_partial.get());
   launch(c, "loss_reduce_kernel", loss_reduce_kernel, dim3(cdiv(RIFT_PI_NPARAM, 256)), dim3(256), 0, (const float*)c->l_partial.get(), nwg,
          out->flat_grad_sum, (const double*)c->l_S.get(), (const double*)c->l_cnt.get(), bs, out->stats, out->exchange);
@@ -125,9 +124,8 @@ int rift_head_backward(RiftCtx* c, const float* dlogits, int bs, int R, const Ri
   TRY(pi_backward_scratch(c, rows, nwg));
   DEVCHK(c, c->l_sink.reserve(2));
   launch(c, "head_dz_kernel", head_dz_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, dlogits, (const uint8_t*)c->last_rkpm, rows, M, c->l_dz.get());
-  const std::string PH = "planning_decoder.pi_head.mlp.";
   launch(c, "pi_backward_kernel", pi_backward_kernel, dim3(nwg), dim3(256), 0, (const float*)c->last_qfinal, (const float*)c->last_hpi,
-         (const float*)c->l_dz.get(), rows, fptr(c, PH + "1.weight"), fptr(c, PH + "1.bias"), fptr(c, PH + "3.weight"), 1e-5f,
+         (const float*)c->l_dz.get(), rows, c->pi.ln_g, c->pi.ln_b, c->pi.w3, 1e-5f,
          c->l_partial.get());
   // (no objective: zero scenes, the two sums land in the sink)
   launch(c, "loss_reduce_kernel", loss_reduce_kernel, dim3(cdiv(RIFT_PI_NPARAM, 256)), dim3(256), 0, (const float*)c->l_partial.get(), nwg,

@@ -3,6 +3,8 @@ that fails, and create / close cycles (csrc/devmem.h: DevBuf; tests/test_devmem_
 
 Default-size scenes with one to three reference lines: the allocation logic does not depend on the scene size.  Forwards run with
 no_drop=True, bn_update=False, so that two engines given the same input answer bit for bit; every comparison is torch.equal."""
+import re
+
 import pytest
 import torch
 
@@ -13,6 +15,13 @@ from tests import helpers as H
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 MISSING = "planning_decoder.pi_head.mlp.3.weight"
+# one tensor of each kind the forward reads: embedding tables, a raw vector, LayerNorms of every module, a Fourier frequency table, a
+# BatchNorm running statistic, a head's LayerNorm, the static-object table (no scene of this batch has static objects) and a mode embedding
+READ_BY_THE_FORWARD = ["map_encoder.on_route_emb.weight", "agent_encoder.ego_state_emb.pos_embed", "agent_encoder.history_encoder.norm1.bias",
+                       "encoder_blocks.2.norm2.bias", "pos_emb.freqs.weight", "map_encoder.polygon_encoder.second_mlp.1.running_var",
+                       "planning_decoder.decoder_blocks.3.norm4.weight", "planning_decoder.loc_head.mlp.1.weight", "ref_free_decoder.mlp.1.bias",
+                       "static_objects_encoder.type_emb.weight", "planning_decoder.m_emb"]
+OPTIONAL = "map_encoder.polygon_encoder.first_mlp.1.num_batches_tracked"
 _cache = {}
 
 
@@ -118,6 +127,30 @@ def test_failed_reload_is_refused_not_run():
         eng.forward(batch["cur_pluto_feature_torch"], no_drop=True, bn_update=False)
     with pytest.raises(RuntimeError, match=r"rift_loss_backward failed \(-3\).*no model is loaded"):
         eng.loss_backward("rift", batch)
+    eng.load_state_dict(_sd())
+    _same(_forward(eng, batch), out1)
+    torch.cuda.synchronize()
+    eng.close()
+
+
+def test_a_load_without_a_tensor_the_forward_reads_is_refused_by_name():
+    """Every tensor the forward reads is resolved by rift_model_load: a state dict that lacks one is refused THERE, with the tensor's name
+    in the message, and leaves no model -- the forward that follows answers RIFT_ERR_STATE (-3) ahead of any launch, so no kernel ever
+    sees the null pointer (forward is never called on a model that loaded with a tensor missing).  Only a BatchNorm's
+    num_batches_tracked is optional: an eval forward does not read it.  The last full load answers as the first one did."""
+    eng = _ffi.Engine(DEV)
+    eng.load_state_dict(_sd())
+    batch = _batch(2)
+    out1 = _forward(eng, batch)
+    for name in READ_BY_THE_FORWARD:
+        assert name in _sd()
+        with pytest.raises(RuntimeError, match=r"rift_model_load failed \(-1\).*missing parameter: " + re.escape(name) + r"$"):
+            eng.load_state_dict({k: v for k, v in _sd().items() if k != name})
+        with pytest.raises(RuntimeError, match=r"rift_forward failed \(-3\).*no model is loaded"):
+            eng.forward(batch["cur_pluto_feature_torch"], no_drop=True, bn_update=False)
+    assert OPTIONAL in _sd()
+    eng.load_state_dict({k: v for k, v in _sd().items() if k != OPTIONAL})
+    _same(_forward(eng, batch), out1)
     eng.load_state_dict(_sd())
     _same(_forward(eng, batch), out1)
     torch.cuda.synchronize()

@@ -454,16 +454,29 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
   pe_fill(f, q.b, Fr, 6, gr, 120, vr, pr);
   const int nt = q.a.ntiles + q.b.ntiles;
   const double rows = (double)q.a.rows + q.b.rows, groups = (double)gm + gr;
+  {   // what the passes hand to one another (tests/test_gpu_points_encoder.py): _a map polygons, _b reference lines; g in fp16 words
+    static const char* const nm[2][6] = {{"pe_s1_a", "pe_t1_a", "pe_s2_a", "pe_t2_a", "pe_gp_a", "pe_g_a"}, {"pe_s1_b", "pe_t1_b", "pe_s2_b", "pe_t2_b", "pe_gp_b", "pe_g_b"}};
+    const PeP* sd[2] = {&q.a, &q.b};
+    const int grp[2] = {gm, gr};
+    for (int i = 0; i < 2; ++i) {
+      tap(c, nm[i][0], (float*)sd[i]->s1, 128); tap(c, nm[i][1], (float*)sd[i]->t1, 128);
+      tap(c, nm[i][2], (float*)sd[i]->s2, 256); tap(c, nm[i][3], (float*)sd[i]->t2, 256);
+      if (!c->sw.pe_w) tap(c, nm[i][4], sd[i]->gp, (int64_t)grp[i] * 256);      // (pe_w_kernel keeps gp in registers: only pe_mid_kernel writes it)
+      tap(c, nm[i][5], (float*)sd[i]->Fmid, (int64_t)sd[i]->rows * 128);
+    }
+  }
   const bool stats_p = f.train && c->sw.pe_w;          // persistent pass A: one partial per workgroup (pe_fused.h)
   // reference lines packed at tile granularity (pe_fused.h: pe_pack_body): table + round count in device memory, built by one extra block
   // of pass A's launch (eval mode: a launch of its own)
   const bool packb = c->sw.pe_w && c->sw.pe_pack && gr > 0 && f.r_tiles != nullptr;
   int* pk_tab = nullptr; int* pk_hdr = nullptr;
   PePackP pk; memset(&pk, 0, sizeof(pk));
+  // (the packing's own bound, not the ceil(lines / 2) rounds of the unpacked walk: segments of an odd number of long lines end on a
+  // one-line round each -- 99 lines of six or more tiles fill 3 * 17 = 51 records, not 50)
+  const int maxr = pe_pack_max_rounds(gr);
   if (packb) {
-    const int maxr = cdiv(q.b.rows, PEW_ROUND_ROWS);
     pk_tab = A_alloc<int>(c, (size_t)std::max(maxr, 1) * PEW_TAB_INTS); pk_hdr = A_alloc<int>(c, 4);
-    pk.tiles = f.r_tiles; pk.nlines = gr; pk.tab = pk_tab; pk.hdr = pk_hdr; pk.max_rounds = maxr;
+    pk.tiles = f.r_tiles; pk.nlines = gr; pk.tab = pk_tab; pk.hdr = pk_hdr; pk.max_rounds = maxr; pk.fail = c->nonfinite.get();
     tap(c, "pe_pack_hdr", (float*)pk_hdr, 4); tap(c, "pe_pack_tab", (float*)pk_tab, (int64_t)std::max(maxr, 1) * PEW_TAB_INTS);
     if (!stats_p) { c->prof_flops = 0.0; launch(c, "pe_pack_lines_kernel", pe_pack_lines_kernel, dim3(1), dim3(256), (size_t)gr * 2 * sizeof(int), pk); }
   }
@@ -489,6 +502,7 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
   PeLiveP lv; memset(&lv, 0, sizeof(lv));
   const bool live = stats_p && c->sw.pe_live;
   int pew_grid = std::max(c->sw.nat_grid, 2), pew_ga = 0;      // (two sides: at one workgroup the split below leaves the polygons none -- RIFT_NAT_GRID=1)
+  // (the two-line round counts only size the grid and its first split here: with packing or a live list the split is remade on the device)
   if (c->sw.pe_w) pew_split(cdiv(q.a.rows, PEW_ROUND_ROWS), cdiv(q.b.rows, PEW_ROUND_ROWS), &pew_grid, &pew_ga);
   if (live || packb) {
     const PeP* sd[2] = {&q.a, &q.b};
@@ -499,6 +513,7 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
     lv.grid = pew_grid; lv.hdr = A_alloc<int>(c, 4);
     lv.packed_b = pk_hdr;
     tap(c, "pe_live_hdr", (float*)lv.hdr, 4);
+    tap(c, "pe_live_a", (float*)lv.live[0], std::max(lv.nr[0], 1)); tap(c, "pe_live_b", (float*)lv.live[1], std::max(lv.nr[1], 1));      // (written in train mode only)
   }
   const bool lvblock = live || packb;       // the extra block of the BatchNorm-1 finalize launch
   for (int mode = dpx ? 1 : 0; mode <= (dpx ? 2 : 0); ++mode) {
@@ -522,7 +537,8 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
     const int nwg[2] = {lvblock ? grid : ga, lvblock ? grid : grid - ga};       // (live / packed: the split is made on the device; room for either extreme)
     for (int i = 0; i < 2; ++i) {
       const PeP& o = *src[i]; PeWSide& d = *dst[i];
-      d.F = o.F; d.Cin = o.Cin; d.valid = o.valid; d.rows = o.rows; d.npts = npts[i]; d.nrounds = cdiv(o.rows, PEW_ROUND_ROWS);
+      d.F = o.F; d.Cin = o.Cin; d.valid = o.valid; d.rows = o.rows; d.npts = npts[i];
+      d.nrounds = (i == 1 && packb) ? maxr : cdiv(o.rows, PEW_ROUND_ROWS);      // (packed: the kernel's end mark has to lie beyond every record)
       d.img = c->img.pew_img[i].get(); d.w3b = o.w3b; d.b1 = o.b1; d.b2 = o.b2; d.b3 = o.b3; d.s1 = o.s1; d.t1 = o.t1;
       d.live = (live && !(i == 1 && packb)) ? lv.live[i] : nullptr;
       if (i == 1) { d.ptab = pk_tab; d.phdr = pk_hdr; }
@@ -582,6 +598,11 @@ float* points_encoder(Fwd& f, const float* F, int Cin, int groups, int n, const 
   float* out = A_alloc<float>(c, (size_t)groups * 128);
   launch(c, "masked_maxpool_kernel", masked_maxpool_kernel, dim3(cdiv((long long)groups * 128, 256)), dim3(256), 0, (const float*)O, 128, groups, n, 128,
          valid, out);
+  {   // the fused pair's taps, as far as this path has them: g here in fp32; no gp (G1 is without second_mlp.0's bias, which rides on `feat`)
+    static const char* const nm[2][5] = {{"pe_s1_a", "pe_t1_a", "pe_s2_a", "pe_t2_a", "pe_g_a"}, {"pe_s1_b", "pe_t1_b", "pe_s2_b", "pe_t2_b", "pe_g_b"}};
+    const char* const* t = nm[n == 20 ? 0 : 1];
+    tap(c, t[0], s1, 128); tap(c, t[1], t1, 128); tap(c, t[2], s2, 256); tap(c, t[3], t2, 256); tap(c, t[4], H2, (int64_t)rows * 256);
+  }
   return out;
 }
 
@@ -2027,7 +2048,9 @@ int rift_check_finite(RiftCtx* h, void* stream) {
   HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));
   if (!flag) return RIFT_OK;
   HIPCHK(c, hipMemsetAsync(c->nonfinite.get(), 0, sizeof(int), (hipStream_t)stream));
-  c->err = (flag & 2) ? "the in-launch ranking of the history encoder's sequences gave up waiting for a predecessor (kernels.h: rank_scene_body): the forward's "
+  c->err = (flag & 4) ? "the reference-line packing of the PointsEncoder wanted more rounds than its table holds (pe_fused.h: pe_pack_body): the forward's "
+                        "results are invalid; non-finite flag raised"
+         : (flag & 2) ? "the in-launch ranking of the history encoder's sequences gave up waiting for a predecessor (kernels.h: rank_scene_body): the forward's "
                         "results are invalid; non-finite flag raised"
                       : "non-finite decoder queries (the reference asserts torch.isfinite(q).all(), planning_decoder.py:175)";
   return RIFT_ERR_NONFINITE;

@@ -50,12 +50,22 @@ struct PeP {
 // Round record: 32 ints -- [T] (T < 16) tile descriptor (first point row of the tile << 8) | (tile index within its line << 4) | line slot of
 // the round, or -1; [16 + s] line slot s: first tile | last tile << 8 | (tiles dropped) << 16 | (exists) << 17.
 #define PEW_TAB_INTS 32
+#define PEW_PACK_SEGS 32
 struct PePackP {
   const uint8_t* tiles; int nlines;     // (nlines) tiles of every line up to its last valid point (prep_kernel: refline_mask_body)
-  int* tab;                             // out: [max rounds][PEW_TAB_INTS]
-  int* hdr;                             // out: [0] packed rounds
-  int max_rounds;
+  int* tab;                             // out: [max_rounds][PEW_TAB_INTS]
+  int* hdr;                             // out: [0] packed rounds (<= max_rounds)
+  int max_rounds;                       // records of `tab` (pe_pack_max_rounds): no record beyond it is written
+  int* fail;                            // the context's sticky flag: value 4 (bit 2) is ORed in if the packing wanted more than max_rounds rounds
 };
+// The segments of pe_pack_body and the table they can fill, for the kernel and for the host that sizes the table: the line sequence is cut
+// into nseg segments of `per` lines (the last one shorter), packed independently.  A segment opens a new round only when the line fits no
+// open one, and a round that holds ONE line has room for any other (a line has at most 8 tiles, a round 16 tiles / 16 lines): whenever a
+// round is opened every other round of the segment holds at least two lines, so a segment of n lines ends with at most ceil(n / 2) rounds
+// -- nseg * ceil(per / 2) in all, which is MORE than the ceil(nlines / 2) two-line rounds of the unpacked walk when `per` is odd.
+__host__ __device__ inline int pe_pack_nseg(int nlines) { const int s = nlines / 32; return s < 1 ? 1 : (s > PEW_PACK_SEGS ? PEW_PACK_SEGS : s); }
+__host__ __device__ inline int pe_pack_per(int nlines) { const int s = pe_pack_nseg(nlines); return (nlines + s - 1) / s; }
+__host__ __device__ inline int pe_pack_max_rounds(int nlines) { return pe_pack_nseg(nlines) * ((pe_pack_per(nlines) + 1) / 2); }
 // Packing = bounded-space first fit (three open rounds; a line goes into the first open round with room, else the oldest round is closed
 // and a new one opened): 16-tile rounds come out ~14.2 tiles full at the benchmark's lengths (plain next-fit: 13.6; ~330 rounds instead
 // of 512 two-line rounds).  It sits on the map chain, i.e. on the step's critical path, so it has to be short: the tiles per line come from
@@ -82,15 +92,13 @@ struct PeLiveP {
   const int* packed_b;             // if set: encoder b's rounds are PACKED (pe_pack_body): their number comes from here, no live list for b
 };
 
-#define PEW_PACK_SEGS 32
 // (runs as one extra block of pe_stats1p_kernel, or as pe_pack_lines_kernel in eval mode: 256 threads; `pk_lds`: 2 * nlines ints)
 __device__ __forceinline__ void pe_pack_body(const PePackP& q, int* __restrict__ pk_lds, int* __restrict__ seg_rounds /*[PEW_PACK_SEGS + 1]*/) {
   const int tid = threadIdx.x, NT = blockDim.x;
   int* const enc = pk_lds + q.nlines;   // (segment-local round << 16) | (tiles << 8) | (first tile << 4) | slot
   for (int l = tid; l < q.nlines; l += NT) pk_lds[l] = q.tiles[l];
   __syncthreads();
-  const int nseg = min(PEW_PACK_SEGS, max(1, q.nlines / 32));
-  const int per = (q.nlines + nseg - 1) / nseg;
+  const int nseg = pe_pack_nseg(q.nlines), per = pe_pack_per(q.nlines);
   if (tid < PEW_PACK_SEGS) {
     int nround = 0;
     if (tid < nseg) {
@@ -122,16 +130,20 @@ __device__ __forceinline__ void pe_pack_body(const PePackP& q, int* __restrict__
   if (tid == 0) {
     seg_rounds[0] = 0;
     for (int i = 1; i <= PEW_PACK_SEGS; ++i) seg_rounds[i] += seg_rounds[i - 1];
-    q.hdr[0] = seg_rounds[PEW_PACK_SEGS];
+    // the table has max_rounds records (pe_pack_max_rounds bounds the count): more would be a packing that broke its own bound --
+    // nothing beyond the table is written or announced, and the forward is flagged invalid (rift_check_finite)
+    if (seg_rounds[PEW_PACK_SEGS] > q.max_rounds && q.fail) atomicOr(q.fail, 4);
+    q.hdr[0] = min(seg_rounds[PEW_PACK_SEGS], q.max_rounds);
   }
   __syncthreads();
-  const int nr = seg_rounds[PEW_PACK_SEGS];
+  const int nr = min(seg_rounds[PEW_PACK_SEGS], q.max_rounds);
   for (int i = tid; i < nr * PEW_TAB_INTS; i += NT) q.tab[i] = (i & 31) < 16 ? -1 : 0;      // unused tiles / line slots
   __syncthreads();                       // (the same block writes the records below: ordered by the barrier)
   for (int l = tid; l < q.nlines; l += NT) {
     const int e = enc[l];
     if (e < 0) continue;
     const int round = (e >> 16) + seg_rounds[l / per], t = (e >> 8) & 0xff, t0 = (e >> 4) & 15, slot = e & 15;
+    if (round >= nr) continue;
     int* rec = q.tab + (size_t)round * PEW_TAB_INTS;
     for (int k = 0; k < t; ++k) rec[t0 + k] = ((l * 120 + 16 * k) << 8) | (k << 4) | slot;
     rec[16 + slot] = t0 | ((t0 + t - 1) << 8) | ((t < 8 ? 1 : 0) << 16) | (1 << 17);

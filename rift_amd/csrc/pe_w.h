@@ -31,7 +31,7 @@ struct PeWSrc { const float *w1, *w2, *w3; int Cin; };   // first_mlp.0 (128, Ci
 struct PeWSide {
   const float* F; int Cin;                // (rows, Cin) fp32 point features
   const uint8_t* valid;                   // (rows)
-  int rows, npts, nrounds;                // npts = 20 | 120 points per polyline; nrounds = ceil(rows / 240)
+  int rows, npts, nrounds;                // npts = 20 | 120 points per polyline; nrounds = ceil(rows / 240), packed side b: the table's records (the end mark of the round walk)
   const unsigned short* img;              // pack_pew_kernel: PEW_FRAGS fragments
   const unsigned short* w3b;              // second_mlp.0 pool half, fragment-major bf16 image [256][256] (engine pack_cols)
   const float *b1, *b2, *b3, *s1, *t1;    // biases; BatchNorm-1 folded to y = x s1 + t1

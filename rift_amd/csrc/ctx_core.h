@@ -8,15 +8,10 @@
 
 #include <set>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/rift_hip.h"
 #include "devmem.h"
-
-namespace rift {
-struct Param { void* data; int64_t numel; int ndim; int64_t shape[4]; };
-}
 
 struct RiftCtxCore {
   int opfmt = 0;                         // FIRST member (set by rift_ctx_create of the build): abi.cpp reads it to route a call to the build (bf16 / fp16 operands) that owns the context
@@ -32,7 +27,6 @@ struct RiftCtxCore {
   std::vector<Rec> prof_recs;
   int poison_lds = -1;                   // RIFT_POISON_LDS diagnostic (see lds_poison_kernel)
   struct { std::string delay_label; long long delay_ticks = 0; } dg;      // RIFT_DELAY diagnostic (see delay_kernel)
-  std::unordered_map<std::string, rift::Param> params;      // written by rift_model_load only
   struct PiHead { const float *w0 = nullptr, *b0 = nullptr, *ln_g = nullptr, *ln_b = nullptr, *w3 = nullptr, *b3 = nullptr; } pi;   // planning_decoder.pi_head.mlp.{0,1,3}: the trainable tensors, read LIVE through these pointers (resolved at load)
   bool loaded = false;
   // state of the last forward, consumed by rift_loss_backward

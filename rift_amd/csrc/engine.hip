@@ -7,7 +7,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <set>
 #include <cmath>
 #include <string>
 #include <unordered_map>
@@ -33,6 +32,7 @@
 #include "ego_fused.h"
 #include "heads_fused.h"
 #include "pi_fused.h"
+#include "model_load.h"
 
 #define ENC_NW 8
 
@@ -61,124 +61,6 @@ float* wconst_get(Ctx* c, Ctx::WConst& slot, size_t n, bool fp32, bool* fill) {
   *fill = !w.ready && !c->dry;
   if (!c->dry) w.ready = true;
   return w.p.get();
-}
-
-// ---- weight packing -------------------------------------------------------------------
-int pack(Ctx* c, const std::string& key, const float* src, int n_src, int N, int K, int src_row_off,
-         int src_col_off, int src_ld, int conv_C, int tap_lo, int tap_n, const float* bias) {
-  PW w;
-  w.N = N; w.K = K; w.Kp = (K + 31) & ~31; w.Npad = (N + 15) & ~15; w.bias = bias;
-  const size_t cnt = (size_t)w.Npad * w.Kp;
-  DEVCHK(c, w.bf.reserve(cnt));
-  DEVCHK(c, w.f32.reserve(cnt));
-  const int blocks = cdiv((long long)cnt, 256);
-  hipLaunchKernelGGL(pack_weight_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, src + src_col_off, (void*)w.bf.get(), n_src, K,
-                     w.Npad, w.Kp, conv_C, tap_lo, tap_n, src_row_off, src_ld);
-  hipLaunchKernelGGL(pack_weight_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, src + src_col_off, (void*)w.f32.get(),
-                     n_src, K, w.Npad, w.Kp, conv_C, tap_lo, tap_n, src_row_off, src_ld);
-  c->pw[key] = std::move(w);
-  return RIFT_OK;
-}
-
-// + the hidden-layer-operand image of an already packed weight (the fused scene encoder's fc2: its A rows are GELU outputs, common.h: gelu4_hid)
-int pack_hid(Ctx* c, const std::string& key) {
-  PW& w = c->pw[key];
-  const size_t cnt = (size_t)w.Npad * w.Kp;
-  DEVCHK(c, w.hid.reserve(cnt));
-  hipLaunchKernelGGL(pack_weight_hid_kernel, dim3(cdiv((long long)cnt, 256)), dim3(256), 0, c->stream, (const float*)w.f32.get(), w.hid.get(), w.Npad, w.Kp);
-  return RIFT_OK;
-}
-
-int pack_linear(Ctx* c, const std::string& prefix) {   // nn.Linear
-  const Param* w = find(c, prefix + ".weight");
-  if (!w || w->ndim != 2) { c->err = "missing linear " + prefix; return RIFT_ERR_ARG; }
-  const Param* b = find(c, prefix + ".bias");
-  return pack(c, prefix, (const float*)w->data, (int)w->shape[0], (int)w->shape[0], (int)w->shape[1], 0, 0,
-              (int)w->shape[1], 0, 0, 0, b ? (const float*)b->data : nullptr);
-}
-
-int pack_conv(Ctx* c, const std::string& prefix) {     // nn.Conv1d k=3 -> tap-major [N][3*C]
-  const Param* w = find(c, prefix + ".weight");
-  if (!w || w->ndim != 3 || w->shape[2] != 3) { c->err = "missing conv " + prefix; return RIFT_ERR_ARG; }
-  const Param* b = find(c, prefix + ".bias");
-  const int C = (int)w->shape[1];
-  return pack(c, prefix, (const float*)w->data, (int)w->shape[0], (int)w->shape[0], 3 * C, 0, 0, 0, C, 0, 3,
-              b ? (const float*)b->data : nullptr);
-}
-
-// rows [r0, r0+n_src) of an (R, K) matrix as a GEMM with N output columns (rows beyond n_src are zero)
-int pack_rows(Ctx* c, const std::string& key, const std::string& wname, const std::string& bname, int r0,
-              int n_src, int N) {
-  const Param* w = find(c, wname);
-  if (!w || w->ndim != 2) { c->err = "missing matrix " + wname; return RIFT_ERR_ARG; }
-  const Param* b = bname.empty() ? nullptr : find(c, bname);
-  return pack(c, key, (const float*)w->data, n_src, N, (int)w->shape[1], r0, 0, (int)w->shape[1], 0, 0, 0,
-              b ? (const float*)b->data + r0 : nullptr);
-}
-
-// columns [c0, c0+K) of a Linear weight (N, Ktot)
-int pack_cols(Ctx* c, const std::string& key, const std::string& prefix, int c0, int K, bool with_bias) {
-  const Param* w = find(c, prefix + ".weight");
-  if (!w || w->ndim != 2) { c->err = "missing linear " + prefix; return RIFT_ERR_ARG; }
-  const Param* b = with_bias ? find(c, prefix + ".bias") : nullptr;
-  return pack(c, key, (const float*)w->data, (int)w->shape[0], (int)w->shape[0], K, 0, c0, (int)w->shape[1], 0, 0, 0,
-              b ? (const float*)b->data : nullptr);
-}
-
-// rows [r0, r0+n) of `nsrc` (N_src, K) matrices stacked into one (nsrc*n, K) GEMM weight (+ stacked bias, engine-owned)
-int pack_stacked_rows(Ctx* c, const std::string& key, const std::vector<std::string>& wnames, const std::vector<std::string>& bnames,
-                      int r0, int n) {
-  const Param* w0 = find(c, wnames[0]);
-  if (!w0 || w0->ndim != 2) { c->err = "missing matrix " + wnames[0]; return RIFT_ERR_ARG; }
-  const int K = (int)w0->shape[1], ns = (int)wnames.size();
-  PW w;
-  w.N = ns * n; w.K = K; w.Kp = (K + 31) & ~31; w.Npad = (w.N + 15) & ~15;
-  if (n % 16) { c->err = "pack_stacked_rows: n % 16"; return RIFT_ERR_ARG; }
-  const size_t cnt = (size_t)w.Npad * w.Kp;
-  DEVCHK(c, w.bf.reserve(cnt));
-  DEVCHK(c, w.f32.reserve(cnt));
-  DEVCHK(c, w.own_bias.reserve((size_t)w.N));
-  float* bias = w.own_bias.get();
-  for (int i = 0; i < ns; ++i) {
-    const Param* wi = find(c, wnames[i]);
-    const Param* bi = find(c, bnames[i]);
-    if (!wi || !bi || wi->shape[1] != K) { c->err = "missing matrix " + wnames[i]; return RIFT_ERR_ARG; }
-    const size_t off = (size_t)i * n * w.Kp;     // a 16-row block of a fragment-major image starts at the row-major offset of its first row
-    const int blocks = cdiv((long long)n * w.Kp, 256);
-    hipLaunchKernelGGL(pack_weight_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, (const float*)wi->data, (void*)(w.bf.get() + off),
-                       n, K, n, w.Kp, 0, 0, 0, r0, K);
-    hipLaunchKernelGGL(pack_weight_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, (const float*)wi->data, (void*)(w.f32.get() + off),
-                       n, K, n, w.Kp, 0, 0, 0, r0, K);
-    HIPCHK(c, hipMemcpyAsync(bias + (size_t)i * n, (const float*)bi->data + r0, (size_t)n * 4, hipMemcpyDeviceToDevice, c->stream));
-  }
-  w.bias = bias;
-  c->pw[key] = std::move(w);
-  return RIFT_OK;
-}
-
-int pack_mlp_layer(Ctx* c, const std::string& p) { TRY(pack_linear(c, p + ".mlp.0")); return pack_linear(c, p + ".mlp.3"); }
-
-int pack_fourier(Ctx* c, const std::string& p, int D) {
-  for (int d = 0; d < D; ++d) {
-    TRY(pack_linear(c, p + ".mlps." + std::to_string(d) + ".0"));
-    TRY(pack_cols(c, p + ".mlps." + std::to_string(d) + ".0.lo", p + ".mlps." + std::to_string(d) + ".0", 0, 128, true));     // fused kernel:
-    TRY(pack_cols(c, p + ".mlps." + std::to_string(d) + ".0.last", p + ".mlps." + std::to_string(d) + ".0", 128, 1, false));  // K = 128 + rank-1
-    TRY(pack_linear(c, p + ".mlps." + std::to_string(d) + ".3"));
-  }
-  return pack_linear(c, p + ".to_out.2");
-}
-
-int pack_points_encoder(Ctx* c, const std::string& p) {
-  TRY(pack_linear(c, p + ".first_mlp.0"));
-  TRY(pack_linear(c, p + ".first_mlp.3"));
-  TRY(pack_cols(c, p + ".second_mlp.0.feat", p + ".second_mlp.0", 0, 256, true));
-  TRY(pack_cols(c, p + ".second_mlp.0.pool", p + ".second_mlp.0", 256, 256, false));
-  return pack_linear(c, p + ".second_mlp.3");
-}
-
-int pack_self_mha(Ctx* c, const std::string& p) {
-  TRY(pack_rows(c, p + ".qkv", p + ".in_proj_weight", p + ".in_proj_bias", 0, 384, 384));
-  return pack_linear(c, p + ".out_proj");
 }
 
 // ---- GEMM dispatch -----------------------------------------------------------------------
@@ -269,8 +151,6 @@ int set_lds_attrs(Ctx* c) {
 #undef SETATTR_N
   return RIFT_OK;
 }
-
-const std::string HE = "agent_encoder.history_encoder", PD = "planning_decoder";
 
 // RCCL through dlopen (rift_comm_*): the library has no link-time dependency on a communication library; an RCCL that is already in the
 // process (torch's) is reused so that one process does not run two of them.
@@ -1562,227 +1442,6 @@ void rift_ctx_destroy(RiftCtx* h) {      // (this build's entry: its own context
 
 const char* rift_last_error(RiftCtx* h) { return h ? h->err.c_str() : "null context"; }
 
-// the parameters of the two NAT blocks of level lv, for the packers of the wave-private level kernels (NatL0WSrc / NatL1WSrc / NatL2WSrc)
-template <class Src>
-static void nat_blocks_src(Ctx* c, Src& q, int lv) {
-  for (int b = 0; b < 2; ++b) {
-    const std::string p = HE + ".levels." + std::to_string(lv) + ".blocks." + std::to_string(b);
-    auto& k = q.blk[b];
-    k.ln1_g = fptr(c, p + ".norm1.weight"); k.ln1_b = fptr(c, p + ".norm1.bias"); k.wqkv = fptr(c, p + ".attn.qkv.weight"); k.bqkv = fptr(c, p + ".attn.qkv.bias");
-    k.rpb = fptr(c, p + ".attn.rpb"); k.wproj = fptr(c, p + ".attn.proj.weight"); k.bproj = fptr(c, p + ".attn.proj.bias");
-    k.ln2_g = fptr(c, p + ".norm2.weight"); k.ln2_b = fptr(c, p + ".norm2.bias"); k.w1 = fptr(c, p + ".mlp.fc1.weight"); k.b1 = fptr(c, p + ".mlp.fc1.bias");
-    k.w2 = fptr(c, p + ".mlp.fc2.weight"); k.b2 = fptr(c, p + ".mlp.fc2.bias");
-  }
-}
-
-// rift_model_load: the history encoder's GEMM images and the weight streams of its wave-private level kernels
-static int pack_history_encoder(Ctx* c) {
-  TRY(pack_conv(c, HE + ".embed.proj"));
-  for (int lv = 0; lv < 3; ++lv) {
-    for (int b = 0; b < 2; ++b) {
-      const std::string p = HE + ".levels." + std::to_string(lv) + ".blocks." + std::to_string(b);
-      TRY(pack_linear(c, p + ".attn.qkv")); TRY(pack_linear(c, p + ".attn.proj"));
-      TRY(pack_linear(c, p + ".mlp.fc1")); TRY(pack_linear(c, p + ".mlp.fc2"));
-    }
-    if (lv < 2) TRY(pack_conv(c, HE + ".levels." + std::to_string(lv) + ".downsample.reduction"));
-    TRY(pack_conv(c, HE + ".lateral_convs." + std::to_string(lv)));
-  }
-  {  // wave-private level-0 kernel: K-permuted weight fragments + parameter block (nat_l0w.h)
-    NatL0WSrc q; memset(&q, 0, sizeof(q));
-    q.w_tok = fptr(c, HE + ".embed.proj.weight"); q.b_tok = fptr(c, HE + ".embed.proj.bias");
-    nat_blocks_src(c, q, 0);
-    q.fn_g = fptr(c, HE + ".norm0.weight"); q.fn_b = fptr(c, HE + ".norm0.bias");
-    q.w_ds = fptr(c, HE + ".levels.0.downsample.reduction.weight"); q.ds_g = fptr(c, HE + ".levels.0.downsample.norm.weight"); q.ds_b = fptr(c, HE + ".levels.0.downsample.norm.bias");
-    if (!c->err.empty()) return RIFT_ERR_ARG;
-    DEVCHK(c, c->img.l0w_img.reserve((size_t)L0W_NFRAG * 512)); DEVCHK(c, c->img.l0w_par.reserve(L0W_NPAR));
-    l0w_pack(q, c->img.l0w_img.get(), c->img.l0w_par.get(), c->stream);
-  }
-  {  // wave-private level-1 kernel (nat_l1w.h)
-    NatL1WSrc q; memset(&q, 0, sizeof(q));
-    nat_blocks_src(c, q, 1);
-    q.fn_g = fptr(c, HE + ".norm1.weight"); q.fn_b = fptr(c, HE + ".norm1.bias");
-    q.w_ds = fptr(c, HE + ".levels.1.downsample.reduction.weight"); q.ds_g = fptr(c, HE + ".levels.1.downsample.norm.weight"); q.ds_b = fptr(c, HE + ".levels.1.downsample.norm.bias");
-    if (!c->err.empty()) return RIFT_ERR_ARG;
-    DEVCHK(c, c->img.l1w_img.reserve((size_t)L1W_NFRAG * 512)); DEVCHK(c, c->img.l1w_par.reserve(L1W_NPAR));
-    l1w_pack(q, c->img.l1w_img.get(), c->img.l1w_par.get(), c->stream);
-  }
-  {  // wave-private level-2 kernel (nat_l2w.h)
-    NatL2WSrc q; memset(&q, 0, sizeof(q));
-    nat_blocks_src(c, q, 2);
-    q.fn_g = fptr(c, HE + ".norm2.weight"); q.fn_b = fptr(c, HE + ".norm2.bias");
-    if (!c->err.empty()) return RIFT_ERR_ARG;
-    DEVCHK(c, c->img.l2w_img.reserve((size_t)2 * L2W_BLK_FRAGS * 512)); DEVCHK(c, c->img.l2w_par.reserve(L2W_NPAR));
-    l2w_pack(q, c->img.l2w_img.get(), c->img.l2w_par.get(), c->stream);
-  }
-  {  // fpn_conv at the last step: taps 0,1 only -> [128][256]
-    const Param* w = find(c, HE + ".fpn_conv.weight");
-    const Param* b = find(c, HE + ".fpn_conv.bias");
-    if (!w || !b) { c->err = "missing fpn_conv"; return RIFT_ERR_ARG; }
-    TRY(pack(c, HE + ".fpn_conv.last", (const float*)w->data, 128, 128, 256, 0, 0, 0, 128, 0, 2, (const float*)b->data));
-  }
-  return RIFT_OK;
-}
-
-// rift_model_load: the weight streams / parameter blocks of the wave-private encoder, Fourier, PointsEncoder and decoder kernels
-static int pack_streamed_images(Ctx* c) {
-  {  // dense-traffic scene encoder (enc_w.h)
-    EncWSrc q; memset(&q, 0, sizeof(q));
-    for (int i = 0; i < 4; ++i) {
-      const std::string p = "encoder_blocks." + std::to_string(i);
-      EncWSrc::L& k = q.l[i];
-      k.ln1_g = fptr(c, p + ".norm1.weight"); k.ln1_b = fptr(c, p + ".norm1.bias"); k.ln2_g = fptr(c, p + ".norm2.weight"); k.ln2_b = fptr(c, p + ".norm2.bias");
-      k.w_in = fptr(c, p + ".attn.in_proj_weight"); k.b_in = fptr(c, p + ".attn.in_proj_bias");
-      k.wo = fptr(c, p + ".attn.out_proj.weight"); k.bo = fptr(c, p + ".attn.out_proj.bias");
-      k.w1 = fptr(c, p + ".mlp.fc1.weight"); k.b1 = fptr(c, p + ".mlp.fc1.bias"); k.w2 = fptr(c, p + ".mlp.fc2.weight"); k.b2 = fptr(c, p + ".mlp.fc2.bias");
-    }
-    q.fn_g = fptr(c, "norm.weight"); q.fn_b = fptr(c, "norm.bias");
-    if (!c->err.empty()) return RIFT_ERR_ARG;
-    for (int i = 0; i < 4; ++i) {
-      const std::string p = PD + ".decoder_blocks." + std::to_string(i) + ".cross_attn";
-      q.dkv_w[i] = fptr(c, p + ".in_proj_weight"); q.dkv_b[i] = fptr(c, p + ".in_proj_bias");
-    }
-    if (!c->err.empty()) return RIFT_ERR_ARG;
-    DEVCHK(c, c->img.encw_img.reserve((size_t)(4 * ENCW_LAYER_FRAGS + ENCW_TAIL_FRAGS) * 512)); DEVCHK(c, c->img.encw_par.reserve(ENCW_NPAR));
-    encw_pack(q, c->img.encw_img.get(), c->img.encw_par.get(), c->stream);
-  }
-  {  // wave-private Fourier embeddings (fo_w.h): weight streams + parameter blocks of the three embeddings of the fused launch
-    const std::string emb[3] = {"pos_emb", "map_encoder.speed_limit_emb", PD + ".r_pos_emb"};
-    const int dims[3] = {3, 1, 3};
-    for (int i = 0; i < 3; ++i) {
-      FoWSrc q; memset(&q, 0, sizeof(q));
-      q.D = dims[i];
-      for (int d = 0; d < q.D; ++d) {
-        const std::string m = emb[i] + ".mlps." + std::to_string(d);
-        q.w0[d] = fptr(c, m + ".0.weight"); q.b0[d] = fptr(c, m + ".0.bias"); q.lng[d] = fptr(c, m + ".1.weight"); q.lnb[d] = fptr(c, m + ".1.bias");
-        q.w3[d] = fptr(c, m + ".3.weight"); q.b3[d] = fptr(c, m + ".3.bias");
-      }
-      q.og = fptr(c, emb[i] + ".to_out.0.weight"); q.ob = fptr(c, emb[i] + ".to_out.0.bias");
-      q.wo = fptr(c, emb[i] + ".to_out.2.weight"); q.bo = fptr(c, emb[i] + ".to_out.2.bias"); q.freqs = fptr(c, emb[i] + ".freqs.weight");
-      if (!c->err.empty()) return RIFT_ERR_ARG;
-      DEVCHK(c, c->img.fow_img[i].reserve((size_t)7 * 32 * 512)); DEVCHK(c, c->img.fow_par[i].reserve(FOW_NPAR));
-      fow_pack(q, c->img.fow_img[i].get(), c->img.fow_par[i].get(), c->stream);
-    }
-  }
-  {  // wave-private PointsEncoder pass B (pe_w.h): W1 | W2 | W3a streams of the two encoders
-    const std::string enc[2] = {"map_encoder.polygon_encoder", PD + ".r_encoder"};
-    const int cin[2] = {10, 6};
-    for (int i = 0; i < 2; ++i) {
-      PeWSrc q; q.Cin = cin[i];
-      q.w1 = fptr(c, enc[i] + ".first_mlp.0.weight"); q.w2 = fptr(c, enc[i] + ".first_mlp.3.weight"); q.w3 = fptr(c, enc[i] + ".second_mlp.0.weight");
-      if (!c->err.empty()) return RIFT_ERR_ARG;
-      DEVCHK(c, c->img.pew_img[i].reserve((size_t)PEW_FRAGS * 512));
-      pew_pack(q, c->img.pew_img[i].get(), c->stream);
-    }
-  }
-  {  // wave-private decoder kernel (dec_w.h): the layers' weight stream and parameter blocks
-    DecWSrc q; memset(&q, 0, sizeof(q));
-    for (int i = 0; i < 4; ++i) {
-      const std::string p = PD + ".decoder_blocks." + std::to_string(i);
-      DecWSrc::L& k = q.l[i];
-      for (int n = 0; n < 4; ++n) { k.ln[2 * n] = fptr(c, p + ".norm" + std::to_string(n + 1) + ".weight"); k.ln[2 * n + 1] = fptr(c, p + ".norm" + std::to_string(n + 1) + ".bias"); }
-      k.r2r_w = fptr(c, p + ".r2r_attn.in_proj_weight"); k.r2r_b = fptr(c, p + ".r2r_attn.in_proj_bias");
-      k.r2ro_w = fptr(c, p + ".r2r_attn.out_proj.weight"); k.r2ro_b = fptr(c, p + ".r2r_attn.out_proj.bias");
-      k.m2m_w = fptr(c, p + ".m2m_attn.in_proj_weight"); k.m2m_b = fptr(c, p + ".m2m_attn.in_proj_bias");
-      k.m2mo_w = fptr(c, p + ".m2m_attn.out_proj.weight"); k.m2mo_b = fptr(c, p + ".m2m_attn.out_proj.bias");
-      k.c_w = fptr(c, p + ".cross_attn.in_proj_weight"); k.c_b = fptr(c, p + ".cross_attn.in_proj_bias");
-      k.co_w = fptr(c, p + ".cross_attn.out_proj.weight"); k.co_b = fptr(c, p + ".cross_attn.out_proj.bias");
-      k.f1_w = fptr(c, p + ".ffn.0.weight"); k.f1_b = fptr(c, p + ".ffn.0.bias"); k.f2_w = fptr(c, p + ".ffn.3.weight"); k.f2_b = fptr(c, p + ".ffn.3.bias");
-    }
-    q.m_pos = fptr(c, PD + ".m_pos");
-    if (!c->err.empty()) return RIFT_ERR_ARG;
-    DEVCHK(c, c->img.decw_img.reserve((size_t)4 * DECW_LAYER_FRAGS * 512)); DEVCHK(c, c->img.decw_par.reserve((size_t)4 * DECW_PAR_LAYER));
-    decw_pack(q, c->img.decw_img.get(), c->img.decw_par.get(), c->stream);
-  }
-  return RIFT_OK;
-}
-
-// rift_model_load, last step: every operand of the forward, looked up ONCE (model.h) -- behind the packers, the only place where a parameter
-// name is spelt.  Both lookups are strict: a name that matches nothing fails the load with "missing parameter: <name>" (the first one)
-// instead of reaching a launch as a null pointer; only a BatchNorm's num_batches_tracked is optional.  The PW pointers are the addresses
-// of nodes of c->pw: an unordered_map never moves its nodes, so they survive rehashing and the insert / erase of rift_op_linear's
-// transient key; pw.clear() at the top of the next load ends them, and the table is reset there with it.
-static int resolve_model(Ctx* c) {
-  auto W = [&](const std::string& key) -> const PW* {
-    auto it = c->pw.find(key);
-    if (it != c->pw.end()) return &it->second;
-    if (c->err.empty()) c->err = "missing parameter: " + key;
-    return nullptr;
-  };
-  auto P = [&](const std::string& name) { return fptr(c, name); };
-  auto ln = [&](const std::string& p) { return LayerNormW{P(p + ".weight"), P(p + ".bias")}; };
-  auto bn = [&](const std::string& p) {
-    const Param* nb = find(c, p + ".num_batches_tracked");
-    return BatchNormW{P(p + ".weight"), P(p + ".bias"), (float*)P(p + ".running_mean"), (float*)P(p + ".running_var"), nb ? (long long*)nb->data : nullptr};
-  };
-  auto mlp = [&](const std::string& p) { return MLPLayerW{W(p + ".mlp.0"), W(p + ".mlp.3"), ln(p + ".mlp.1")}; };
-  auto fourier = [&](const std::string& p, int D) {
-    FourierW f; f.D = D; f.freqs = P(p + ".freqs.weight");
-    for (int d = 0; d < D; ++d) {
-      const std::string m = p + ".mlps." + std::to_string(d);
-      f.mlps[d] = {W(m + ".0"), W(m + ".0.lo"), W(m + ".0.last"), W(m + ".3"), ln(m + ".1")};
-    }
-    f.out_ln = ln(p + ".to_out.0"); f.out = W(p + ".to_out.2");
-    return f;
-  };
-  auto points = [&](const std::string& p) {
-    return PointsEncoderW{W(p + ".first_mlp.0"), W(p + ".first_mlp.3"), W(p + ".second_mlp.0.feat"), W(p + ".second_mlp.0.pool"), W(p + ".second_mlp.3"),
-                          bn(p + ".first_mlp.1"), bn(p + ".second_mlp.1")};
-  };
-  Model& m = c->m;
-  m.agent.embed_proj = W(HE + ".embed.proj");
-  for (int lv = 0; lv < 3; ++lv) {
-    const std::string l = HE + ".levels." + std::to_string(lv), n = std::to_string(lv);
-    NatLevelW& k = m.agent.levels[lv];
-    for (int b = 0; b < 2; ++b) {
-      const std::string p = l + ".blocks." + std::to_string(b);
-      k.blocks[b] = {ln(p + ".norm1"), ln(p + ".norm2"), W(p + ".attn.qkv"), W(p + ".attn.proj"), W(p + ".mlp.fc1"), W(p + ".mlp.fc2"), P(p + ".attn.rpb")};
-    }
-    k.norm = ln(HE + ".norm" + n);
-    if (lv < 2) { k.reduction = W(l + ".downsample.reduction"); k.ds_norm = ln(l + ".downsample.norm"); }
-    k.lateral = W(HE + ".lateral_convs." + n);
-  }
-  m.agent.fpn_last = W(HE + ".fpn_conv.last");
-  m.agent.type_emb = P("agent_encoder.type_emb.weight");
-  const std::string EG = "agent_encoder.ego_state_emb";
-  m.agent.ego = {P(EG + ".query"), P(EG + ".pos_embed"), W(EG + ".attn.q"), W(EG + ".attn.kv"), W(EG + ".attn.out_proj")};
-  m.map.polygon_encoder = points("map_encoder.polygon_encoder");
-  m.map.speed_limit_emb = fourier("map_encoder.speed_limit_emb", 1);
-  m.map.type_emb = P("map_encoder.type_emb.weight"); m.map.on_route_emb = P("map_encoder.on_route_emb.weight");
-  m.map.traffic_light_emb = P("map_encoder.traffic_light_emb.weight"); m.map.unknown_speed_emb = P("map_encoder.unknown_speed_emb.weight");
-  m.stat.obj_encoder = fourier("static_objects_encoder.obj_encoder", 2);
-  m.stat.type_emb = P("static_objects_encoder.type_emb.weight");
-  m.pos_emb = fourier("pos_emb", 3);
-  for (int i = 0; i < 4; ++i) {
-    const std::string p = "encoder_blocks." + std::to_string(i);
-    m.encoder_blocks[i] = {ln(p + ".norm1"), ln(p + ".norm2"), W(p + ".attn.qkv"), W(p + ".attn.out_proj"), W(p + ".mlp.fc1"), W(p + ".mlp.fc2")};
-  }
-  m.norm = ln("norm");
-  const char* three[3] = {"loc", "yaw", "vel"};
-  for (int i = 0; i < 3; ++i) {
-    m.predictor[i] = mlp(std::string("agent_predictor.") + three[i] + "_predictor");
-    m.dec.head[i] = mlp(PD + "." + three[i] + "_head");
-  }
-  m.dec.r_encoder = points(PD + ".r_encoder");
-  m.dec.r_pos_emb = fourier(PD + ".r_pos_emb", 3);
-  m.dec.q_proj_r = W(PD + ".q_proj.r"); m.dec.q_proj_m = W(PD + ".q_proj.m");
-  m.dec.m_emb = P(PD + ".m_emb"); m.dec.m_pos = P(PD + ".m_pos");
-  for (int i = 0; i < 4; ++i) {
-    const std::string p = PD + ".decoder_blocks." + std::to_string(i);
-    DecoderBlockW& k = m.dec.decoder_blocks[i];
-    for (int j = 0; j < 4; ++j) k.norm[j] = ln(p + ".norm" + std::to_string(j + 1));
-    k.r2r_qkv = W(p + ".r2r_attn.qkv"); k.r2r_out = W(p + ".r2r_attn.out_proj");
-    k.m2m_qkv = W(p + ".m2m_attn.qkv"); k.m2m_qk0 = W(p + ".m2m_attn.qk0"); k.m2m_out = W(p + ".m2m_attn.out_proj");
-    k.cross_q = W(p + ".cross_attn.q"); k.cross_kv = W(p + ".cross_attn.kv"); k.cross_out = W(p + ".cross_attn.out_proj");
-    k.ffn0 = W(p + ".ffn.0"); k.ffn3 = W(p + ".ffn.3");
-  }
-  m.dec.kv_all = W(PD + ".kv_all"); m.dec.cat_x_proj_q = W(PD + ".cat_x_proj.q"); m.dec.cat_x_proj_x = W(PD + ".cat_x_proj.x");
-  m.hidden_proj0 = W("hidden_proj.0"); m.hidden_proj2 = W("hidden_proj.2");
-  m.ref_free_decoder = mlp("ref_free_decoder");
-  const std::string PH = PD + ".pi_head.mlp.";      // (the trainable tensors: the head and both backward entries of shared.hip read them live through these pointers)
-  c->pi = {P(PH + "0.weight"), P(PH + "0.bias"), P(PH + "1.weight"), P(PH + "1.bias"), P(PH + "3.weight"), P(PH + "3.bias")};
-  return c->err.empty() ? RIFT_OK : RIFT_ERR_ARG;
-}
-
 int rift_model_load(RiftCtx* h, const RiftTensorDesc* params, int n, void* stream) {
   Ctx* c = static_cast<Ctx*>(h);
   if (!c || !params) return RIFT_ERR_ARG;
@@ -1790,87 +1449,12 @@ int rift_model_load(RiftCtx* h, const RiftTensorDesc* params, int n, void* strea
   c->stream = (hipStream_t)stream;
   HIPCHK(c, hipSetDevice(c->device));
   c->loaded = false;                    // (until this load has succeeded there is no model: the entries that launch refuse to run)
-  c->pw.clear(); c->params.clear(); c->m = Model(); c->pi = RiftCtxCore::PiHead(); c->wc = Ctx::WeightOnly();      // (frees the images and the weight-only products; the table pointed into both maps)
+  c->pw.clear(); c->m = Model(); c->pi = RiftCtxCore::PiHead(); c->wc = Ctx::WeightOnly();      // (frees the images and the weight-only products; the table pointed at the images)
   c->dry_need = 0;                      // (the first forward on new weights sizes its arena again: it also computes the weight-only products)
-  for (int i = 0; i < n; ++i) {
-    Param p; p.data = params[i].data; p.numel = params[i].numel; p.ndim = params[i].ndim;
-    for (int d = 0; d < 4; ++d) p.shape[d] = params[i].shape[d];
-    c->params[params[i].name] = p;
-  }
-  TRY(pack_history_encoder(c));
-  const std::string EG = "agent_encoder.ego_state_emb";
-  TRY(pack_rows(c, EG + ".attn.q", EG + ".attn.in_proj_weight", EG + ".attn.in_proj_bias", 0, 128, 128));
-  TRY(pack_rows(c, EG + ".attn.kv", EG + ".attn.in_proj_weight", EG + ".attn.in_proj_bias", 128, 256, 256));
-  TRY(pack_linear(c, EG + ".attn.out_proj"));
-  DEVCHK(c, c->img.ego_w.reserve(6 * 128)); DEVCHK(c, c->img.ego_b.reserve(6 * 128));
-  for (int i = 0; i < 6; ++i) {
-    const float* w = fptr(c, EG + ".linears." + std::to_string(i) + ".weight");
-    const float* b = fptr(c, EG + ".linears." + std::to_string(i) + ".bias");
-    if (!w || !b) return RIFT_ERR_ARG;
-    HIPCHK(c, hipMemcpyAsync(c->img.ego_w.get() + i * 128, w, 128 * 4, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->img.ego_b.get() + i * 128, b, 128 * 4, hipMemcpyDeviceToDevice, c->stream));
-  }
-  TRY(pack_points_encoder(c, "map_encoder.polygon_encoder"));
-  TRY(pack_fourier(c, "map_encoder.speed_limit_emb", 1));
-  TRY(pack_fourier(c, "static_objects_encoder.obj_encoder", 2));
-  TRY(pack_fourier(c, "pos_emb", 3));
-  for (int i = 0; i < 4; ++i) {
-    const std::string p = "encoder_blocks." + std::to_string(i);
-    TRY(pack_self_mha(c, p + ".attn"));
-    TRY(pack_linear(c, p + ".mlp.fc1")); TRY(pack_linear(c, p + ".mlp.fc2")); TRY(pack_hid(c, p + ".mlp.fc2"));
-  }
-  {  // chunked in_proj image for the fused encoder kernel: per 2-head chunk (q_h0 | k_h0 | q_h1 | k_h1 | v_h0 | v_h1)
-    int idx[384];
-    for (int ch = 0; ch < 2; ++ch)
-      for (int seg = 0; seg < 6; ++seg) {
-        const int part = seg < 4 ? (seg & 1) : 2;                 // 0 q, 1 k, 2 v
-        const int head = 2 * ch + (seg < 4 ? (seg >> 1) : (seg - 4));
-        for (int d = 0; d < 32; ++d) idx[ch * 192 + seg * 32 + d] = part * 128 + head * 32 + d;
-      }
-    DEVCHK(c, c->img.enc_idx.reserve(384));
-    HIPCHK(c, hipMemcpyAsync(c->img.enc_idx.get(), idx, sizeof(idx), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // idx is a stack buffer
-    for (int i = 0; i < 4; ++i) {
-      const std::string p = "encoder_blocks." + std::to_string(i) + ".attn";
-      const float* w = fptr(c, p + ".in_proj_weight"); const float* bsrc = fptr(c, p + ".in_proj_bias");
-      if (!w || !bsrc) return RIFT_ERR_ARG;
-      DEVCHK(c, c->img.enc_wqkv[i].reserve(384 * 128)); DEVCHK(c, c->img.enc_bqkv[i].reserve(384));
-      hipLaunchKernelGGL(pack_rows_indexed_kernel, dim3(cdiv(384 * 128, 256)), dim3(256), 0, c->stream, w, bsrc, (const int*)c->img.enc_idx.get(),
-                         384, 128, c->img.enc_wqkv[i].get(), c->img.enc_bqkv[i].get());
-    }
-  }
-  const char* ap[3] = {"loc_predictor", "yaw_predictor", "vel_predictor"};
-  for (int i = 0; i < 3; ++i) TRY(pack_mlp_layer(c, std::string("agent_predictor.") + ap[i]));
-  TRY(pack_points_encoder(c, PD + ".r_encoder"));
-  TRY(pack_fourier(c, PD + ".r_pos_emb", 3));
-  TRY(pack_cols(c, PD + ".q_proj.r", PD + ".q_proj", 0, 128, true));
-  TRY(pack_cols(c, PD + ".q_proj.m", PD + ".q_proj", 128, 128, false));
-  for (int i = 0; i < 4; ++i) {
-    const std::string p = PD + ".decoder_blocks." + std::to_string(i);
-    TRY(pack_self_mha(c, p + ".r2r_attn"));
-    TRY(pack_self_mha(c, p + ".m2m_attn"));
-    TRY(pack_rows(c, p + ".m2m_attn.qk0", p + ".m2m_attn.in_proj_weight", "", 0, 256, 384));
-    TRY(pack_rows(c, p + ".cross_attn.q", p + ".cross_attn.in_proj_weight", p + ".cross_attn.in_proj_bias", 0, 128, 128));
-    TRY(pack_rows(c, p + ".cross_attn.kv", p + ".cross_attn.in_proj_weight", p + ".cross_attn.in_proj_bias", 128, 256, 256));
-    TRY(pack_linear(c, p + ".cross_attn.out_proj"));
-    TRY(pack_linear(c, p + ".ffn.0")); TRY(pack_linear(c, p + ".ffn.3"));
-  }
-  {
-    std::vector<std::string> wn, bn;
-    for (int i = 0; i < 4; ++i) {
-      wn.push_back(PD + ".decoder_blocks." + std::to_string(i) + ".cross_attn.in_proj_weight");
-      bn.push_back(PD + ".decoder_blocks." + std::to_string(i) + ".cross_attn.in_proj_bias");
-    }
-    TRY(pack_stacked_rows(c, PD + ".kv_all", wn, bn, 128, 256));
-  }
-  TRY(pack_streamed_images(c));
-  TRY(pack_cols(c, PD + ".cat_x_proj.q", PD + ".cat_x_proj", 0, 128, true));
-  TRY(pack_cols(c, PD + ".cat_x_proj.x", PD + ".cat_x_proj", 128, 128, false));
-  const char* hd[3] = {"loc_head", "yaw_head", "vel_head"};
-  for (int i = 0; i < 3; ++i) TRY(pack_mlp_layer(c, PD + "." + hd[i]));
-  TRY(pack_linear(c, "hidden_proj.0")); TRY(pack_linear(c, "hidden_proj.2"));
-  TRY(pack_mlp_layer(c, "ref_free_decoder"));
-  TRY(resolve_model(c));      // (every tensor the forward reads: a missing one fails the load here)
+  Load load(c, params, n);              // (model_load.h) the descriptors by name, for this call only
+  load.walk();                          // every tensor looked up once: GEMM images packed, c->m and c->pi written
+  if (load.rc != RIFT_OK) return load.rc;
+  TRY(load.pack_streams());             // the wave-private kernels' images, from the raw tensors the walk found
   HIPCHK(c, hipGetLastError());
   c->loaded = true;
   return RIFT_OK;
@@ -2117,17 +1701,13 @@ int rift_op_linear(RiftCtx* h, const float* X, int M, int K, const float* W, con
   c->err.clear();
   HIPCHK(c, hipSetDevice(c->device));
   c->stream = (hipStream_t)stream; c->dry = false;
-  const std::string key = "__op_linear__";
-  // transient pack (test entry point; not on the hot path)
-  TRY(pack(c, key, W, N, N, K, 0, 0, K, 0, 0, 0, bias));
-  const PW& w = c->pw[key];
+  PW w;      // transient images of its own (test entry point; not on the hot path): freed on every way out, the model's are not touched
+  TRY(pack_image(c, w, W, N, N, K, 0, 0, K, 0, 0, 0, bias));
   GemmP g = mk(X, K, M, w, Y, N);
   if (ln_w) { g.pro = PRO_LN; g.pg = ln_w; g.pb = ln_b; }
   g.act = act;
   gemm(c, g, w, fp32 != 0);
-  const hipError_t done = hipStreamSynchronize(c->stream);
-  c->pw.erase(key);                     // (frees the transient images, whatever the wait answered)
-  HIPCHK(c, done);
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // (the images outlive the GEMM)
   HIPCHK(c, hipGetLastError());
   return RIFT_OK;
 }
@@ -2141,9 +1721,8 @@ int rift_op_linear_bench(RiftCtx* h, const float* X, int M, int K, const float* 
   c->err.clear();
   HIPCHK(c, hipSetDevice(c->device));
   c->stream = (hipStream_t)stream; c->dry = false;
-  const std::string key = "__op_linear_bench__";
-  TRY(pack(c, key, W, N, N, K, 0, 0, K, 0, 0, 0, bias));
-  const PW& w = c->pw[key];
+  PW w;
+  TRY(pack_image(c, w, W, N, N, K, 0, 0, K, 0, 0, 0, bias));
   GemmP g = mk(X, K, M, w, Y, N);
   if (ln_w) { g.pro = PRO_LN; g.pg = ln_w; g.pb = ln_b; }
   g.act = act;
@@ -2159,7 +1738,6 @@ int rift_op_linear_bench(RiftCtx* h, const float* X, int M, int K, const float* 
   HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
   if (ms_out) *ms_out = ms / reps;
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  c->pw.erase(key);
   return RIFT_OK;
 }
 

@@ -1,5 +1,8 @@
 // The context of one engine build (included by engine.hip inside the build: one type per MFMA operand format) and the per-forward context.
 #pragma once
+#include <deque>
+#include <unordered_map>
+
 #include "model.h"
 #include "dec_w.h"
 #include "dropstats.h"
@@ -12,8 +15,8 @@ struct Tap { float* p; int64_t numel; };
 // The context of this build: the model side on top of the format-free core (ctx_core.h).  One type per operand format (rift_bf::Ctx,
 // rift_hf::Ctx); the entries of this build's table cast the C handle down once at the top.
 struct Ctx : RiftCtx {
-  std::unordered_map<std::string, PW> pw;      // the packed images by name: written by rift_model_load (and the transient key of rift_op_linear) only
-  Model m;                                     // the forward's operands, resolved from `pw` and `params` once per load (model.h)
+  std::deque<PW> pw;                           // owns the packed images (a deque: its elements never move); cleared and refilled by rift_model_load only
+  Model m;                                     // the forward's operands: pointers at `pw` and at the caller's tensors, written by the load's one walk (model_load.h)
   // activations that depend on (frozen) weights only, computed once per model load, each for the fp32 and the 16-bit mode
   struct WConst { struct V { DevBuf<float> p; bool ready = false; } v[2]; };
   struct WeightOnly { WConst ego_q, Mb, mp[4]; } wc;      // the ego query through attn.q, m_emb through q_proj.m, m_pos through the layers' m2m qk0

@@ -85,16 +85,5 @@ void launch(RiftCtxCore* c, const char* label, void (*kern)(KArgs...), dim3 grid
   launch_call(c, label, [&] { hipLaunchKernelGGL(kern, grid, block, shmem, c->stream, static_cast<KArgs>(args)...); });
 }
 
-inline const Param* find(RiftCtxCore* c, const std::string& name) {
-  auto it = c->params.find(name);
-  return it == c->params.end() ? nullptr : &it->second;
-}
-
-inline const float* fptr(RiftCtxCore* c, const std::string& name) {
-  const Param* p = find(c, name);
-  if (!p) { if (c->err.empty()) c->err = "missing parameter: " + name; return nullptr; }
-  return reinterpret_cast<const float*>(p->data);
-}
-
 }  // namespace
 }  // namespace rift

@@ -1,6 +1,6 @@
-// The model's operands, resolved ONCE by rift_model_load (engine.hip: resolve_model): plain structs of pointers that mirror the module
-// tree of the reference.  Parameter names exist at load only; the forward reads these fields.  A `const PW*` points at a node of
-// Ctx::pw (packed images), a `const float*` at a tensor of the caller's state dict (RiftCtxCore::params).
+// The model's operands, written ONCE by rift_model_load's walk over the module tree (model_load.h): plain structs of pointers that mirror
+// the module tree of the reference.  Parameter names exist at load only; the forward reads these fields.  A `const PW*` points at an
+// element of Ctx::pw (packed images), a `const float*` at a tensor of the caller's state dict.
 #pragma once
 #include "launch.h"
 #include "opfmt.h"

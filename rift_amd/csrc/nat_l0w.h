@@ -18,6 +18,7 @@
 #pragma once
 #include "common.h"
 #include "dropstats.h"
+#include "nat_src.h"
 #include "wp_stream.h"
 
 namespace RIFT_NS {
@@ -70,7 +71,7 @@ __host__ __device__ __forceinline__ float nat_band_entry(const float* rpb, int L
 
 struct NatL0WSrc {    // raw fp32 parameters (views onto the state_dict) for pack_l0w_kernel
   const float* w_tok; const float* b_tok;                                   // embed.proj (32, 9, 3), (32)
-  struct Blk { const float *ln1_g, *ln1_b, *wqkv, *bqkv, *rpb, *wproj, *bproj, *ln2_g, *ln2_b, *w1, *b1, *w2, *b2; } blk[2];
+  NatBlkSrc blk[2];
   const float* fn_g; const float* fn_b;                                     // norm0
   const float* w_ds; const float* ds_g; const float* ds_b;                  // levels.0.downsample.reduction (64, 32, 3), norm (64)
 };
@@ -88,7 +89,7 @@ __global__ void pack_l0w_kernel(NatL0WSrc s, unsigned short* __restrict__ img, f
       if (w < 27) v = s.w_tok[(n * 9 + (w % 9)) * 3 + (w / 9)];
     } else if (f < L0W_F_DS) {
       const int b = (f - 2) / 20, g = (f - 2) % 20;
-      const NatL0WSrc::Blk& k = s.blk[b];
+      const NatBlkSrc& k = s.blk[b];
       const float fg1 = k.ln1_g[l0w_chan(l4, j, 0)], fg2 = k.ln2_g[l0w_chan(l4, j, 0)];      // gamma of the norm in front folded into the weights (l0w_layer_norm)
       if (g < 6) v = k.wqkv[(g * 16 + l15) * 32 + l0w_chan(l4, j, 0)] * (g < 2 ? L0W_QSCALE : 1.0f) * fg1;  // q scaled by head_dim^-0.5 (x log2 e: MFMA attention)
       else if (g < 8) v = k.wproj[((g - 6) * 16 + l15) * 32 + l0w_chan(l4, j, 0)];
@@ -105,7 +106,7 @@ __global__ void pack_l0w_kernel(NatL0WSrc s, unsigned short* __restrict__ img, f
     if (e < 32) v = s.b_tok[e];
     else if (e < L0W_P_FN) {
       const int b = (e - 32) / 400, o = (e - 32) % 400;
-      const NatL0WSrc::Blk& k = s.blk[b];
+      const NatBlkSrc& k = s.blk[b];
       if (o < 32) v = k.ln1_g[o];
       else if (o < 64) v = k.ln1_b[o - 32];
       else if (o < 160) {

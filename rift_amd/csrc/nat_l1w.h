@@ -46,7 +46,7 @@ namespace RIFT_NS {
 #define L1W_LDS (L1W_BLK_FRAGS * 1024 + L1W_NPAR * 4 + L1W_NWV * 40 * L1W_ST * 2)
 
 struct NatL1WSrc {
-  struct Blk { const float *ln1_g, *ln1_b, *wqkv, *bqkv, *rpb, *wproj, *bproj, *ln2_g, *ln2_b, *w1, *b1, *w2, *b2; } blk[2];
+  NatBlkSrc blk[2];
   const float* fn_g; const float* fn_b;                                     // norm1
   const float* w_ds; const float* ds_g; const float* ds_b;                  // levels.1.downsample.reduction (128, 64, 3), norm (128)
 };
@@ -60,7 +60,7 @@ __global__ void pack_l1w_kernel(NatL1WSrc s, unsigned short* __restrict__ img, f
     bool hid = false;                              // fc2 fragments: hidden-layer operand words (common.h: f2h_hid)
     if (f < 2 * L1W_BLK_FRAGS) {
       const int b = f / L1W_BLK_FRAGS, g = f % L1W_BLK_FRAGS;
-      const NatL1WSrc::Blk& k = s.blk[b];
+      const NatBlkSrc& k = s.blk[b];
       if (g < 24) { const int nt = g >> 1, ks = g & 1, ch = l0w_chan(l4, j, 2 * ks); v = k.wqkv[(nt * 16 + l15) * 64 + ch] * (nt < 4 ? L0W_QSCALE : 1.0f) * k.ln1_g[ch]; }      // (gamma of the norm in front folded into the weights: nat_l0w.h, l0w_layer_norm)
       else if (g < 32) { const int nt = (g - 24) >> 1, ks = (g - 24) & 1; v = k.wproj[(nt * 16 + l15) * 64 + l0w_chan(l4, j, 2 * ks)]; }
       else if (g < 56) { const int nt = (g - 32) >> 1, ks = (g - 32) & 1, ch = l0w_chan(l4, j, 2 * ks); v = k.w1[(nt * 16 + l15) * 64 + ch] * k.ln2_g[ch]; }
@@ -75,7 +75,7 @@ __global__ void pack_l1w_kernel(NatL1WSrc s, unsigned short* __restrict__ img, f
     float v = 0.f;
     if (e < 1600) {
       const int b = e / 800, o = e % 800;
-      const NatL1WSrc::Blk& k = s.blk[b];
+      const NatBlkSrc& k = s.blk[b];
       if (o < 64) v = k.ln1_g[o];
       else if (o < 128) v = k.ln1_b[o - 64];
       else if (o < 320) {             // (beta of the norm in front through the weights into the bias)

@@ -9,6 +9,7 @@
 
 #include "opfmt.h"
 #include "dropstats.h"
+#include "nat_src.h"
 
 namespace RIFT_NS {
 
@@ -30,7 +31,7 @@ namespace RIFT_NS {
 #define L2W_LDS (L2W_SLOTS * 32768 + L2W_NPAR * 4)
 
 struct NatL2WSrc {
-  struct Blk { const float *ln1_g, *ln1_b, *wqkv, *bqkv, *rpb, *wproj, *bproj, *ln2_g, *ln2_b, *w1, *b1, *w2, *b2; } blk[2];
+  NatBlkSrc blk[2];
   const float* fn_g; const float* fn_b;
 };
 

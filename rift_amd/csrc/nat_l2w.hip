@@ -14,7 +14,7 @@ __global__ void pack_l2w_kernel(NatL2WSrc s, unsigned short* __restrict__ img, f
     const int j = e & 7, lane = (e >> 3) & 63, fr = e >> 9, bi = fr / L2W_BLK_FRAGS, g = (fr % L2W_BLK_FRAGS) >> 5, f = fr & 31;
     const int ks = f >> 3, nt = f & 7, l15 = lane & 15, l4 = lane >> 4;
     const int ch = l0w_chan(l4, j, 2 * ks), o = nt * 16 + l15;
-    const NatL2WSrc::Blk& k = s.blk[bi];
+    const NatBlkSrc& k = s.blk[bi];
     float v;
     const bool hid = g >= 4 && ((g - 4) & 1);      // fc2 fragments: hidden-layer operand words (common.h: f2h_hid)
     if (g < 3) v = k.wqkv[(g * 128 + o) * 128 + ch] * (g == 0 ? SC : 1.0f) * k.ln1_g[ch];      // (gamma of the norm in front folded into the weights: layer_norm below)
@@ -29,7 +29,7 @@ __global__ void pack_l2w_kernel(NatL2WSrc s, unsigned short* __restrict__ img, f
     float v = 0.f;
     if (e < 2 * 1664) {
       const int bi = e / 1664, o = e % 1664;
-      const NatL2WSrc::Blk& k = s.blk[bi];
+      const NatBlkSrc& k = s.blk[bi];
       if (o < 128) v = k.ln1_g[o];
       else if (o < 256) v = k.ln1_b[o - 128];
       else if (o < 640) {             // (beta of the norm in front through the weights into the bias)

@@ -20,7 +20,12 @@ MISSING = "planning_decoder.pi_head.mlp.3.weight"
 READ_BY_THE_FORWARD = ["map_encoder.on_route_emb.weight", "agent_encoder.ego_state_emb.pos_embed", "agent_encoder.history_encoder.norm1.bias",
                        "encoder_blocks.2.norm2.bias", "pos_emb.freqs.weight", "map_encoder.polygon_encoder.second_mlp.1.running_var",
                        "planning_decoder.decoder_blocks.3.norm4.weight", "planning_decoder.loc_head.mlp.1.weight", "ref_free_decoder.mlp.1.bias",
-                       "static_objects_encoder.type_emb.weight", "planning_decoder.m_emb"]
+                       "static_objects_encoder.type_emb.weight", "planning_decoder.m_emb",
+                       # and one of each kind that is packed into a GEMM image: a linear's weight, a linear's bias, an in_proj_bias that is
+                       # sliced, a conv weight, and the bias of the conv that is packed from two of its taps
+                       "encoder_blocks.1.mlp.fc1.weight", "planning_decoder.decoder_blocks.0.ffn.3.bias",
+                       "planning_decoder.decoder_blocks.2.cross_attn.in_proj_bias", "agent_encoder.history_encoder.lateral_convs.1.weight",
+                       "agent_encoder.history_encoder.fpn_conv.bias"]
 OPTIONAL = "map_encoder.polygon_encoder.first_mlp.1.num_batches_tracked"
 _cache = {}
 
@@ -153,6 +158,27 @@ def test_a_load_without_a_tensor_the_forward_reads_is_refused_by_name():
     _same(_forward(eng, batch), out1)
     eng.load_state_dict(_sd())
     _same(_forward(eng, batch), out1)
+    torch.cuda.synchronize()
+    eng.close()
+
+
+def test_op_linear_shares_no_storage_with_the_model():
+    """load, forward, op_linear on a small matrix, forward: the two forwards are bit-identical -- the test entry packs into images of its
+    own and leaves the model's alone.  M = 5, K = 40, N = 24: K is padded to 64 and N to 32 in the image.  The result holds the bars of
+    tests/test_gpu_parity.py::test_mfma_gemm_kernel (same operand recipe): 2e-5 in fp32, 4e-2 with 16-bit operands."""
+    eng = _ffi.Engine(DEV)
+    eng.load_state_dict(_sd())
+    batch = _batch(2)
+    out1 = _forward(eng, batch)
+    M, K, N = 5, 40, 24
+    g = torch.Generator().manual_seed(M * 131 + K * 17 + N)
+    x, w, b = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) / K ** 0.5, torch.randn(N, generator=g)
+    ref = torch.nn.functional.linear(x, w, b)
+    y32, y16 = eng.op_linear(x, w, b, fp32=True).cpu(), eng.op_linear(x, w, b, fp32=False).cpu()
+    _same(_forward(eng, batch), out1)
+    assert y32.shape == ref.shape and torch.isfinite(y32).all() and torch.isfinite(y16).all()
+    assert float((y32 - ref).abs().max()) < 2e-5
+    assert float((y16 - ref).abs().max()) < 4e-2
     torch.cuda.synchronize()
     eng.close()
 

@@ -216,8 +216,9 @@ void layernorm(Fwd& f, const float* X, int ldx, float* Y, int ldy, int rows, int
          ln.b, 1e-5f, relu);
 }
 
-// FourierEmbedding (fourier_embedding.py:45-55): in (rows, D) -> out (rows, 128)
-FourierP fourier_desc(Fwd& f, const float* in, int in_ld, int rows, const FourierW& p, int wrap_dim, float* add_to) {
+// FourierEmbedding (fourier_embedding.py:45-55): in (rows, D) -> out (rows, 128), a new buffer; add: added into the (rows, 128) buffer `to` instead
+// (`add` and not the pointer says which: the sizing pass has no pointers)
+FourierP fourier_desc(Fwd& f, const float* in, int in_ld, int rows, const FourierW& p, int wrap_dim, bool add, float* to) {
   Ctx* c = f.c;
   const int D = p.D;
   FourierP q; memset(&q, 0, sizeof(q));
@@ -231,67 +232,30 @@ FourierP fourier_desc(Fwd& f, const float* in, int in_ld, int rows, const Fourie
   }
   q.og = p.out_ln.g; q.ob = p.out_ln.b;
   q.wo = p.out->bf.get(); q.bo = p.out->bias;
-  q.Y = add_to ? add_to : A_alloc<float>(c, (size_t)rows * 128);
-  q.accumulate = add_to ? 1 : 0;
+  q.Y = add ? to : A_alloc<float>(c, (size_t)rows * 128);
+  q.accumulate = add ? 1 : 0;
   return q;
 }
 
-// add_to != nullptr: the embedding is added into that (rows, 128) buffer, which is returned
-float* fourier(Fwd& f, const float* in, int in_ld, int rows, const FourierW& p, int wrap_dim, float* add_to = nullptr) {
+// DropPath rates and level shapes of the history encoder (linspace(0, 0.2, 6), embedding.py:30) and of the scene encoder (linspace(0, 0.2, 4),
+// pluto_model.py:80-83): read by the fused and the layer-wise path alike
+static const float NAT_DPR[6] = {0.f, 0.04f, 0.08f, 0.12f, 0.16f, 0.2f};
+static const int NAT_L[3] = {20, 10, 5}, NAT_C[3] = {32, 64, 128};
+static const float ENC_DPR[4] = {0.f, 0.2f / 3.f, 0.4f / 3.f, 0.2f};
+
+#include "fwd_layerwise.h"      // the reference forward: the *_layerwise functions the stages below fall to by the kernel plan
+
+// one embedding on its own; returns the buffer it wrote or added into
+float* fourier(Fwd& f, const float* in, int in_ld, int rows, const FourierW& p, int wrap_dim, bool add = false, float* to = nullptr) {
   Ctx* c = f.c;
   const int D = p.D;
-  if (!f.fp32 && c->sw.fo_fused && D <= 3) {
-    FourierP3 q3; memset(&q3, 0, sizeof(q3));
-    q3.e[0] = fourier_desc(f, in, in_ld, rows, p, wrap_dim, add_to);
-    q3.nblk[0] = cdiv(rows, FO_ROWS); q3.count = 1;
-    c->prof_flops = 2.0 * rows * 128.0 * (D * (129.0 + 128.0) + 128.0);
-    launch(c, "fourier_fused_kernel", fourier_fused_kernel, dim3(q3.nblk[0]), dim3(256), (size_t)FO_LDS, q3);
-    return q3.e[0].Y;
-  }
-  float* FF = A_alloc<float>(c, (size_t)D * rows * 129);
-  launch(c, "fourier_feature_kernel", fourier_feature_kernel, dim3(cdiv((long long)D * rows * 65, 256)), dim3(256), 0, in, in_ld, rows, D,
-         p.freqs, wrap_dim, FF);
-  float* T1 = A_alloc<float>(c, (size_t)rows * 128);
-  float* acc = A_alloc<float>(c, (size_t)rows * 128);
-  for (int d = 0; d < D; ++d) {
-    const FourierW::Dim& m = p.mlps[d];
-    GemmP g = mk(FF + (size_t)d * rows * 129, 129, rows, *m.l0, T1, 128);
-    gemm(c, g, *m.l0, f.fp32);
-    GemmP g2 = mk(T1, 128, rows, *m.l3, acc, 128);
-    g2.pro = PRO_LN; g2.pg = m.ln.g; g2.pb = m.ln.b; g2.pro_relu = 1;
-    if (d > 0) { g2.residual = acc; g2.ldr = 128; }
-    gemm(c, g2, *m.l3, f.fp32);
-  }
-  float* out = A_alloc<float>(c, (size_t)rows * 128);
-  GemmP g3 = mk(acc, 128, rows, *p.out, out, 128);
-  g3.pro = PRO_LN; g3.pg = p.out_ln.g; g3.pb = p.out_ln.b; g3.pro_relu = 1;
-  gemm(c, g3, *p.out, f.fp32);
-  if (add_to) {
-    launch(c, "add_inplace_kernel", add_inplace_kernel, dim3(cdiv((long long)rows * 128, 256)), dim3(256), 0, add_to, (const float*)out, (size_t)rows * 128);
-    return add_to;
-  }
-  return out;
-}
-
-// BatchNorm1d folded to an affine (scale, shift) for the next GEMM prologue.
-void batchnorm_affine(Fwd& f, const float* X, int rows, int C, const uint8_t* valid, const BatchNormW& bn,
-                      float** scale, float** shift) {
-  Ctx* c = f.c;
-  *scale = A_alloc<float>(c, C); *shift = A_alloc<float>(c, C);
-  const int rows_per_blk = 128;
-  const int nblk = cdiv(rows, rows_per_blk);
-  double* part = A_alloc<double>(c, (size_t)nblk * 2 * C);
-  int* cnt = A_alloc<int>(c, nblk);
-  if (f.train) launch(c, "bn_partial_kernel", bn_partial_kernel, dim3(nblk), dim3(C), 0, X, C, rows, C, valid, part, cnt, rows_per_blk);
-  const bool dpx = f.dp && f.train;      // data parallel: batch statistics over the GLOBAL minibatch (sums all-reduced between two launches)
-  double* sums = dpx ? c->dp.xchg + f.kb : nullptr;
-  for (int mode = dpx ? 1 : 0; mode <= (dpx ? 2 : 0); ++mode) {
-    launch(c, "bn_finalize_kernel", bn_finalize_kernel, dim3(cdiv(C, 4)), dim3(256), 0, (const double*)part, (const int*)cnt, nblk, C,
-           bn.g, bn.b, bn.mean,
-           bn.var, bn.num_batches, f.train ? 1 : 0,
-           f.bn_update ? 1 : 0, 1e-5f, *scale, *shift, sums, mode);
-    if (mode == 1) dp_exchange(f, 2 * C + 1);
-  }
+  if (f.kp.fourier == FO_LAYERWISE || D > 3) return fourier_layerwise(f, in, in_ld, rows, p, wrap_dim, add, to);      // (FourierP holds three dimensions)
+  FourierP3 q3; memset(&q3, 0, sizeof(q3));
+  q3.e[0] = fourier_desc(f, in, in_ld, rows, p, wrap_dim, add, to);
+  q3.nblk[0] = cdiv(rows, FO_ROWS); q3.count = 1;
+  c->prof_flops = 2.0 * rows * 128.0 * (D * (129.0 + 128.0) + 128.0);
+  launch(c, "fourier_fused_kernel", fourier_fused_kernel, dim3(q3.nblk[0]), dim3(256), (size_t)FO_LDS, q3);
+  return q3.e[0].Y;
 }
 
 // The two PointsEncoders (map polygons 10 -> 128 with 20 points, reference lines 6 -> 128 with 120 points) in the fused
@@ -333,6 +297,7 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
   pe_fill(f, q.a, Fm, 10, gm, 20, vm, pm);
   pe_fill(f, q.b, Fr, 6, gr, 120, vr, pr);
   const int nt = q.a.ntiles + q.b.ntiles;
+  const bool pe_w = f.kp.pe == PE_PAIR_W;
   const double rows = (double)q.a.rows + q.b.rows, groups = (double)gm + gr;
   {   // what the passes hand to one another (tests/test_gpu_points_encoder.py): _a map polygons, _b reference lines; g in fp16 words
     static const char* const nm[2][6] = {{"pe_s1_a", "pe_t1_a", "pe_s2_a", "pe_t2_a", "pe_gp_a", "pe_g_a"}, {"pe_s1_b", "pe_t1_b", "pe_s2_b", "pe_t2_b", "pe_gp_b", "pe_g_b"}};
@@ -341,14 +306,14 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
     for (int i = 0; i < 2; ++i) {
       tap(c, nm[i][0], (float*)sd[i]->s1, 128); tap(c, nm[i][1], (float*)sd[i]->t1, 128);
       tap(c, nm[i][2], (float*)sd[i]->s2, 256); tap(c, nm[i][3], (float*)sd[i]->t2, 256);
-      if (!c->sw.pe_w) tap(c, nm[i][4], sd[i]->gp, (int64_t)grp[i] * 256);      // (pe_w_kernel keeps gp in registers: only pe_mid_kernel writes it)
+      if (!pe_w) tap(c, nm[i][4], sd[i]->gp, (int64_t)grp[i] * 256);      // (pe_w_kernel keeps gp in registers: only pe_mid_kernel writes it)
       tap(c, nm[i][5], (float*)sd[i]->Fmid, (int64_t)sd[i]->rows * 128);
     }
   }
-  const bool stats_p = f.train && c->sw.pe_w;          // persistent pass A: one partial per workgroup (pe_fused.h)
+  const bool stats_p = f.kp.pe_stats_persistent;       // persistent pass A: one partial per workgroup (pe_fused.h)
   // reference lines packed at tile granularity (pe_fused.h: pe_pack_body): table + round count in device memory, built by one extra block
   // of pass A's launch (eval mode: a launch of its own)
-  const bool packb = c->sw.pe_w && c->sw.pe_pack && gr > 0 && f.r_tiles != nullptr;
+  const bool packb = f.kp.pe_pack;
   int* pk_tab = nullptr; int* pk_hdr = nullptr;
   PePackP pk; memset(&pk, 0, sizeof(pk));
   // (the packing's own bound, not the ceil(lines / 2) rounds of the unpacked walk: segments of an odd number of long lines end on a
@@ -380,10 +345,10 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
   double* xs = dpx ? c->dp.xchg + f.kb : nullptr;
   // pass B's live rounds and workgroup split, from pass A's counts (pe_fused.h: PeLiveP): one extra block of the BatchNorm-1 finalize
   PeLiveP lv; memset(&lv, 0, sizeof(lv));
-  const bool live = stats_p && c->sw.pe_live;
+  const bool live = f.kp.pe_live;
   int pew_grid = std::max(c->sw.nat_grid, 2), pew_ga = 0;      // (two sides: at one workgroup the split below leaves the polygons none -- RIFT_NAT_GRID=1)
   // (the two-line round counts only size the grid and its first split here: with packing or a live list the split is remade on the device)
-  if (c->sw.pe_w) pew_split(cdiv(q.a.rows, PEW_ROUND_ROWS), cdiv(q.b.rows, PEW_ROUND_ROWS), &pew_grid, &pew_ga);
+  if (pe_w) pew_split(cdiv(q.a.rows, PEW_ROUND_ROWS), cdiv(q.b.rows, PEW_ROUND_ROWS), &pew_grid, &pew_ga);
   if (live || packb) {
     const PeP* sd[2] = {&q.a, &q.b};
     for (int i = 0; i < 2; ++i) {
@@ -408,7 +373,7 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
   }
   c->prof_flops = 2.0 * rows * (128.0 * 8 + 128.0 * 256 + (f.train ? 256.0 * 256 : 0.0)) + 2.0 * groups * 256.0 * 256;
   BnFinP fa, fb;
-  if (c->sw.pe_w) {     // wave-private pass B: rounds of 240 rows, one statistics partial per workgroup
+  if (pe_w) {     // wave-private pass B: rounds of 240 rows, one statistics partial per workgroup
     PeWP w; memset(&w, 0, sizeof(w));
     const PeP* src[2] = {&q.a, &q.b};
     PeWSide* dst[2] = {&w.a, &w.b};
@@ -448,91 +413,6 @@ void points_encoder_pair(Fwd& f, const float* Fm, int gm, const uint8_t* vm, con
   *out_m = q.a.out; *out_r = q.b.out;
 }
 
-// PointsEncoder (embedding.py:271-296): F (groups*n, Cin) -> (groups, 128)
-float* points_encoder(Fwd& f, const float* F, int Cin, int groups, int n, const uint8_t* valid, const PointsEncoderW& p) {
-  Ctx* c = f.c;
-  const int rows = groups * n;
-  float* H1 = A_alloc<float>(c, (size_t)rows * 128);
-  gemm(c, mk(F, Cin, rows, *p.first0, H1, 128), *p.first0, f.fp32);
-  float *s1, *t1;
-  batchnorm_affine(f, H1, rows, 128, valid, p.bn1, &s1, &t1);
-  float* F256 = A_alloc<float>(c, (size_t)rows * 256);
-  GemmP g = mk(H1, 128, rows, *p.first3, F256, 256);
-  g.pro = PRO_AFFINE; g.pg = s1; g.pb = t1; g.pro_relu = 1;
-  gemm(c, g, *p.first3, f.fp32);
-  float* pooled = A_alloc<float>(c, (size_t)groups * 256);
-  launch(c, "masked_maxpool_kernel", masked_maxpool_kernel, dim3(cdiv((long long)groups * 256, 256)), dim3(256), 0, (const float*)F256, 256, groups, n, 256,
-         valid, pooled);
-  float* G1 = A_alloc<float>(c, (size_t)groups * 256);
-  gemm(c, mk(pooled, 256, groups, *p.pool, G1, 256), *p.pool, f.fp32);
-  float* H2 = A_alloc<float>(c, (size_t)rows * 256);
-  GemmP g2 = mk(F256, 256, rows, *p.feat, H2, 256);
-  g2.gbias = G1; g2.gb_div = n; g2.gb_mod = 0;
-  gemm(c, g2, *p.feat, f.fp32);
-  float *s2, *t2;
-  batchnorm_affine(f, H2, rows, 256, valid, p.bn2, &s2, &t2);
-  float* O = A_alloc<float>(c, (size_t)rows * 128);
-  GemmP g3 = mk(H2, 256, rows, *p.second3, O, 128);
-  g3.pro = PRO_AFFINE; g3.pg = s2; g3.pb = t2; g3.pro_relu = 1;
-  gemm(c, g3, *p.second3, f.fp32);
-  float* out = A_alloc<float>(c, (size_t)groups * 128);
-  launch(c, "masked_maxpool_kernel", masked_maxpool_kernel, dim3(cdiv((long long)groups * 128, 256)), dim3(256), 0, (const float*)O, 128, groups, n, 128,
-         valid, out);
-  {   // the fused pair's taps, as far as this path has them: g here in fp32; no gp (G1 is without second_mlp.0's bias, which rides on `feat`)
-    static const char* const nm[2][5] = {{"pe_s1_a", "pe_t1_a", "pe_s2_a", "pe_t2_a", "pe_g_a"}, {"pe_s1_b", "pe_t1_b", "pe_s2_b", "pe_t2_b", "pe_g_b"}};
-    const char* const* t = nm[n == 20 ? 0 : 1];
-    tap(c, t[0], s1, 128); tap(c, t[1], t1, 128); tap(c, t[2], s2, 256); tap(c, t[3], t2, 256); tap(c, t[4], H2, (int64_t)rows * 256);
-  }
-  return out;
-}
-
-template <int NKT>
-void run_mha_mfma(Ctx* c, const MhaP& p) {
-  const int nqt = (p.Lq + 15) / 16;
-  const int waves = nqt < 4 ? nqt : 4;
-  const size_t lds = (size_t)NKT * 16 * 40 * 2 + (size_t)32 * (NKT * 16 + 8) * 2 + NKT * 16;
-  launch(c, "mha_mfma_kernel", mha_mfma_kernel<NKT>, dim3(p.nb_outer * p.nb_inner * p.H), dim3(64 * waves), lds, p);
-}
-
-// bf16 mode: MFMA attention; fp32 mode (or unaligned / very long inputs): exact-fp32 VALU kernel
-void run_mha(Ctx* c, const MhaP& p, bool fp32) {
-  const bool al = ((((uintptr_t)p.Q) | ((uintptr_t)p.K) | ((uintptr_t)p.V)) & 15) == 0 && p.ldq % 4 == 0 && p.ldkv % 4 == 0;
-  if (!fp32 && al && p.Lk <= 192) {
-    if (p.Lk <= 32) run_mha_mfma<2>(c, p);
-    else if (p.Lk <= 96) run_mha_mfma<6>(c, p);
-    else run_mha_mfma<12>(c, p);
-    return;
-  }
-  const long long total = (long long)p.nb_outer * p.nb_inner * p.H * p.Lq;
-  launch(c, "mha_kernel", mha_kernel, dim3(cdiv(total, 64)), dim3(64), 0, p);
-}
-
-// NAT block (embedding.py:196-202) on X (rows, C) in place
-void nat_layer(Fwd& f, float* X, int rows, int C, int H, int ksz, int L, const NatBlockW& p, float droppath) {
-  Ctx* c = f.c;
-  float* QKV = A_alloc<float>(c, (size_t)rows * 3 * C);
-  GemmP g = mk(X, C, rows, *p.qkv, QKV, 3 * C);
-  g.pro = PRO_LN; g.pg = p.norm1.g; g.pb = p.norm1.b;
-  gemm(c, g, *p.qkv, f.fp32);
-  float* AO = A_alloc<float>(c, (size_t)rows * C);
-  const int nthreads = rows * H;
-  if (ksz == 3) launch(c, "nat_attention_kernel", nat_attention_kernel<3>, dim3(cdiv(nthreads, 256)), dim3(256), 0, (const float*)QKV, p.rpb, rows / L, L, H, AO);
-  else launch(c, "nat_attention_kernel", nat_attention_kernel<5>, dim3(cdiv(nthreads, 256)), dim3(256), 0, (const float*)QKV, p.rpb, rows / L, L, H, AO);
-  GemmP g2 = mk(AO, C, rows, *p.proj, X, C);
-  g2.residual = X; g2.ldr = C;
-  if (f.drop && droppath > 0.f) { g2.droppath_p = droppath; g2.dp_div = L; g2.seed = f.seed; g2.stream = f.next_stream(); }
-  gemm(c, g2, *p.proj, f.fp32);
-  float* Hh = A_alloc<float>(c, (size_t)rows * 3 * C);
-  GemmP g3 = mk(X, C, rows, *p.fc1, Hh, 3 * C);
-  g3.pro = PRO_LN; g3.pg = p.norm2.g; g3.pb = p.norm2.b; g3.act = ACT_GELU;
-  gemm(c, g3, *p.fc1, f.fp32);
-  GemmP g4 = mk(Hh, 3 * C, rows, *p.fc2, X, C);
-  g4.residual = X; g4.ldr = C;
-  if (f.drop && droppath > 0.f) { g4.droppath_p = droppath; g4.dp_div = L; g4.seed = f.seed; g4.stream = f.next_stream(); }
-  gemm(c, g4, *p.fc2, f.fp32);
-}
-
-// MLPLayer (mlp_layer.py:8-16): X (rows,128) -> out (rows, Nout) with hidden width Hd
 // three MLPLayer(128, 256, 160) heads -> interleaved (rows, 80, 6), one launch (heads_fused.h); bf16 mode
 void heads3_fused(Fwd& f, const float* X, int ldx, int rows, int g_per, int g_stride, int g_off, const MLPLayerW heads[3], float* out) {
   Ctx* c = f.c;
@@ -547,26 +427,6 @@ void heads3_fused(Fwd& f, const float* X, int ldx, int rows, int g_per, int g_st
   launch(c, "heads3_fused_kernel", heads3_fused_kernel, dim3(24 * cdiv(cdiv(rows, HD_ROWS), 8)), dim3(512), (size_t)HD_LDS, q);      // (groups of 8 tiles x 3 heads: heads_fused.h)
 }
 
-void mlp_layer(Fwd& f, const float* X, int ldx, int rows, const MLPLayerW& p, float* out, int ldo, bool fp32) {
-  Ctx* c = f.c;
-  const PW& w0 = *p.l0;
-  float* T = A_alloc<float>(c, (size_t)rows * w0.N);
-  gemm(c, mk(X, ldx, rows, w0, T, w0.N), w0, fp32);
-  const PW& w3 = *p.l3;
-  GemmP g = mk(T, w0.N, rows, w3, out, ldo);
-  g.pro = PRO_LN; g.pg = p.ln.g; g.pb = p.ln.b; g.pro_relu = 1;
-  gemm(c, g, w3, fp32);
-}
-
-__global__ void interleave_traj_kernel(const float* __restrict__ loc, const float* __restrict__ yaw,
-                                       const float* __restrict__ vel, int rows, float* __restrict__ out) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;   // (row, t, c6)
-  if (idx >= rows * 480) return;
-  const int c6 = idx % 6, t = (idx / 6) % 80, r = idx / 480;
-  const float* src = c6 < 2 ? loc : (c6 < 4 ? yaw : vel);
-  out[idx] = src[(size_t)r * 160 + t * 2 + (c6 & 1)];
-}
-
 // The policy head of a forward: cat_x_proj -> pi_head (read LIVE: the only trainable parameters) -> masked logits, then the trajectory
 // heads on its q_final.  Launched on c->stream; leaves what rift_loss_backward consumes.
 int head_impl(Ctx* c, const Ctx::Head& h) {
@@ -575,7 +435,7 @@ int head_impl(Ctx* c, const Ctx::Head& h) {
   // Everything before reads frozen, load-time-packed weights only; pi_head.* is read LIVE from here on.  A host that updates pi_head on
   // another stream (all-reduce + clip + AdamW of the previous step) hands over the event that marks the update's end.
   if (c->st.param_event && !c->dry) HIPCHK(c, hipStreamWaitEvent(c->stream, c->st.param_event, 0));
-  if (!h.fp32 && c->sw.pi_fused) {
+  if (h.pi_fused) {
     // cat_x_proj (bf16) -> pi_head first Linear (exact fp32, live parameters) -> LayerNorm -> ReLU -> Linear -> masked logits: one launch
     PiFwdP q; memset(&q, 0, sizeof(q));
     q.Q = h.Q; q.rows = nQ; q.rows_per_scene = R * M;
@@ -586,33 +446,10 @@ int head_impl(Ctx* c, const Ctx::Head& h) {
     q.r_kpm = h.r_kpm; q.M = M; q.eps = 1e-5f; q.QF = h.QF; q.Hpi = h.Hpi; q.prob = h.prob; q.nonfinite = c->nonfinite.get();
     c->prof_flops = 2.0 * nQ * (2.0 * 128 * 128 + 128);
     launch(c, "pi_forward_kernel", pi_forward_kernel, dim3(cdiv(nQ, PI_ROWS)), dim3(512), (size_t)PI_LDS, q);
-  } else {
-    GemmP g = mk(h.Q, 128, nQ, *c->m.dec.cat_x_proj_q, h.QF, 128);
-    g.gbias = h.x0p; g.gb_div = R * M; g.gb_mod = 0;
-    gemm(c, g, *c->m.dec.cat_x_proj_q, h.fp32);
-    // pi head: first Linear straight from the live (trainable) fp32 parameters, exact-fp32 MFMA
-    PWShape w; w.N = 128; w.K = 128; w.Kp = 128; w.Npad = 128; w.bias = c->pi.b0;
-    gemm(c, mk(h.QF, 128, nQ, w, h.Hpi, 128), (const void*)c->pi.w0, true);
-    launch(c, "pi_tail_kernel", pi_tail_kernel, dim3(cdiv(nQ, 4)), dim3(256), 0, (const float*)h.Hpi, nQ, M, c->pi.ln_g,
-           c->pi.ln_b, c->pi.w3, c->pi.b3,
-           (const uint8_t*)h.r_kpm, 1e-5f, h.prob, c->nonfinite.get());
-  }
+  } else policy_head_layerwise(c, h);
   tap(c, "q_final", h.QF, (int64_t)nQ * 128);
-  if (h.need_traj && !h.fp32 && c->sw.heads_fused) {
-    heads3_fused(f, h.QF, 128, nQ, 0, 0, 0, c->m.dec.head, h.traj);
-  } else if (h.need_traj) {
-    for (int i = 0; i < 3; ++i) {      // MLPLayer(128, 256, 160) as in mlp_layer(), on the buffers the trunk reserved
-      const PW& w0 = *c->m.dec.head[i].l0;
-      const PW& w3 = *c->m.dec.head[i].l3;
-      float* T = h.oT[i];
-      gemm(c, mk(h.QF, 128, nQ, w0, T, w0.N), w0, h.fp32);
-      GemmP g = mk(T, w0.N, nQ, w3, h.o3[i], 160);
-      g.pro = PRO_LN; g.pg = c->m.dec.head[i].ln.g; g.pb = c->m.dec.head[i].ln.b; g.pro_relu = 1;
-      gemm(c, g, w3, h.fp32);
-    }
-    launch(c, "interleave_traj_kernel", interleave_traj_kernel, dim3(cdiv((long long)nQ * 480, 256)), dim3(256), 0, (const float*)h.o3[0], (const float*)h.o3[1],
-           (const float*)h.o3[2], nQ, h.traj);
-  }
+  if (h.need_traj && h.heads_fused) heads3_fused(f, h.QF, 128, nQ, 0, 0, 0, c->m.dec.head, h.traj);
+  else if (h.need_traj) traj_heads_layerwise(c, h);
   if (!c->dry) {
     c->last_qfinal = h.QF; c->last_hpi = h.Hpi; c->last_prob = h.prob; c->last_rkpm = h.r_kpm; c->last_bs = h.bs; c->last_R = h.R;
   }
@@ -631,10 +468,10 @@ int prepare_inputs(Fwd& f) {
   f.valid_agent = A_alloc<uint8_t>(c, nA);
   // the fused history encoder runs on the sequences its output is read of -- valid agents other than the ego (agent_encoder.py:77-87) -- in
   // compacted order (nat_l0w.h ranks them); the layer-wise / fp32 path keeps all nA sequences
-  f.nat_compact = c->sw.nat_compact && c->sw.nat_fused && !f.fp32 && c->sw.fpn_fused;
-  uint8_t* hist_agent = f.nat_compact ? A_alloc<uint8_t>(c, nA) : nullptr;
-  f.nat_aidx = f.nat_compact ? A_alloc<int>(c, nA) : nullptr;
-  f.nat_cnt = f.nat_compact ? A_alloc<int>(c, 4) : nullptr;
+  const bool compact = f.kp.nat_compact, rank_in_prep = f.kp.rank_in_prep;
+  uint8_t* hist_agent = compact ? A_alloc<uint8_t>(c, nA) : nullptr;
+  f.nat_aidx = compact ? A_alloc<int>(c, nA) : nullptr;
+  f.nat_cnt = compact ? A_alloc<int>(c, 4) : nullptr;
   f.F10 = A_alloc<float>(c, (size_t)nP * 20 * 10);
   f.F6 = A_alloc<float>(c, (size_t)nL * 120 * 6);
   f.kpm = A_alloc<uint8_t>(c, nT);
@@ -656,7 +493,6 @@ int prepare_inputs(Fwd& f) {
   int tot = 0;
   for (int i = 0; i < 7; ++i) tot += q.nb[i];
   // (round 6) the ranking as the first bs blocks of this launch (kernels.h: rank_scene_body): no launch of its own on the history chain
-  const bool rank_in_prep = f.nat_compact && c->sw.rank_in_prep && A <= 256;
   if (rank_in_prep) {
     const int sl = c->parity;
     DevBuf<unsigned long long>& pub = c->slots[sl].rk_pub;
@@ -675,7 +511,7 @@ int prepare_inputs(Fwd& f) {
     tot += bs;
   }
   launch(c, "prep_kernel", prep_kernel, dim3(tot), dim3(256), 0, q);
-  if (f.nat_compact && !rank_in_prep) launch(c, "nat_rank_kernel", nat_rank_kernel, dim3(1), dim3(NAT_RANK_THREADS), 0, (const uint8_t*)hist_agent, nA, f.nat_aidx, f.nat_cnt);
+  if (compact && !rank_in_prep) launch(c, "nat_rank_kernel", nat_rank_kernel, dim3(1), dim3(NAT_RANK_THREADS), 0, (const uint8_t*)hist_agent, nA, f.nat_aidx, f.nat_cnt);
   return RIFT_OK;
 }
 
@@ -713,7 +549,7 @@ int dp_mask_and_drop_counters(Fwd& f) {
     tap(c, "drop_scale", f.ds.scale, RIFT_DS_SITES + RIFT_DS_DEC_SITES); tap(c, "drop_elem", (float*)f.ds.elem, 4 * RIFT_DS_DEC_SITES);
   }
 #endif
-  if (f.nat_compact) { tap(c, "nat_aidx", (float*)f.nat_aidx, nA); tap(c, "nat_cnt", (float*)f.nat_cnt, 3); }      // (int32 words read back through the float tap)
+  if (f.kp.nat_compact) { tap(c, "nat_aidx", (float*)f.nat_aidx, nA); tap(c, "nat_cnt", (float*)f.nat_cnt, 3); }      // (int32 words read back through the float tap)
   tap(c, "nat_f9", f.F9, (int64_t)nA * 20 * 9);      // the prepared 9-channel rows, all nA slots (prep_kernel)
   return RIFT_OK;
 }
@@ -723,26 +559,24 @@ void history_encoder(Fwd& f) {
   Ctx* c = f.c;
   const auto& he = c->m.agent;
   const int nA = f.nA;
-  static const float dpr[6] = {0.f, 0.04f, 0.08f, 0.12f, 0.16f, 0.2f};   // linspace(0, 0.2, 6), embedding.py:30
-  const bool fused = c->sw.nat_fused && !f.fp32;
-  static const int Ll[3] = {20, 10, 5}, Cl[3] = {32, 64, 128}, Hl[3] = {2, 4, 8}, Kl[3] = {3, 3, 5};
+  static const int Kl[3] = {3, 3, 5};
   float* Oc[3];   // LayerNorm(norm_i) of the last 3 steps of level i: all that out[:, :, -1] of the FPN depends on
-  for (int i = 0; i < 3; ++i) Oc[i] = A_alloc<float>(c, (size_t)nA * 3 * Cl[i]);
+  for (int i = 0; i < 3; ++i) Oc[i] = A_alloc<float>(c, (size_t)nA * 3 * NAT_C[i]);
   // the wave-private level kernels hand these rows to fpn_tail_kernel as bf16 (it rounds them to bf16 first thing anyway): same values, half the bytes
-  const bool oc_bf16 = fused && c->sw.fpn_fused;
+  const bool oc_bf16 = f.kp.fpn_fused;
   unsigned short* Ocb[3] = {nullptr, nullptr, nullptr};
-  if (oc_bf16) for (int i = 0; i < 3; ++i) Ocb[i] = A_alloc<unsigned short>(c, (size_t)nA * 3 * Cl[i]);
-  if (fused) {
+  if (oc_bf16) for (int i = 0; i < 3; ++i) Ocb[i] = A_alloc<unsigned short>(c, (size_t)nA * 3 * NAT_C[i]);
+  if (f.kp.hist_wave) {
     // one launch per level: [ConvTokenizer ->] 2 NAT blocks -> {FPN LayerNorm of the last 3 steps, downsample conv + LN}
     float* Xin[3] = {nullptr, A_alloc<float>(c, (size_t)nA * 10 * 64), A_alloc<float>(c, (size_t)nA * 5 * 128)};
     for (int lv = 0; lv < 3; ++lv) {
-      const int C = Cl[lv], H = Hl[lv], ksz = Kl[lv], L = Ll[lv], rows = nA * L;
+      const int C = NAT_C[lv], ksz = Kl[lv], L = NAT_L[lv], rows = nA * L;
       if (lv == 0) {   // level 0 as wave-private, register-resident tiles (no workgroup barriers): nat_l0w.h
         NatL0WP q; memset(&q, 0, sizeof(q));
         q.aidx = f.nat_aidx; q.cnt = f.nat_cnt;
         q.F9 = f.F9; q.nseq = nA; q.img = c->img.l0w_img.get(); q.par = c->img.l0w_par.get(); q.Oc = Oc[0]; q.Ocb = Ocb[0]; q.Xnext = Xin[1];
         { if (c->sw.nat_ts == 1) { q.ts = A_alloc<long long>(c, 64); tap(c, "nat_ts", (float*)q.ts, 128); } }
-        q.droppath[0] = f.drop ? dpr[0] : 0.f; q.droppath[1] = f.drop ? dpr[1] : 0.f; q.seed = f.seed; q.stream = f.next_stream(); f.stream_id += 4;
+        q.droppath[0] = f.drop ? NAT_DPR[0] : 0.f; q.droppath[1] = f.drop ? NAT_DPR[1] : 0.f; q.seed = f.seed; q.stream = f.next_stream(); f.stream_id += 4;
         q.ds = f.ds;
         c->prof_flops = 2.0 * rows * (20.0 * C * C + 4.0 * ksz * C) + 2.0 * rows * 27 * 32 + (rows / 2) * 2.0 * 3 * C * 2 * C;
         { const int g0 = std::min(cdiv(cdiv(nA, 4), L0W_NWV), c->sw.nat_grid); launch_call(c, "nat_l0w_kernel", [&] { l0w_launch(q, g0, c->stream); }); }
@@ -752,7 +586,7 @@ void history_encoder(Fwd& f) {
         NatL1WP q; memset(&q, 0, sizeof(q));
         q.cnt = f.nat_cnt;
         q.X = Xin[1]; q.nseq = nA; q.img = c->img.l1w_img.get(); q.par = c->img.l1w_par.get(); q.Oc = Oc[1]; q.Ocb = Ocb[1]; q.Xnext = Xin[2];
-        q.droppath[0] = f.drop ? dpr[2] : 0.f; q.droppath[1] = f.drop ? dpr[3] : 0.f; q.seed = f.seed; q.stream = f.next_stream(); f.stream_id += 4;
+        q.droppath[0] = f.drop ? NAT_DPR[2] : 0.f; q.droppath[1] = f.drop ? NAT_DPR[3] : 0.f; q.seed = f.seed; q.stream = f.next_stream(); f.stream_id += 4;
         q.ds = f.ds;
         c->prof_flops = 2.0 * rows * (20.0 * C * C + 4.0 * ksz * C) + (rows / 2) * 2.0 * 3 * C * 2 * C;
         { const int g1 = std::min(cdiv(cdiv(nA, 4), L1W_NWV), c->sw.nat_grid); launch_call(c, "nat_l1w_kernel", [&] { l1w_launch(q, g1, c->stream); }); }
@@ -762,7 +596,7 @@ void history_encoder(Fwd& f) {
         NatL2WP q; memset(&q, 0, sizeof(q));
         q.cnt = f.nat_cnt;
         q.X = Xin[2]; q.nseq = nA; q.img = c->img.l2w_img.get(); q.par = c->img.l2w_par.get(); q.Oc = Oc[2]; q.Ocb = Ocb[2];
-        q.droppath[0] = f.drop ? dpr[4] : 0.f; q.droppath[1] = f.drop ? dpr[5] : 0.f; q.seed = f.seed; q.stream = f.next_stream(); f.stream_id += 4;
+        q.droppath[0] = f.drop ? NAT_DPR[4] : 0.f; q.droppath[1] = f.drop ? NAT_DPR[5] : 0.f; q.seed = f.seed; q.stream = f.next_stream(); f.stream_id += 4;
         q.ds = f.ds;
         { if (c->sw.nat_ts == 3) { q.ts = A_alloc<long long>(c, 64); tap(c, "nat_ts", (float*)q.ts, 128); } }
         c->prof_flops = 2.0 * rows * (20.0 * C * C + 4.0 * ksz * C);
@@ -775,78 +609,27 @@ void history_encoder(Fwd& f) {
     }
     // level boundaries of the fused path, rows in the launch's own (compacted) order: the downsampled inputs of levels 1 and 2
     tap(c, "nat_x1", Xin[1], (int64_t)nA * 10 * 64); tap(c, "nat_x2", Xin[2], (int64_t)nA * 5 * 128);
-  } else {
-    float* X0 = A_alloc<float>(c, (size_t)nA * 20 * 32);
-    {
-      GemmP g = mk(f.F9, 9, nA * 20, *he.embed_proj, X0, 32);
-      g.amode = AMODE_CONV3; g.cv_C = 9; g.cv_Lin = 20; g.cv_nout = 20; g.cv_t0 = 0; g.cv_stride = 1;
-      gemm(c, g, *he.embed_proj, f.fp32);
-    }
-    auto nat_level = [&](float* Xl, int lv, int rows, int C, int H, int ksz, int L) {
-      nat_layer(f, Xl, rows, C, H, ksz, L, he.levels[lv].blocks[0], dpr[2 * lv]);
-      nat_layer(f, Xl, rows, C, H, ksz, L, he.levels[lv].blocks[1], dpr[2 * lv + 1]);
-    };
-    nat_level(X0, 0, nA * 20, 32, 2, 3, 20);
-    float* X1 = A_alloc<float>(c, (size_t)nA * 10 * 64);
-    {
-      GemmP g = mk(X0, 32, nA * 10, *he.levels[0].reduction, X1, 64);
-      g.amode = AMODE_CONV3; g.cv_C = 32; g.cv_Lin = 20; g.cv_nout = 10; g.cv_t0 = 0; g.cv_stride = 2;
-      gemm(c, g, *he.levels[0].reduction, f.fp32);
-      layernorm(f, X1, 64, X1, 64, nA * 10, 64, he.levels[0].ds_norm);
-    }
-    nat_level(X1, 1, nA * 10, 64, 4, 3, 10);
-    // level outputs are the PRE-downsample activations (NATBlock returns (downsample(x), x)); X0/X1 are
-    // still needed below, so the downsample writes new buffers.
-    float* X2 = A_alloc<float>(c, (size_t)nA * 5 * 128);
-    {
-      GemmP g = mk(X1, 64, nA * 5, *he.levels[1].reduction, X2, 128);
-      g.amode = AMODE_CONV3; g.cv_C = 64; g.cv_Lin = 10; g.cv_nout = 5; g.cv_t0 = 0; g.cv_stride = 2;
-      gemm(c, g, *he.levels[1].reduction, f.fp32);
-      layernorm(f, X2, 128, X2, 128, nA * 5, 128, he.levels[1].ds_norm);
-    }
-    nat_level(X2, 2, nA * 5, 128, 8, 5, 5);
-    tap(c, "nat_level2", X2, (int64_t)nA * 5 * 128);
-    float* Xl[3] = {X0, X1, X2};
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j)   // rows (a, j) <- level rows (a*L + L-3 + j): 3 strided LN calls
-        launch(c, "layernorm_kernel", layernorm_kernel, dim3(cdiv(nA, 4)), dim3(256), 0, (const float*)(Xl[i] + (size_t)(Ll[i] - 3 + j) * Cl[i]),
-               Ll[i] * Cl[i], Oc[i] + (size_t)j * Cl[i], 3 * Cl[i], nA, Cl[i],
-               he.levels[i].norm.g, he.levels[i].norm.b,
-               1e-5f, 0);
-  }
+  } else history_levels_layerwise(f, Oc);
   // the FPN inputs (LayerNorm of the last three steps of level i): as the 16-bit operand words the fused tail receives (two per float of
   // the tap, in the launch's compacted order), else fp32 rows of all nA slots
   static const char* const oc_tap[3] = {"nat_oc0", "nat_oc1", "nat_oc2"};
   for (int i = 0; i < 3; ++i) {
-    if (oc_bf16) tap(c, oc_tap[i], (float*)Ocb[i], (int64_t)nA * 3 * Cl[i] / 2);
-    else tap(c, oc_tap[i], Oc[i], (int64_t)nA * 3 * Cl[i]);
+    if (oc_bf16) tap(c, oc_tap[i], (float*)Ocb[i], (int64_t)nA * 3 * NAT_C[i] / 2);
+    else tap(c, oc_tap[i], Oc[i], (int64_t)nA * 3 * NAT_C[i]);
   }
   // FPN restricted to what out[:, :, -1] depends on
   f.nat_out = A_alloc<float>(c, (size_t)nA * 128);
-  if (fused && c->sw.fpn_fused) {
+  if (f.kp.fpn_fused) {
     FpnP q; memset(&q, 0, sizeof(q));
     for (int i = 0; i < 3; ++i) {
       const PW& w = *he.levels[i].lateral;
       q.oc[i] = Oc[i]; q.ocb[i] = Ocb[i]; q.wl[i] = w.bf.get(); q.bl[i] = w.bias;
     }
     q.wf = he.fpn_last->bf.get(); q.bf_ = he.fpn_last->bias;
-    q.out = f.nat_out; q.nA = nA; q.cnt = fused ? f.nat_cnt : nullptr; q.aidx = fused ? f.nat_aidx : nullptr;
+    q.out = f.nat_out; q.nA = nA; q.cnt = f.nat_cnt; q.aidx = f.nat_aidx;
     c->prof_flops = 2.0 * nA * (2.0 * 128 * (96 + 192 + 384) + 256.0 * 128);
     launch(c, "fpn_tail_kernel", fpn_tail_kernel, dim3(cdiv(nA, FPN_AG)), dim3(512), (size_t)FPN_LDS, q);
-  } else {
-    float* lat[3];
-    for (int i = 0; i < 3; ++i) {
-      lat[i] = A_alloc<float>(c, (size_t)nA * 2 * 128);
-      const PW& lc = *he.levels[i].lateral;
-      GemmP g = mk(Oc[i], Cl[i], nA * 2, lc, lat[i], 128);
-      g.amode = AMODE_CONV3; g.cv_C = Cl[i]; g.cv_Lin = 3; g.cv_nout = 2; g.cv_t0 = 1; g.cv_stride = 1;
-      gemm(c, g, lc, f.fp32);
-    }
-    float* Z = A_alloc<float>(c, (size_t)nA * 256);
-    launch(c, "fpn_merge_kernel", fpn_merge_kernel, dim3(cdiv((long long)nA * 128, 256)), dim3(256), 0, (const float*)lat[0], (const float*)lat[1],
-           (const float*)lat[2], nA, Z);
-    gemm(c, mk(Z, 256, nA, *he.fpn_last, f.nat_out, 128), *he.fpn_last, f.fp32);
-  }
+  } else fpn_layerwise(f, Oc);
   tap(c, "nat_out", f.nat_out, (int64_t)nA * 128);
 }
 
@@ -860,7 +643,7 @@ void ego_token(Fwd& f) {
   float* eq = wconst_get(c, c->wc.ego_q, 128, f.fp32, &fill_eq);
   if (fill_eq) gemm(c, mk(eg.query, 128, 1, *eg.q, eq, 128), *eg.q, f.fp32);
   f.x_ego = A_alloc<float>(c, (size_t)bs * 128);
-  if (!f.fp32 && c->sw.ego_fused) {
+  if (f.kp.ego_fused) {
     EgoP q; memset(&q, 0, sizeof(q));
     q.cs = B->current_state; q.cs_ld = B->cs_ld; q.lw = c->img.ego_w.get(); q.lb = c->img.ego_b.get(); q.pos = eg.pos_embed;
     q.wkv = eg.kv->bf.get(); q.bkv = eg.kv->bias; q.q = eq;
@@ -869,28 +652,7 @@ void ego_token(Fwd& f) {
     q.ds = f.ds;
     c->prof_flops = 2.0 * bs * (6.0 * 128 * 256 + 128.0 * 128);
     launch(c, "ego_fused_kernel", ego_fused_kernel, dim3(bs), dim3(256), 0, q);
-  } else {
-  float* E = A_alloc<float>(c, (size_t)bs * 6 * 128);
-  launch(c, "ego_token_kernel", ego_token_kernel, dim3(cdiv((long long)bs * 6 * 128, 256)), dim3(256), 0, B->current_state, B->cs_ld,
-         (const float*)c->img.ego_w.get(), (const float*)c->img.ego_b.get(), eg.pos_embed, bs, E);
-  float* EKV = A_alloc<float>(c, (size_t)bs * 6 * 256);
-  gemm(c, mk(E, 128, bs * 6, *eg.kv, EKV, 256), *eg.kv, f.fp32);
-  uint8_t* edrop = nullptr;
-  if (f.drop) {
-    edrop = A_alloc<uint8_t>(c, (size_t)bs * 6);
-    launch(c, "ego_dropmask_kernel", ego_dropmask_kernel, dim3(cdiv(bs * 6, 256)), dim3(256), 0, bs, 0.75f, f.seed, f.next_stream(), edrop);
-  }
-  float* EAO = A_alloc<float>(c, (size_t)bs * 128);
-  {
-    MhaP p; memset(&p, 0, sizeof(p));
-    p.Q = eq; p.ldq = 128; p.K = EKV; p.V = EKV + 128; p.ldkv = 256; p.O = EAO; p.ldo = 128;
-    p.nb_outer = bs; p.nb_inner = 1; p.H = 4; p.Lq = 1; p.Lk = 6;
-    p.q_outer = 0; p.q_inner = 0; p.q_stride = 0; p.kv_outer = 6; p.kv_inner = 0; p.kv_stride = 1;
-    p.o_outer = 1; p.o_inner = 0; p.o_stride = 0; p.mask = edrop; p.mask_quirk = 0; p.mask_mod = 1;
-    run_mha(c, p, f.fp32);
-  }
-  gemm(c, mk(EAO, 128, bs, *eg.out_proj, f.x_ego, 128), *eg.out_proj, f.fp32);
-  }
+  } else ego_token_layerwise(f, eq);
   tap(c, "x_ego", f.x_ego, (int64_t)bs * 128);
 }
 
@@ -904,17 +666,13 @@ int build_q0(Fwd& f) {
   float* Mb = wconst_get(c, c->wc.Mb, (size_t)M * 128, f.fp32, &fill);
   if (fill) gemm(c, mk(pd.m_emb, 128, M, *pd.q_proj_m, Mb, 128), *pd.q_proj_m, f.fp32);
   f.Q = A_alloc<float>(c, (size_t)nQ * 128);
-  if (!f.fp32 && c->sw.pi_fused) {
+  if (f.kp.pi_fused) {
     Q0P q; memset(&q, 0, sizeof(q));
     q.r_emb = f.r_emb; q.nL = nL; q.M = M; q.wr = pd.q_proj_r->bf.get(); q.br = pd.q_proj_r->bias;
     q.Mb = Mb; q.Q = f.Q;
     c->prof_flops = 2.0 * nL * 128.0 * 128;
     launch(c, "q0_fused_kernel", q0_fused_kernel, dim3(cdiv(nL, 16)), dim3(256), 0, q);
-  } else {
-    float* Ra = A_alloc<float>(c, (size_t)nL * 128);
-    gemm(c, mk(f.r_emb, 128, nL, *pd.q_proj_r, Ra, 128), *pd.q_proj_r, f.fp32);
-    launch(c, "build_q0_kernel", build_q0_kernel, dim3(cdiv((long long)nQ * 128, 256)), dim3(256), 0, (const float*)Ra, (const float*)Mb, nL, M, f.Q);
-  }
+  } else build_q0_layerwise(f, Mb);
   return RIFT_OK;
 }
 
@@ -922,25 +680,23 @@ int build_q0(Fwd& f) {
 int map_and_embeddings(Fwd& f) {
   Ctx* c = f.c;
   const RiftFeatureBatch* B = f.B;
-  const int S = f.S, nP = f.nP, nL = f.nL, nT = f.nT;
+  const int nP = f.nP, nL = f.nL, nT = f.nT;
   // map encoder (map_encoder.py:31-93)
   // reference-line features are input-only too: both PointsEncoders run side by side (fused path)
-  f.pe_pair = !f.fp32 && c->sw.pe_fused;
-  if (f.pe_pair) points_encoder_pair(f, f.F10, nP, B->map_valid_mask, c->m.map.polygon_encoder, f.F6, nL, B->ref_valid_mask, c->m.dec.r_encoder, &f.poly, &f.r_emb);
-  else f.poly = points_encoder(f, f.F10, 10, nP, 20, B->map_valid_mask, c->m.map.polygon_encoder);
+  if (f.kp.pe != PE_LAYERWISE) points_encoder_pair(f, f.F10, nP, B->map_valid_mask, c->m.map.polygon_encoder, f.F6, nL, B->ref_valid_mask, c->m.dec.r_encoder, &f.poly, &f.r_emb);
+  else f.poly = points_encoder_layerwise(f, f.F10, 10, nP, 20, B->map_valid_mask, c->m.map.polygon_encoder);
   tap(c, "poly_pe", f.poly, (int64_t)nP * 128);
   // the three Fourier embeddings (token positions, speed limits, reference-line positions) depend on inputs only: with both
   // PointsEncoders done they run as ONE launch, and the token kernels add the positional embedding on the way
-  f.fo3 = f.pe_pair && !f.fp32 && c->sw.fo_fused && S == 0;
-  if (f.fo3) {
+  if (f.kp.fourier == FO_THREE || f.kp.fourier == FO_THREE_W) {
     tap(c, "r_pe", f.r_emb, (int64_t)nL * 128);
     FourierP3 q3; memset(&q3, 0, sizeof(q3));
-    q3.e[0] = fourier_desc(f, f.pos, 3, nT, c->m.pos_emb, 2, nullptr);
-    q3.e[1] = fourier_desc(f, B->map_polygon_speed_limit, 1, nP, c->m.map.speed_limit_emb, -1, nullptr);
-    q3.e[2] = fourier_desc(f, f.r_pos, 3, nL, c->m.dec.r_pos_emb, -1, f.r_emb);
+    q3.e[0] = fourier_desc(f, f.pos, 3, nT, c->m.pos_emb, 2, false, nullptr);
+    q3.e[1] = fourier_desc(f, B->map_polygon_speed_limit, 1, nP, c->m.map.speed_limit_emb, -1, false, nullptr);
+    q3.e[2] = fourier_desc(f, f.r_pos, 3, nL, c->m.dec.r_pos_emb, -1, true, f.r_emb);
     q3.nblk[0] = cdiv(nT, FO_ROWS); q3.nblk[1] = cdiv(nP, FO_ROWS); q3.nblk[2] = cdiv(nL, FO_ROWS); q3.count = 3;
     c->prof_flops = 2.0 * 128.0 * ((nT + nL) * (3 * 257.0 + 128.0) + nP * (257.0 + 128.0));
-    if (c->sw.fo_w) {          // wave-private form: one 16-row tile per wave, 8 tiles per pass, the one-dimensional embedding two passes per workgroup
+    if (f.kp.fourier == FO_THREE_W) {          // wave-private form: one 16-row tile per wave, 8 tiles per pass, the one-dimensional embedding two passes per workgroup
       FoWP w; memset(&w, 0, sizeof(w));
       w.count = 3;
       for (int i = 0; i < 3; ++i) {
@@ -951,11 +707,11 @@ int map_and_embeddings(Fwd& f) {
       launch_call(c, "fo_w_kernel", [&] { fow_launch(w, c->stream); });
     } else
     launch(c, "fourier_fused_kernel", fourier_fused_kernel, dim3(q3.nblk[0] + q3.nblk[1] + q3.nblk[2]), dim3(256), (size_t)FO_LDS, q3);
-    f.PEtok = q3.e[0].Y; f.speed_emb = q3.e[1].Y; f.rpe_done = true;
+    f.PEtok = q3.e[0].Y; f.speed_emb = q3.e[1].Y;
   } else {
     f.speed_emb = fourier(f, B->map_polygon_speed_limit, 1, nP, c->m.map.speed_limit_emb, -1);
   }
-  if (f.plan.forked && f.rpe_done) TRY(build_q0(f));      // ahead of the join
+  if (f.kp.q0_early) TRY(build_q0(f));      // ahead of the join
   return RIFT_OK;
 }
 
@@ -978,20 +734,17 @@ void assemble_tokens(Fwd& f) {
     launch(c, "static_token_kernel", static_token_kernel, dim3(cdiv((long long)bs * S * 128, 256)), dim3(256), 0, (const float*)semb, B->static_category,
            B->static_valid_mask, c->m.stat.type_emb, bs, A, Mp, S, N, f.X);
   }
-  if (!f.fo3) fourier(f, f.pos, 3, nT, c->m.pos_emb, 2, f.X);
+  if (f.kp.fourier != FO_THREE && f.kp.fourier != FO_THREE_W) fourier(f, f.pos, 3, nT, c->m.pos_emb, 2, true, f.X);      // (else token_kernel added it on the way)
   tap(c, "x_tokens", f.X, (int64_t)nT * 128);
 }
 
 // ================= encoder blocks (transformer.py:73-94) =================
 void scene_encoder(Fwd& f) {
   Ctx* c = f.c;
-  const int bs = f.bs, R = f.R, N = f.N, nT = f.nT;
-  static const float edpr[4] = {0.f, 0.2f / 3.f, 0.4f / 3.f, 0.2f};   // linspace(0, 0.2, 4), pluto_model.py:80-83
+  const int bs = f.bs, N = f.N, nT = f.nT;
   f.ENC = A_alloc<float>(c, (size_t)nT * 128);
-  // 97 .. 112 token slots (what train_cbv collates: 49 + 60 = 109): the fused kernel on its 112-row layout (enc_fused.h: EncLay<112>) when the
-  // decoder's eight-key-tile variant consumes its K | V^T image; RIFT_ENC112=0 keeps those shapes on enc_w_kernel
-  f.enc_wide = N > 96 && N <= 112 && c->sw.enc112 && c->sw.dec_fused && R <= 8 && ENC_NW == 8;
-  if (c->sw.enc_fused && !f.fp32 && (N <= 96 || f.enc_wide)) {
+  const bool wide = f.kp.enc == ENC_FUSED112;      // the fused kernel on its 112-row layout (enc_fused.h: EncLay<112>)
+  if (f.kp.enc == ENC_FUSED96 || wide) {
     EncFusedP ep; memset(&ep, 0, sizeof(ep));
     ep.X = f.X; ep.Y = f.ENC; ep.kpm = f.kpm; ep.bs = bs; ep.N = N; ep.seed = f.seed; ep.stream = f.next_stream(); f.stream_id += 8;
     for (int i = 0; i < 4; ++i) {
@@ -1003,62 +756,34 @@ void scene_encoder(Fwd& f) {
       w.wo = p.out_proj->bf.get(); w.bo = p.out_proj->bias;
       w.w1 = p.fc1->bf.get(); w.b1 = p.fc1->bias;
       w.w2 = p.fc2->hid.get(); w.b2 = p.fc2->bias;      // (hidden-layer operand words: pack_hid)
-      w.droppath = f.drop ? edpr[i] : 0.f;
+      w.droppath = f.drop ? ENC_DPR[i] : 0.f;
     }
     ep.norm_g = c->m.norm.g; ep.norm_b = c->m.norm.b; ep.nonfinite = c->nonfinite.get();
     ep.ds = f.ds; ep.dbg = c->sw.no_skip ? 1 : 0;
     if (c->sw.enc_ts) { ep.ts = A_alloc<long long>(c, 256); tap(c, "enc_ts", (float*)ep.ts, 512); }
     c->prof_flops = 4.0 * bs * N * (2.0 * 128 * 384 + 4.0 * N * 128 + 2.0 * 128 * 128 + 4.0 * 128 * 512);
-    if (c->sw.dec_fused && R <= 8 && ENC_NW == 8) {   // the decoder kernel will run: emit its cross-attention K | V operand fragments here
-      f.enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * (f.enc_wide ? 96 : DECW_KV_FRAGS) * 512);      // (wide: the dense per-head image, dec_kv.h)
+    if (f.kp.enc_image != IMG_NONE) {   // the decoder kernel will run: emit its cross-attention K | V operand fragments here
+      f.enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * (f.kp.enc_image == IMG_DENSE ? 96 : DECW_KV_FRAGS) * 512);      // (dense: the per-head image, dec_kv.h)
       ep.wkv = c->m.dec.kv_all->bf.get(); ep.bkv = c->m.dec.kv_all->bias;
       ep.KT = f.enc_KT;
-      f.kpm_c = A_alloc<uint8_t>(c, (size_t)bs * (f.enc_wide ? 112 : 96)); ep.kpm_c = f.kpm_c;
+      f.kpm_c = A_alloc<uint8_t>(c, (size_t)bs * (wide ? 112 : 96)); ep.kpm_c = f.kpm_c;
       f.enc_x0p = A_alloc<float>(c, (size_t)bs * 128);
       ep.wx0 = c->m.dec.cat_x_proj_x->bf.get(); ep.x0p = f.enc_x0p;
       c->prof_flops += 2.0 * bs * N * 128.0 * 1024;
     }
-    if (f.enc_wide) launch_call(c, "enc_fused112_kernel", [&] { enc112_launch(ep, c->stream); });
+    if (wide) launch_call(c, "enc_fused112_kernel", [&] { enc112_launch(ep, c->stream); });
     else launch(c, "enc_fused_kernel", enc_fused_kernel<ENC_NW>, dim3(bs), dim3(64 * ENC_NW), (size_t)RIFT_ENC_LDS_BYTES, ep);
-  } else if (c->sw.enc_fused && !f.fp32 && N <= 192) {   // dense-traffic shapes: the wave-private, weight-streaming encoder (two passes per layer)
+  } else if (f.kp.enc == ENC_W) {   // dense-traffic shapes: the wave-private, weight-streaming encoder (two passes per layer)
     EncWP eq; memset(&eq, 0, sizeof(eq));
     eq.X = f.X; eq.Y = f.ENC; eq.kpm = f.kpm; eq.bs = bs; eq.N = N; eq.seed = f.seed; eq.stream = f.next_stream(); f.stream_id += 8;
     eq.KVs = A_alloc<unsigned short>(c, (size_t)bs * 96 * 512);
     eq.img = c->img.encw_img.get(); eq.par = c->img.encw_par.get(); eq.nonfinite = c->nonfinite.get();
-    if (c->sw.dec_fused && R <= 16) { f.enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * 96 * 512); eq.DKV = f.enc_KT; }   // the decoder's (dense-variant) operands
-    for (int i = 0; i < 4; ++i) eq.droppath[i] = f.drop ? edpr[i] : 0.f;
+    if (f.kp.enc_image == IMG_DENSE) { f.enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * 96 * 512); eq.DKV = f.enc_KT; }   // the decoder's (dense-variant) operands
+    for (int i = 0; i < 4; ++i) eq.droppath[i] = f.drop ? ENC_DPR[i] : 0.f;
     eq.ds = f.ds;
     c->prof_flops = 4.0 * bs * N * (2.0 * 128 * 384 + 4.0 * N * 128 + 2.0 * 128 * 128 + 4.0 * 128 * 512);
     launch_call(c, "enc_w_kernel", [&] { encw_launch(eq, c->stream); });
-  } else {
-  float* QKV = A_alloc<float>(c, (size_t)nT * 384);
-  float* AO = A_alloc<float>(c, (size_t)nT * 128);
-  float* H512 = A_alloc<float>(c, (size_t)nT * 512);
-  for (int i = 0; i < 4; ++i) {
-    const SceneBlockW& p = c->m.encoder_blocks[i];
-    GemmP g = mk(f.X, 128, nT, *p.qkv, QKV, 384);
-    g.pro = PRO_LN; g.pg = p.norm1.g; g.pb = p.norm1.b;
-    gemm(c, g, *p.qkv, f.fp32);
-    MhaP m; memset(&m, 0, sizeof(m));
-    m.Q = QKV; m.ldq = 384; m.K = QKV + 128; m.V = QKV + 256; m.ldkv = 384; m.O = AO; m.ldo = 128;
-    m.nb_outer = bs; m.nb_inner = 1; m.H = 4; m.Lq = N; m.Lk = N;
-    m.q_outer = N; m.q_stride = 1; m.kv_outer = N; m.kv_stride = 1; m.o_outer = N; m.o_stride = 1;
-    m.mask = f.kpm; m.mask_mod = 1;
-    run_mha(c, m, f.fp32);
-    GemmP g2 = mk(AO, 128, nT, *p.out_proj, f.X, 128);
-    g2.residual = f.X; g2.ldr = 128;
-    if (f.drop && edpr[i] > 0.f) { g2.droppath_p = edpr[i]; g2.dp_div = N; g2.seed = f.seed; g2.stream = f.next_stream(); }
-    gemm(c, g2, *p.out_proj, f.fp32);
-    GemmP g3 = mk(f.X, 128, nT, *p.fc1, H512, 512);
-    g3.pro = PRO_LN; g3.pg = p.norm2.g; g3.pb = p.norm2.b; g3.act = ACT_GELU;
-    gemm(c, g3, *p.fc1, f.fp32);
-    GemmP g4 = mk(H512, 512, nT, *p.fc2, f.X, 128);
-    g4.residual = f.X; g4.ldr = 128;
-    if (f.drop && edpr[i] > 0.f) { g4.droppath_p = edpr[i]; g4.dp_div = N; g4.seed = f.seed; g4.stream = f.next_stream(); }
-    gemm(c, g4, *p.fc2, f.fp32);
-  }
-  layernorm(f, f.X, 128, f.ENC, 128, nT, 128, c->m.norm);
-  }
+  } else scene_encoder_layerwise(f);
   tap(c, "enc_out", f.ENC, (int64_t)nT * 128);
 }
 
@@ -1069,100 +794,8 @@ void agent_predictor(Fwd& f) {
   const int bs = f.bs, A = f.A, N = f.N;
   if (f.need_traj && out->prediction && A > 1) {
     const int rows = bs * (A - 1);
-    if (!f.fp32 && c->sw.heads_fused) {
-      heads3_fused(f, f.ENC, 128, rows, A - 1, N, 1, c->m.predictor, out->prediction);
-    } else {
-    float* Xa = A_alloc<float>(c, (size_t)rows * 128);
-    launch(c, "gather_rows_kernel", gather_rows_kernel, dim3(cdiv((long long)rows * 128, 256)), dim3(256), 0, (const float*)f.ENC, 128, Xa, 128, rows, 128,
-           A - 1, N, 1);
-    float* o3[3];
-    for (int i = 0; i < 3; ++i) {
-      o3[i] = A_alloc<float>(c, (size_t)rows * 160);
-      mlp_layer(f, Xa, 128, rows, c->m.predictor[i], o3[i], 160, f.fp32);
-    }
-    launch(c, "interleave_traj_kernel", interleave_traj_kernel, dim3(cdiv((long long)rows * 480, 256)), dim3(256), 0, (const float*)o3[0], (const float*)o3[1],
-           (const float*)o3[2], rows, out->prediction);
-    }
-  }
-}
-
-// the four decoder blocks as GEMM / attention launches (fp32 mode, RIFT_DEC_UNFUSED=1, shapes outside the fused kernel's)
-void decoder_layerwise(Fwd& f, float dp) {
-  Ctx* c = f.c;
-  const int bs = f.bs, R = f.R, N = f.N, M = f.M, nL = f.nL, nQ = f.nQ, nT = f.nT;
-  float* DQKV = A_alloc<float>(c, (size_t)nQ * 384);
-  float* DAO = A_alloc<float>(c, (size_t)nQ * 128);
-  float* DQc = A_alloc<float>(c, (size_t)nQ * 128);
-  float* DH = A_alloc<float>(c, (size_t)nQ * 512);
-  float* KVm = A_alloc<float>(c, (size_t)nT * 256);
-  const int n_layers = c->sw.dec_layers == 0 || c->sw.dec_layers == 2 ? c->sw.dec_layers : 4;      // (RIFT_DEC_LAYERS)
-  for (int i = 0; i < n_layers; ++i) {
-    const DecoderBlockW& p = c->m.dec.decoder_blocks[i];
-    // ---- r2r self attention over the R reference lines of each (scene, mode), with the mask quirk
-    GemmP g = mk(f.Q, 128, nQ, *p.r2r_qkv, DQKV, 384);
-    g.pro = PRO_LN; g.pg = p.norm[0].g; g.pb = p.norm[0].b;
-    gemm(c, g, *p.r2r_qkv, f.fp32);
-    {
-      MhaP m; memset(&m, 0, sizeof(m));
-      m.Q = DQKV; m.ldq = 384; m.K = DQKV + 128; m.V = DQKV + 256; m.ldkv = 384; m.O = DAO; m.ldo = 128;
-      m.nb_outer = bs; m.nb_inner = M; m.H = 4; m.Lq = R; m.Lk = R;
-      m.q_outer = R * M; m.q_inner = 1; m.q_stride = M; m.kv_outer = R * M; m.kv_inner = 1; m.kv_stride = M;
-      m.o_outer = R * M; m.o_inner = 1; m.o_stride = M;
-      m.mask = f.q_kpm; m.mask_quirk = 1; m.mask_mod = f.q_bs; m.mask_off = f.q_off * M;   // tgt_key_padding_mask.repeat(M, 1), planning_decoder.py:56-60
-      if (dp > 0.f) { m.dropout_p = dp; m.seed = f.seed; m.stream = f.next_stream(); }
-      run_mha(c, m, f.fp32);
-    }
-    GemmP g2 = mk(DAO, 128, nQ, *p.r2r_out, f.Q, 128);
-    g2.residual = f.Q; g2.ldr = 128;
-    if (dp > 0.f) { g2.dropout_p = dp; g2.seed = f.seed; g2.stream = f.next_stream(); }
-    gemm(c, g2, *p.r2r_out, f.fp32);
-    // ---- m2m self attention over the 12 modes: q = k = (h + m_pos) W + b, v = h W + b
-    bool fill_mp;
-    float* MP = wconst_get(c, c->wc.mp[i], (size_t)M * 384, f.fp32, &fill_mp);
-    if (fill_mp) gemm(c, mk(c->m.dec.m_pos, 128, M, *p.m2m_qk0, MP, 384), *p.m2m_qk0, f.fp32);
-    GemmP g3 = mk(f.Q, 128, nQ, *p.m2m_qkv, DQKV, 384);
-    g3.pro = PRO_LN; g3.pg = p.norm[1].g; g3.pb = p.norm[1].b;
-    g3.gbias = MP; g3.gb_div = 1; g3.gb_mod = M;
-    gemm(c, g3, *p.m2m_qkv, f.fp32);
-    {
-      MhaP m; memset(&m, 0, sizeof(m));
-      m.Q = DQKV; m.ldq = 384; m.K = DQKV + 128; m.V = DQKV + 256; m.ldkv = 384; m.O = DAO; m.ldo = 128;
-      m.nb_outer = nL; m.nb_inner = 1; m.H = 4; m.Lq = M; m.Lk = M;
-      m.q_outer = M; m.q_stride = 1; m.kv_outer = M; m.kv_stride = 1; m.o_outer = M; m.o_stride = 1;
-      if (dp > 0.f) { m.dropout_p = dp; m.seed = f.seed; m.stream = f.next_stream(); }
-      run_mha(c, m, f.fp32);
-    }
-    GemmP g4 = mk(DAO, 128, nQ, *p.m2m_out, f.Q, 128);
-    g4.residual = f.Q; g4.ldr = 128; g4.rowzero = f.r_kpm; g4.rz_div = M;   // rows of padded ref lines become 0 (:65-72)
-    if (dp > 0.f) { g4.dropout_p = dp; g4.seed = f.seed; g4.stream = f.next_stream(); }
-    gemm(c, g4, *p.m2m_out, f.fp32);
-    // ---- cross attention: R*12 queries per scene against the encoder tokens
-    GemmP g5 = mk(f.Q, 128, nQ, *p.cross_q, DQc, 128);
-    g5.pro = PRO_LN; g5.pg = p.norm[2].g; g5.pb = p.norm[2].b;
-    gemm(c, g5, *p.cross_q, f.fp32);
-    gemm(c, mk(f.ENC, 128, nT, *p.cross_kv, KVm, 256), *p.cross_kv, f.fp32);
-    {
-      MhaP m; memset(&m, 0, sizeof(m));
-      m.Q = DQc; m.ldq = 128; m.K = KVm; m.V = KVm + 128; m.ldkv = 256; m.O = DAO; m.ldo = 128;
-      m.nb_outer = bs; m.nb_inner = 1; m.H = 4; m.Lq = R * M; m.Lk = N;
-      m.q_outer = R * M; m.q_stride = 1; m.kv_outer = N; m.kv_stride = 1; m.o_outer = R * M; m.o_stride = 1;
-      m.mask = f.kpm; m.mask_mod = 1;
-      if (dp > 0.f) { m.dropout_p = dp; m.seed = f.seed; m.stream = f.next_stream(); }
-      run_mha(c, m, f.fp32);
-    }
-    GemmP g6 = mk(DAO, 128, nQ, *p.cross_out, f.Q, 128);
-    g6.residual = f.Q; g6.ldr = 128;
-    if (dp > 0.f) { g6.dropout_p = dp; g6.seed = f.seed; g6.stream = f.next_stream(); }
-    gemm(c, g6, *p.cross_out, f.fp32);
-    // ---- FFN
-    GemmP g7 = mk(f.Q, 128, nQ, *p.ffn0, DH, 512);
-    g7.pro = PRO_LN; g7.pg = p.norm[3].g; g7.pb = p.norm[3].b; g7.act = ACT_RELU;
-    if (dp > 0.f) { g7.dropout_p = dp; g7.seed = f.seed; g7.stream = f.next_stream(); }
-    gemm(c, g7, *p.ffn0, f.fp32);
-    GemmP g8 = mk(DH, 512, nQ, *p.ffn3, f.Q, 128);
-    g8.residual = f.Q; g8.ldr = 128;
-    if (dp > 0.f) { g8.dropout_p = dp; g8.seed = f.seed; g8.stream = f.next_stream(); }
-    gemm(c, g8, *p.ffn3, f.fp32);
+    if (f.kp.heads_fused) heads3_fused(f, f.ENC, 128, rows, A - 1, N, 1, c->m.predictor, out->prediction);
+    else agent_predictor_layerwise(f, rows);
   }
 }
 
@@ -1170,32 +803,31 @@ void decoder_layerwise(Fwd& f, float dp) {
 int planning_decoder(Fwd& f) {
   Ctx* c = f.c;
   const RiftFeatureBatch* B = f.B;
-  const int flags = f.flags;
+  const KernelPlan& kp = f.kp;
   const int bs = f.bs, R = f.R, N = f.N, M = f.M, nL = f.nL, nQ = f.nQ;
-  if (!f.pe_pair) f.r_emb = points_encoder(f, f.F6, 6, nL, 120, B->ref_valid_mask, c->m.dec.r_encoder);
-  if (!f.rpe_done) {
+  if (kp.pe == PE_LAYERWISE) f.r_emb = points_encoder_layerwise(f, f.F6, 6, nL, 120, B->ref_valid_mask, c->m.dec.r_encoder);
+  if (kp.fourier != FO_THREE && kp.fourier != FO_THREE_W) {
     tap(c, "r_pe", f.r_emb, (int64_t)nL * 128);
-    fourier(f, f.r_pos, 3, nL, c->m.dec.r_pos_emb, -1, f.r_emb);
+    fourier(f, f.r_pos, 3, nL, c->m.dec.r_pos_emb, -1, true, f.r_emb);
   }
   tap(c, "r_emb", f.r_emb, (int64_t)nL * 128);
-  if (!f.Q) TRY(build_q0(f));
+  if (!kp.q0_early) TRY(build_q0(f));
   tap(c, "q0", f.Q, (int64_t)nQ * 128);
 
   f.dec_deferred = false; memset(&f.dec_later, 0, sizeof(f.dec_later));
   dp_exchange(f, 0);                      // (eval forward under data parallelism: the mask slots have not travelled yet)
   const float dp = f.drop ? 0.1f : 0.f;   // pluto_model.py:35,93
-  const bool dec_dense = (R > 8 || N > 96) && R <= 16 && N <= 192;      // dense-traffic shapes: the kernel's round-of-eight-tiles variant
-  if (c->sw.dec_fused && !f.fp32 && dec_dense && !f.enc_KT) {   // its K | V^T operand fragments from the (layer-wise) encoder's output
+  if (kp.dec_kv_frag) {   // the dense variant's K | V^T operand fragments from the output of an encoder that emitted none
     f.enc_KT = A_alloc<unsigned short>(c, (size_t)bs * 4 * 96 * 512);
     DecKvP kq; memset(&kq, 0, sizeof(kq));
     kq.ENC = f.ENC; kq.bs = bs; kq.N = N; kq.wkv = c->m.dec.kv_all->bf.get(); kq.bkv = c->m.dec.kv_all->bias; kq.KV = f.enc_KT;
     c->prof_flops = 2.0 * bs * N * 128.0 * 1024;
     launch(c, "dec_kv_frag_kernel", dec_kv_frag_kernel, dim3(bs), dim3(512), (size_t)DEC_KV_LDS, kq);
   }
-  if (c->sw.dec_fused && !f.fp32 && ((R <= 8 && N <= 96) || dec_dense) && f.enc_KT) {
+  if (kp.dec != DEC_LAYERWISE) {
     DecWP dq; memset(&dq, 0, sizeof(dq));
     dq.Q = f.Q; dq.kpm = f.kpm; dq.r_kpm = f.r_kpm; dq.q_kpm = f.q_kpm; dq.q_bs = f.q_bs; dq.q_off = f.q_off; dq.bs = bs; dq.N = N; dq.R = R; dq.dropout = dp; dq.seed = f.seed;
-    if (f.kpm_c) { dq.kpm = f.kpm_c; dq.N = f.enc_wide ? 112 : 96; dq.compact = 1; }      // (the encoder compacted its rows: its own key padding, valid keys a prefix)
+    if (kp.enc_kpm_x0p) { dq.kpm = f.kpm_c; dq.N = kp.enc == ENC_FUSED112 ? 112 : 96; dq.compact = 1; }      // (the encoder compacted its rows: its own key padding, valid keys a prefix)
     dq.stream = f.next_stream(); f.stream_id += 64;
     dq.KV = f.enc_KT; dq.img = c->img.decw_img.get(); dq.par = c->img.decw_par.get(); dq.nonfinite = c->nonfinite.get();
     dq.ds = f.ds;
@@ -1203,37 +835,15 @@ int planning_decoder(Fwd& f) {
     dq.dbg = c->sw.dec_dbg | (c->sw.no_skip ? 64 : 0);
     dq.prob_only = f.need_traj ? 0 : 1;      // no trajectory heads: the policy head and the objectives mask the rows of padded reference lines, nobody else reads them
     c->prof_flops = 4.0 * bs * (R * M) * (2.0 * 128 * (384 + 128) * 2 + 2.0 * 128 * 128 * 2 + 4.0 * 128 * 512 + 4.0 * 128 * (N + R + M));
-    // (with the trajectory heads on, the tail behind the decoder is longer and the caller's queue carries the prediction head too: measured
-    // worth it up to twice the batch -- 128 scenes 0.419 -> 0.391 ms, 256 scenes 0.707 -> 0.713)
-    dq.l0 = 0; dq.l1 = 4;
-    // Which batches: measured per size (profiles/r04_batch_sweep.txt; ms per step with / without): 32 0.18 / 0.23, 64 0.21 / 0.24, 80 0.253 / 0.264, 88 0.259 / 0.254,
-    // 96 0.315 / 0.300, 104 0.325 / 0.321, 112 0.338 / 0.359, 128 0.368 / 0.381, 160 0.433 / 0.440, 192 0.503 / 0.520, 256 0.656 / 0.65 -- a win except between 84 and 108
-    // scenes and at a chip-filling batch.  RIFT_DEC_DEFER=<n> replaces the table by bs <= n (0: never).
-    const bool dec_size_ok = c->sw.dec_defer_max >= 0 ? bs <= c->sw.dec_defer_max : (f.need_traj ? bs <= 128 : (bs <= 84 || (bs >= 108 && bs <= 192)));
-    const bool dec_may_defer = (flags & RIFT_F_DEFER_HEAD) && dec_size_ok && !c->prof_on;      // (the same in the sizing pass)
-    // ... and split: layers 0 - 1 here, behind the encoder, layers 2 - 3 in front of the deferred head -- token assembly + encoder + half a decoder
-    // on the caller's queue against half a decoder + tail on the update stream (9 + 88 + 55 against 55 + 80 us at 32 scenes) instead of 97 against
-    // 190.  The dropout streams of the second launch carry on from the states the first one leaves (rng_io): the draws are a single launch's.
-    // Measured (ms per step, split / one launch): 64 scenes 0.217 / 0.229, 32 scenes 0.20 - 0.21 / 0.20 - 0.21 (the host issues a 32-scene step in 0.15 - 0.2 ms: it
-    // bounds that one now); with the trajectory heads on the caller's queue carries the prediction head as well and the split LOSES (0.30 / 0.26 at 64): off there.
-    uint32_t* rng_io = (dec_may_defer && c->sw.dec_split && !f.need_traj) ? A_alloc<uint32_t>(c, (size_t)bs * 512 * 4) : nullptr;
-    f.dec_deferred = dec_may_defer && !c->dry && !dq.ts;
-    if (f.dec_deferred) {
-      f.dec_later = dq;
-      if (rng_io) {
-        dq.l1 = 2; dq.rng_io = rng_io;
-        launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });
-        f.dec_later.l0 = 2; f.dec_later.rng_io = rng_io;
-      }
-    } else if (c->sw.dec_layers == 22 && dp == 0.f) {      // (RIFT_DEC_LAYERS=22: an eval forward's layers as two launches; the rows travel through Q as in the deferred split)
-      dq.l1 = 2;
+    // which layers run here and which with the deferred head: the plan's (fwd_kernels.h).  The rows travel through Q between two launches;
+    // the dropout streams of a deferred second half carry on from the states the first one leaves (rng_io): the draws are a single launch's
+    dq.rng_io = kp.dec_split ? A_alloc<uint32_t>(c, (size_t)bs * 512 * 4) : nullptr;
+    for (int i = 0; i < kp.dec_n_now; ++i) {
+      dq.l0 = kp.dec_now[i].l0; dq.l1 = kp.dec_now[i].l1;
       launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });
-      dq.l0 = 2; dq.l1 = 4;
-      launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });
-    } else if (c->sw.dec_layers == 2) {                    // (RIFT_DEC_LAYERS=2: `dec3` taps the output of layer 1)
-      dq.l1 = 2;
-      launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });
-    } else if (c->sw.dec_layers != 0) launch_call(c, "dec_w_kernel", [&] { decw_launch(dq, c->stream); });      // (RIFT_DEC_LAYERS=0: `dec3` taps q0)
+    }
+    f.dec_deferred = kp.dec_defer;
+    if (kp.dec_defer) { f.dec_later = dq; f.dec_later.l0 = kp.dec_later.l0; f.dec_later.l1 = kp.dec_later.l1; }
   } else decoder_layerwise(f, dp);
   tap(c, "dec3", f.Q, (int64_t)nQ * 128);
   return RIFT_OK;
@@ -1247,7 +857,7 @@ int policy_and_ego_heads(Fwd& f) {
   const int bs = f.bs, R = f.R, N = f.N, nQ = f.nQ;
   // cat_x_proj(cat[q, enc_emb[:, 0]]) (planning_decoder.py:177-179): ego-token part is a per-scene bias
   float* x0p = f.enc_x0p;
-  if (!x0p) {
+  if (!f.kp.enc_kpm_x0p) {      // (the encoder's tail did not emit it)
     x0p = A_alloc<float>(c, (size_t)bs * 128);
     gemm(c, mk(f.ENC, N * 128, bs, *c->m.dec.cat_x_proj_x, x0p, 128), *c->m.dec.cat_x_proj_x, f.fp32);
   }
@@ -1255,18 +865,18 @@ int policy_and_ego_heads(Fwd& f) {
   // rift_forward_head on a stream of the caller's choice, so that it (and the loss / backward / update behind it) runs beside the next
   // forward's frozen trunk
   Ctx::Head hs;
-  hs.valid = true; hs.fp32 = f.fp32; hs.need_traj = f.need_traj && out->trajectory != nullptr; hs.Q = f.Q; hs.x0p = x0p; hs.r_kpm = f.r_kpm;
+  hs.valid = true; hs.fp32 = f.fp32; hs.need_traj = f.kp.head_traj; hs.pi_fused = f.kp.pi_fused; hs.heads_fused = f.kp.heads_fused; hs.Q = f.Q; hs.x0p = x0p; hs.r_kpm = f.r_kpm;
   hs.bs = bs; hs.R = R; hs.nQ = nQ; hs.traj = out->trajectory;
   hs.QF = A_alloc<float>(c, (size_t)nQ * 128);
   hs.Hpi = A_alloc<float>(c, (size_t)nQ * 128);
   hs.prob = out->probability ? out->probability : A_alloc<float>(c, nQ);
-  if (hs.need_traj && (f.fp32 || !c->sw.heads_fused))      // layer-wise trajectory heads: their buffers come out of this forward's arena
-    for (int i = 0; i < 3; ++i) { hs.oT[i] = A_alloc<float>(c, (size_t)nQ * 256); hs.o3[i] = A_alloc<float>(c, (size_t)nQ * 160); }
+  if (hs.need_traj && !hs.heads_fused) traj_heads_reserve(c, hs);      // layer-wise trajectory heads: their buffers come out of this forward's arena
   hs.dec_pending = f.dec_deferred; hs.dec = f.dec_later;
   if (flags & RIFT_F_DEFER_HEAD) { if (!c->dry) c->slots[c->parity].head = hs; }
   else TRY(head_impl(c, hs));
   // hidden_proj / ref_free_decoder on the ego token (pluto_model.py:173-180)
-  if (!f.fp32 && c->sw.heads_fused && (out->hidden || (f.need_traj && out->ref_free_trajectory))) {      // one launch (heads_fused.h: ego_heads_kernel)
+  if (!f.kp.heads_fused) ego_heads_layerwise(f);
+  else if (out->hidden || (f.need_traj && out->ref_free_trajectory)) {      // one launch (heads_fused.h: ego_heads_kernel)
     const PW &h0 = *c->m.hidden_proj0, &h2 = *c->m.hidden_proj2, &r0 = *c->m.ref_free_decoder.l0, &r3 = *c->m.ref_free_decoder.l3;
     EgoHeadsP q; memset(&q, 0, sizeof(q));
     q.X = f.ENC; q.ldx = N * 128; q.rows = bs;
@@ -1276,18 +886,7 @@ int policy_and_ego_heads(Fwd& f) {
     q.hidden = out->hidden; q.ref = (f.need_traj && out->ref_free_trajectory) ? out->ref_free_trajectory : nullptr;
     c->prof_flops = 2.0 * bs * (2.0 * 128 * 128 + 128.0 * 256 + 256.0 * 320);
     launch(c, "ego_heads_kernel", ego_heads_kernel, dim3(cdiv(bs, 16)), dim3(256), 0, q);
-    return RIFT_OK;
   }
-  if (out->hidden) {
-    float* Th = A_alloc<float>(c, (size_t)bs * 128);
-    GemmP g = mk(f.ENC, N * 128, bs, *c->m.hidden_proj0, Th, 128);
-    g.act = ACT_RELU;
-    gemm(c, g, *c->m.hidden_proj0, f.fp32);
-    gemm(c, mk(Th, 128, bs, *c->m.hidden_proj2, out->hidden, 128), *c->m.hidden_proj2, f.fp32);
-  }
-  if (f.need_traj && out->ref_free_trajectory)
-    mlp_layer(f, f.ENC, N * 128, bs, c->m.ref_free_decoder, out->ref_free_trajectory, 320, f.fp32);
-
   return RIFT_OK;
 }
 
@@ -1300,14 +899,32 @@ int plan_resources(Ctx* c, const StreamPlan& p) {
   return RIFT_OK;
 }
 
-StreamPlan plan_of(const Ctx* c, bool fp32, int bs) {
-  PlanIn in;
-  in.two_streams = c->sw.two_streams; in.nat_fused = c->sw.nat_fused; in.nat_aside = c->sw.nat_aside; in.side_gate = c->sw.side_gate;
-  in.fp32 = fp32; in.prof_on = c->prof_on; in.dry = c->dry; in.prep_set = c->st.prep_set; in.dp_on = c->dp.on; in.bs = bs;
-  return plan_streams(in);
+// What the kernel plan may depend on (fwd_kernels.h), but for `forked`, which forward_impl takes from the stream plan.
+KernelIn kernel_in(const Ctx* c, const RiftFeatureBatch* B, const RiftOutputs* out, int flags) {
+  const Ctx::Switches& sw = c->sw;
+  KernelIn in;
+  in.nat_fused = sw.nat_fused; in.dec_fused = sw.dec_fused; in.enc_fused = sw.enc_fused; in.pe_fused = sw.pe_fused; in.fo_fused = sw.fo_fused;
+  in.fpn_fused = sw.fpn_fused; in.ego_fused = sw.ego_fused; in.heads_fused = sw.heads_fused; in.pi_fused = sw.pi_fused;
+  in.fo_w = sw.fo_w; in.pe_w = sw.pe_w; in.nat_compact = sw.nat_compact; in.pe_live = sw.pe_live; in.pe_pack = sw.pe_pack;
+  in.rank_in_prep = sw.rank_in_prep; in.enc112 = sw.enc112;
+  in.dec_defer_max = sw.dec_defer_max; in.dec_split = sw.dec_split; in.dec_layers = sw.dec_layers; in.dec_ts = sw.dec_ts != 0;
+  in.fp32 = (flags & RIFT_F_FP32) != 0; in.train = (flags & RIFT_F_TRAIN) != 0; in.drop = in.train && !(flags & RIFT_F_NO_DROP);
+  in.need_traj = (flags & RIFT_F_NEED_TRAJ) != 0; in.want_traj = out->trajectory != nullptr;
+  in.defer_head = (flags & RIFT_F_DEFER_HEAD) != 0; in.prof_on = c->prof_on;
+  in.forked = false;
+  in.bs = B->bs; in.A = B->A; in.Mp = B->Mp; in.S = B->S; in.R = B->R; in.enc_nw = ENC_NW;
+  return in;
 }
 
-// One forward on c->stream (the caller's), in the arena of c->parity; with c->dry set, the sizing pass: the same code, no launch.  The
+PlanIn plan_in(const Ctx* c, const KernelIn& k) {
+  PlanIn in;
+  in.two_streams = c->sw.two_streams; in.nat_fused = plan_hist_wave(k); in.nat_aside = c->sw.nat_aside; in.side_gate = c->sw.side_gate;
+  in.fp32 = k.fp32; in.prof_on = k.prof_on; in.dry = c->dry; in.prep_set = c->st.prep_set; in.dp_on = c->dp.on; in.bs = k.bs;
+  return in;
+}
+
+// One forward on c->stream (the caller's), in the arena of c->parity; with c->dry set, the sizing pass: the same stages under the same
+// kernel plan, so the same allocations, and no launch (rift_forward checks the two passes' arena use against each other).  The
 // stages switch c->stream by the plan (fwd_plan.h) and an early error return leaves it switched: rift_forward restores it.
 int forward_impl(Ctx* c, const RiftFeatureBatch* B, const RiftOutputs* out, int flags, uint32_t seed) {
   Fwd f;
@@ -1318,8 +935,12 @@ int forward_impl(Ctx* c, const RiftFeatureBatch* B, const RiftOutputs* out, int 
   f.bs = B->bs; f.A = B->A; f.Mp = B->Mp; f.R = B->R; f.S = B->S; f.T = B->T;
   f.N = f.A + f.Mp + f.S;
   f.nA = f.bs * f.A; f.nP = f.bs * f.Mp; f.nL = f.bs * f.R; f.nQ = f.nL * f.M; f.nT = f.bs * f.N;
-  const StreamPlan& p = f.plan = plan_of(c, f.fp32, f.bs);
+  KernelIn kin = kernel_in(c, B, out, flags);
+  PlanIn pin = plan_in(c, kin);
+  const StreamPlan& p = f.plan = plan_streams(pin);
   TRY(plan_resources(c, p));
+  pin.dry = false; kin.forked = plan_streams(pin).forked;      // (the launch pass's streams: the sizing pass forks nothing, and gets the same kernel plan)
+  f.kp = plan_kernels(kin);
   f.on[ON_CALLER] = c->stream; f.on[ON_PREPARE] = c->st.prep_stream; f.on[ON_SIDE] = c->st.side;
 
   c->stream = f.on[p.prep_on];
@@ -1477,9 +1098,10 @@ int rift_forward(RiftCtx* h, const RiftFeatureBatch* B, const RiftOutputs* out, 
   // descriptor only: a forward like the previous one skips pass 1 (it is half of the call's host time, which bounds a small-batch step)
   long long omask = 0;      // which outputs are wanted
   { const void* const* op = reinterpret_cast<const void* const*>(out); for (size_t i = 0; i < sizeof(RiftOutputs) / sizeof(void*); ++i) omask |= (long long)(op[i] != nullptr) << i; }
-  // (everything forward_impl's A_alloc sequence depends on: batch dimensions, flags, the data-parallel descriptor, the wanted outputs and the
-  // profiler switch; the environment-driven diagnostic taps are read per call and allocate at most a few KB, which the 1/8 slack of the
-  // arena covers -- and the launch pass is checked against the capacity below)
+  // (everything forward_impl's A_alloc sequence depends on, besides the switches fixed when the context is made: batch dimensions, flags, the
+  // data-parallel descriptor, the wanted outputs and the profiler switch.  The kernel plan (fwd_kernels.h: KernelIn) is a function of this
+  // key and of those switches, and so are the diagnostic timestamp buffers: the launch pass allocates exactly what the sizing pass
+  // counted, which is checked below)
   const long long dkey[11] = {B->bs, B->A, B->Mp, B->R, B->S, B->T, flags, c->dp.on ? 1 : 0, c->dp.on ? c->dp.gbs : 0, omask, c->prof_on ? 1 : 0};
   int rc = RIFT_OK;
   if (c->dry_need == 0 || memcmp(dkey, c->dry_key, sizeof(dkey)) != 0) {
@@ -1501,15 +1123,15 @@ int rift_forward(RiftCtx* h, const RiftFeatureBatch* B, const RiftOutputs* out, 
   // diagnostic: RIFT_POISON_ARENA=<byte> fills the scratch arena before every forward (0xFF = NaN pattern), so that a kernel reading
   // scratch it never wrote shows up as NaN / as run-to-run differences instead of depending on what the memory held before
   // (on the prepare stream if the preparation runs there: every other stream of the forward waits for the preparation)
-  if (c->sw.poison_arena >= 0 && c->arena) { HIPCHK(c, hipMemsetAsync(c->arena, c->sw.poison_arena, c->arena_cap, plan_of(c, (flags & RIFT_F_FP32) != 0, B->bs).prefetched ? c->st.prep_stream : c->stream)); }
+  if (c->sw.poison_arena >= 0 && c->arena) { HIPCHK(c, hipMemsetAsync(c->arena, c->sw.poison_arena, c->arena_cap, plan_streams(plan_in(c, kernel_in(c, B, out, flags))).prefetched ? c->st.prep_stream : c->stream)); }
   rc = forward_impl(c, B, out, flags, seed);
   c->stream = (hipStream_t)stream;
   if (rc != RIFT_OK) return rc;
   if (!c->err.empty()) return RIFT_ERR_ARG;
-  if (c->arena_off > c->arena_cap) {     // the launch pass allocated more than the sizing pass it was matched with: kernels were given scratch beyond the arena
+  if (c->arena_off != need) {     // the launch pass did not walk the allocations of the sizing pass it was matched with: past the count, kernels were given scratch beyond the arena
     c->dry_need = 0;
     char msg[160];
-    snprintf(msg, sizeof(msg), "activation arena overrun: the forward allocated %zu B of a %zu B arena (stale sizing pass)", c->arena_off, c->arena_cap);
+    snprintf(msg, sizeof(msg), "activation arena: the forward allocated %zu B, its sizing pass counted %zu B (stale or diverging sizing pass)", c->arena_off, need);
     c->err = msg;
     (void)hipDeviceSynchronize();
     return RIFT_ERR_STATE;

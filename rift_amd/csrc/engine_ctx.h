@@ -7,6 +7,7 @@
 #include "dec_w.h"
 #include "dropstats.h"
 #include "fwd_plan.h"
+#include "fwd_kernels.h"
 
 namespace RIFT_NS {
 
@@ -27,6 +28,7 @@ struct Ctx : RiftCtx {
   long long dry_key[11] = {}; size_t dry_need = 0;      // the arena size of the last sized forward and what it depended on
   struct Head {   // what the policy head of a forward needs (pi_forward .. trajectory heads); kept per arena for the deferred form
     bool valid = false, fp32 = false, need_traj = false;
+    bool pi_fused = false, heads_fused = false;      // the kernel plan of the forward that made it (fwd_kernels.h): the deferred call runs the same path
     float *Q = nullptr, *x0p = nullptr, *QF = nullptr, *Hpi = nullptr, *prob = nullptr, *traj = nullptr, *o3[3] = {nullptr, nullptr, nullptr}, *oT[3] = {nullptr, nullptr, nullptr};
     uint8_t* r_kpm = nullptr; int bs = 0, R = 0, nQ = 0;
     bool dec_pending = false; DecWP dec;      // the planning decoder deferred along with the head (small batches, see dec_defer_max)
@@ -109,7 +111,7 @@ inline void tap(Ctx* c, const char* name, float* p, int64_t numel) {
   if (!c->dry) c->taps[name] = Tap{p, numel};
 }
 
-// per-forward context: the flags, the stream plan, the batch dimensions, and what one stage of forward_impl hands to the next
+// per-forward context: the flags, the stream plan, the kernel plan, the batch dimensions, and what one stage of forward_impl hands to the next
 struct Fwd {
   Ctx* c; bool train, drop, fp32, need_traj, bn_update; uint32_t seed; uint32_t stream_id = 1;
   uint32_t next_stream() { return stream_id++; }
@@ -117,23 +119,22 @@ struct Fwd {
   bool dp = false, kpm_pending = false; int kb = 0; uint8_t* g_rkpm = nullptr;
   uint8_t* r_tiles = nullptr;                        // tiles of every reference line up to its last valid point (prep_kernel), for pe_w_kernel's packed rounds
   const RiftFeatureBatch* B = nullptr; const RiftOutputs* out = nullptr; int flags = 0;
+  KernelPlan kp;                                     // which kernel every stage runs (fwd_kernels.h): the same in the sizing and the launch pass
   StreamPlan plan; hipStream_t on[3] = {nullptr, nullptr, nullptr};      // (indexed by PlanStream)
   int bs = 0, A = 0, Mp = 0, R = 0, S = 0, T = 0, N = 0, M = 12, nA = 0, nP = 0, nL = 0, nQ = 0, nT = 0;
   DropStats ds = {};                                 // diagnostic build (dropstats.h): this forward's counters; all zero in the product library
   // prepare_inputs
   float *F9 = nullptr, *F10 = nullptr, *F6 = nullptr, *pos = nullptr, *r_pos = nullptr;
   uint8_t *valid_agent = nullptr, *kpm = nullptr, *r_kpm = nullptr;
-  bool nat_compact = false; int *nat_aidx = nullptr, *nat_cnt = nullptr;      // the history encoder on the compacted sequences (nat_l0w.h ranks them)
+  int *nat_aidx = nullptr, *nat_cnt = nullptr;      // the history encoder on the compacted sequences (kp.nat_compact; nat_l0w.h ranks them)
   const uint8_t* q_kpm = nullptr; int q_bs = 0, q_off = 0;                    // the r2r mask quirk's rows: this shard's, or the gathered global minibatch's
   // history_encoder, ego_token, map_and_embeddings, assemble_tokens
   float *nat_out = nullptr, *x_ego = nullptr, *poly = nullptr, *r_emb = nullptr, *speed_emb = nullptr, *PEtok = nullptr, *Q = nullptr, *X = nullptr;
-  bool pe_pair = false, fo3 = false, rpe_done = false;
   // scene_encoder
   float* ENC = nullptr;
   unsigned short* enc_KT = nullptr;   // the decoder's cross-attention K | V^T operand fragments, written by the encoder kernel's tail
   uint8_t* kpm_c = nullptr;           // the key padding of the compacted encoder rows (bs, 96): what the decoder masks those fragments with
   float* enc_x0p = nullptr;           // cat_x_proj's ego-token half, written by the encoder kernel's tail
-  bool enc_wide = false;
   // planning_decoder
   bool dec_deferred = false; DecWP dec_later;
 };

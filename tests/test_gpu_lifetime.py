@@ -34,9 +34,15 @@ def _to_dev(d):
     return {k: _to_dev(v) if isinstance(v, dict) else (v.to(DEV) if torch.is_tensor(v) else v) for k, v in d.items()}
 
 
+# two scenes each: 49 agents + 60 polygons = 109 token slots (the scene encoder's 112-row layout, the decoder's dense variant on its image),
+# and nine reference lines (the decoder's dense variant on dec_kv_frag_kernel's image)
+SHAPES = {"wide": dict(num_agents=49, num_polygons=60, r_min=1, r_max=3), "dense": dict(r_min=9, r_max=9)}
+
+
 def _batch(n):
     if n not in _cache:
-        _cache[n] = _to_dev(syn.collate_scenes([syn.make_scene(7300 + 10 * n + i, r_min=1, r_max=3) for i in range(n)]))
+        kind, count, base = (SHAPES[n], 2, 7400 + 10 * sorted(SHAPES).index(n)) if n in SHAPES else (dict(r_min=1, r_max=3), n, 7300 + 10 * n)
+        _cache[n] = _to_dev(syn.collate_scenes([syn.make_scene(base + i, **kind) for i in range(count)]))
     return _cache[n]
 
 
@@ -75,7 +81,8 @@ def _same(a, b):
 
 
 def test_scratch_grows_and_is_reused_on_one_engine():
-    """One bf16 engine at 2, 5, 2 scenes (forward, loss, finalize; head_backward behind the 5-scene forward) and its critic at 3, 40, 3
+    """One bf16 engine at 2, 5, 2 scenes, then at two scenes of 109 token slots, two of nine reference lines and 2 again (forward, loss,
+    finalize; head_backward behind the 5-scene forward) and its critic at 3, 40, 3
     rows: every result equals that of a fresh engine given the same input alone.  Each grow path of the arena, the loss scratch, the
     pi_head backward scratch and the critic scratch runs once, and so does the reuse below capacity.  The growth of the ranking's
     published words (rk_pub) needs a batch of more than 4096 scenes and is NOT exercised here."""
@@ -83,7 +90,7 @@ def test_scratch_grows_and_is_reused_on_one_engine():
     eng = _ffi.Engine(DEV)
     eng.load_state_dict(_sd())
     got, got_head = [], None
-    for n in (2, 5, 2):
+    for n in (2, 5, 2, "wide", "dense", 2):
         got.append(_step(eng, _batch(n)))
         if n == 5:
             dz = dz[:, :got[-1][0].shape[1]].contiguous()
@@ -92,16 +99,18 @@ def test_scratch_grows_and_is_reused_on_one_engine():
     torch.cuda.synchronize()
     eng.close()
     want = {}
-    for n, nc in ((2, 3), (5, 40)):
+    for n, nc in ((2, 3), (5, 40), ("wide", None), ("dense", None)):
         fresh = _ffi.Engine(DEV)
         fresh.load_state_dict(_sd())
         want[n] = _step(fresh, _batch(n))
         if n == 5:
             _same([got_head], [fresh.head_backward(dz).clone()])
-        want["c%d" % nc] = _critic(fresh, nc)
+        if nc:
+            want["c%d" % nc] = _critic(fresh, nc)
         torch.cuda.synchronize()
         fresh.close()
     _same(got[0], want[2]); _same(got[1], want[5]); _same(got[2], want[2])
+    _same(got[3], want["wide"]); _same(got[4], want["dense"]); _same(got[5], want[2])
     _same(got_critic[0], want["c3"]); _same(got_critic[1], want["c40"]); _same(got_critic[2], want["c3"])
     assert not torch.equal(got[0][3], torch.zeros_like(got[0][3]))            # (the gradient sums are not trivially equal)
 

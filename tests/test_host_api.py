@@ -269,6 +269,141 @@ def test_stream_plan_orders_every_reader_behind_the_preparation(tmp_path):
     assert n == 2 ** 9 * 4
 
 
+def test_kernel_plan_picks_one_consistent_path_per_stage(tmp_path):
+    """csrc/fwd_kernels.h (host-only) compiled by g++ and run over its inputs, by groups of fields; every field of every row is compared
+    with the table written out here, independently of the header's formulas, and the invariants that tie the stages together hold in
+    every row.  A group crosses every input its fields read, directly or through another field, at the smallest shapes on both sides of
+    every boundary (token slots 96 | 97, 112 | 113, 192 | 193; reference lines 8 | 9, 16 | 17; agents 256 | 257; static objects 0 | 1;
+    scenes 84 | 85, 107 | 108, 128 | 129, 192 | 193; RIFT_DEC_DEFER unset, 0, 64; the eight-wave encoder build and a four-wave one).
+    To keep the test at a few seconds, the group of the decoder's launches (`dec_now`, `dec_later`), which reads the shape only through
+    `dec`, crosses all its inputs at four shapes -- the two sides of the tile | dense boundary, each with R = 8 and R = 17; the two groups
+    before it check `dec` and the deferral at every boundary."""
+    import shutil
+    import subprocess
+    import numpy as np
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B = (0, 1)
+    default = dict(nat_fused=1, dec_fused=1, enc_fused=1, pe_fused=1, fo_fused=1, fpn_fused=1, ego_fused=1, heads_fused=1, pi_fused=1, fo_w=1, pe_w=1,
+                   nat_compact=1, pe_live=1, pe_pack=1, rank_in_prep=1, enc112=1, dec_defer_max=-1, dec_split=1, dec_layers=4, dec_ts=0,
+                   fp32=0, train=0, drop=0, need_traj=0, want_traj=0, defer_head=0, prof_on=0, forked=1, bs=32, A=64, Mp=20, S=0, R=4, enc_nw=8)
+    ins = list(default)
+    # token slots N = A + Mp + S with Mp = 20, S = 0: the agents carry the boundary
+    slots = [n - 20 for n in (96, 97, 112, 113, 192, 193)]
+    enc_dec = dict(enc_fused=B, dec_fused=B, enc112=B, fp32=B, enc_nw=(8, 4), A=slots, R=(8, 9, 16, 17))
+    defer = dict(defer_head=B, prof_on=B, dec_ts=B, need_traj=B, dec_split=B, dec_defer_max=(-1, 0, 64), bs=(84, 85, 107, 108, 128, 129, 192, 193))
+    groups = [
+        dict(nat_fused=B, fpn_fused=B, nat_compact=B, rank_in_prep=B, ego_fused=B, fp32=B, A=(256, 257)),                       # history, ego
+        dict(pe_fused=B, pe_w=B, pe_pack=B, pe_live=B, fo_fused=B, fo_w=B, fp32=B, train=B, forked=B, S=B),                   # PointsEncoders, Fourier, q0
+        enc_dec,                                                                                                              # encoder, operand image, decoder path
+        dict(enc_dec, **defer),                                                                                               # deferral and split
+        dict(defer, dec_layers=(0, 2, 22, 4), drop=B, dec_fused=B, fp32=B, enc_fused=B, enc112=B, enc_nw=(8, 4), A=(76, 77), R=(8, 17)),      # the decoder's launches
+        dict(heads_fused=B, pi_fused=B, fp32=B, need_traj=B, want_traj=B),                                                    # heads
+    ]
+    outs = ["hist_wave", "fpn_fused", "nat_compact", "rank_in_prep", "ego_fused", "pe", "pe_stats_persistent", "pe_pack", "pe_live", "fourier", "q0_early",
+            "enc", "enc_image", "enc_kpm_x0p", "dec_kv_frag", "dec", "dec_n_now", "dec_now[0].l0", "dec_now[0].l1", "dec_now[1].l0", "dec_now[1].l1",
+            "dec_defer", "dec_split", "dec_later.l0", "dec_later.l1", "pi_fused", "heads_fused", "head_traj"]
+    code = ['#include <cstdio>', '#include <initializer_list>', '#include "fwd_kernels.h"', 'static void row(const KernelIn& in) {', '  const KernelPlan p = plan_kernels(in);',
+            '  const short r[] = {' + ", ".join(f"(short)in.{k}" for k in ins) + ", " + ", ".join(f"(short)p.{o}" for o in outs) + '};',
+            '  fwrite(r, sizeof(r), 1, stdout);', '}', 'int main() {']
+    n_rows = 0
+    for g in groups:
+        code += ['  {', '    KernelIn in;'] + [f'    in.{k} = {v};' for k, v in default.items()]
+        for k, vals in g.items():
+            code.append(f'    for (int {k} : {{{", ".join(map(str, vals))}}}) {{ in.{k} = {k};')
+        code.append('    row(in);' + ' }' * len(g))
+        code.append('  }')
+        n_rows += int(np.prod([len(v) for v in g.values()]))
+    code += ['  return 0;', '}']
+    src = tmp_path / "kplan.cpp"
+    src.write_text("\n".join(code))
+    exe = tmp_path / "kplan"
+    subprocess.check_call([gxx, "-std=c++17", "-O1", "-I", os.path.join(repo, "rift_amd", "csrc"), str(src), "-o", str(exe)])
+    t = np.ascontiguousarray(np.frombuffer(subprocess.check_output([str(exe)]), dtype=np.int16).reshape(-1, len(ins) + len(outs)).T)
+    assert t.shape[1] == n_rows
+    i = {k: (t[j] != 0 if default[k] in (0, 1) and k != "S" else t[j]) for j, k in enumerate(ins)}      # flags as booleans, numbers as they are
+    p = {o: t[len(ins) + j] for j, o in enumerate(outs)}
+    N, R, bs, bf = i["A"] + i["Mp"] + i["S"], i["R"], i["bs"], ~i["fp32"]
+
+    def same(name, want):
+        bad = np.flatnonzero(p[name] != np.asarray(want).astype(np.int16))
+        assert bad.size == 0, (name, {k: int(t[j][bad[0]]) for j, k in enumerate(ins)}, int(p[name][bad[0]]))
+
+    # ---- the table.  History: wave-private levels in the 16-bit mode; the fused FPN tail only behind them; compaction only with both; the
+    # in-launch ranking only with compaction and up to 256 agents
+    wave = i["nat_fused"] & bf
+    same("hist_wave", wave); same("fpn_fused", wave & i["fpn_fused"]); same("nat_compact", wave & i["fpn_fused"] & i["nat_compact"])
+    same("rank_in_prep", wave & i["fpn_fused"] & i["nat_compact"] & i["rank_in_prep"] & (i["A"] <= 256))
+    same("ego_fused", bf & i["ego_fused"])
+    # ---- PointsEncoders: 0 layer-wise, 1 pair + pe_mid_kernel, 2 pair + pe_w_kernel
+    LAYERWISE = 0
+    pe = np.select([i["fp32"] | ~i["pe_fused"], i["pe_w"]], [LAYERWISE, 2], 1)
+    same("pe", pe); same("pe_stats_persistent", (pe == 2) & i["train"]); same("pe_pack", (pe == 2) & i["pe_pack"])
+    same("pe_live", (pe == 2) & i["train"] & i["pe_live"])
+    # ---- Fourier: 0 layer-wise, 1 one launch per embedding, 2 three in one by fourier_fused_kernel, 3 three in one by fo_w_kernel
+    fo = np.select([i["fp32"] | ~i["fo_fused"], (pe == LAYERWISE) | (i["S"] > 0), i["fo_w"]], [LAYERWISE, 1, 3], 2)
+    same("fourier", fo); same("q0_early", i["forked"] & (fo >= 2))
+    # ---- scene encoder: 0 layer-wise, 1 fused on 96 rows, 2 fused on 112 rows, 3 enc_w_kernel.  Image: 0 none, 1 key tiles, 2 dense
+    tail = i["dec_fused"] & (R <= 8) & (i["enc_nw"] == 8)
+    enc = np.select([i["fp32"] | ~i["enc_fused"], N <= 96, (N <= 112) & i["enc112"] & tail, N <= 192], [LAYERWISE, 1, 2, 3], LAYERWISE)
+    img = np.select([(enc == 1) & tail, enc == 2, (enc == 3) & i["dec_fused"] & (R <= 16)], [1, 2, 2], 0)
+    same("enc", enc); same("enc_image", img); same("enc_kpm_x0p", (img > 0) & (enc != 3))
+    # ---- decoder: 0 layer-wise, 1 fused on key tiles, 2 fused dense.  The kernel takes R <= 8 and N <= 96 from the encoder's tile image
+    # only, and every other shape up to R = 16, N = 192 from a dense image
+    small = (R <= 8) & (N <= 96)
+    dec = np.select([i["fp32"] | ~i["dec_fused"], small & (img == 1), ~small & (R <= 16) & (N <= 192)], [LAYERWISE, 1, 2], LAYERWISE)
+    same("dec", dec); same("dec_kv_frag", (dec == 2) & (img == 0))
+    # ---- deferral: the measured table of batch sizes, by value (without / with the trajectory heads), or RIFT_DEC_DEFER
+    wins = {False: {84: 1, 85: 0, 107: 0, 108: 1, 128: 1, 129: 1, 192: 1, 193: 0, 32: 1}, True: {84: 1, 85: 1, 107: 1, 108: 1, 128: 1, 129: 0, 192: 0, 193: 0, 32: 1}}
+    table = np.array([wins[bool(tr)][int(b)] for tr, b in zip(i["need_traj"], bs)], dtype=bool)
+    size_ok = np.where(i["dec_defer_max"] < 0, table, bs <= i["dec_defer_max"])
+    defer_ = (dec != LAYERWISE) & i["defer_head"] & size_ok & ~i["prof_on"] & ~i["dec_ts"]
+    split = defer_ & i["dec_split"] & ~i["need_traj"]
+    same("dec_defer", defer_); same("dec_split", split)
+    # ---- the decoder's launches: (number now, first range, second range, the deferred range)
+    two = ~defer_ & (i["dec_layers"] == 22) & (dec != LAYERWISE) & ~i["drop"]
+    want = np.zeros((7, n_rows), dtype=np.int64)
+    want[:] = np.array([1, 0, 4, 0, 0, 0, 0])[:, None]                                  # all four layers, one launch
+    for cond, vals in ((i["dec_layers"] == 0, [0, 0, 0, 0, 0, 0, 0]), (i["dec_layers"] == 2, [1, 0, 2, 0, 0, 0, 0]), (two, [2, 0, 2, 2, 4, 0, 0]),
+                       (defer_, [0, 0, 0, 0, 0, 0, 4]), (split, [1, 0, 2, 0, 0, 2, 4])):       # (later rows override earlier ones)
+        want[:, cond] = np.array(vals)[:, None]
+    for j, name in enumerate(["dec_n_now", "dec_now[0].l0", "dec_now[0].l1", "dec_now[1].l0", "dec_now[1].l1", "dec_later.l0", "dec_later.l1"]):
+        same(name, want[j])
+    # ---- heads
+    same("pi_fused", bf & i["pi_fused"]); same("heads_fused", bf & i["heads_fused"]); same("head_traj", i["need_traj"] & i["want_traj"])
+
+    # ---- invariants, in all rows
+    def holds(cond, what):
+        bad = np.flatnonzero(~np.asarray(cond, dtype=bool))
+        assert bad.size == 0, (what, {k: int(t[j][bad[0]]) for j, k in enumerate(ins)})
+    q = {k: v != 0 for k, v in p.items()}          # (the plan's flags as booleans; the enums and layer numbers are read from p)
+    f32 = i["fp32"]
+    holds(~f32 | ((p["hist_wave"] + p["fpn_fused"] + p["nat_compact"] + p["rank_in_prep"] + p["ego_fused"] + p["pe"] + p["fourier"] + p["enc"] + p["enc_image"]
+                   + p["dec_kv_frag"] + p["dec"] + p["dec_defer"] + p["dec_split"] + p["pi_fused"] + p["heads_fused"] + p["pe_pack"] + p["pe_live"]
+                   + p["pe_stats_persistent"] + p["q0_early"]) == 0), "fp32: every stage layer-wise, nothing compacted, decoder not deferred")
+    makers = (p["enc_image"] > 0).astype(int) + p["dec_kv_frag"]
+    holds((p["dec"] == 0) | (makers == 1), "fused decoder: exactly one producer of the K | V^T image")
+    holds((p["dec"] != 1) | ((p["enc_image"] == 1) & (N <= 96) & (R <= 8)), "tile variant: the encoder's tile image, N <= 96, R <= 8")
+    holds((p["dec"] != 2) | (p["enc_image"] == 2) | q["dec_kv_frag"], "dense variant: a dense image")
+    holds((p["enc_image"] != 2) | (p["enc"] == 2) | (p["enc"] == 3), "dense image from the wide encoder or enc_w_kernel")
+    holds((p["enc_image"] != 1) | (p["enc"] == 1), "tile image from the 96-row encoder")
+    holds((p["dec"] != 0) | (makers == 0), "layer-wise decoder: nobody makes the image")
+    holds(~q["enc_kpm_x0p"] | (p["enc_image"] > 0), "kpm_c and x0p only with an image")
+    holds(~q["nat_compact"] | (q["hist_wave"] & q["fpn_fused"]), "nat_compact => wave-private history and fused FPN")
+    holds(~q["rank_in_prep"] | (q["nat_compact"] & (i["A"] <= 256)), "rank_in_prep => nat_compact and A <= 256")
+    holds((p["fourier"] < 2) | ((p["pe"] > 0) & (i["S"] == 0)), "three-in-one Fourier => the pair and S = 0")
+    holds(~q["q0_early"] | (i["forked"] & (p["fourier"] >= 2)), "q0_early => forked and that launch")
+    holds(~q["dec_defer"] | (i["defer_head"] & (p["dec"] > 0) & ~i["prof_on"]), "dec_defer => defer_head, fused decoder, not profiling")
+    holds(~q["dec_split"] | (q["dec_defer"] & ~i["need_traj"]), "dec_split => dec_defer and no trajectory heads")
+    holds(~(q["pe_pack"] | q["pe_live"] | q["pe_stats_persistent"]) | (p["pe"] == 2), "pe_pack, pe_live, persistent statistics => pe_w_kernel")
+    # every layer of a fused decoder that is not cut short by RIFT_DEC_LAYERS runs exactly once, now or later
+    full = (p["dec"] > 0) & (q["dec_defer"] | ((i["dec_layers"] != 0) & (i["dec_layers"] != 2)))
+    ran = (p["dec_now[0].l1"] - p["dec_now[0].l0"]) + (p["dec_now[1].l1"] - p["dec_now[1].l0"]) + (p["dec_later.l1"] - p["dec_later.l0"])
+    holds(~full | (ran == 4), "four decoder layers in all")
+
+
 def test_product_package_never_touches_the_oracle():
     """oracle/ is test infrastructure: nothing under rift_amd/ may import or reference it."""
     import pathlib

@@ -129,15 +129,16 @@ typedef struct RiftLossIn {
 /* Gradients of planning_decoder.pi_head (the trainable set of rift_training.yaml:26-27) are
  * written into caller-owned buffers (the torch .grad tensors), so clip_grad_norm_ and
  * torch.optim.AdamW run unchanged (rift_trainer.py:279-362). */
+#define RIFT_PI_NPARAM 16897   /* the six pi_head tensors, flat: mlp.0.weight 128x128 | mlp.0.bias 128 | mlp.1.weight 128 | mlp.1.bias 128 | mlp.3.weight 128 | mlp.3.bias 1 */
 typedef struct RiftLossOut {
   double* loss;            /* device scalar, f64: -(sum objective)/(count) */
   double* stats;           /* device [2] f64: (sum objective, count) -- all-reduce these for DP */
-  float*  flat_grad_sum;   /* device [16897] unnormalised d(sum objective)/d(pi_head params): all-reduce for DP */
+  float*  flat_grad_sum;   /* device [RIFT_PI_NPARAM] unnormalised d(sum objective)/d(pi_head params): all-reduce for DP */
   float*  grad_w1;  float* grad_b1;      /* mlp.0.weight (128,128), mlp.0.bias (128) */
   float*  grad_ln_w; float* grad_ln_b;   /* mlp.1.weight (128), mlp.1.bias (128) */
   float*  grad_w2;  float* grad_b2;      /* mlp.3.weight (1,128), mlp.3.bias (1) */
   int64_t* argmax_rm;      /* (bs,2) int64 chosen (r,m) -- REINFORCE, bit-exact integer output */
-  double* exchange;        /* optional device [16899] f64: flat_grad_sum (as f64) followed by stats -- ONE buffer to all-reduce for DP;
+  double* exchange;        /* optional device [RIFT_PI_NPARAM + 2] f64: flat_grad_sum (as f64) followed by stats -- ONE buffer to all-reduce for DP;
                               when set, rift_loss_finalize reads the sums and the stats from here */
 } RiftLossOut;
 
@@ -304,7 +305,7 @@ int rift_loss_backward_ex(RiftCtx* ctx, int kind, const RiftLossIn* in, const Ri
  * get_rift_loss, another clip, a KL to a reference policy, a pairwise loss) -- rift_loss_backward covers the five compiled-in objectives only.
  * dlogits = d loss / d probability as torch autograd hands it over, (bs,R,12) f32 with the bs and R of the latest rift_forward whose policy
  * head has run (RIFT_F_DEFER_HEAD forwards are not meant); its activations are used, so the call belongs between that forward and the next.
- *   out->flat_grad_sum[16897] = sum_rows dz[row] * d logit[row] / d theta: positive sign, no division by a count.  dz = dlogits, except
+ *   out->flat_grad_sum[RIFT_PI_NPARAM] = sum_rows dz[row] * d logit[row] / d theta: positive sign, no division by a count.  dz = dlogits, except
  *   dz = 0 on the rows of padded reference lines, where `probability` is the constant -1e6 whatever the parameters are;
  *   the six out->grad_* pointers that are not NULL receive that vector: overwritten (accumulate == 0) or added to (accumulate != 0, the
  *   semantics of autograd's .grad);
@@ -486,7 +487,7 @@ int rift_group_advantage_tick_ex(RiftCtx* ctx, const float* trajectory, int Rb, 
  *   control  PIDController.control_pid with `sample_interval`: thinning path[k-1::k], target speed = mean spacing, aim range
  *            clamp(0.5 v + 2.5, 5, 8), aim point = first minimum over the thinned points but the last, brake when target < 0.4 or (then
  *            only) v / target > 1.1, both windowed PIDs step on every call, steer clamped to [-1, 1].
- * pid_state: (n_slots, 44) f64, caller-owned and persistent between calls like the rollout's PID buffers in RiftRolloutIO; a row is
+ * pid_state: (n_slots, RIFT_CONTROL_STATE) f64, caller-owned and persistent between calls like the rollout's PID buffers in RiftRolloutIO; a row is
  *   [0,20) turn-PID ring | [20,40) speed-PID ring | 40, 41 turn head (slot of the oldest sample, stored as a double) and last error |
  *   42, 43 the same two for the speed PID.  An all-zero row is a freshly constructed PIDController: the host resets a slot with a memset.
  * decision: (K, 8) f64 = throttle, steer, brake (0 / 1), flat index r * 12 + m of the chosen candidate (-1: ref-free), its position in the
@@ -494,6 +495,7 @@ int rift_group_advantage_tick_ex(RiftCtx* ctx, const float* trajectory, int Rb, 
  * RIFT_ERR_ARG, decided on the host before any launch: K < 0; topk < 1 or > Rb * 12; sample_interval < 1; Tfull < 2 * sample_interval; a
  * slot outside [0, n_slots); two CBVs with the same slot; a batch_index < 0; Rb * 12 > 1024 (the kernel holds at most 16 logits per lane).
  * K == 0 returns RIFT_OK without a launch.  `cbvs` is a HOST array of K entries. */
+#define RIFT_CONTROL_STATE 44   /* doubles per pid_state row */
 typedef struct RiftControlCBV {
   int32_t batch_index;         /* row of the tick's collated batch */
   int32_t slot;                /* row of pid_state owned by this CBV; distinct within one call */
@@ -502,7 +504,7 @@ typedef struct RiftControlCBV {
 } RiftControlCBV;              /* 40 bytes */
 int rift_control_tick(RiftCtx* ctx, const float* trajectory /*(bs,Rb,12,Tfull,6)*/, const float* probability /*(bs,Rb,12) logits*/,
                       const float* ref_free_trajectory /*(bs,Tfull,4) or NULL: no ref-free candidate*/, int Rb, int Tfull,
-                      const RiftControlCBV* cbvs, int K, int topk, int sample_interval, double* pid_state /*(n_slots,44) f64, in/out*/,
+                      const RiftControlCBV* cbvs, int K, int topk, int sample_interval, double* pid_state /*(n_slots,RIFT_CONTROL_STATE) f64, in/out*/,
                       int n_slots, double* decision /*(K,8) f64*/, void* stream);
 
 /* Device-side collation (PlutoFeature.collate, pluto_feature.py:83-94 + RIFTCollate,

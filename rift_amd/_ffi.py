@@ -1,5 +1,10 @@
 """ctypes binding of ``librift_hip.so`` (C-ABI in ``include/rift_hip.h``).
 
+The mirror of the header -- its constants, structs and function signatures -- is ``rift_amd/_abi.py``, which
+``tools/gen/abi_trampolines.py`` generates from the header; this module gives those names the spellings the package uses and adds what
+the header does not say: the order the feature batch is filled in, the parameter names and sizes behind the flat gradient vectors, and
+the Engine.
+
 The product path has NO CPU fallback: if the shared library is missing or fails
 to load, importing the engine raises immediately.
 """
@@ -11,22 +16,30 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
+from rift_amd import _abi
+from rift_amd._abi import (EXPORTS, RiftControlCBV, RiftCritic, RiftDp, RiftEvalParams, RiftFeatureBatch, RiftLossIn,  # noqa: F401
+                           RiftLossOut, RiftObjectiveParams, RiftOutputs, RiftReplayArena, RiftRolloutIO, RiftTensorDesc, RiftTickCBV)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librift_hip.so")
 
-# forward flags / loss kinds (include/rift_hip.h)
-F_TRAIN, F_NEED_TRAJ, F_FP32, F_NO_DROP, F_NO_BN_UPDATE, F_DEFER_HEAD = 1, 2, 4, 8, 16, 32
-DEFER_SLOTS = 4        # RIFT_DEFER_SLOTS: activation arenas the deferred-head forwards cycle through
-LOSS_KINDS = {"rift": 0, "grpo": 1, "ppo": 2, "reinforce": 3, "sft": 4}
-PI_NPARAM = 16897
+
+def _enum(prefix: str) -> Dict[str, int]:
+    """{"rift": 0, ...} from the header's enumerators RIFT_LOSS_RIFT = 0, ..., in header order."""
+    return {k[len(prefix):].lower(): v for k, v in vars(_abi).items() if k.startswith(prefix)}
+
+
+F_TRAIN, F_NEED_TRAJ, F_FP32, F_NO_DROP = _abi.RIFT_F_TRAIN, _abi.RIFT_F_NEED_TRAJ, _abi.RIFT_F_FP32, _abi.RIFT_F_NO_DROP
+F_NO_BN_UPDATE, F_DEFER_HEAD = _abi.RIFT_F_NO_BN_UPDATE, _abi.RIFT_F_DEFER_HEAD
+DEFER_SLOTS = _abi.RIFT_DEFER_SLOTS        # activation arenas the deferred-head forwards cycle through
+LOSS_KINDS = _enum("RIFT_LOSS_")
+REWARD_MODELS = _enum("RIFT_REWARD_")
+OPERANDS = _enum("RIFT_OPERANDS_")         # the 16-bit MFMA operand format of a context's fused kernels
+PI_NPARAM, CRITIC_NPARAM = _abi.RIFT_PI_NPARAM, _abi.RIFT_CRITIC_NPARAM_C
+CONTROL_STATE = _abi.RIFT_CONTROL_STATE    # doubles per pid_state row of rift_control_tick: turn ring (20) | speed ring (20) | turn head, last | speed head, last
+EXCHANGE_FN = _abi.RiftExchangeFn
 
 vp = C.c_void_p
-
-
-class RiftTensorDesc(C.Structure):
-    _fields_ = [("name", C.c_char_p), ("data", vp), ("numel", C.c_int64), ("ndim", C.c_int32),
-                ("shape", C.c_int64 * 4)]
-
 
 _FB_PTRS = [
     "agent_position", "agent_heading", "agent_velocity", "agent_shape", "agent_category", "agent_valid_mask",
@@ -35,72 +48,7 @@ _FB_PTRS = [
     "map_valid_mask", "ref_position", "ref_vector", "ref_orientation", "ref_valid_mask", "static_position",
     "static_heading", "static_shape", "static_category", "static_valid_mask", "current_state",
 ]
-
-
-class RiftFeatureBatch(C.Structure):
-    _fields_ = ([(n, C.c_int32) for n in ("bs", "A", "Mp", "R", "S", "T")] + [(n, vp) for n in _FB_PTRS]
-                + [("cs_ld", C.c_int32)])
-
-
-class RiftOutputs(C.Structure):
-    _fields_ = [(n, vp) for n in ("probability", "hidden", "trajectory", "prediction", "ref_free_trajectory")]
-
-
-class RiftLossIn(C.Structure):
-    _fields_ = [(n, vp) for n in ("old_group_logits", "ref_group_logits", "group_advantage", "group_valid_mask",
-                                  "action_mode", "advantage", "old_log_prob", "returns")] + \
-               [("clip_epsilon", C.c_float), ("lambda_entropy", C.c_float)]
-
-
-class RiftLossOut(C.Structure):
-    _fields_ = [(n, vp) for n in ("loss", "stats", "flat_grad_sum", "grad_w1", "grad_b1", "grad_ln_w", "grad_ln_b",
-                                  "grad_w2", "grad_b2", "argmax_rm", "exchange")]
-
-
-class RiftCritic(C.Structure):
-    _fields_ = [(n, vp) for n in ("w0", "b0", "w1", "b1", "w2", "b2", "state_avg", "state_std", "value_avg", "value_std")]
-
-
-class RiftReplayArena(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("n_scenes", "A", "Mp", "Rcap", "S", "T", "cs_ld")] + \
-               [("scenes", RiftFeatureBatch)] + \
-               [(n, vp) for n in ("r_count", "old_group_logits", "ref_group_logits", "group_advantage",
-                                  "group_valid_mask")]
-
-
-EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)
-
-
-class RiftDp(C.Structure):
-    _fields_ = [("scene_offset", C.c_int32), ("global_bs", C.c_int32), ("xchg", vp), ("xchg_len", C.c_int64),
-                ("exchange", EXCHANGE_FN), ("user", vp)]
-
-
-class RiftRolloutIO(C.Structure):
-    _fields_ = [("trajectories", vp), ("G", C.c_int32), ("Tfull", C.c_int32), ("G_per_group", C.c_int32), ("center_state", vp),
-                ("turn_buf", vp), ("turn_ptr", vp), ("turn_len", vp), ("speed_buf", vp), ("speed_ptr", vp), ("speed_len", vp),
-                ("center", vp), ("angle", vp), ("speed", vp), ("acc", vp), ("ang_vel", vp), ("ang_acc", vp), ("vertices", vp),
-                ("closest_index", vp), ("aim_idx", vp)]
-
-
-class RiftTickCBV(C.Structure):        # include/rift_hip.h: one CBV of rift_group_advantage_tick (every pointer a device pointer)
-    _fields_ = [("batch_index", C.c_int32), ("R", C.c_int32), ("Pmax", C.c_int32), ("n_actors", C.c_int32), ("center_state", vp),
-                ("ref_pos", vp), ("ref_angle", vp), ("ref_len", vp), ("actors", vp), ("off_road_mask", vp), ("H", C.c_int32), ("W", C.c_int32),
-                ("pose", C.c_double * 3)]
-
-
-class RiftControlCBV(C.Structure):     # include/rift_hip.h: one CBV of rift_control_tick (40 bytes)
-    _fields_ = [("batch_index", C.c_int32), ("slot", C.c_int32), ("x", C.c_double), ("y", C.c_double), ("heading", C.c_double),
-                ("speed", C.c_double)]
-
-
-class RiftEvalParams(C.Structure):     # include/rift_hip.h: the evaluator's run-time settings (104 bytes)
-    _fields_ = [("reward_model", C.c_int32), ("near_lane_change", C.c_int32), ("gamma", C.c_double)] + \
-               [(n, C.c_double) for n in ("alpha_collision", "alpha_boundary", "alpha_comfort", "alpha_l_align", "alpha_vel_align", "alpha_l_center",
-                                          "alpha_center_bias", "alpha_velocity", "alpha_timestep", "bbox_inflation_ratio", "resolution")]
-
-
-REWARD_MODELS = {"dense": 0, "sparse": 1}       # RIFT_REWARD_* of include/rift_hip.h
+assert _FB_PTRS == [n for n, t in RiftFeatureBatch._fields_ if t is vp], "_FB_PTRS and the pointers of RiftFeatureBatch (include/rift_hip.h) differ"
 
 
 def eval_params(reward_model=None, gamma: float = 0.98, bbox_inflation_ratio: float = 1.1, resolution: float = 0.5,
@@ -125,10 +73,6 @@ def eval_params(reward_model=None, gamma: float = 0.98, bbox_inflation_ratio: fl
     return p
 
 
-class RiftObjectiveParams(C.Structure):     # include/rift_hip.h: the settings of the RIFT / GRPO objective at run time (40 bytes)
-    _fields_ = [(n, C.c_double) for n in ("clip_low", "clip_high", "dual_clip", "kl_beta", "entropy_coef")]
-
-
 OBJECTIVE_KEYS = tuple(n for n, _ in RiftObjectiveParams._fields_)
 OBJECTIVE_KINDS = ("rift", "grpo")
 
@@ -151,26 +95,12 @@ def objective_params(kind: str, **settings) -> RiftObjectiveParams:
     return p
 
 
-CONTROL_STATE = 44     # doubles per pid_state row of rift_control_tick: turn ring (20) | speed ring (20) | turn head, last | speed head, last
-OPERANDS = {"bf16": 0, "fp16": 1}       # RIFT_OPERANDS_* of include/rift_hip.h: the 16-bit MFMA operand format of a context's fused kernels
-EXPORTS = [
-    "rift_ctx_create", "rift_ctx_create_ex", "rift_ctx_operand_format", "rift_ctx_destroy", "rift_last_error", "rift_model_load", "rift_forward", "rift_forward_head", "rift_forward_head_back", "rift_loss_backward",
-    "rift_loss_finalize", "rift_loss_finalize_clip", "rift_set_param_event", "rift_tap", "rift_op_linear", "rift_gae", "rift_discounted_return",
-    "rift_normalize_advantage", "rift_group_advantage", "rift_rollout_return", "rift_collate",
-    "rift_prof_enable", "rift_prof_report", "rift_op_linear_bench", "rift_ref_line_info", "rift_rollout",
-    "rift_critic_forward", "rift_critic_loss_backward", "rift_critic_finalize", "rift_clip_grad_norm", "rift_adamw_step", "rift_update_tail", "rift_collision_matrix", "rift_off_road_matrix", "rift_other_vehicle_rollout", "rift_sft_teacher_mode",
-    "rift_check_finite", "rift_set_dp", "rift_set_prepare_stream", "rift_set_side_stream",
-    "rift_comm_unique_id", "rift_comm_init", "rift_comm_all_reduce", "rift_comm_destroy", "rift_group_advantage_tick",
-    "rift_control_tick", "rift_head_backward", "rift_critic_backward",
-    "rift_eval_params_default", "rift_rollout_return_ex", "rift_group_advantage_tick_ex",
-    "rift_objective_params_default", "rift_loss_backward_ex",
-]
-CRITIC_NPARAM = 99331
 PI_KEYS = ("mlp.0.weight", "mlp.0.bias", "mlp.1.weight", "mlp.1.bias", "mlp.3.weight", "mlp.3.bias")       # flat order of PI_NPARAM
 PI_SIZES = (128 * 128, 128, 128, 128, 128, 1)
 CRITIC_SIZES = (256 * 128, 256, 256 * 256, 256, 256, 1, 128, 128, 1, 1)                                       # flat order of CRITIC_NPARAM
 CRITIC_KEYS = ("net.0.weight", "net.0.bias", "net.2.weight", "net.2.bias", "net.4.weight", "net.4.bias",
                "state_avg", "state_std", "value_avg", "value_std")
+assert sum(PI_SIZES) == PI_NPARAM and sum(CRITIC_SIZES) == CRITIC_NPARAM, "the flat layouts and the counts of include/rift_hip.h differ"
 
 _libs = {}
 
@@ -187,76 +117,7 @@ def load_library(variant: str = "") -> C.CDLL:
         raise RuntimeError(
             f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). rift_amd has no CPU fallback.")
-    lib = C.CDLL(path)
-    for name in EXPORTS:
-        if not hasattr(lib, name):
-            raise RuntimeError(f"librift_hip.so does not export {name}")
-    lib.rift_ctx_create.argtypes = [C.c_int, C.POINTER(vp)]
-    lib.rift_ctx_create_ex.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]
-    lib.rift_ctx_operand_format.argtypes = [vp]
-    lib.rift_ctx_destroy.argtypes = [vp]
-    lib.rift_ctx_destroy.restype = None
-    lib.rift_last_error.argtypes = [vp]
-    lib.rift_last_error.restype = C.c_char_p
-    lib.rift_model_load.argtypes = [vp, C.POINTER(RiftTensorDesc), C.c_int, vp]
-    lib.rift_forward.argtypes = [vp, C.POINTER(RiftFeatureBatch), C.POINTER(RiftOutputs), C.c_int, C.c_uint32, vp]
-    lib.rift_forward_head.argtypes = [vp, vp]
-    lib.rift_forward_head_back.argtypes = [vp, C.c_int, vp]
-    lib.rift_loss_backward.argtypes = [vp, C.c_int, C.POINTER(RiftLossIn), C.POINTER(RiftLossOut), vp]
-    lib.rift_loss_backward_ex.argtypes = [vp, C.c_int, C.POINTER(RiftLossIn), C.POINTER(RiftObjectiveParams), C.POINTER(RiftLossOut), vp, vp]
-    lib.rift_objective_params_default.argtypes = [C.c_int, C.POINTER(RiftObjectiveParams)]
-    lib.rift_loss_finalize.argtypes = [vp, C.POINTER(RiftLossOut), C.c_int, vp]
-    lib.rift_head_backward.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(RiftLossOut), C.c_int, vp]
-    lib.rift_critic_backward.argtypes = [vp, C.POINTER(RiftCritic), vp, vp, C.c_int, vp, vp]
-    lib.rift_set_param_event.argtypes = [vp, vp]
-    lib.rift_check_finite.argtypes = [vp, vp]
-    lib.rift_set_dp.argtypes = [vp, C.POINTER(RiftDp)]
-    lib.rift_set_prepare_stream.argtypes = [vp, vp]
-    lib.rift_set_side_stream.argtypes = [vp, vp]
-    lib.rift_comm_unique_id.argtypes = [vp, vp]
-    lib.rift_comm_init.argtypes = [vp, vp, C.c_int, C.c_int]
-    lib.rift_comm_all_reduce.argtypes = [vp, vp, C.c_int64, vp]
-    lib.rift_group_advantage_tick.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(RiftTickCBV), C.c_int, vp, vp, vp, vp, vp, vp, C.c_double, vp, vp]
-    lib.rift_group_advantage_tick_ex.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(RiftTickCBV), C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(RiftEvalParams),
-                                                 vp, vp, vp, vp]
-    lib.rift_eval_params_default.argtypes = [vp, C.POINTER(RiftEvalParams)]
-    lib.rift_rollout_return_ex.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(RiftEvalParams), vp, vp, vp]
-    lib.rift_control_tick.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(RiftControlCBV), C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]
-    lib.rift_comm_destroy.argtypes = [vp]
-    lib.rift_loss_finalize_clip.argtypes = [vp, C.POINTER(RiftLossOut), C.c_int, C.c_float, vp, vp]
-    lib.rift_tap.argtypes = [vp, C.c_char_p, vp, C.POINTER(C.c_int64), vp]
-    lib.rift_critic_forward.argtypes = [vp, C.POINTER(RiftCritic), vp, C.c_int, vp, vp]
-    lib.rift_critic_loss_backward.argtypes = [vp, C.POINTER(RiftCritic), vp, vp, C.c_int, vp, vp, vp]
-    lib.rift_critic_finalize.argtypes = [vp] * 14
-    lib.rift_clip_grad_norm.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64), C.c_int, C.c_float, vp, vp]
-    lib.rift_update_tail.argtypes = [vp, C.POINTER(RiftLossOut), C.c_int, C.c_float, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
-                                     C.POINTER(vp), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, C.c_double, vp]
-    lib.rift_adamw_step.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
-                                    C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_double,
-                                    C.c_double, C.c_double, vp]
-    lib.rift_sft_teacher_mode.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
-    lib.rift_other_vehicle_rollout.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp]
-    lib.rift_collision_matrix.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp]
-    lib.rift_off_road_matrix.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int] + [C.c_double] * 7 + [vp, vp]
-    lib.rift_op_linear.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp]
-    lib.rift_gae.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_int, vp, vp]
-    lib.rift_discounted_return.argtypes = [vp, vp, vp, C.c_double, C.c_int, vp, vp]
-    lib.rift_normalize_advantage.argtypes = [vp, vp, C.c_int, vp]
-    lib.rift_group_advantage.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
-    lib.rift_rollout_return.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int,
-                                        C.c_double, vp, vp]
-    lib.rift_collate.argtypes = [vp, C.POINTER(RiftReplayArena), vp, C.c_int, C.c_int, C.POINTER(RiftFeatureBatch),
-                                 vp, vp, vp, vp, vp]
-    lib.rift_op_linear_bench.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int,
-                                         C.POINTER(C.c_float), vp]
-    lib.rift_ref_line_info.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp]
-    lib.rift_rollout.argtypes = [vp, C.POINTER(RiftRolloutIO), vp]
-    lib.rift_prof_enable.argtypes = [vp, C.c_int]
-    lib.rift_prof_report.argtypes = [vp, C.c_char_p, C.c_int]
-    for name in EXPORTS:
-        if name not in ("rift_ctx_destroy", "rift_last_error"):
-            getattr(lib, name).restype = C.c_int
-    _libs[variant] = lib
+    _libs[variant] = lib = _abi.bind(C.CDLL(path))
     return lib
 
 
@@ -375,7 +236,7 @@ class Engine:
         self._keep = []
         self._stage_host = self._stage_dev = None
         self._stage_off = 0
-        self._ctl_state = None         # control_tick: (n_slots, 44) f64, grow-only
+        self._ctl_state = None         # control_tick: (n_slots, CONTROL_STATE) f64, grow-only
         self.generation = 0            # counts the calls that overwrite the policy head's activations (forward, forward_raw, forward_head):
                                        # head_backward refers to the latest one, a caller that kept a graph compares (rift_amd/autograd.py)
 
@@ -708,7 +569,7 @@ class Engine:
     # ---- loss + backward ---------------------------------------------------------------------
     def loss_backward(self, kind: str, batch: Dict[str, torch.Tensor], clip_epsilon=0.2, lambda_entropy=0.01, objective=None,
                       terms: bool = False):
-        """Phase 1: per-rank sums.  Returns (stats[2] f64, flat_grad_sum[16897] f32, argmax_rm or None).
+        """Phase 1: per-rank sums.  Returns (stats[2] f64, flat_grad_sum[PI_NPARAM] f32, argmax_rm or None).
         objective (kinds 'rift' / 'grpo'): a dict of settings (objective_params' keys; {} = the kind's defaults) or a ready
         RiftObjectiveParams -- the call is rift_loss_backward_ex; None: rift_loss_backward.  terms=True (with `objective`): the device
         [8] f64 term sums of that call join the result as a fourth element."""
@@ -770,7 +631,7 @@ class Engine:
 
     def head_backward(self, dlogits: torch.Tensor, grads: Optional[Dict[str, torch.Tensor]] = None, accumulate: bool = False) -> torch.Tensor:
         """rift_head_backward: the gradient sums of the six pi_head tensors for an upstream gradient `dlogits` = d loss / d probability
-        (bs, R, 12) over the activations of the latest forward.  Returns flat[16897] = sum_rows dz * d logit / d theta (PI_KEYS order, no
+        (bs, R, 12) over the activations of the latest forward.  Returns flat[PI_NPARAM] = sum_rows dz * d logit / d theta (PI_KEYS order, no
         sign, no count; rows of padded reference lines contribute nothing); `grads` (keyed like loss_finalize's) are overwritten with it or,
         with `accumulate`, added to.  A data-parallel host all-reduces `flat` itself."""
         if dlogits.dim() != 3 or dlogits.shape[2] != 12:
@@ -1001,7 +862,7 @@ class Engine:
         return res
 
     def control_state(self, n_slots: int = 0) -> torch.Tensor:
-        """The (n_slots, 44) f64 controller state of control_tick, owned by the engine and grow-only (a zero row = a fresh PIDController);
+        """The (n_slots, CONTROL_STATE) f64 controller state of control_tick, owned by the engine and grow-only (a zero row = a fresh PIDController);
         growing copies the rows in use into a NEW tensor, on the current stream: a tensor returned earlier is the state only until the next
         growth (ask again instead of keeping it)."""
         cur = self._ctl_state
@@ -1130,7 +991,7 @@ class Engine:
 
     def critic_backward(self, sd: Dict[str, torch.Tensor], state: torch.Tensor, dvalue: torch.Tensor,
                         grads: Optional[Dict[str, torch.Tensor]] = None, accumulate: bool = False) -> torch.Tensor:
-        """rift_critic_backward: flat[99331] = sum_i dvalue[i] * d value_net(state)[i] / d theta over the ten critic tensors (CRITIC_KEYS
+        """rift_critic_backward: flat[CRITIC_NPARAM] = sum_i dvalue[i] * d value_net(state)[i] / d theta over the ten critic tensors (CRITIC_KEYS
         order; no sign, no count) for an upstream gradient `dvalue` = d loss / d value (n).  `grads` (keyed by CRITIC_KEYS, any subset)
         receive their segments of it -- copied, or added with `accumulate`.  The forward is recomputed from `state`: no forward needs to
         have run."""

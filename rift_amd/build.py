@@ -2,7 +2,8 @@
 
 The library holds TWO builds of the engine -- bf16 and fp16 MFMA operands (csrc/opfmt.h: -DRIFT_OP_F16=0/1, kernels in namespace
 rift_bf / rift_hf) -- behind one set of exported `rift_*` symbols (csrc/abi.cpp, generated from include/rift_hip.h by
-tools/gen/abi_trampolines.py): a context is created for one format and every call is routed to the build that owns it.
+tools/gen/abi_trampolines.py, which also generates the Python side of the interface, rift_amd/_abi.py, that _ffi.py binds the library
+with): a context is created for one format and every call is routed to the build that owns it.
 What does not depend on the operand format is built ONCE per library (SHARED_UNITS: csrc/shared.hip -- objective and backward, AdamW and
 clipping, critic, advantages, rollout, ticks, collate, the device-memory hooks; namespace rift) and serves the contexts of both builds.
 """

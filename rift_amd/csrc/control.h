@@ -10,13 +10,15 @@
 // One sum is not numpy's tree: the segment lengths behind the target speed are added in path order, which is what np.mean does below eight
 // segments (the default: 80 frames, interval 10, seven segments); from eight segments on numpy sums pairwise and the two agree to rounding.
 #pragma once
+#include "../../include/rift_hip.h"
 #include "lanes.h"
 
 namespace rift {
 
 #define RIFT_CTL_CHUNK 16                        // CBVs per launch
-#define RIFT_CTL_STATE 44                        // doubles per pid_state row: turn ring [0,20) | speed ring [20,40) | turn head, last | speed head, last
 #define RIFT_CTL_RING 20
+// a pid_state row (RIFT_CONTROL_STATE doubles, rift_hip.h): turn ring [0,20) | speed ring [20,40) | turn head, last | speed head, last
+static_assert(2 * RIFT_CTL_RING + 4 == RIFT_CONTROL_STATE, "the pid_state row and RIFT_CONTROL_STATE of rift_hip.h disagree");
 
 struct CtlK {                                    // one CBV
   const float* traj;                             // (G, Tfull, 6) candidates of the CBV's batch row

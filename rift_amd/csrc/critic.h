@@ -5,6 +5,7 @@
 // Backward is split so that every sum has a fixed order: a row kernel (16 rows per workgroup) produces the per-row deltas,
 // then each parameter gradient is a column / outer-product sum over the rows computed by exactly one thread.
 #pragma once
+#include "../../include/rift_hip.h"
 #include "lanes.h"
 
 namespace rift {
@@ -23,6 +24,8 @@ namespace rift {
 #define RIFT_CRITIC_OFF_SSTD (RIFT_CRITIC_OFF_SAVG + RIFT_CRITIC_IN)
 #define RIFT_CRITIC_OFF_VAVG (RIFT_CRITIC_OFF_SSTD + RIFT_CRITIC_IN)
 #define RIFT_CRITIC_OFF_VSTD (RIFT_CRITIC_OFF_VAVG + 1)
+static_assert(RIFT_CRITIC_OFF_VSTD + 1 == RIFT_CRITIC_NPARAM, "the flat layout and RIFT_CRITIC_NPARAM disagree");
+static_assert(RIFT_CRITIC_NPARAM == RIFT_CRITIC_NPARAM_C, "RIFT_CRITIC_NPARAM and RIFT_CRITIC_NPARAM_C of rift_hip.h disagree");
 
 struct CriticW { const float *w0, *b0, *w1, *b1, *w2, *b2, *savg, *sstd, *vavg, *vstd; };
 

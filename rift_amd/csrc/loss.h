@@ -3,6 +3,7 @@
 // Row softmax / LayerNorm reductions are wavefront shuffles; objective sums are fp64
 // (the reference promotes fp64 advantage x fp32 ratio, rift_trainer.py:160-178).
 #pragma once
+#include "../../include/rift_hip.h"
 #include "lanes.h"
 
 namespace rift {
@@ -316,8 +317,8 @@ __global__ __launch_bounds__(64) void sft_teacher_mode_kernel(const float* __res
 }
 
 // Backward through pi_head for a chunk of rows.  partial layout per workgroup (floats):
-//   [0,16384) dW1[c][k] | +128 db1 | +128 dgamma | +128 dbeta | +128 dw2 | +1 db2      (= 16897)
-#define RIFT_PI_NPARAM 16897
+//   [0,16384) dW1[c][k] | +128 db1 | +128 dgamma | +128 dbeta | +128 dw2 | +1 db2      (= RIFT_PI_NPARAM, rift_hip.h)
+static_assert(128 * 128 + 128 + 128 + 128 + 128 + 1 == RIFT_PI_NPARAM, "the pi_head layout and RIFT_PI_NPARAM of rift_hip.h disagree");
 #define RIFT_PI_BWD_ROWS 128
 // Rows are handled 16 lanes per row (8 channels per lane): the LayerNorm-backward reductions are DPP row sums, four
 // rows per wave in flight; dW1 += dh^T q accumulates an 8 x 8 register block per thread from LDS-staged 32-row slabs.

@@ -605,7 +605,7 @@ int rift_control_tick(RiftCtx* c, const float* trajectory, const float* probabil
       d.traj = trajectory + (size_t)v.batch_index * (size_t)G * Tfull * 6;
       d.prob = probability + (size_t)v.batch_index * (size_t)G;
       d.rf = ref_free_trajectory ? ref_free_trajectory + (size_t)v.batch_index * Tfull * 4 : nullptr;
-      d.state = pid_state + (size_t)v.slot * RIFT_CTL_STATE;
+      d.state = pid_state + (size_t)v.slot * RIFT_CONTROL_STATE;
       d.dec = decision + (size_t)(k0 + j) * 8;
       d.ox = v.x; d.oy = v.y; d.ch = std::cos(v.heading); d.sh = std::sin(v.heading); d.speed = v.speed;
     }

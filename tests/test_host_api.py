@@ -42,16 +42,23 @@ def test_library_exports_every_declared_symbol():
     assert set(_ffi.EXPORTS) == declared
 
 
-def test_trampolines_are_generated_from_the_header():
-    """csrc/abi.cpp / abi_list.h (the exported symbols: routing onto the bf16- or fp16-operand build that owns a context) are what
-    tools/gen/abi_trampolines.py derives from include/rift_hip.h -- the header stays the single statement of the interface."""
+def _generator():
     import importlib.util
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     spec = importlib.util.spec_from_file_location("abi_trampolines", os.path.join(repo, "tools", "gen", "abi_trampolines.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
+    return mod
+
+
+def test_trampolines_are_generated_from_the_header():
+    """csrc/abi.cpp / abi_list.h (the exported symbols: routing onto the bf16- or fp16-operand build that owns a context) and
+    rift_amd/_abi.py (the ctypes mirror the Python binding applies) are what tools/gen/abi_trampolines.py derives from
+    include/rift_hip.h -- the header stays the single statement of the interface."""
+    mod = _generator()
     lst, cpp = mod.render()
     assert open(mod.OUT_LIST).read() == lst and open(mod.OUT_CPP).read() == cpp, "run python tools/gen/abi_trampolines.py"
+    assert open(mod.OUT_PY).read() == mod.binding(), "run python tools/gen/abi_trampolines.py"
     from rift_amd import _ffi
     lib = _ffi.load_library()
     for sym in ("rift_vtable_bf16", "rift_vtable_fp16"):          # one table per operand-format build
@@ -69,7 +76,6 @@ def test_format_free_entries_are_defined_once_and_the_context_types_cannot_colli
     (c) the device-memory hooks are defined in shared.o only;
     (d) the library exports the `rift_*` symbols of tests/golden/exported_symbols.txt (the functions include/rift_hip.h declares, by the
         generator's own parse, and one table per engine build), no more and no fewer."""
-    import importlib.util
     import shutil
     import subprocess
     from rift_amd import build
@@ -93,9 +99,7 @@ def test_format_free_entries_are_defined_once_and_the_context_types_cannot_colli
     assert not both, both
     assert any(s.startswith("rift_bf::Ctx::~Ctx") for s in sym["engine_bf"]) and any(s.startswith("rift_hf::Ctx::~Ctx") for s in sym["engine_hf"])
     # (b), (c)
-    spec = importlib.util.spec_from_file_location("abi_trampolines", os.path.join(repo, "tools", "gen", "abi_trampolines.py"))
-    gen = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gen)
+    gen = _generator()
     assert len(gen.FORMAT_FREE) == 29 and not set(gen.FORMAT_FREE) & set(gen.SPECIAL) and not set(gen.FORMAT_FREE) & set(gen.NO_CTX)
 
     def names(symbols):          # "rift::abi::rift_gae(RiftCtx*, ...)" -> "rift_gae"
@@ -145,34 +149,102 @@ def test_struct_layouts_match_header_sizes():
 
 
 def test_ctypes_structs_match_the_header_as_a_c_compiler_lays_it_out(tmp_path):
-    """include/rift_hip.h compiled by gcc as C: sizeof and every field offset of the structs the Python binding mirrors (a ctypes Structure
-    that drifts from the header corrupts arguments silently)."""
+    """include/rift_hip.h compiled by gcc as C: sizeof and every field offset of every struct the header defines, as the Python binding
+    mirrors it (a ctypes Structure that drifts from the header corrupts arguments silently), and the size of every scalar C type of the
+    generator's mapping table against the ctypes type it maps to."""
     import shutil
     import subprocess
-    from rift_amd import _ffi
+    from rift_amd import _abi
     gcc = shutil.which("gcc")
     if gcc is None:
         pytest.skip("no gcc")
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    structs = {"RiftTickCBV": _ffi.RiftTickCBV, "RiftRolloutIO": _ffi.RiftRolloutIO, "RiftFeatureBatch": _ffi.RiftFeatureBatch,
-               "RiftOutputs": _ffi.RiftOutputs, "RiftLossIn": _ffi.RiftLossIn, "RiftLossOut": _ffi.RiftLossOut}
+    hdr = open(os.path.join(repo, "include", "rift_hip.h")).read()
+    structs = {n: c for n, c in vars(_abi).items() if isinstance(c, type) and issubclass(c, ctypes.Structure) and c is not ctypes.Structure}
+    assert set(structs) == set(re.findall(r"\}\s*(Rift\w+)\s*;", hdr)) and len(structs) == 13          # every `typedef struct { ... } Name;`
+    scalars = _generator().SCALARS
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "rift_hip.h"', 'int main(void) {']
     for name, st in structs.items():
         lines.append(f'  printf("{name} %zu", sizeof({name}));')
         for field, *_ in st._fields_:
             lines.append(f'  printf(" %zu", offsetof({name}, {field}));')
         lines.append('  printf("\\n");')
+    for c in scalars:
+        lines.append(f'  printf("scalar:{c} %zu\\n", sizeof({c}));')
     lines += ['  return 0;', '}']
     src = tmp_path / "layout.c"
     src.write_text("\n".join(lines))
     exe = tmp_path / "layout"
     subprocess.check_call([gcc, "-std=c99", "-I", os.path.join(repo, "include"), str(src), "-o", str(exe)])
     out = subprocess.check_output([str(exe)], text=True).strip().splitlines()
+    assert len(out) == len(structs) + len(scalars)
     for line in out:
         name, size, *offs = line.split()
+        if name.startswith("scalar:"):
+            c = name.split(":", 1)[1]
+            assert ctypes.sizeof(getattr(ctypes, scalars[c])) == int(size), (c, scalars[c], size)
+            continue
         st = structs[name]
         assert ctypes.sizeof(st) == int(size), (name, ctypes.sizeof(st), size)
         assert [getattr(st, f).offset for f, *_ in st._fields_] == [int(o) for o in offs], name
+
+
+def test_bound_signatures_match_a_table_written_from_the_header():
+    """argtypes and restype of the loaded library against rows typed here by hand from include/rift_hip.h, independently of the generator:
+    the entries where a slip is silent (a float where the header says double passes every CPU test and corrupts the argument)."""
+    from rift_amd import _ffi, build
+    build.build()
+    lib = _ffi.load_library()
+    vp, i, u32, f, d, P = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_float, ctypes.c_double, ctypes.POINTER
+    table = {
+        # ctx, rewards f64*, undones, values, next_values, unterminated, float gamma, float lambda_, int n, advantages, stream
+        "rift_gae": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, f, f, i, vp, vp]),
+        # ctx, rewards, dones, double gamma, int n, returns, stream
+        "rift_discounted_return": (ctypes.c_int, [vp, vp, vp, d, i, vp, vp]),
+        # ctx, out, int accumulate, float max_norm, total_norm, stream
+        "rift_loss_finalize_clip": (ctypes.c_int, [vp, P(_ffi.RiftLossOut), i, f, vp, vp]),
+        # ctx, rollout_center, int n_points, off_road_mask, int H, int W, double origin_x, origin_y, heading, res_x, res_y, off_x, off_y, off_road, stream
+        "rift_off_road_matrix": (ctypes.c_int, [vp, vp, i, vp, i, i, d, d, d, d, d, d, d, vp, vp]),
+        # ctx, batch, out, int flags, uint32_t seed, stream
+        "rift_forward": (ctypes.c_int, [vp, P(_ffi.RiftFeatureBatch), P(_ffi.RiftOutputs), i, u32, vp]),
+        # ctx, out, int accumulate, float max_norm, total_norm, int n_tensors, params, grads, exp_avg, exp_avg_sq, steps, lr, weight_decay,
+        # double step_new, beta1, beta2, eps, stream
+        "rift_update_tail": (ctypes.c_int, [vp, P(_ffi.RiftLossOut), i, f, vp, i, vp, vp, vp, vp, vp, vp, vp, d, d, d, d, vp]),
+        # ctx, delta_dis, delta_angle, speed, acc, ang_vel, ang_acc, collision, int collision_ld, off_road, int off_road_ld, int G, int Ts,
+        # params, returns, terms, stream
+        "rift_rollout_return_ex": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i, vp, i, i, i, P(_ffi.RiftEvalParams), vp, vp, vp]),
+        # ctx, trajectory, probability, ref_free_trajectory, int Rb, int Tfull, cbvs, int K, int topk, int sample_interval, pid_state,
+        # int n_slots, decision, stream
+        "rift_control_tick": (ctypes.c_int, [vp, vp, vp, vp, i, i, P(_ffi.RiftControlCBV), i, i, i, vp, i, vp, vp]),
+        "rift_last_error": (ctypes.c_char_p, [vp]),
+        "rift_ctx_destroy": (None, [vp]),
+    }
+    for name, (restype, argtypes) in table.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype, (name, fn.restype)
+        assert list(fn.argtypes) == argtypes, (name, fn.argtypes)
+    # every other entry: bound, with the arity of its declaration
+    gen = _generator()
+    decls = gen.declarations(open(gen.HEADER).read())
+    assert len(decls) == 53 == len(_ffi.EXPORTS) and [n for _, n, _ in decls] == list(_ffi.EXPORTS)
+    for _, name, params in decls:
+        assert len(getattr(lib, name).argtypes) == len(params), name
+
+
+def test_generator_refuses_a_type_outside_its_table():
+    """A parameter or field whose C type the mapping table does not hold is an error that names the declaration, not a guess."""
+    gen = _generator()
+    good = "typedef struct RiftCtx RiftCtx;\ntypedef struct RiftP { double a; const float* b; } RiftP;\nint rift_good(RiftCtx* ctx, const RiftP* p, float x);\n"
+    text = gen.binding(good)
+    assert '"rift_good": (C.c_int, [C.c_void_p, C.POINTER(RiftP), C.c_float])' in text
+    with pytest.raises(ValueError, match=r"rift_bad, parameter x.*long double"):
+        gen.binding(good + "int rift_bad(RiftCtx* ctx, long double x);\n")
+    with pytest.raises(ValueError, match=r"rift_bad, parameter q.*RiftUnknown"):
+        gen.binding(good + "int rift_bad(RiftCtx* ctx, const RiftUnknown* q);\n")
+    with pytest.raises(ValueError, match=r"struct RiftQ, field n.*size_t"):
+        gen.binding(good + "typedef struct RiftQ { size_t n; } RiftQ;\n")
+    with pytest.raises(ValueError, match=r"RIFT_B"):
+        gen.binding(good + "enum { RIFT_A = 1, RIFT_B };\n")
 
 
 def test_stream_plan_orders_every_reader_behind_the_preparation(tmp_path):

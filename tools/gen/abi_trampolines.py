@@ -1,4 +1,4 @@
-"""Generates rift_amd/csrc/abi_list.h and rift_amd/csrc/abi.cpp from include/rift_hip.h.
+"""Generates rift_amd/csrc/abi_list.h, rift_amd/csrc/abi.cpp and rift_amd/_abi.py from include/rift_hip.h.
 
 librift_hip.so carries two builds of the engine -- bf16 and fp16 MFMA operands (csrc/opfmt.h) -- and ONE set of exported `rift_*`
 symbols.  An exported function whose entry depends on the build (context, model load, forward, streams, profiler, taps) is a trampoline
@@ -6,10 +6,17 @@ that reads the operand format a context was created with (RiftCtxCore::opfmt, cs
 of the build that owns the context through that build's RiftVTable (csrc/abi_table.h: the RIFT_FN list of abi_list.h).  The entries that
 do not depend on the operand format (FORMAT_FREE below) exist once per library (csrc/shared.hip, namespace rift::abi): their trampolines
 null-check the context and call them directly, and abi_list.h names them in a second list, RIFT_SHARED_FN.  The trampolines are derived
-from the declarations of the header, so the header stays the single statement of the interface (tests/test_host_api.py regenerates both
+from the declarations of the header, so the header stays the single statement of the interface (tests/test_host_api.py regenerates the
 files and compares).
 
-    python tools/gen/abi_trampolines.py          # rewrites the two files in place
+rift_amd/_abi.py is the Python side of the same statement: the header's enumerators and integer #defines as ints, one ctypes.Structure
+per `typedef struct`, SIGNATURES (name -> restype, argtypes) and bind(lib).  One table maps the types: int / int32_t -> c_int32,
+uint32_t -> c_uint32, int64_t -> c_int64, float -> c_float, double -> c_double, uint8_t -> c_uint8; a pointer to a struct of the header ->
+POINTER(it); char* -> c_char_p; every other pointer -> c_void_p (the type alone cannot tell a device pointer from a host array).  A type
+outside the table is an error that names the declaration.
+
+    python tools/gen/abi_trampolines.py          # rewrites the three files in place
+    python tools/gen/abi_trampolines.py --check  # exit status 1 when one of them differs
 """
 import os
 import re
@@ -19,6 +26,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 HEADER = os.path.join(REPO, "include", "rift_hip.h")
 OUT_LIST = os.path.join(REPO, "rift_amd", "csrc", "abi_list.h")
 OUT_CPP = os.path.join(REPO, "rift_amd", "csrc", "abi.cpp")
+OUT_PY = os.path.join(REPO, "rift_amd", "_abi.py")
 
 # entry points the trampoline file implements by hand (they create a context / work without one)
 SPECIAL = {"rift_ctx_create", "rift_ctx_create_ex", "rift_ctx_operand_format", "rift_ctx_destroy", "rift_last_error"}
@@ -33,10 +41,13 @@ FORMAT_FREE = ("rift_loss_backward", "rift_loss_backward_ex", "rift_head_backwar
                "rift_eval_params_default")
 
 
+def strip_comments(text):
+    return re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", text, flags=re.S))
+
+
 def declarations(text):
     """[(return type, name, [(param type, param name)])] of every `rift_*` function the header declares."""
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", " ", text)
+    text = strip_comments(text)
     out = []
     for m in re.finditer(r"^(int|void|const char\*)\s+(rift_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", text, re.M | re.S):
         ret, name, args = m.group(1), m.group(2), " ".join(m.group(3).split())
@@ -48,8 +59,89 @@ def declarations(text):
     return out
 
 
+SCALARS = {"int": "c_int32", "int32_t": "c_int32", "uint32_t": "c_uint32", "int64_t": "c_int64", "float": "c_float", "double": "c_double",
+           "uint8_t": "c_uint8"}
+POINTEES = set(SCALARS) | {"void", "char", "int8_t"}          # what a `c_void_p` may point to, beside the header's own types
+RETURNS = {"int": "C.c_int", "void": "None", "const char*": "C.c_char_p"}
+
+
+def ctype(typ, known, where):
+    """The ctypes spelling of one C type of the header (the table of the module docstring); `known`: the header's own type names ->
+    "struct" | "opaque" | "fn".  A type outside the table raises, naming the declaration `where`."""
+    base = " ".join(t for t in typ.replace("*", " ").split() if t != "const")
+    stars = typ.count("*")
+    if stars == 0 and base in SCALARS:
+        return "C." + SCALARS[base]
+    if stars == 0 and known.get(base) in ("struct", "fn"):
+        return base
+    if stars == 1 and known.get(base) == "struct":
+        return f"C.POINTER({base})"
+    if stars == 1 and base == "char":
+        return "C.c_char_p"
+    if stars >= 1 and (base in POINTEES or base in known):
+        return "C.c_void_p"
+    raise ValueError(f"{where}: no ctypes mapping for the C type `{typ}`")
+
+
+def binding(text=None):
+    """The text of rift_amd/_abi.py for the header `text` (default: include/rift_hip.h): constants, structs, SIGNATURES and bind()."""
+    text = strip_comments(open(HEADER).read() if text is None else text)
+    out = ['"""GENERATED by tools/gen/abi_trampolines.py from include/rift_hip.h -- do not edit.',
+           "", "The ctypes mirror of the C-ABI: the header's constants, structs and function signatures; bind(lib) applies them to a loaded library.",
+           '"""', "import ctypes as C", ""]
+    consts = []          # (name, value) of every enumerator and every integer #define, in header order
+    for m in re.finditer(r"\benum\s*\{([^}]*)\}\s*;|^[ \t]*#define[ \t]+(RIFT_\w+)[ \t]+(-?\d+)[ \t]*$", text, re.M):
+        if m.group(2):
+            consts.append((m.group(2), m.group(3)))
+            continue
+        for e in filter(None, (x.strip() for x in m.group(1).split(","))):
+            em = re.fullmatch(r"(RIFT_\w+)\s*=\s*(-?\d+)", e)
+            if not em:
+                raise ValueError(f"enum {{ {' '.join(m.group(1).split())} }}: enumerator `{e}` is not NAME = integer")
+            consts.append((em.group(1), em.group(2)))
+    out += [f"{name} = {value}" for name, value in consts] + ["", ""]
+    # the header's own types, in header order: opaque handles, structs, function-pointer typedefs
+    types = sorted([(m.start(), "opaque", m) for m in re.finditer(r"typedef\s+struct\s+(\w+)\s+(\w+)\s*;", text)]
+                   + [(m.start(), "struct", m) for m in re.finditer(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", text, re.S)]
+                   + [(m.start(), "fn", m) for m in re.finditer(r"typedef\s+(\w+)\s*\(\s*\*\s*(\w+)\s*\)\s*\(([^)]*)\)\s*;", text)], key=lambda t: t[0])
+    known = {}
+    for _, kind, m in types:
+        if kind == "opaque":
+            known[m.group(2)] = kind
+        elif kind == "fn":
+            ret, name, params = m.group(1), m.group(2), [p.strip() for p in m.group(3).split(",")]
+            args = [ctype(re.match(r"^(.*?)\w+$", p).group(1), known, f"typedef {name}") for p in params]
+            out += [f"{name} = C.CFUNCTYPE({', '.join([ctype(ret, known, f'typedef {name}')] + args)})", "", ""]
+            known[name] = kind
+        else:
+            name, body = m.group(3), m.group(2)
+            fields = []
+            for stmt in filter(None, (" ".join(s.split()) for s in body.split(";"))):
+                sm = re.match(r"^((?:const )?\w+)\s*(.*)$", stmt)          # `const float` | `*a, *b` or `a[4]`
+                for d in sm.group(2).split(",") if sm else [""]:
+                    dm = re.fullmatch(r"\s*(\**)\s*(\w+)\s*(?:\[(\d+)\])?\s*", d)
+                    if not dm:
+                        raise ValueError(f"struct {name}: cannot read the field declaration `{stmt}`")
+                    t = ctype(sm.group(1) + dm.group(1), known, f"struct {name}, field {dm.group(2)}")
+                    fields.append(f'("{dm.group(2)}", {t} * {dm.group(3)})' if dm.group(3) else f'("{dm.group(2)}", {t})')
+            out += [f"class {name}(C.Structure):", "    _fields_ = [" + ",\n                ".join(fields) + "]", "", ""]
+            known[name] = kind
+    out += ["# name -> (restype, [argtypes]) of every function the header declares, in header order", "SIGNATURES = {"]
+    for ret, name, params in declarations(text):
+        args = [ctype(t, known, f"{name}, parameter {n}") for t, n in params]
+        out.append(f'    "{name}": ({RETURNS[ret]}, [{", ".join(args)}]),')
+    out += ["}", "EXPORTS = list(SIGNATURES)", "", "",
+            "def bind(lib):", '    """Check that `lib` exports every function of the header and set its argtypes / restype."""',
+            "    for name in EXPORTS:", "        if not hasattr(lib, name):",
+            '            raise RuntimeError(f"librift_hip.so does not export {name}")',
+            "    for name, (restype, argtypes) in SIGNATURES.items():", "        fn = getattr(lib, name)",
+            "        fn.argtypes, fn.restype = argtypes, restype", "    return lib"]
+    return "\n".join(out) + "\n"
+
+
 def render():
-    decls = declarations(open(HEADER).read())
+    text = open(HEADER).read()
+    decls = declarations(text)
     assert set(FORMAT_FREE) <= {d[1] for d in decls}, set(FORMAT_FREE) - {d[1] for d in decls}
     per_build = [d for d in decls if d[1] not in NO_CTX and d[1] not in FORMAT_FREE]
     shared = [d for d in decls if d[1] in FORMAT_FREE]
@@ -129,9 +221,8 @@ def render():
 
 
 if __name__ == "__main__":
-    lst, cpp = render()
+    files = list(zip((OUT_LIST, OUT_CPP, OUT_PY), render() + (binding(),)))
     if len(sys.argv) > 1 and sys.argv[1] == "--check":
-        ok = open(OUT_LIST).read() == lst and open(OUT_CPP).read() == cpp
-        sys.exit(0 if ok else 1)
-    open(OUT_LIST, "w").write(lst)
-    open(OUT_CPP, "w").write(cpp)
+        sys.exit(0 if all(os.path.exists(p) and open(p).read() == t for p, t in files) else 1)
+    for p, t in files:
+        open(p, "w").write(t)

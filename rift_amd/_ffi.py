@@ -16,9 +16,10 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from rift_amd import _abi
+from rift_amd import _abi, _abi_drivable
 from rift_amd._abi import (EXPORTS, RiftControlCBV, RiftCritic, RiftDp, RiftEvalParams, RiftFeatureBatch, RiftLossIn,  # noqa: F401
                            RiftLossOut, RiftObjectiveParams, RiftOutputs, RiftReplayArena, RiftRolloutIO, RiftTensorDesc, RiftTickCBV)
+from rift_amd._abi_drivable import RiftDrivableInfo      # the drivable-area-map extension (include/rift_drivable.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librift_hip.so")
@@ -117,7 +118,7 @@ def load_library(variant: str = "") -> C.CDLL:
         raise RuntimeError(
             f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). rift_amd has no CPU fallback.")
-    _libs[variant] = lib = _abi.bind(C.CDLL(path))
+    _libs[variant] = lib = _abi_drivable.bind(_abi.bind(C.CDLL(path)))
     return lib
 
 
@@ -775,7 +776,10 @@ class Engine:
         bbox_inflation_ratio, near_lane_change, resolution and a pixel offset from each CBV's own raster.  With want_returns / want_terms the
         result is a dict: "advantage" (K, Rb, 12), "returns" (K, Rb, 12), "terms" (K, Rb, 12, 8) -- the ones asked for, views of the ONE device
         tensor "packed" (K * Rb * 12 * 10 doubles, zero where nothing is written), so that a tick reads all of it back in one copy.  With
-        params None and nothing wanted the call is rift_group_advantage_tick, as ever."""
+        params None and nothing wanted the call is rift_group_advantage_tick, as ever.
+        An entry without off_road that carries "raster": (H, W) and "pose": (x, y, heading) takes its off-road flags from the loaded
+        drivable-area map (load_drivable_map): the call is riftdm_group_advantage_tick (params None: eval_params(gamma=gamma)); a tick
+        may mix such entries with mask entries and with entries that have neither."""
         dev = self.device
         traj = _dev(trajectory, torch.float32, dev)
         bs, Rb, M, Tfull, Cc = traj.shape
@@ -816,6 +820,10 @@ class Engine:
                 b8.append(mask.reshape(-1)); o8 += mask.size
                 pad = (-o8) % 16
                 if pad: b8.append(np.zeros(pad, dtype=np.uint8)); o8 += pad
+            elif v.get("raster") is not None:        # no mask: the flags come from the loaded drivable-area map (riftdm_group_advantage_tick)
+                if v.get("pose") is None:
+                    raise ValueError("group_advantage_tick: an entry with 'raster' needs 'pose' (x, y, heading of the footprint centre)")
+                e["map"], e["H"], e["W"], e["pose"] = True, int(v["raster"][0]), int(v["raster"][1]), [float(x) for x in v["pose"]]
             plan.append(e)
         n64 = o64 * 8
         n32 = o32 * 4
@@ -835,11 +843,15 @@ class Engine:
             if e["mask"] is not None:
                 t.off_road_mask, t.H, t.W = base8 + e["mask"], e["H"], e["W"]
                 t.pose[0], t.pose[1], t.pose[2] = e["pose"]
+            elif e.get("map"):
+                t.H, t.W = e["H"], e["W"]
+                t.pose[0], t.pose[1], t.pose[2] = e["pose"]
+        use_map = any(e.get("map") for e in plan)
         Gmax = 12 * max(e["R"] for e in plan)
         for k in ("turn_buf", "turn_ptr", "turn_len", "speed_buf", "speed_ptr", "speed_len"):
             assert pid_state[k].shape[0] >= Gmax
         pid = [_ptr(pid_state[k]) for k in ("turn_buf", "turn_ptr", "turn_len", "speed_buf", "speed_ptr", "speed_len")]
-        if params is None and not want_returns and not want_terms:
+        if params is None and not want_returns and not want_terms and not use_map:
             out = torch.zeros(K, Rb, 12, dtype=torch.float64, device=dev)
             self._check(self.lib.rift_group_advantage_tick(self.ctx, _ptr(traj), Rb, Tfull, arr, K, *pid, float(gamma), _ptr(out), _stream()),
                         "rift_group_advantage_tick")
@@ -851,9 +863,10 @@ class Engine:
         packed = torch.zeros(n * 10, dtype=torch.float64, device=dev)
         res = {"packed": packed, "advantage": packed[:n].view(K, Rb, 12), "returns": packed[n:2 * n].view(K, Rb, 12),
                "terms": packed[2 * n:].view(K, Rb, 12, 8)}
-        self._check(self.lib.rift_group_advantage_tick_ex(self.ctx, _ptr(traj), Rb, Tfull, arr, K, *pid, C.byref(params), _ptr(res["advantage"]),
-                                                          _ptr(res["returns"]) if want_returns else None, _ptr(res["terms"]) if want_terms else None,
-                                                          _stream()), "rift_group_advantage_tick_ex")
+        fn, name = (self.lib.riftdm_group_advantage_tick, "riftdm_group_advantage_tick") if use_map else \
+                   (self.lib.rift_group_advantage_tick_ex, "rift_group_advantage_tick_ex")
+        self._check(fn(self.ctx, _ptr(traj), Rb, Tfull, arr, K, *pid, C.byref(params), _ptr(res["advantage"]),
+                       _ptr(res["returns"]) if want_returns else None, _ptr(res["terms"]) if want_terms else None, _stream()), name)
         self._keep_tick = (traj, up)
         if not want_returns and not want_terms:
             return res["advantage"]
@@ -951,6 +964,52 @@ class Engine:
                                                   float(resolution_hw[0]), float(resolution_hw[1]), float(offset[0]), float(offset[1]),
                                                   _ptr(out), _stream()), "rift_off_road_matrix")
         return out.bool()
+
+    # ---- the drivable-area map: off-road flags without a raster (include/rift_drivable.h states the rule) ------------
+    def load_drivable_map(self, polygons, cell: float = 16.0, margin: float = 1.0) -> dict:
+        """The drivable polygons of a town -> the device, once: `polygons` is a list of (n, 2) float64 vertex arrays in the global frame (a ring
+        may repeat its first vertex as its last, as shapely's exterior.coords does).  A second call replaces the map.  Returns drivable_map_info()."""
+        polys = [np.ascontiguousarray(np.asarray(p, dtype=np.float64)).reshape(-1, 2) for p in polygons]
+        start = np.zeros(len(polys) + 1, dtype=np.int32)
+        if polys:
+            start[1:] = np.cumsum([p.shape[0] for p in polys])
+        verts = np.ascontiguousarray(np.concatenate(polys, 0)) if polys else np.zeros((0, 2), dtype=np.float64)
+        self._check(self.lib.riftdm_load(self.ctx, verts.ctypes.data_as(vp), start.ctypes.data_as(vp), len(polys), float(cell), float(margin),
+                                                    _stream()), "riftdm_load")
+        return self.drivable_map_info()
+
+    def clear_drivable_map(self):
+        self._check(self.lib.riftdm_clear(self.ctx), "riftdm_clear")
+
+    def drivable_map_info(self) -> Optional[dict]:
+        """The loaded map's numbers (RiftDrivableInfo as a dict), or None when no map is loaded."""
+        info = RiftDrivableInfo()
+        rc = self.lib.riftdm_info(self.ctx, C.byref(info))
+        if rc == _abi.RIFT_ERR_STATE:
+            return None
+        self._check(rc, "riftdm_info")
+        return {k: getattr(info, k) for k, _ in RiftDrivableInfo._fields_ if k != "reserved"}
+
+    def off_road_matrix_map(self, rollout_center, pose, raster_size=(400, 400), params: Optional[RiftEvalParams] = None):
+        """get_off_road_matrix from the loaded map: rollout_center (G, T, 2), pose (x, y, heading) of the footprint centre, raster_size (H, W) of
+        the raster the rule speaks of, params (eval_params: its resolution is read) -> (G, T) bool."""
+        dev = self.device
+        rc = _dev(rollout_center, torch.float32, dev)
+        G, T = rc.shape[:2]
+        params = eval_params() if params is None else params
+        out = torch.empty(G, T, dtype=torch.uint8, device=dev)
+        self._check(self.lib.riftdm_off_road_matrix(self.ctx, _ptr(rc), G * T, int(raster_size[0]), int(raster_size[1]), float(pose[0]), float(pose[1]),
+                                                      float(pose[2]), C.byref(params), _ptr(out), _stream()), "riftdm_off_road_matrix")
+        return out.bool()
+
+    def drivable_raster(self, pose, raster_size=(400, 400), params: Optional[RiftEvalParams] = None) -> torch.Tensor:
+        """The (H, W) uint8 device mask the reference would hand to the lookup, drawn by the rule from the loaded map: 1 = off road."""
+        H, W = int(raster_size[0]), int(raster_size[1])
+        params = eval_params() if params is None else params
+        out = torch.empty(max(H, 0), max(W, 0), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.riftdm_raster(self.ctx, H, W, float(pose[0]), float(pose[1]), float(pose[2]), C.byref(params), _ptr(out), _stream()),
+                    "riftdm_raster")
+        return out
 
     def make_clip_list(self, grads):
         """Pre-build the (pointer, numel) arrays of a fixed list of .grad tensors for clip_grad_norm_raw."""

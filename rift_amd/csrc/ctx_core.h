@@ -12,6 +12,7 @@
 
 #include "../../include/rift_hip.h"
 #include "devmem.h"
+#include "drivable_grid.h"
 
 struct RiftCtxCore {
   int opfmt = 0;                         // FIRST member (set by rift_ctx_create of the build): abi.cpp reads it to route a call to the build (bf16 / fp16 operands) that owns the context
@@ -41,6 +42,9 @@ struct RiftCtxCore {
   bool ro8 = true;                  // candidate rollout with eight lanes per candidate (rollout.h; RIFT_RO8=0: one lane, the round-1 form)
   DevBuf<float> ro_raw;             // rift_rollout: the unsmoothed speed history handed from the closed-loop kernel to the kinematics kernel
   DevBuf<char> tick_scratch;        // rift_group_advantage_tick: per-CBV intermediates (reused CBV by CBV in stream order)
+  // riftdm_load: the town's drivable polygons and their grid (drivable_grid.h).  `grid` keeps the host-side numbers only (its vectors
+  // are emptied after the upload); used_on: the stream of the last launch that read the images -- waited for before they are released
+  struct DMap { bool loaded = false; DrivableGrid grid; DrivableImages img; hipStream_t used_on = nullptr; bool used = false; } dmap;
 };
 
 // The C handle of include/rift_hip.h.  It adds nothing: a build's context derives from it and its entries cast down once at the top.

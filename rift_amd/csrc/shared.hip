@@ -1,5 +1,5 @@
 // The entries of include/rift_hip.h that do not depend on the MFMA operand format: the objective and its backward, AdamW and clipping,
-// the PPO critic, the advantage scans, the candidate rollout, the group-advantage tick, the control tick and collate.  They use no MFMA and
+// the PPO critic, the advantage scans, the candidate rollout, the drivable-area map, the group-advantage tick, the control tick and collate.  They use no MFMA and
 // no operand conversion and touch the format-free half of a context only (ctx_core.h), so they are compiled ONCE per library and serve
 // contexts of both engine builds; the exported trampolines (abi.cpp) call them directly.
 #include <hip/hip_runtime.h>
@@ -13,11 +13,13 @@
 #include <vector>
 
 #include "launch.h"
+#include "../../include/rift_drivable.h"
 #include "lanes.h"
 #include "loss.h"
 #include "critic.h"
 #include "adv.h"
 #include "rollout.h"
+#include "drivable_map.h"
 #include "tick_multi.h"
 #include "control.h"
 #include "eval_params.h"
@@ -473,24 +475,127 @@ int rift_rollout(RiftCtx* c, const RiftRolloutIO* io, void* stream) {
   return RIFT_OK;
 }
 
+// ---- the drivable-area map (include/rift_drivable.h; drivable_grid.h, drivable_map.h) ------------------------------
+// the images are released only after the stream that last read them has been waited for
+static int drivable_map_release(RiftCtx* c) {
+  if (c->dmap.used) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, hipStreamSynchronize(c->dmap.used_on)); }
+  c->dmap.img.reset(); c->dmap.grid = DrivableGrid(); c->dmap.loaded = false; c->dmap.used = false; c->dmap.used_on = nullptr;
+  return RIFT_OK;
+}
+
+int riftdm_load(RiftCtx* c, const double* vertices, const int32_t* poly_start, int n_polys, double cell, double margin, void* stream) {
+  if (!c) return RIFT_ERR_ARG;
+  c->err.clear();
+  DrivableGrid g;
+  if (const char* why = drivable_grid_build(vertices, poly_start, n_polys, cell, margin, &g)) { c->err = std::string("riftdm_load: ") + why; return RIFT_ERR_ARG; }
+  TRY(drivable_map_release(c));
+  HIPCHK(c, hipSetDevice(c->device));
+  DrivableImages& im = c->dmap.img;
+  DEVCHK(c, im.reserve(g));
+  const hipStream_t st = (hipStream_t)stream;
+  auto up = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess; };
+  hipError_t e = up(im.vertices.get(), vertices, (size_t)g.n_vertices * 2 * sizeof(double));
+  if (e == hipSuccess) e = up(im.aabb.get(), g.aabb.data(), g.aabb.size() * sizeof(double));
+  if (e == hipSuccess) e = up(im.poly_start.get(), poly_start, n_polys ? ((size_t)n_polys + 1) * sizeof(int32_t) : 0);
+  if (e == hipSuccess) e = up(im.cell_start.get(), g.cell_start.data(), g.cell_start.size() * sizeof(int32_t));
+  if (e == hipSuccess) e = up(im.cell_poly.get(), g.cell_poly.data(), g.cell_poly.size() * sizeof(int32_t));
+  if (e == hipSuccess) e = hipStreamSynchronize(st);         // the host arrays are the caller's and this function's: done with them on return (once per town)
+  if (e != hipSuccess) { im.reset(); c->err = std::string("riftdm_load: ") + hipGetErrorString(e); return RIFT_ERR_HIP; }
+  g.aabb = {}; g.cell_start = {}; g.cell_poly = {};          // (the numbers stay: riftdm_info)
+  c->dmap.grid = std::move(g); c->dmap.loaded = true;
+  return RIFT_OK;
+}
+
+int riftdm_clear(RiftCtx* c) {
+  if (!c) return RIFT_ERR_ARG;
+  c->err.clear();
+  return drivable_map_release(c);
+}
+
+int riftdm_info(RiftCtx* c, RiftDrivableInfo* out) {
+  if (!c || !out) return RIFT_ERR_ARG;
+  c->err.clear();
+  if (!c->dmap.loaded) { c->err = "riftdm_info: no drivable-area map is loaded (riftdm_load)"; return RIFT_ERR_STATE; }
+  const DrivableGrid& g = c->dmap.grid;
+  memset(out, 0, sizeof(*out));
+  out->n_polys = g.n_polys; out->n_vertices = g.n_vertices; out->nx = g.nx; out->ny = g.ny; out->max_cell_list = g.max_list;
+  out->cell = g.cell; out->margin = g.margin; out->x0 = g.x0; out->y0 = g.y0; out->device_bytes = (int64_t)c->dmap.img.bytes();
+  return RIFT_OK;
+}
+
+// Every refusal of a call that reads the map, on the host and ahead of any launch; then the images as a kernel takes them, and the stream noted
+static int drivable_map_use(RiftCtx* c, const char* who, double resolution, void* stream, DrivableMapDev* m) {
+  if (!c->dmap.loaded) { c->err = std::string(who) + ": no drivable-area map is loaded (riftdm_load)"; return RIFT_ERR_STATE; }
+  const DrivableGrid& g = c->dmap.grid;
+  if (const char* why = drivable_res_refusal(g.margin, (double)(float)resolution)) { c->err = std::string(who) + ": " + why; return RIFT_ERR_ARG; }
+  const DrivableImages& im = c->dmap.img;
+  m->vertices = im.vertices.get(); m->aabb = im.aabb.get(); m->poly_start = im.poly_start.get(); m->cell_start = im.cell_start.get(); m->cell_poly = im.cell_poly.get();
+  m->x0 = g.x0; m->y0 = g.y0; m->cell = g.cell; m->margin = g.margin; m->nx = g.nx; m->ny = g.ny;
+  c->dmap.used = true; c->dmap.used_on = (hipStream_t)stream;
+  return RIFT_OK;
+}
+
+static int drivable_call(RiftCtx* c, const char* who, int H, int W, double ox, double oy, double heading, const RiftEvalParams* params, void* stream,
+                         DrivableMapDev* m, RasterPose* q) {
+  c->err.clear();
+  if (const char* why = rift_eval_params_refusal(params)) { c->err = std::string(who) + ": " + why; return RIFT_ERR_ARG; }
+  if (H <= 0 || W <= 0 || (long long)H * W > (1LL << 30)) { c->err = std::string(who) + ": H or W <= 0 (or H * W above 2^30)"; return RIFT_ERR_ARG; }
+  if (!std::isfinite(ox) || !std::isfinite(oy) || !std::isfinite(heading)) { c->err = std::string(who) + ": a pose that is not finite"; return RIFT_ERR_ARG; }
+  TRY(drivable_map_use(c, who, params->resolution, stream, m));
+  *q = RasterPose{ox, oy, std::cos(heading), std::sin(heading), (double)(float)params->resolution, (double)(float)(H / 2.0), (double)(float)(W / 2.0),
+                  drivable_inv_res((double)(float)params->resolution)};
+  return RIFT_OK;
+}
+
+int riftdm_off_road_matrix(RiftCtx* c, const float* rollout_center, int n_points, int H, int W, double ox, double oy, double heading,
+                             const RiftEvalParams* params, uint8_t* off_road, void* stream) {
+  if (!c) return RIFT_ERR_ARG;
+  if (n_points <= 0 || !rollout_center || !off_road) { c->err = "riftdm_off_road_matrix: n_points <= 0 or a null pointer"; return RIFT_ERR_ARG; }
+  DrivableMapDev m; RasterPose q;
+  TRY(drivable_call(c, "riftdm_off_road_matrix", H, W, ox, oy, heading, params, stream, &m, &q));
+  HIPCHK(c, hipSetDevice(c->device));
+  hipLaunchKernelGGL(off_road_map_kernel, dim3(cdiv(n_points, 256)), dim3(256), 0, (hipStream_t)stream, rollout_center, n_points, m, q, H, W, off_road);
+  HIPCHK(c, hipGetLastError());
+  return RIFT_OK;
+}
+
+int riftdm_raster(RiftCtx* c, int H, int W, double ox, double oy, double heading, const RiftEvalParams* params, uint8_t* mask, void* stream) {
+  if (!c) return RIFT_ERR_ARG;
+  if (!mask) { c->err = "riftdm_raster: mask == NULL"; return RIFT_ERR_ARG; }
+  DrivableMapDev m; RasterPose q;
+  TRY(drivable_call(c, "riftdm_raster", H, W, ox, oy, heading, params, stream, &m, &q));
+  HIPCHK(c, hipSetDevice(c->device));
+  hipLaunchKernelGGL(drivable_raster_kernel, dim3(cdiv((long long)H * W, 256)), dim3(256), 0, (hipStream_t)stream, m, q, H, W, mask);
+  HIPCHK(c, hipGetLastError());
+  return RIFT_OK;
+}
+
 // One rollout tick's group advantages (rift_hip.h).  Everything but the candidate rollouts is independent between the CBVs: one launch per
 // stage serves a chunk of up to RIFT_TICK_CHUNK of them (tick_multi.h) -- reference-line deviations and neighbour forecasts first, then the
 // rollouts CBV by CBV in list order (the shared PID state), then kinematics, flags, returns and z-scores: K + 7 launches instead of 9 K.
 // (own_offset: the pixel offset of a CBV comes from its own raster -- the _ex entry; else 200, 200 whatever the raster)
 static int group_advantage_tick(RiftCtx* c, const float* trajectory, int Rb, int Tfull, const RiftTickCBV* cbvs, int K,
                                 float* turn_buf, int32_t* turn_ptr, int32_t* turn_len, float* speed_buf, int32_t* speed_ptr, int32_t* speed_len,
-                                const RiftEvalParams& ev, bool own_offset, double* advantage, double* returns, double* terms, void* stream) {
+                                const RiftEvalParams& ev, bool own_offset, double* advantage, double* returns, double* terms, void* stream,
+                                bool use_map = false) {
   if (!c || !trajectory || !cbvs || K <= 0 || Rb <= 0 || Tfull < 80 || !advantage || !turn_buf || !turn_ptr || !turn_len || !speed_buf || !speed_ptr || !speed_len) return RIFT_ERR_ARG;
   c->err.clear();
-  HIPCHK(c, hipSetDevice(c->device));
   constexpr int M = 12, Ts = 40, TR = RIFT_RO_LEN;
   int Gmax = 0, Nmax = 0;
+  bool any_map = false;
   for (int k = 0; k < K; ++k) {
     const RiftTickCBV& v = cbvs[k];
     if (v.R <= 0 || v.R > Rb || v.batch_index < 0 || v.Pmax <= 0 || v.n_actors < 0 || !v.center_state || !v.ref_pos || !v.ref_angle || !v.ref_len ||
         (v.n_actors > 0 && !v.actors) || (v.off_road_mask && (v.H <= 0 || v.W <= 0))) { c->err = "rift_group_advantage_tick: bad entry"; return RIFT_ERR_ARG; }
+    if (use_map && !v.off_road_mask) {             // (the map entry: NULL mask and H, W > 0 -- from the map; H == W == 0 -- no flags)
+      if (v.H < 0 || v.W < 0 || (v.H == 0) != (v.W == 0)) { c->err = "riftdm_group_advantage_tick: H or W <= 0 where the map is asked for"; return RIFT_ERR_ARG; }
+      any_map = any_map || v.H > 0;
+    }
     Gmax = std::max(Gmax, v.R * M); Nmax = std::max(Nmax, v.n_actors);
   }
+  DrivableMapDev dmap; memset(&dmap, 0, sizeof(dmap));
+  if (any_map) TRY(drivable_map_use(c, "riftdm_group_advantage_tick", ev.resolution, stream, &dmap));
+  HIPCHK(c, hipSetDevice(c->device));
   // per-CBV scratch (bytes, 256-aligned pieces), one set per CBV of a chunk
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
@@ -509,8 +614,11 @@ static int group_advantage_tick(RiftCtx* c, const float* trajectory, int Rb, int
     a.res = (double)(float)ev.resolution;                       // resolution_hw is a float32 array in the reference (traj_evaluator.py:102)
     a.reward = reward_of(ev); a.reward_default = reward_is_default(a.reward) ? 1 : 0;
     int gmax = 0, nmax = 0;
+    bool chunk_map = false;
+    a.map = dmap; a.map_inv_res = drivable_inv_res(a.res);
     for (int j = 0; j < a.K; ++j) {
       const RiftTickCBV& v = cbvs[k0 + j];
+      chunk_map = chunk_map || (any_map && !v.off_road_mask && v.H > 0);
       char* S = c->tick_scratch.get() + per * (size_t)j;
       TickK& d = a.d[j];
       d.traj = trajectory + (size_t)v.batch_index * Rb * M * Tfull * 6; d.G = v.R * M; d.Tfull = Tfull; d.Pmax = v.Pmax; d.N = v.n_actors; d.H = v.H; d.W = v.W;
@@ -540,7 +648,8 @@ static int group_advantage_tick(RiftCtx* c, const float* trajectory, int Rb, int
     }
     hipLaunchKernelGGL(tick_multi_kernel<2>, dim3(cdiv(gmax * TR, 256), a.K), dim3(256), 0, st, a);
     hipLaunchKernelGGL(tick_multi_kernel<3>, dim3(cdiv(gmax * Ts, 256), a.K), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(tick_multi_kernel<4>, dim3(cdiv(gmax * TR, 256), a.K), dim3(256), 0, st, a);
+    if (chunk_map) hipLaunchKernelGGL(tick_multi_kernel<7>, dim3(cdiv(gmax * TR, 256), a.K), dim3(256), 0, st, a);      // (in place of stage 4: masks, the map and "no flags" in one launch)
+    else hipLaunchKernelGGL(tick_multi_kernel<4>, dim3(cdiv(gmax * TR, 256), a.K), dim3(256), 0, st, a);
     hipLaunchKernelGGL(tick_multi_kernel<5>, dim3(cdiv(gmax, 4), a.K), dim3(256), 0, st, a);
     hipLaunchKernelGGL(tick_multi_kernel<6>, dim3(1, a.K), dim3(256), 0, st, a);
     (void)gy;
@@ -566,6 +675,15 @@ int rift_group_advantage_tick_ex(RiftCtx* c, const float* trajectory, int Rb, in
   if (const char* why = rift_eval_params_refusal(params)) { c->err = std::string("rift_group_advantage_tick_ex: ") + why; return RIFT_ERR_ARG; }
   return group_advantage_tick(c, trajectory, Rb, Tfull, cbvs, K, turn_buf, turn_ptr, turn_len, speed_buf, speed_ptr, speed_len, *params, true,
                               advantage, returns, terms, stream);
+}
+
+int riftdm_group_advantage_tick(RiftCtx* c, const float* trajectory, int Rb, int Tfull, const RiftTickCBV* cbvs, int K,
+                                  float* turn_buf, int32_t* turn_ptr, int32_t* turn_len, float* speed_buf, int32_t* speed_ptr, int32_t* speed_len,
+                                  const RiftEvalParams* params, double* advantage, double* returns, double* terms, void* stream) {
+  if (!c) return RIFT_ERR_ARG;
+  if (const char* why = rift_eval_params_refusal(params)) { c->err = std::string("riftdm_group_advantage_tick: ") + why; return RIFT_ERR_ARG; }
+  return group_advantage_tick(c, trajectory, Rb, Tfull, cbvs, K, turn_buf, turn_ptr, turn_len, speed_buf, speed_ptr, speed_len, *params, true,
+                              advantage, returns, terms, stream, true);
 }
 
 // One rollout tick's decisions (rift_hip.h): every refusal is decided here, on the host, before anything is launched; then one wave per CBV
@@ -662,3 +780,30 @@ int rift_collate(RiftCtx* c, const RiftReplayArena* ar, const int32_t* scene_idx
 #define RIFT_SHARED_FN(name) static_assert(std::is_same<decltype(&::name), decltype(&rift::abi::name)>::value, #name);
 #include "abi_list.h"
 #undef RIFT_SHARED_FN
+
+// The drivable-area-map extension (include/rift_drivable.h): operand-format free, so its six exported symbols are defined here, once per
+// library, and forward to the entries above without a table; an entry whose signature drifts from its header does not compile.
+#define RIFT_DM_FN(name) static_assert(std::is_same<decltype(&::name), decltype(&rift::abi::name)>::value, #name);
+RIFT_DM_FN(riftdm_load) RIFT_DM_FN(riftdm_clear) RIFT_DM_FN(riftdm_info) RIFT_DM_FN(riftdm_off_road_matrix) RIFT_DM_FN(riftdm_raster)
+RIFT_DM_FN(riftdm_group_advantage_tick)
+#undef RIFT_DM_FN
+extern "C" {
+int riftdm_load(RiftCtx* ctx, const double* vertices, const int32_t* poly_start, int n_polys, double cell, double margin, void* stream) {
+  return rift::abi::riftdm_load(ctx, vertices, poly_start, n_polys, cell, margin, stream);
+}
+int riftdm_clear(RiftCtx* ctx) { return rift::abi::riftdm_clear(ctx); }
+int riftdm_info(RiftCtx* ctx, RiftDrivableInfo* out) { return rift::abi::riftdm_info(ctx, out); }
+int riftdm_off_road_matrix(RiftCtx* ctx, const float* rollout_center, int n_points, int H, int W, double ox, double oy, double heading,
+                           const RiftEvalParams* params, uint8_t* off_road, void* stream) {
+  return rift::abi::riftdm_off_road_matrix(ctx, rollout_center, n_points, H, W, ox, oy, heading, params, off_road, stream);
+}
+int riftdm_raster(RiftCtx* ctx, int H, int W, double ox, double oy, double heading, const RiftEvalParams* params, uint8_t* mask, void* stream) {
+  return rift::abi::riftdm_raster(ctx, H, W, ox, oy, heading, params, mask, stream);
+}
+int riftdm_group_advantage_tick(RiftCtx* ctx, const float* trajectory, int Rb, int Tfull, const RiftTickCBV* cbvs, int K,
+                                float* turn_buf, int32_t* turn_ptr, int32_t* turn_len, float* speed_buf, int32_t* speed_ptr, int32_t* speed_len,
+                                const RiftEvalParams* params, double* advantage, double* returns, double* terms, void* stream) {
+  return rift::abi::riftdm_group_advantage_tick(ctx, trajectory, Rb, Tfull, cbvs, K, turn_buf, turn_ptr, turn_len, speed_buf, speed_ptr, speed_len,
+                                                params, advantage, returns, terms, stream);
+}
+}  // extern "C"

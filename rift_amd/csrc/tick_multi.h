@@ -5,6 +5,7 @@
 // never-reset controller).  The bodies are the single-CBV kernels' (adv.h, rollout.h), unchanged: same arithmetic, same results.
 #pragma once
 #include "adv.h"
+#include "drivable_map.h"
 #include "rollout.h"
 
 namespace rift {
@@ -26,6 +27,7 @@ struct TickK {                                   // one CBV: inputs and its own 
 struct TickArr {                                 // the evaluator's settings are those of RiftEvalParams (the old entry: the reference's defaults)
   TickK d[RIFT_TICK_CHUNK]; int K, near_lane_change; double gamma, inflation, res;
   RewardP reward; int reward_default;            // reward_default: the weights are the reference's defaults -> the instance that folds them (adv.h)
+  DrivableMapDev map; double map_inv_res;        // LAST (the stages before them keep their argument offsets): read by stage 7 only; a CBV uses the map when mask == NULL and H > 0
 };
 static_assert(sizeof(TickArr) <= 4096, "TickArr travels as a kernel argument");
 
@@ -38,6 +40,7 @@ __device__ __forceinline__ void tick_return(const TickK& d, double gamma, const 
 
 // STAGE 0: reference-line deviations (block 128)   1: neighbour forecast (block 64)   2: kinematics + corners (block 256)
 //       3: collision flags (256)   4: off-road flags (256)   5: returns (256)   6: z-score (256)
+//       7: off-road flags of a chunk with CBVs that use the drivable-area map (256): launched IN PLACE of stage 4 (riftdm_group_advantage_tick)
 template <int STAGE>
 __global__ void tick_multi_kernel(const TickArr a) {
   if ((int)blockIdx.y >= a.K) return;
@@ -49,6 +52,11 @@ __global__ void tick_multi_kernel(const TickArr a) {
   if (STAGE == 3) collision_matrix_body(d.ro.vertices, d.G, TR, d.ov, d.N, Ts, d.col);          // (no neighbours: the loop over them is empty, every flag 0)
   if (STAGE == 4) {
     if (d.mask) off_road_body(d.ro.center, d.G * TR, d.mask, d.H, d.W, d.ox, d.oy, d.ch, d.sh, a.res, -a.res, d.off_x, d.off_y, d.offr);
+    else { const int i = blockIdx.x * 256 + threadIdx.x; if (i < d.G * TR) d.offr[i] = 0; }
+  }
+  if (STAGE == 7) {
+    if (d.mask) off_road_body(d.ro.center, d.G * TR, d.mask, d.H, d.W, d.ox, d.oy, d.ch, d.sh, a.res, -a.res, d.off_x, d.off_y, d.offr);
+    else if (d.H > 0) off_road_map_body(d.ro.center, d.G * TR, a.map, RasterPose{d.ox, d.oy, d.ch, d.sh, a.res, d.off_x, d.off_y, a.map_inv_res}, d.H, d.W, d.offr);
     else { const int i = blockIdx.x * 256 + threadIdx.x; if (i < d.G * TR) d.offr[i] = 0; }
   }
   if (STAGE == 5) {                                // (wave-uniform branches: nothing of the breakdown runs without `terms`)

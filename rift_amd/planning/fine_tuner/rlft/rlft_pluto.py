@@ -461,7 +461,8 @@ class _GroupRelativePluto(RLFTPluto):
     """Shared rollout side of RIFT and GRPO (rift_pluto.py:74-161): in train mode every tick also yields, per CBV, the raw logits of
     its valid reference lines (the "old policy" of the coming update) and the group-relative advantage of all R x 12 candidates."""
     EXTRA_COLUMNS = ('CBVs_actions_old_group_logits', 'CBVs_group_advantage')
-    TRAJ_EVAL_KEYS = ('gamma', 'reward_model', 'reward_params', 'bbox_inflation_ratio', 'resolution', 'near_lane_change', 'breakdown')
+    TRAJ_EVAL_KEYS = ('gamma', 'reward_model', 'reward_params', 'bbox_inflation_ratio', 'resolution', 'near_lane_change', 'breakdown',
+                      'off_road', 'raster_size', 'map_cell', 'map_margin')      # the last three are read with 'off_road': 'map' only
     OBJECTIVE_KEYS = ('clip_low', 'clip_high', 'dual_clip', 'kl_beta', 'entropy_coef')      # the fields of RiftObjectiveParams
     GROUP_OBJECTIVE = True
 
@@ -512,6 +513,15 @@ class _GroupRelativePluto(RLFTPluto):
               'bbox_inflation_ratio': float(section.get('bbox_inflation_ratio', 1.1)), 'resolution': float(section.get('resolution', 0.5)),
               'near_lane_change': bool(section.get('near_lane_change', True)), 'breakdown': bool(section.get('breakdown', False))}
         ev['params'] = _ffi.eval_params(ev['reward_model'], ev['gamma'], ev['bbox_inflation_ratio'], ev['resolution'], ev['near_lane_change'])
+        # 'off_road': 'raster' (the source draws a mask per CBV and tick: the call made without the key) | 'map' (the town's drivable polygons
+        # on the device, loaded when the source's key changes; the source sends poses)
+        ev['off_road'] = section.get('off_road', 'raster')
+        if ev['off_road'] not in ('raster', 'map'):
+            raise ValueError(f"config['traj_eval']['off_road'] = {ev['off_road']!r}; known: ['map', 'raster']")
+        if ev['off_road'] == 'map':
+            H, W = section.get('raster_size', (400, 400))
+            ev['raster_size'] = (int(H), int(W))
+            ev['map_cell'], ev['map_margin'] = float(section.get('map_cell', 16.0)), float(section.get('map_margin', 1.0))
         return ev
 
     @property
@@ -524,6 +534,21 @@ class _GroupRelativePluto(RLFTPluto):
         if eng is not None and self._traj_evaluator.engine is not eng:      # the model re-bound (precision / device change): the PID state is torch's, it carries over
             self._traj_evaluator.engine = eng
         return self._traj_evaluator
+
+    def _load_drivable_map(self, src, env_id):
+        """'off_road': 'map' -- the town's drivable polygons go to the device when the source's key changes (or the engine did): once per
+        town, not per tick."""
+        area_of = getattr(src, "drivable_area", None)
+        area = area_of(env_id) if area_of is not None else None
+        if area is None:
+            raise RuntimeError(f"{type(src).__name__}.drivable_area returned None (or is missing): config['traj_eval']['off_road'] = 'map' needs "
+                               "(key, polygons) of the environment's town")
+        key, polygons = area
+        eng = self.traj_evaluator.engine
+        if getattr(self, "_drivable_loaded", None) != (id(eng), key):
+            self.drivable_map_info = eng.load_drivable_map(polygons, cell=self._eval['map_cell'], margin=self._eval['map_margin'])
+            self._drivable_loaded = (id(eng), key)
+            self.drivable_map_loads = getattr(self, "drivable_map_loads", 0) + 1
 
     def _get_action(self, CBVs_obs_list, infos, deterministic=False):
         self._tick_reads, self._breakdown_reads = [], []       # (a tick that raised half-way must not leave its read-backs to the next one)
@@ -547,6 +572,9 @@ class _GroupRelativePluto(RLFTPluto):
                 self._host(out, key)
         src = self.state_source
         pending = []
+        use_map = self._eval is not None and self._eval['off_road'] == 'map'
+        if use_map:
+            self._load_drivable_map(src, env_id)
         for index, (cbv_id, obs) in enumerate(CBVs_obs.items()):
             # the CBV's reference lines come from its own observation (host memory: the rows the collated batch was built from), so the
             # ragged valid points of every valid line are cut on the host -- the device-side boolean indexing of the collated batch was a
@@ -556,7 +584,13 @@ class _GroupRelativePluto(RLFTPluto):
             keep = valid.any(-1)
             pos, ang = np.asarray(rl["position"]), np.asarray(rl["orientation"])
             lines = np.nonzero(keep)[0]
-            raster = src.off_road_raster(env_id, cbv_id)
+            if use_map:                          # no raster is drawn: the CBV's pose goes up instead of its mask
+                pose_of = getattr(src, "off_road_pose", None)
+                if pose_of is None:
+                    raise RuntimeError(f"{type(src).__name__} has no off_road_pose(env_id, cbv_id): config['traj_eval']['off_road'] = 'map' needs it")
+                raster, map_pose = NoFlagSource.ALL_CLEAR, tuple(float(x) for x in pose_of(env_id, cbv_id))
+            else:
+                raster, map_pose = src.off_road_raster(env_id, cbv_id), None
             actors = src.nearby_actor_states(env_id, cbv_id)
             # (a source without these inputs raises NotImplementedError: the reference's advantage always carries both penalties; zeros
             # only when the source says so explicitly or, for collisions, when the CBV has no neighbours right now)
@@ -568,7 +602,8 @@ class _GroupRelativePluto(RLFTPluto):
                 "batch_index": index, "center_state": states[cbv_id].rollout_tuple(), "lines": lines,
                 "ref_pos": [pos[r][valid[r]] for r in lines], "ref_angle": [ang[r][valid[r]] for r in lines],     # ragged: only the valid points of each valid line
                 "actors": None if (actors is None or actors is NoFlagSource.ALL_CLEAR) else actors,
-                "off_road": None if raster is NoFlagSource.ALL_CLEAR else raster, "column": column})
+                "off_road": None if raster is NoFlagSource.ALL_CLEAR else raster, "column": column,
+                "raster": self._eval['raster_size'] if use_map else None, "pose": map_pose})
         ev = self.traj_evaluator
         prefix = all(len(v["lines"]) and int(v["lines"][-1]) == len(v["lines"]) - 1 for v in pending)
         cfg = self._eval
@@ -589,7 +624,9 @@ class _GroupRelativePluto(RLFTPluto):
         for cbv_id, v in zip(CBVs_obs.keys(), pending):
             kw = {} if cfg is None else {"near_lane_change": cfg['near_lane_change'], "return_terms": breakdown}
             G = len(v["lines"]) * 12
-            if v["off_road"] is None:
+            if use_map:
+                kw["drivable_map"], kw["center_pose"], kw["raster_size"] = True, v["pose"], v["raster"]
+            elif v["off_road"] is None:
                 kw["off_road_matrix"] = np.zeros((G, 80), dtype=np.bool_)
             else:
                 kw["off_road_mask"], kw["center_pose"] = v["off_road"]

@@ -36,7 +36,7 @@ class TrajEvaluator:
     def get_grpo_advantage(self, center_state, trajectories: torch.Tensor, ref_line_pos: List[torch.Tensor],
                            ref_line_angle: List[torch.Tensor], collision_matrix=None, off_road_matrix=None, gamma: Optional[float] = None,
                            other_vehicle_vertices=None, off_road_mask=None, center_pose=None, nearby_actor_states=None, to_host: bool = True,
-                           near_lane_change: bool = True, return_terms: bool = False):
+                           near_lane_change: bool = True, return_terms: bool = False, drivable_map: bool = False, raster_size=None):
         """center_state: (x, y, heading, speed, width, length) of the CBV rear axle / footprint.
         trajectories: (R, M, 80, 6) raw model output of the valid reference lines.
         collision_matrix (G, >=40) / off_road_matrix (G, >=40): bool flags per candidate and frame, OR
@@ -44,7 +44,9 @@ class TrajEvaluator:
         centre, get_off_road_matrix's origin / angle) to have them computed on the device from this call's rollout; OR, instead of
         other_vehicle_vertices, nearby_actor_states = dict(steer, throttle, brake, speed, location (N,3), yaw_deg, extent (N,2)) read
         off the CARLA actors, forecast on the device (get_other_vehicle_rollout, with near_lane_change and the constructor's
-        bbox_inflation_ratio).  gamma None: the constructor's.  return_terms: also "returns" (R, M) and "terms" (R, M, 8), the seven
+        bbox_inflation_ratio).  drivable_map=True with center_pose (and raster_size (H, W); None: the constructor's map_height, map_width):
+        the off-road matrix comes from the engine's loaded drivable-area map (Engine.load_drivable_map) -- no mask is drawn or uploaded.
+        gamma None: the constructor's.  return_terms: also "returns" (R, M) and "terms" (R, M, 8), the seven
         discounted reward-term sums and the steps counted of every candidate."""
         eng = self.engine
         gamma = self.gamma if gamma is None else gamma
@@ -62,6 +64,11 @@ class TrajEvaluator:
             if other_vehicle_vertices is None:
                 raise ValueError("pass collision_matrix, other_vehicle_vertices or nearby_actor_states")
             collision_matrix = eng.collision_matrix(ro["vertices"], other_vehicle_vertices, Ts=T)
+        if off_road_matrix is None and drivable_map:
+            if center_pose is None:
+                raise ValueError("drivable_map=True needs center_pose")
+            size = (self.map_height, self.map_width) if raster_size is None else tuple(raster_size)
+            off_road_matrix = eng.off_road_matrix_map(ro["center"], center_pose, size, eng.eval_params(resolution=self.resolution))
         if off_road_matrix is None:
             if off_road_mask is None or center_pose is None:
                 raise ValueError("pass off_road_matrix or off_road_mask + center_pose")

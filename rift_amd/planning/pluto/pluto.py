@@ -70,6 +70,18 @@ class CBVStateSource:
         raise NotImplementedError(f"{type(self).__name__}.off_road_raster: the group advantage needs the drivable-area raster "
                                   "(traj_evaluator.py:273-322); return NoFlagSource.ALL_CLEAR to evaluate without an off-road term on purpose")
 
+    # The two below are read only with config['traj_eval'] = {'off_road': 'map'}: the off-road flags come from the town's drivable polygons,
+    # loaded on the device once, and no raster is drawn or uploaded (include/rift_drivable.h: riftdm_load states the rule).
+    def drivable_area(self, env_id):
+        """(key, polygons) or None: the drivable polygons of the environment's town -- a list of (n, 2) float64 vertex arrays in the global
+        frame -- and a hashable key that changes when they do (the town's name): the policy loads the map when the key changes."""
+        return None
+
+    def off_road_pose(self, env_id, cbv_id):
+        """(x, y, heading) of the CBV's footprint centre: get_off_road_matrix's origin / angle (traj_evaluator.py:279-280)."""
+        raise NotImplementedError(f"{type(self).__name__}.off_road_pose: config['traj_eval']['off_road'] = 'map' needs the pose of the CBV's "
+                                  "footprint centre (traj_evaluator.py:279-280)")
+
 
 def raster_drivable_area(polygons_xy, origin_xy, heading, map_height=400, map_width=400, resolution=0.5, fill_polygon=None):
     """The reference's drivable-area raster (traj_evaluator.py:273-292,324-331): ones = off road, every drivable polygon filled with 0 after
@@ -136,6 +148,19 @@ class CarlaStateSource(CBVStateSource):
         mask = raster_drivable_area(polys, origin, heading, self.map_height, self.map_width, self.resolution,
                                     fill_polygon=lambda m, v, val: cv2.fillPoly(m, [v], val))
         return mask, (float(origin[0]), float(origin[1]), heading)
+
+    def drivable_area(self, env_id):                                                    # pragma: no cover - needs CARLA
+        api = self._cdp.get_map_api()
+        key = id(api)                                                                   # one CarlaMap object per town (nuplan_map_utils.py:42-66)
+        if getattr(self, "_area", (None, None))[0] != key:                              # the town's polygons are static: read once per town
+            frames = (api.lane_gdf, api.lane_connector_gdf)                             # the tables behind LANE and LANE_CONNECTOR (DRIVABLE_LAYERS)
+            polys = [np.stack(p.exterior.coords.xy, axis=1) for gdf in frames for p in gdf["polygon"] if p is not None]
+            self._area = (key, polys, api)                                              # (api kept: its id stays this town's)
+        return self._area[:2]
+
+    def off_road_pose(self, env_id, cbv_id):                                            # pragma: no cover - needs CARLA
+        st = self._agent_state(cbv_id)
+        return float(st.center.array[0]), float(st.center.array[1]), float(st.center.heading)
 
 
 class CBVBasePolicy:   # rift/cbv/planning/base_policy.py:9-52
@@ -244,6 +269,9 @@ class PLUTO(CBVBasePolicy):
     def __init__(self, config, logger):
         if config.get('objective') is not None and not self.GROUP_OBJECTIVE:
             raise ValueError(f"config['objective'] sets the RIFT / GRPO group objective (rift_pluto, grpo_pluto); {self.name} has no such settings")
+        if 'off_road' in (config.get('traj_eval') or {}) and not self.GROUP_OBJECTIVE:
+            raise ValueError(f"config['traj_eval']['off_road'] selects the off-road source of the group advantage (rift_pluto, grpo_pluto); "
+                             f"{self.name} evaluates no group advantage")
         super().__init__(config, logger)
         self.logger = logger
         self.radius = config.get('obs', {}).get('radius', config.get('radius', 120))

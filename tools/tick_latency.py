@@ -5,7 +5,10 @@ lines): host wall time per tick (the caller waits for the controls), median / p9
     python tools/tick_latency.py [--ticks 60] [--cbvs 1,2,4,8] [--profile rift_pluto/4] [--device-control] [--traj-eval '{"breakdown": true}']
 --traj-eval: the policies' config['traj_eval'] section as JSON (reward model and evaluator settings at run time, the per-term breakdown).
 --device-control: the A/B of config['device_control'] (candidate choice + waypoint PID in one device call, rift_control_tick) in ONE process:
-the host leg, the device leg, the host leg again (its run-to-run spread is the yardstick of the difference)."""
+the host leg, the device leg, the host leg again (its run-to-run spread is the yardstick of the difference).
+--drivable-map: the A/B of config['traj_eval']['off_road'] on rift_pluto in train mode, in ONE process: the raster leg (a mask per CBV goes up
+every tick), the map leg (a seeded town of --map-polygons lane polygons on the device, poses go up), the raster leg again; then the one-time
+cost of loading that map.  The raster leg's mask is drawn once, ahead of the ticks: the host draw the map removes is in neither leg."""
 import argparse, json, os, sys, tempfile, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -23,7 +26,23 @@ def _actors(seed, N=4):
             "yaw_deg": g.uniform(-180, 180, N), "extent": np.stack([g.uniform(1.8, 2.6, N), g.uniform(0.8, 1.1, N)], -1)}
 
 
-def _source():
+def _lane_polygons(seed, n, span):
+    """A seeded town: n lane polygons of 20 - 60 m (left boundary forward, right boundary back, every third ring closed by its first vertex)
+    at random places and headings in a span x span square around the CBVs."""
+    g = np.random.default_rng(seed)
+    out = []
+    for k in range(n):
+        start = np.array([10.0, -5.0]) + g.uniform(-span / 2, span / 2, 2)
+        m = int(g.uniform(20.0, 60.0) / 2.0) + 1
+        h = g.uniform(-np.pi, np.pi) + g.choice([0.0, 0.0, 0.02, -0.03]) * 2.0 * np.arange(m)
+        pts = start + np.concatenate([np.zeros((1, 2)), np.cumsum(np.stack([np.cos(h[:-1]), np.sin(h[:-1])], -1) * 2.0, 0)], 0)
+        nrm = np.stack([-np.sin(h), np.cos(h)], -1) * (g.choice([3.0, 3.5, 7.0]) / 2)
+        ring = np.concatenate([pts + nrm, (pts - nrm)[::-1]], 0)
+        out.append(np.concatenate([ring, ring[:1]], 0) if k % 3 == 0 else ring)
+    return out
+
+
+def _source(polygons=None):
     from rift_amd.planning.pluto.pluto import CBVStateSource, CenterState
 
     class Recorded(CBVStateSource):
@@ -37,6 +56,12 @@ def _source():
             mask = np.ones((400, 400), dtype=np.uint8)
             mask[150:250, :300] = 0
             return mask, (10.0 + cbv_id, -5.0, 0.3)
+
+        def drivable_area(self, env_id):
+            return None if polygons is None else ("seeded", polygons)
+
+        def off_road_pose(self, env_id, cbv_id):
+            return 10.0 + cbv_id, -5.0, 0.3
     return Recorded()
 
 
@@ -50,7 +75,7 @@ def _ticks(n, ids):
 
 
 def run(ticks=40, cbvs=(1, 8), precision="fp16", policies=(("pluto", "eval"), ("rift_pluto", "train")), profile="", verbose=False,
-        device_control=False, traj_eval=None):
+        device_control=False, traj_eval=None, polygons=None):
     """{"<policy>/<mode>/K=<k>": {"median_ms", "p90_ms", "min_ms"}}"""
     from rift_amd.planning import CBV_POLICY_LIST
     from rift_amd.planning.pluto.model.pluto_model import PlanningModel
@@ -61,7 +86,7 @@ def run(ticks=40, cbvs=(1, 8), precision="fp16", policies=(("pluto", "eval"), ("
         for name, mode in policies:
             if profile and profile.split("/")[0] != name:
                 continue
-            cfg = {'num_scenario': 1, 'ROOT_DIR': tmp, 'model_path': 'ckpt', 'device': 'cuda:0', 'state_source': _source(),
+            cfg = {'num_scenario': 1, 'ROOT_DIR': tmp, 'model_path': 'ckpt', 'device': 'cuda:0', 'state_source': _source(polygons),
                    'compute_precision': precision, 'device_control': bool(device_control)}
             if traj_eval is not None:
                 cfg['traj_eval'] = traj_eval
@@ -106,8 +131,30 @@ def main():
     ap.add_argument("--device-control", action="store_true", help="A/B of config['device_control']: host, device, host again, in this process")
     ap.add_argument("--traj-eval", default="", help="config['traj_eval'] as JSON, e.g. '{\"breakdown\": true}'")
     ap.add_argument("--policies", default="", help="comma-separated subset of pluto,rift_pluto")
+    ap.add_argument("--drivable-map", action="store_true", help="A/B of config['traj_eval']['off_road']: raster, map, raster again, in this process")
+    ap.add_argument("--map-seed", type=int, default=1)
+    ap.add_argument("--map-polygons", type=int, default=5000, help="lane polygons of the seeded town (--drivable-map)")
+    ap.add_argument("--map-span", type=float, default=1500.0, help="side of the town's square in metres (--drivable-map)")
     args = ap.parse_args()
     traj_eval = json.loads(args.traj_eval) if args.traj_eval else None
+    if args.drivable_map:
+        polygons = _lane_polygons(args.map_seed, args.map_polygons, args.map_span)
+        legs = {}
+        for leg, how in (("raster", "raster"), ("map", "map"), ("raster_again", "raster")):
+            print(f"-- {leg} leg (off_road={how})", flush=True)
+            legs[leg] = run(args.ticks, [int(k) for k in args.cbvs.split(",")], args.precision, policies=(("rift_pluto", "train"),), verbose=True,
+                            traj_eval=dict(traj_eval or {}, off_road=how), polygons=polygons)
+        from rift_amd import _ffi
+        eng = _ffi.Engine("cuda:0")
+        loads = []
+        for _ in range(5):                         # (the call returns when the upload is complete)
+            t0 = time.perf_counter()
+            info = eng.load_drivable_map(polygons)
+            loads.append((time.perf_counter() - t0) * 1e3)
+        eng.close()
+        legs["map_load"] = {"ms": [round(x, 3) for x in loads], "info": info}
+        print(json.dumps(legs))
+        return
     if args.device_control:
         legs = {}
         for leg, on in (("host", False), ("device", True), ("host_again", False)):

@@ -10,10 +10,9 @@ the replay columns the update consumes: old log-prob + chosen (r, m) (PPO / REIN
 group-relative advantage of every candidate (RIFT / GRPO; TrajEvaluator on the device).  Live CARLA state comes through the injected
 state source (rift_amd.planning.pluto.pluto.CBVStateSource).
 """
-import contextlib
 import math
-import os
 import re
+import threading
 import time
 from pathlib import Path
 from typing import Any, Dict, List, Optional
@@ -57,20 +56,193 @@ def buffer_to_scenes(buffer: CBVRolloutBuffer) -> List[Dict]:
         if has('CBVs_actions_ref_group_logits'):
             ex["ref_group_logits"] = torch.as_tensor(np.asarray(buffer.buffer_data['CBVs_actions_ref_group_logits'][i]['logits']),
                                                      dtype=torch.float32)
-        R = pf.data["reference_line"]["position"].shape[0]
-        ex.setdefault("group_advantage", torch.zeros(R, 12, dtype=torch.float64))
-        ex.setdefault("group_advantage_mask", torch.ones(R, 12, dtype=torch.bool))
-        ex.setdefault("old_group_logits", torch.zeros(R, 12))
-        ex.setdefault("old_group_logits_mask", torch.ones(R, 12, dtype=torch.bool))
+        for k, v in replay_dummy_extras(pf.data).items():
+            ex.setdefault(k, v)
         scenes.append({"feature": pf.data, "extras": ex})
     return scenes
 
 
+def draw_passes(n: int, e_i, cfg) -> List[torch.Tensor]:
+    """The scene order of every pass over an n-scene replay: one per epoch, drawn up front (the same generator sequence as a draw per epoch:
+    validation draws nothing), then the validation indices.  Seeded by the episode alone: the same split and order on every rank."""
+    g = torch.Generator().manual_seed(int(e_i) + 1234)
+    perm = torch.randperm(n, generator=g)                      # random_split(dataset, [0.9, 0.1]), rift_datamodule.py:93
+    n_train = int(math.floor(n * cfg["train_ratio"]))
+    train_idx, val_idx = perm[:n_train], perm[n_train:]
+    passes = [train_idx[torch.randperm(n_train, generator=g)] if cfg["shuffle"] else train_idx for _ in range(cfg["epochs"])]
+    return passes + [val_idx]
+
+
+def minibatch_shards(count: int, bs: int, rank: int, world: int):
+    """(start, m, lo, hi) of every kept minibatch of a `count`-scene pass: scenes [start, start + m), of which [lo, hi) are this rank's."""
+    for s in range(0, count, bs):
+        m = min(bs, count - s)
+        if m < world:       # a tail with fewer scenes than ranks cannot give every rank a scene (each one has to join the
+            continue        # exchanges of the forward): dropped on ALL ranks alike -- at most world - 1 scenes per pass
+        yield (s, m) + (split_minibatch(m, rank, world) if world > 1 else (0, m))
+
+
+def check_batch_covers_ranks(train_batch_size: int, world: int):
+    """With a batch size below the rank count `minibatch_shards` drops EVERY minibatch of every pass: the update would train zero steps,
+    report a loss of 0 and write a checkpoint of untouched weights."""
+    if world > 1 and train_batch_size < world:
+        raise ValueError(f"train_batch_size = {train_batch_size} is smaller than the {world} data-parallel ranks: every rank needs a scene of every minibatch")
+
+
+class _Minibatches:
+    """An update's passes on the device (ONE upload; the reference-line count of a minibatch comes off the host copy) and the step a minibatch takes."""
+
+    def __init__(self, trainer: RLFTTrainer, replay: DeviceReplay, extras: Dict[str, torch.Tensor], passes: List[torch.Tensor], bs: int, device):
+        self.trainer, self.replay, self.extras, self.passes, self.bs = trainer, replay, extras, passes, bs
+        self.passes_dev = torch.cat(passes).to(torch.int32).to(device).split([p_.numel() for p_ in passes])      # (views of the one upload)
+        self.up = torch.cuda.Event()          # the upload is queued on this stream; the prefetch stream's gathers wait for it
+        self.up.record()
+
+    def of(self, which: int, bs: int):
+        """(device index slice of this rank, R of the whole minibatch, shard descriptor, upload event) per kept minibatch of pass `which`."""
+        idx, idx_dev = self.passes[which], self.passes_dev[which]
+        r_all = self.replay.r_count_cpu[idx]
+        world = self.trainer.world
+        for s, m, lo, hi in minibatch_shards(idx.numel(), bs, self.trainer.rank, world):
+            yield idx_dev[s + lo:s + hi], int(r_all[s:s + m].max()), ((lo, m) if world > 1 else None), self.up
+
+    def run(self, batch, train: bool, out=None):
+        idx_dev, R_out, shard, up = batch
+        trainer = self.trainer
+        # training steps cycle through _ffi.DEFER_SLOTS batch-buffer sets: the tail of step k (policy head .. AdamW) runs beside the trunk of step
+        # k + 1, whose batch is gathered on the prefetch stream (RLFTTrainer.gather); so is the batch of a validation through the step pipeline
+        # (`out`: RLFTTrainer.validation_step); any other validation joins the update stream first and uses slot 0
+        if train or out is not None:
+            fb, b = trainer.gather(self.replay, idx_dev, R_out, ready=up)
+        else:
+            fb, b = self.replay.collate(trainer.engine, idx_dev, R_out, slot=0)
+        if self.extras:
+            b = dict(b)
+            for k, v in self.extras.items():
+                b[k] = v[idx_dev.long()].contiguous()
+        return trainer.training_step(fb, b, shard=shard) if train else trainer.validation_step(fb, b, shard=shard, out=out)
+
+    def train_epoch(self, epoch: int):
+        for mb in self.of(epoch, self.bs):
+            self.run(mb, True)
+
+
+class _BufferCommit:
+    """The update's one commit point for the rollout buffer.  `reset_early()` empties it reversibly (the rows move into a token) while the outcome
+    is open; an exception anywhere inside the `with` block -- a non-finite flag at the host read, a checkpoint that cannot be written -- puts
+    the rows back, once: the generation's rollout data survives a failed update, as in the reference, whose reset follows the fit.  Leaving
+    the block without one commits: a helper thread drops the token (the 9 ms of freeing 4096 rows) off the critical path, the main thread
+    goes on to the reload.  `finish()` resets a buffer that was not reset early."""
+
+    def __init__(self, buffer: CBVRolloutBuffer):
+        self.buffer, self.box, self.taken = buffer, [], False      # (the box holds the only reference to the token: clearing it frees the rows)
+
+    def reset_early(self, trunk):       # (`trunk`: the training model's _trunk_version, read in the same shadow of the device: kept for the update's end)
+        self.box.append(self.buffer.reset_buffer_reversibly())
+        self.taken, self.trunk = True, trunk
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if self.box and exc_type is not None:
+            self.buffer.restore(self.box.pop())
+        elif self.box:
+            threading.Thread(target=self.box.clear, daemon=True).start()
+
+    def finish(self):
+        if not self.taken:
+            self.buffer.reset_buffer()
+
+
+def _deferred_top1(policy: "RLFTPluto", steps: _Minibatches, e_i, base_cpu, commit: _BufferCommit):
+    """The epochs without the host.  Lightning reads the epoch's losses on the host and decides top-1 there (training_builder.py:131-140):
+    two host reads per epoch, each draining the step pipeline (16 x ~1.7 ms of an update).  Single process, no file per improvement: nothing of an
+    epoch comes back to the host -- its mean training loss and validation loss go into a device table, the tensors that move (pi_head,
+    BatchNorm statistics: `moving`) are copied into that epoch's snapshot on the stream, and the whole table is read ONCE behind the last
+    epoch; top-1 = the FIRST epoch with the minimal validation loss, exactly what the strict `<` of the per-epoch decision selects, and
+    the checkpoint is written from that epoch's snapshot.  The non-finite flag is sticky and checked at that one read."""
+    cfg, model, trainer, dev = policy.cfg, policy.train_model, steps.trainer, policy.device
+    moving = policy._moving_keys(model)
+    own = model.state_dict()
+    src = [own[k] for k in moving]
+    snaps, lrs = [], []
+    table = torch.zeros(cfg["epochs"], 2, dtype=torch.float64, device=dev)
+    # validation through the step pipeline: the epoch's validation trunks follow its last training trunk on this stream without
+    # waiting for that step's update, their heads / objectives and the epoch's bookkeeping (mean losses, the snapshot of the trained
+    # parameters) sit on the update stream between the tails -- this stream never waits for the update stream inside an update.
+    # BatchNorm statistics are written by the training trunks on THIS stream: their snapshot stays here
+    piped = trainer.pipelined_validation
+    val_mbs = list(steps.of(cfg["epochs"], cfg["val_batch_size"]))
+    vtab = torch.zeros(cfg["epochs"], max(len(val_mbs), 1), dtype=torch.float64, device=dev)
+    tp = {n for n, p_ in model.named_parameters() if p_.requires_grad}      # (state_dict() tensors are detached: ask the parameters)
+    trained = [i for i, k in enumerate(moving) if k in tp]           # written by AdamW on the update stream
+    buffers = [i for i, k in enumerate(moving) if k not in tp]       # BatchNorm running statistics, written by the training trunks
+    for epoch in range(cfg["epochs"]):
+        snaps.append([torch.empty_like(t) for t in src])   # (per epoch, behind the steps issued so far: 0.4 ms of host time each, hidden)
+        steps.train_epoch(epoch)
+        if piped:
+            for j, mb in enumerate(val_mbs):
+                steps.run(mb, False, out=vtab[epoch, j:j + 1])
+            with trainer.update_stream():
+                trainer.pop_mean_loss_async(table[epoch, 0], in_update_stream=True)
+                table[epoch, 1].copy_(vtab[epoch].mean() if val_mbs else table[epoch, 0])
+                if trained:
+                    torch._foreach_copy_([snaps[epoch][i] for i in trained], [src[i] for i in trained])
+            if buffers:
+                torch._foreach_copy_([snaps[epoch][i] for i in buffers], [src[i] for i in buffers])
+        else:
+            trainer.pop_mean_loss_async(table[epoch, 0])
+            vl = [steps.run(mb, False).clone() for mb in val_mbs]
+            table[epoch, 1].copy_(torch.stack(vl).mean() if vl else table[epoch, 0])
+            torch._foreach_copy_(snaps[epoch], src)      # (behind the validation steps on this stream; the next epoch's updates are ordered behind it)
+        trainer.on_epoch_end()
+        lrs.append(trainer.optimizer.param_groups[0]["lr"])
+    trainer.wait_update()                                  # (the table and the snapshots of the trained parameters come off the update stream)
+    # the host is ~100 ms ahead of the device here: what the end of the update needs from the host and does not depend on the
+    # outcome happens now, in the device's shadow -- the frozen trunk's identity (nothing queued writes it) and the buffer reset
+    # (4096 committed rows to free, 9 ms; the arena was uploaded from the pinned mirror before the first epoch; reversibly: _BufferCommit)
+    commit.reset_early(policy._trunk_version(model))
+    host = table.cpu()                                     # the update's one host read
+    trainer.check_finite()
+    history = [{"epoch": e, "train_loss": float(host[e, 0]), "val_loss": float(host[e, 1]), "lr": lr} for e, lr in enumerate(lrs)]
+    best_epoch = min(range(cfg["epochs"]), key=lambda e: (history[e]["val_loss"], e))
+    best = history[best_epoch]["val_loss"]
+    return history, best_epoch, best, policy._ckpt_file(e_i, best_epoch, best), dict(zip(moving, snaps[best_epoch]))
+
+
+def _per_epoch_top1(policy: "RLFTPluto", steps: _Minibatches, e_i, base_cpu, commit: _BufferCommit):
+    """The epochs as Lightning runs them: the epoch's losses are read on the host (two reads per epoch) and top-1 is decided there,
+    ModelCheckpoint(save_top_k=1, monitor loss/val_loss).  Lightning writes the file at every improvement and deletes the previous best;
+    what survives an update is ONE file, the best epoch's.  Here an improvement snapshots the tensors that move (a few device-to-device
+    copies) and the file is written once, after the last epoch -- same name, same content (`checkpoint_every_improvement: True` restores
+    the write per improvement for those who want the intermediate files to survive a crash mid-update)."""
+    cfg, model, trainer = policy.cfg, policy.train_model, steps.trainer
+    moving = policy._moving_keys(model)
+    history, best, best_epoch, best_path, snapshot = [], None, None, None, None
+    for epoch in range(cfg["epochs"]):
+        steps.train_epoch(epoch)
+        train_loss = trainer.pop_mean_loss()    # mean of the step losses; also joins the update stream (parameters are final)
+        vl = [steps.run(mb, False).clone() for mb in steps.of(cfg["epochs"], cfg["val_batch_size"])]
+        trainer.on_epoch_end()
+        val_loss = float(torch.stack(vl).mean().item()) if vl else train_loss
+        history.append({"epoch": epoch, "train_loss": train_loss, "val_loss": val_loss, "lr": trainer.optimizer.param_groups[0]["lr"]})
+        if best is None or val_loss < best:
+            if trainer.rank == 0 and best_path is not None and best_path.exists():
+                best_path.unlink()
+            best, best_epoch, best_path = val_loss, epoch, policy._ckpt_file(e_i, epoch, val_loss)
+            own = model.state_dict()
+            snapshot = {k: own[k].detach().clone() for k in moving}
+            if trainer.rank == 0 and cfg.get("checkpoint_every_improvement", False):
+                policy._write_checkpoint(best_path, base_cpu, snapshot, epoch, e_i)
+    return history, best_epoch, best, best_path, snapshot
+
+
 class RLFTPluto(PLUTO):
-    name = 'rlft_pluto'
-    type = 'rlft'
-    kind = 'rift'
+    name, type, kind = 'rlft_pluto', 'rlft', 'rift'
     EXTRA_COLUMNS = ('CBVs_actions_old_log_prob', 'CBVs_actions_mode')      # rlft_pluto.py:131-135
+    clip_epsilon, lambda_entropy = 0.2, 0.01       # (PPO's; ppo_pluto.yaml sets them)
+    _objective = None                              # run-time settings of the group objective (_GroupRelativePluto)
 
     def __init__(self, config, logger):
         super().__init__(config, logger)
@@ -89,6 +261,8 @@ class RLFTPluto(PLUTO):
         self.train_model: Optional[PlanningModel] = None
         self.buffer: Optional[CBVRolloutBuffer] = None
         self.last_fit: Dict = {}
+        self._mem_ckpt: Optional[Dict] = None        # device snapshot of the moving tensors behind the checkpoint the last update wrote
+        self._infer_bound = None                     # (checkpoint, tensor version) the inference model was last loaded from / refreshed to
 
     def _log(self, msg, color=None):
         if self.logger is not None and hasattr(self.logger, "log"):
@@ -123,7 +297,7 @@ class RLFTPluto(PLUTO):
         self.mode = mode
         if mode == 'train':
             self._mem_ckpt = None           # (a fresh training model: its trunk is NOT the one the snapshot belongs to)
-            self.train_model = PlanningModel(radius=self.radius).to(self.device)
+            self.train_model = self._new_train_model().to(self.device)
             self.train_model.compute_precision = self.compute_precision
             self.train_model.train()
             self.pluto_model.eval()
@@ -131,6 +305,9 @@ class RLFTPluto(PLUTO):
             self.pluto_model.eval()
         else:
             raise ValueError(f'Unknown mode {mode}')
+
+    def _new_train_model(self) -> PlanningModel:
+        return PlanningModel(radius=self.radius)
 
     def _per_cbv(self, env_id, cbv_id, obs, data, out, index, state, decision):
         """rlft_pluto.py:172-176: log of the chosen candidate's softmax score and its (r, m) -- integer, bit-exact."""
@@ -215,6 +392,7 @@ class RLFTPluto(PLUTO):
         the exchanges of RLFTTrainer make the sharded step equal the single-process one -- same losses, gradients, BatchNorm running
         statistics and therefore the same checkpoint on every rank; rank 0 writes it."""
         assert self.buffer is not None and self.buffer.buffer_full, 'The buffer should be full before training'
+        check_batch_covers_ranks(self.cfg["train_batch_size"], torch.distributed.get_world_size(process_group) if process_group is not None else 1)
         with capped_host_threads(self.cfg.get("host_threads", 4)), paused_cyclic_gc(self.cfg.get("pause_gc", True)):
             return self._train(e_i, process_group)
 
@@ -224,210 +402,35 @@ class RLFTPluto(PLUTO):
         if self.train_model is None:
             self.set_mode('train')
         cfg = self.cfg
+        every = cfg.get("checkpoint_every_improvement", False)
         lr = max(self.initial_lr * (cfg["cl_lr_decay"] ** self.current_epoch), cfg["min_lr"])   # rlft_pluto.py:212
-        # Where the training model's weights come from (rlft_pluto.py:214-222: the latest checkpoint).  Only the trainable layers and the
-        # BatchNorm running statistics move during an update (`_moving_keys`); when the checkpoint to load is the one THIS process wrote at
-        # the end of its previous update, the frozen trunk is already in place and the moving tensors are restored from the device
-        # snapshot kept with it -- no 17 MB read + 438 host-to-device copies per update.
-        mem = self.__dict__.get("_mem_ckpt")
-        loaded_from = "file" if self.checkpoint else "inference model"
-        base_cpu = None                       # CPU copy of the whole state_dict the update starts from (the frozen part of the next checkpoint)
-        if (self.checkpoint and mem is not None and mem["path"] == self.checkpoint and Path(self.checkpoint).exists()
-                and mem["model"] is self.train_model and mem["trunk"] == self._trunk_version(self.train_model)):
-            with torch.no_grad():
-                own = self.train_model.state_dict()
-                for k, v in mem["moving"].items():
-                    own[k].copy_(v)
-            base_cpu = mem["base_cpu"]
-            loaded_from = "device snapshot"
-        elif self.checkpoint:
-            if not Path(self.checkpoint).exists():
-                raise FileNotFoundError(f"{self.name}: checkpoint {self.checkpoint} does not exist")
-            sd = torch.load(self.checkpoint, map_location="cpu", weights_only=False)["state_dict"]
-            base_cpu = {k.replace("model.", "", 1): v for k, v in sd.items()}
-            self.train_model.load_state_dict(base_cpu, strict=False)
-            # the next checkpoint is the TRAINING MODEL's state_dict (Lightning saves the module, training_builder.py:131-140): keys the
-            # source file lacked (loaded with strict=False) come off the device, keys the model does not have are not carried forward
-            own = self.train_model.state_dict()
-            base_cpu = {k: (base_cpu[k] if k in base_cpu else v.detach().cpu()) for k, v in own.items()}
-        else:
-            self.train_model.load_state_dict(self.pluto_model.state_dict(), strict=False)
-            if cfg.get("checkpoint_every_improvement", False):      # (a file per improvement needs the frozen part before the first epoch ends)
-                base_cpu = {k: v.detach().cpu() for k, v in self.train_model.state_dict().items()}
-        infer_in_sync = (not self.checkpoint) or self.__dict__.get("_infer_bound") == (self.checkpoint, self.pluto_model._tensor_version())
+        base_cpu, loaded_from = self._load_training_weights()
+        infer_in_sync = (not self.checkpoint) or self._infer_bound == (self.checkpoint, self.pluto_model._tensor_version())
         mark("load_checkpoint")
         trainer = RLFTTrainer(self.train_model, kind=self.kind, lr=lr, cl_lr_decay=cfg["cl_lr_decay"],
                               weight_decay=cfg["weight_decay"], epochs=cfg["epochs"], warmup_epochs=cfg["warmup_epochs"],
                               trainable_layers=tuple(cfg["trainable_layers"]), gradient_clip_val=cfg["gradient_clip_val"],
-                              clip_epsilon=getattr(self, "clip_epsilon", 0.2), lambda_entropy=getattr(self, "lambda_entropy", 0.01),
-                              process_group=process_group, seed=int(e_i) + 1, objective=getattr(self, "_objective", None))
-        rank, world = trainer.rank, trainer.world
-        eng = trainer.engine
+                              clip_epsilon=self.clip_epsilon, lambda_entropy=self.lambda_entropy,
+                              process_group=process_group, seed=int(e_i) + 1, objective=self._objective)
         mark("trainer")
         replay = self._arena()
         mark("arena")
         extras = self.preprocess_buffer(trainer, replay)
         mark("preprocess")
-        n = replay.n
-        g = torch.Generator().manual_seed(int(e_i) + 1234)          # same split and order on every rank
-        perm = torch.randperm(n, generator=g)                      # random_split(dataset, [0.9, 0.1]), rift_datamodule.py:93
-        n_train = int(math.floor(n * cfg["train_ratio"]))
-        train_idx, val_idx = perm[:n_train], perm[n_train:]
-        save_dir = self.model_path / self.load_agent_info
-        save_dir.mkdir(parents=True, exist_ok=True)
-        best, best_path, best_epoch, snapshot, history = None, None, None, None, []
-        moving = self._moving_keys(self.train_model)
-
-        # every epoch's minibatch order is drawn up front (the same generator sequence as a draw per epoch: validation draws nothing) and goes
-        # to the device in ONE upload, with the reference-line count of every minibatch taken off the host copy
-        passes = [train_idx[torch.randperm(train_idx.numel(), generator=g)] if cfg["shuffle"] else train_idx for _ in range(cfg["epochs"])]
-        passes.append(val_idx)
-        flat_dev = torch.cat(passes).to(torch.int32).to(self.device)
-        up = torch.cuda.Event()               # the upload is queued on this stream; the prefetch stream's gathers wait for it
-        up.record()
-        starts = [0]
-        for p_ in passes:
-            starts.append(starts[-1] + p_.numel())
-
-        def minibatches(which, bs):
-            """(device index slice of this rank, R of the whole minibatch, shard descriptor) per minibatch of pass `which`."""
-            idx, idx_dev = passes[which], flat_dev[starts[which]:starts[which + 1]]
-            r_all = replay.r_count_cpu[idx]
-            for s in range(0, idx.numel(), bs):
-                m = min(bs, idx.numel() - s)
-                if m < world:       # a tail with fewer scenes than ranks cannot give every rank a scene (each one has to join the
-                    continue        # exchanges of the forward): dropped on ALL ranks alike -- at most world - 1 scenes per pass
-                lo, hi = split_minibatch(m, rank, world) if world > 1 else (0, m)
-                yield idx_dev[s + lo:s + hi], int(r_all[s:s + m].max()), ((lo, m) if world > 1 else None), up
-
-        def run(batch, train, out=None):
-            idx_dev, R_out, shard, up = batch
-            if out is not None:       # validation through the step pipeline (RLFTTrainer.validation_step): its batch is gathered like a training batch
-                fb, b = trainer.gather(replay, idx_dev, R_out, ready=up)
-                if extras:
-                    b = dict(b)
-                    for k, v in extras.items():
-                        b[k] = v[idx_dev.long()].contiguous()
-                return trainer.validation_step(fb, b, shard=shard, out=out)
-            # training steps cycle through _ffi.DEFER_SLOTS batch-buffer sets: the tail of step k (policy head .. AdamW) runs beside the trunk of step
-            # k + 1, whose batch is gathered on the prefetch stream (RLFTTrainer.gather); validation joins the update stream first and uses slot 0
-            fb, b = trainer.gather(replay, idx_dev, R_out, ready=up) if train else replay.collate(eng, idx_dev, R_out, slot=0)
-            if extras:
-                b = dict(b)
-                for k, v in extras.items():
-                    b[k] = v[idx_dev.long()].contiguous()
-            return trainer.training_step(fb, b, shard=shard) if train else trainer.validation_step(fb, b, shard=shard)
-
-        # Epoch bookkeeping.  Lightning reads the epoch's losses on the host and decides top-1 there (training_builder.py:131-140): two host
-        # reads per epoch, each draining the step pipeline (16 x ~1.7 ms of an update).  Single process, no file per improvement: nothing of an
-        # epoch comes back to the host -- its mean training loss and validation loss go into a device table, the tensors that move (pi_head,
-        # BatchNorm statistics: `moving`) are copied into that epoch's snapshot on the stream, and the whole table is read ONCE behind the last
-        # epoch; top-1 = the FIRST epoch with the minimal validation loss, exactly what the strict `<` of the per-epoch decision selects, and
-        # the checkpoint is written from that epoch's snapshot.  The non-finite flag is sticky and checked at that one read.
-        deferred = world == 1 and not cfg.get("checkpoint_every_improvement", False)
-        trunk_after, buffer_reset, undo_reset = None, False, None
-
-        def uncommitted():                  # the update did not commit: the rollout buffer keeps this generation's data
-            if undo_reset is not None:
-                self.buffer.restore(undo_reset)
-
-        try:
-            if deferred:
-                own = self.train_model.state_dict()
-                src = [own[k] for k in moving]
-                snaps = []
-                table = torch.zeros(cfg["epochs"], 2, dtype=torch.float64, device=self.device)
-                lrs = []
-                # validation through the step pipeline: the epoch's validation trunks follow its last training trunk on this stream without
-                # waiting for that step's update, their heads / objectives and the epoch's bookkeeping (mean losses, the snapshot of the trained
-                # parameters) sit on the update stream between the tails -- this stream never waits for the update stream inside an update.
-                # BatchNorm statistics are written by the training trunks on THIS stream: their snapshot stays here
-                piped = trainer.pipelined_validation
-                val_mbs = list(minibatches(cfg["epochs"], cfg["val_batch_size"]))
-                vtab = torch.zeros(cfg["epochs"], max(len(val_mbs), 1), dtype=torch.float64, device=self.device)
-                tp = {n for n, p_ in self.train_model.named_parameters() if p_.requires_grad}      # (state_dict() tensors are detached: ask the parameters)
-                trained = [i for i, k in enumerate(moving) if k in tp]           # written by AdamW on the update stream
-                buffers = [i for i, k in enumerate(moving) if k not in tp]       # BatchNorm running statistics, written by the training trunks
-                for epoch in range(cfg["epochs"]):
-                    snaps.append([torch.empty_like(t) for t in src])   # (per epoch, behind the steps issued so far: 0.4 ms of host time each, hidden)
-                    for mb in minibatches(epoch, cfg["train_batch_size"]):
-                        run(mb, True)
-                    if piped:
-                        for j, mb in enumerate(val_mbs):
-                            run(mb, False, out=vtab[epoch, j:j + 1])
-                        with trainer.update_stream():
-                            trainer.pop_mean_loss_async(table[epoch, 0], in_update_stream=True)
-                            table[epoch, 1].copy_(vtab[epoch].mean() if val_mbs else table[epoch, 0])
-                            if trained:
-                                torch._foreach_copy_([snaps[epoch][i] for i in trained], [src[i] for i in trained])
-                        if buffers:
-                            torch._foreach_copy_([snaps[epoch][i] for i in buffers], [src[i] for i in buffers])
-                    else:
-                        trainer.pop_mean_loss_async(table[epoch, 0])
-                        vl = [run(mb, False).clone() for mb in val_mbs]
-                        table[epoch, 1].copy_(torch.stack(vl).mean() if vl else table[epoch, 0])
-                        torch._foreach_copy_(snaps[epoch], src)      # (behind the validation steps on this stream; the next epoch's updates are ordered behind it)
-                    trainer.on_epoch_end()
-                    lrs.append(trainer.optimizer.param_groups[0]["lr"])
-                trainer.wait_update()                                  # (the table and the snapshots of the trained parameters come off the update stream)
-                # the host is ~100 ms ahead of the device here: what the end of the update needs from the host and does not depend on the
-                # outcome happens now, in the device's shadow -- the frozen trunk's identity (nothing queued writes it) and the buffer reset
-                # (4096 committed rows to free, 9 ms; the arena was uploaded from the pinned mirror before the first epoch)
-                trunk_after = self._trunk_version(self.train_model)
-                # (reversibly: the rows move into a token.  A non-finite flag at the read below, or a checkpoint that cannot be written,
-                # puts them back -- the generation's rollout data survives a failed update, as in the reference, whose reset follows the
-                # fit; the token is dropped -- the 9 ms of freeing -- by a helper thread once the checkpoint is on disk)
-                undo_reset = self.buffer.reset_buffer_reversibly()
-                buffer_reset = True
-                host = table.cpu()                                     # the update's one host read
-                trainer.check_finite()
-                for epoch in range(cfg["epochs"]):
-                    history.append({"epoch": epoch, "train_loss": float(host[epoch, 0]), "val_loss": float(host[epoch, 1]), "lr": lrs[epoch]})
-                best_epoch = min(range(cfg["epochs"]), key=lambda e: (history[e]["val_loss"], e))
-                best = history[best_epoch]["val_loss"]
-                best_path = save_dir / f"carla_episode={e_i}-epoch={best_epoch}-val_loss={best:.3f}.ckpt"   # training_builder.py:133
-                snapshot = dict(zip(moving, snaps[best_epoch]))
-            for epoch in (() if deferred else range(cfg["epochs"])):
-                for mb in minibatches(epoch, cfg["train_batch_size"]):
-                    run(mb, True)
-                train_loss = trainer.pop_mean_loss()    # mean of the step losses; also joins the update stream (parameters are final)
-                vl = [run(mb, False).clone() for mb in minibatches(cfg["epochs"], cfg["val_batch_size"])]
-                trainer.on_epoch_end()
-                val_loss = float(torch.stack(vl).mean().item()) if vl else train_loss
-                history.append({"epoch": epoch, "train_loss": train_loss, "val_loss": val_loss,
-                                "lr": trainer.optimizer.param_groups[0]["lr"]})
-                if best is None or val_loss < best:                    # ModelCheckpoint(save_top_k=1, monitor loss/val_loss)
-                    # Lightning writes the file at every improvement and deletes the previous best; what survives an update is ONE file,
-                    # the best epoch's.  Here an improvement snapshots the tensors that move (a few device-to-device copies) and the file
-                    # is written once, after the last epoch -- same name, same content (`checkpoint_every_improvement: True` restores the
-                    # write per improvement for those who want the intermediate files to survive a crash mid-update)
-                    if rank == 0 and best_path is not None and best_path.exists():
-                        best_path.unlink()
-                    best, best_epoch = val_loss, epoch
-                    best_path = save_dir / f"carla_episode={e_i}-epoch={epoch}-val_loss={val_loss:.3f}.ckpt"   # training_builder.py:133
-                    own = self.train_model.state_dict()
-                    snapshot = {k: own[k].detach().clone() for k in moving}
-                    if rank == 0 and cfg.get("checkpoint_every_improvement", False):
-                        self._write_checkpoint(best_path, base_cpu, snapshot, epoch, e_i)
-        except BaseException:
-            uncommitted()
-            raise
-        finally:
-            trainer.close()             # the data-parallel hooks sit on the model-owned engine: detach them also when an epoch raises
-        mark("epochs")
-        try:
+        (self.model_path / self.load_agent_info).mkdir(parents=True, exist_ok=True)
+        steps = _Minibatches(trainer, replay, extras, draw_passes(replay.n, e_i, cfg), cfg["train_batch_size"], self.device)
+        top1 = _deferred_top1 if trainer.world == 1 and not every else _per_epoch_top1      # (how an epoch is closed and the result is read)
+        with _BufferCommit(self.buffer) as commit:
+            try:
+                history, best_epoch, best, best_path, snapshot = top1(self, steps, e_i, base_cpu, commit)
+            finally:
+                trainer.close()             # the data-parallel hooks sit on the model-owned engine: detach them also when an epoch raises
+            mark("epochs")
             if base_cpu is None:               # first update of a policy without a checkpoint: the frozen part comes off the device once
                 base_cpu = {k: v.detach().cpu() for k, v in self.train_model.state_dict().items()}
-            if rank == 0 and not cfg.get("checkpoint_every_improvement", False):
+            if trainer.rank == 0 and not every:
                 self._write_checkpoint(best_path, base_cpu, snapshot, best_epoch, e_i)
-        except BaseException:
-            uncommitted()
-            raise
-        mark("write_checkpoint")
-        if undo_reset is not None:           # committed: the rows are freed off the critical path (the main thread goes on to the reload)
-            import threading
-            box, undo_reset = [undo_reset], None
-            threading.Thread(target=box.clear, daemon=True).start()
+            mark("write_checkpoint")
         if process_group is not None:
             torch.distributed.barrier(group=process_group)         # the checkpoint of rank 0 is on disk before anyone reloads
         self.last_fit = {"history": history, "best_val_loss": best, "checkpoint": best_path.as_posix(), "lr": lr}
@@ -435,10 +438,49 @@ class RLFTPluto(PLUTO):
         # the snapshot pairs with the file THIS update wrote and with this very training model (set_mode / load_model drop it; a
         # checkpoint directory in which update_training_ckpt resolves to another file never takes the fast path)
         self._mem_ckpt = {"path": best_path.as_posix(), "moving": snapshot, "base_cpu": base_cpu, "model": self.train_model,
-                          "trunk": trunk_after if trunk_after is not None else self._trunk_version(self.train_model)}
-        # refresh the inference model (rlft_pluto.py:244-246).  Its frozen trunk equals the training model's when both came from the same
-        # checkpoint (or the training model was copied from it) and nobody has touched it since: then only the moving tensors are copied,
-        # in place, device to device -- and the engine reads exactly those through their pointers, so no re-bind either
+                          "trunk": commit.trunk if commit.taken else self._trunk_version(self.train_model)}
+        self._refresh_inference_model(snapshot, best_path, infer_in_sync)
+        mark("reload")
+        commit.finish()
+        mark("reset_buffer")
+        self.last_fit["timing"] = {b[0] + "_s": b[1] - a[1] for a, b in zip(marks, marks[1:])}
+        self.last_fit["loaded_from"] = loaded_from
+        return self.last_fit
+
+    def _load_training_weights(self):
+        """-> (base_cpu: CPU copy of the whole state_dict the update starts from, the frozen part of the next checkpoint -- None: taken off
+        the device behind the epochs; the source's name), rlft_pluto.py:214-222: the latest checkpoint.  Only the trainable layers and the BatchNorm running
+        statistics move during an update (`_moving_keys`); when the checkpoint to load is the one THIS process wrote at the end of its
+        previous update, the frozen trunk is already in place and the moving tensors are restored from the device snapshot kept with it --
+        no 17 MB read + 438 host-to-device copies per update."""
+        mem, model = self._mem_ckpt, self.train_model
+        if not self.checkpoint:
+            model.load_state_dict(self.pluto_model.state_dict(), strict=False)
+            every = self.cfg.get("checkpoint_every_improvement", False)      # (a file per improvement needs the frozen part before the first epoch ends)
+            return ({k: v.detach().cpu() for k, v in model.state_dict().items()} if every else None), "inference model"
+        if (mem is not None and mem["path"] == self.checkpoint and Path(self.checkpoint).exists()
+                and mem["model"] is model and mem["trunk"] == self._trunk_version(model)):
+            with torch.no_grad():
+                own = model.state_dict()
+                for k, v in mem["moving"].items():
+                    own[k].copy_(v)
+            return mem["base_cpu"], "device snapshot"
+        if not Path(self.checkpoint).exists():
+            raise FileNotFoundError(f"{self.name}: checkpoint {self.checkpoint} does not exist")
+        sd = torch.load(self.checkpoint, map_location="cpu", weights_only=False)["state_dict"]
+        base_cpu = {k.replace("model.", "", 1): v for k, v in sd.items()}
+        model.load_state_dict(base_cpu, strict=False)
+        # the next checkpoint is the TRAINING MODEL's state_dict (Lightning saves the module, training_builder.py:131-140): keys the
+        # source file lacked (loaded with strict=False) come off the device, keys the model does not have are not carried forward
+        return {k: (base_cpu[k] if k in base_cpu else v.detach().cpu()) for k, v in model.state_dict().items()}, "file"
+
+    def _ckpt_file(self, e_i, epoch: int, val_loss: float) -> Path:
+        return self.model_path / self.load_agent_info / f"carla_episode={e_i}-epoch={epoch}-val_loss={val_loss:.3f}.ckpt"   # training_builder.py:133
+
+    def _refresh_inference_model(self, snapshot: Dict[str, torch.Tensor], best_path: Path, infer_in_sync: bool):
+        """rlft_pluto.py:244-246.  The inference model's frozen trunk equals the training model's when both came from the same checkpoint
+        (or the training model was copied from it) and nobody has touched it since: then only the moving tensors are copied, in place,
+        device to device -- and the engine reads exactly those through their pointers, so no re-bind either."""
         if infer_in_sync and self.checkpoint == best_path.as_posix():
             with torch.no_grad():
                 own = self.pluto_model.state_dict()
@@ -448,13 +490,6 @@ class RLFTPluto(PLUTO):
         else:
             self.pluto_model.load_state_dict(self.load_infer_checkpoint(self.checkpoint, self.device))
         self._infer_bound = (self.checkpoint, self.pluto_model._tensor_version())
-        mark("reload")
-        if not buffer_reset:
-            self.buffer.reset_buffer()
-        mark("reset_buffer")
-        self.last_fit["timing"] = {b[0] + "_s": b[1] - a[1] for a, b in zip(marks, marks[1:])}
-        self.last_fit["loaded_from"] = loaded_from
-        return self.last_fit
 
 
 class _GroupRelativePluto(RLFTPluto):
@@ -736,21 +771,10 @@ class PPOPluto(RLFTPluto):         # fine_tuner/rlft/ppo_pluto/ppo_pluto.py:40-1
         self.clip_epsilon, self.lambda_entropy = ppo.get('clip_epsilon', 0.2), ppo.get('lambda_entropy', 0.01)
         self.cfg["trainable_layers"] = ["planning_decoder.pi_head", "value_net"]   # ppo_training.yaml:26-28
 
-    def set_mode(self, mode):
-        self.mode = mode
-        if mode == 'train':
-            from rift_amd.planning.fine_tuner.rlft.ppo_pluto.ppo_pluto import PPOPlutoModel
-            self._mem_ckpt = None
-            self.train_model = PPOPlutoModel(radius=self.radius, state_dim=self.state_dim, action_dim=self.action_dim,
-                                             hidden_dim=self.hidden_dim, clip_epsilon=self.clip_epsilon,
-                                             lambda_entropy=self.lambda_entropy).to(self.device)
-            self.train_model.compute_precision = self.compute_precision
-            self.train_model.train()
-            self.pluto_model.eval()
-        elif mode == 'eval':
-            self.pluto_model.eval()
-        else:
-            raise ValueError(f'Unknown mode {mode}')
+    def _new_train_model(self):
+        from rift_amd.planning.fine_tuner.rlft.ppo_pluto.ppo_pluto import PPOPlutoModel
+        return PPOPlutoModel(radius=self.radius, state_dim=self.state_dim, action_dim=self.action_dim, hidden_dim=self.hidden_dim,
+                             clip_epsilon=self.clip_epsilon, lambda_entropy=self.lambda_entropy)
 
     def _sweep(self, trainer, replay: DeviceReplay, seed0: int):
         """hidden (n,128) and value (n) of every scene of `replay`, in chunks of the train batch size, model in train mode under

@@ -359,15 +359,12 @@ class RLFTTrainer:
         self.li = _ffi.RiftLossIn()
         self.li.clip_epsilon, self.li.lambda_entropy = clip_epsilon, lambda_entropy
         self.out = _ffi.RiftOutputs()
-        self._prob = None
-        self._hidden = None
-        self._argmax = None
+        self._prob = self._hidden = self._argmax = None
         self._traj, self._A, self._traj_A = None, 0, 0
         self.step_count = 0
         # dropout / DropPath / state-dropout stream: a fresh stream per fit (the caller mixes carla_episode into `seed`) and per DP rank,
         # as the reference draws fresh torch RNG per fit and per process; the step counter is added on top (forward_loss)
-        rank = self.rank
-        self.seed_base = (int(seed) * 0x9E3779B1 + rank * 0x85EBCA77) & 0x7FFFFFFF
+        self.seed_base = (int(seed) * 0x9E3779B1 + self.rank * 0x85EBCA77) & 0x7FFFFFFF
         self.training = True
         self._clip_list = None
         self._fast_groups = None
@@ -502,18 +499,24 @@ class RLFTTrainer:
             if self._prefetch is not None:
                 self._ev_serial.record(torch.cuda.current_stream())
 
+    def _issue_forward(self, fb: "_ffi.RiftFeatureBatch", shard, flags: int, seed: Optional[int] = None):
+        """What every forward of the trainer shares.  `seed` None: a step's own forward -- it advances `step_count`, seeds the drops with it and
+        computes the trajectory heads where the kind needs them; else the caller's seed, `step_count` untouched, no trajectory heads (forward_hidden)."""
+        self._A = fb.A
+        self._outputs(fb.bs, fb.R)
+        self._set_shard(fb, shard)
+        flags |= (_ffi.F_FP32 if self.model.compute_precision == "fp32" else 0) | (_ffi.F_NO_DROP if getattr(self.model, "_no_drop", False) else 0)
+        if seed is None:
+            self.step_count += 1
+            flags |= _ffi.F_NEED_TRAJ if self.need_traj else 0
+            seed = (self.seed_base + self.step_count) & 0xFFFFFFFF
+        self.engine.forward_raw(fb, self.out, flags, seed)
+
     def _forward_loss(self, fb: "_ffi.RiftFeatureBatch", extras: Dict[str, torch.Tensor], train: bool = True,
                       backward: bool = True, flags_extra: int = 0, clip_val: Optional[float] = None, defer_update: bool = False,
                       shard=None):
         eng = self.engine
-        self._A = fb.A
-        self._outputs(fb.bs, fb.R)
-        self._set_shard(fb, shard)
-        flags = (_ffi.F_TRAIN if train else 0) | (_ffi.F_NEED_TRAJ if self.need_traj else 0) | \
-                 (_ffi.F_FP32 if self.model.compute_precision == "fp32" else 0) | \
-                (_ffi.F_NO_DROP if getattr(self.model, "_no_drop", False) else 0) | flags_extra
-        self.step_count += 1
-        eng.forward_raw(fb, self.out, flags, (self.seed_base + self.step_count) & 0xFFFFFFFF)
+        self._issue_forward(fb, shard, (_ffi.F_TRAIN if train else 0) | flags_extra)
         if self.kind == "sft":   # label = (the policy's best line, the teacher's mode); extras["teacher_infos"]: (bs, 5) as SFTDataModule yields
             extras = dict(extras)
             extras["action_mode"] = eng.sft_teacher_mode(self._traj[0][:fb.bs], extras["teacher_infos"])
@@ -543,13 +546,7 @@ class RLFTTrainer:
     def forward_trunk(self, fb: "_ffi.RiftFeatureBatch", shard=None, train: bool = True):
         """The frozen part of a forward (everything up to the decoder output) on the current stream; the policy head follows through
         Engine.forward_head() wherever the caller orders it.  `train` False: the validation forward (BatchNorm running statistics, no drops)."""
-        self._A = fb.A
-        self._outputs(fb.bs, fb.R)
-        self._set_shard(fb, shard)
-        flags = (_ffi.F_TRAIN if train else 0) | _ffi.F_DEFER_HEAD | (_ffi.F_NEED_TRAJ if self.need_traj else 0) | \
-            (_ffi.F_FP32 if self.model.compute_precision == "fp32" else 0) | (_ffi.F_NO_DROP if getattr(self.model, "_no_drop", False) else 0)
-        self.step_count += 1
-        self.engine.forward_raw(fb, self.out, flags, (self.seed_base + self.step_count) & 0xFFFFFFFF)
+        self._issue_forward(fb, shard, (_ffi.F_TRAIN if train else 0) | _ffi.F_DEFER_HEAD)
 
     def _finalize_and_step(self, fused_clip: bool):
         """The tail behind the backward pass: exchange, loss / gradient finalization + clip, AdamW.  Once torch has created the optimizer
@@ -589,12 +586,7 @@ class RLFTTrainer:
 
     def forward_hidden(self, fb: "_ffi.RiftFeatureBatch", seed: int, shard="replicated") -> torch.Tensor:
         """Train-mode forward for the PPO buffer sweeps: returns the `hidden` output (bs, 128) (pluto_model.py:173-176)."""
-        self._A = fb.A
-        self._outputs(fb.bs, fb.R)
-        self._set_shard(fb, shard)
-        flags = _ffi.F_TRAIN | (_ffi.F_FP32 if self.model.compute_precision == "fp32" else 0) | \
-                (_ffi.F_NO_DROP if getattr(self.model, "_no_drop", False) else 0)
-        self.engine.forward_raw(fb, self.out, flags, seed)
+        self._issue_forward(fb, shard, _ffi.F_TRAIN, seed)
         return self._hidden[:fb.bs]
 
     LOSS_SLOTS = 1024
@@ -648,41 +640,17 @@ class RLFTTrainer:
         self._loss_slot(k)
         fused_clip = bool(self.gradient_clip_val) and self.critic is None
         if self.pipeline and self._slot_taken:
-            # trunk on the current stream, everything behind it on the update stream (which is serial in itself: head k waits for AdamW k-1)
-            self._slot_taken = False
-            slot = self._slot
-            if self._slot_prefetch:
-                self.engine.set_prepare_stream(self.prefetch_stream)
-            main = torch.cuda.current_stream()
             late = self.exchange is not None and (self.world > 1 or self.force_exchange) and self._slot_prefetch
-            if not late:
-                # a tail held back by an earlier late-path step names its forward relative to the LATEST one: it has to be issued before this
-                # step's trunk, or its head would pick up this step's forward (a caller alternating gather() with next_slot(prefetch=False))
-                self._flush_tail()
-            try:
-                with _ffi.known_stream(main):
-                    self.forward_trunk(fb, shard)
-            finally:                          # (a forward that raises must not leave later forwards preparing on the prefetch stream)
-                if self._slot_prefetch:
-                    self.engine.set_prepare_stream(None)
+            # (not late: a tail held back by an earlier late-path step names its forward relative to the LATEST one: it has to be issued before
+            # this step's trunk, or its head would pick up this step's forward -- a caller alternating gather() with next_slot(prefetch=False))
+            main, issue = self._pipelined_step(fb, extras, shard, True, not late, lambda: self._finalize_and_step(fused_clip))
             loss_t, loss_ptr, amax_ptr = self.loss, self.lo.loss, self.lo.argmax_rm      # (what of the loss descriptor belongs to THIS step: a tail
                                                                                          # issued late runs behind the next step's _outputs() / _loss_slot())
 
             def tail(back):
                 """Head, loss, backward, exchange, finalize + clip, AdamW of THIS step on the update stream (`back`: forwards issued since)."""
                 self.loss, self.lo.loss, self.lo.argmax_rm = loss_t, loss_ptr, amax_ptr
-                with torch.cuda.stream(self._side), _ffi.known_stream(self._side):
-                    self._side.wait_event(self._ev_loss)          # (the record behind this step's trunk: the latest one when the tail is issued)
-                    self.engine.forward_head(back)
-                    if not getattr(extras, "persistent", False):      # (DeviceReplay's cached batch buffers outlive the step: replay.PersistentBatch)
-                        for t in extras.values():         # per-step tensors (buffer-wide extras indexed by the minibatch) are read on this stream:
-                            if torch.is_tensor(t) and t.is_cuda:      # keep the caching allocator from recycling them under it
-                                t.record_stream(self._side)
-                    self.set_loss_inputs(extras)
-                    self.engine.loss_backward_raw(self.kind_id, self.li, self.lo, self.objective, self._terms_ptr)
-                    self._finalize_and_step(fused_clip)
-                    self._ev_param.record(self._side)
-                    self._ev_tail[slot].record(self._side)
+                issue(back)
 
             if late:
                 # data parallel: the tail is ISSUED one step late -- behind the next step's forward.  The all-reduces of a process group
@@ -694,7 +662,6 @@ class RLFTTrainer:
                     self.loss, self.lo.loss, self.lo.argmax_rm = loss_t, loss_ptr, amax_ptr
                 self._ev_loss.record(main)
             else:
-                self._flush_tail()
                 self._ev_loss.record(main)
                 tail(0)
             self.loss_n += 1
@@ -703,8 +670,7 @@ class RLFTTrainer:
             self.wait_update()
         if self.overlap_update:
             self.forward_loss(fb, extras, train=True, defer_update=True, shard=shard)
-            main = torch.cuda.current_stream()
-            self._ev_loss.record(main)
+            self._ev_loss.record(torch.cuda.current_stream())
             with torch.cuda.stream(self._side):
                 self._side.wait_event(self._ev_loss)
                 self._finalize_and_step(fused_clip)
@@ -719,6 +685,38 @@ class RLFTTrainer:
         self._optimizer_step()
         self.loss_n += 1
         return loss
+
+    def _pipelined_step(self, fb, extras, shard, train: bool, flush: bool, finish):
+        """The trunk now, on the caller's stream (returned; `flush`: a tail still held back is issued first); everything behind it -- head, objective,
+        backward, `finish()` -- on the update stream (serial in itself: head k waits for AdamW k-1) at issue(back), behind the caller's `_ev_loss` record."""
+        self._slot_taken = False
+        slot = self._slot
+        if self._slot_prefetch:
+            self.engine.set_prepare_stream(self.prefetch_stream)
+        main = torch.cuda.current_stream()
+        if flush:
+            self._flush_tail()
+        try:
+            with _ffi.known_stream(main):
+                self.forward_trunk(fb, shard, train=train)
+        finally:                          # (a forward that raises must not leave later forwards preparing on the prefetch stream)
+            if self._slot_prefetch:
+                self.engine.set_prepare_stream(None)
+
+        def issue(back):
+            with torch.cuda.stream(self._side), _ffi.known_stream(self._side):
+                self._side.wait_event(self._ev_loss)          # (the record behind this step's trunk: the latest one when the tail is issued)
+                self.engine.forward_head(back)
+                if not getattr(extras, "persistent", False):      # (DeviceReplay's cached batch buffers outlive the step: replay.PersistentBatch)
+                    for t in extras.values():         # per-step tensors (buffer-wide extras indexed by the minibatch) are read on this stream:
+                        if torch.is_tensor(t) and t.is_cuda:      # keep the caching allocator from recycling them under it
+                            t.record_stream(self._side)
+                self.set_loss_inputs(extras)
+                self.engine.loss_backward_raw(self.kind_id, self.li, self.lo, self.objective, self._terms_ptr)
+                finish()
+                self._ev_param.record(self._side)
+                self._ev_tail[slot].record(self._side)
+        return main, issue
 
     def _flush_tail(self):
         """Issue the tail of the last data-parallel step if it is still held back (see training_step)."""
@@ -835,32 +833,10 @@ class RLFTTrainer:
         objective on the update stream behind the tails already queued there (so it sees the parameters of the last update without the caller's
         stream waiting for them), loss written to `out` on that stream: read it behind wait_update() / inside update_stream()."""
         if out is not None and self._slot_taken and self.pipelined_validation:
-            self._slot_taken = False
-            slot = self._slot
-            if self._slot_prefetch:
-                self.engine.set_prepare_stream(self.prefetch_stream)
-            main = torch.cuda.current_stream()
-            self._flush_tail()
-            try:
-                with _ffi.known_stream(main):
-                    self.forward_trunk(fb, shard, train=False)
-            finally:
-                if self._slot_prefetch:
-                    self.engine.set_prepare_stream(None)
+            main, issue = self._pipelined_step(fb, extras, shard, False, True, lambda: self._exchange_and_finalize(False, None))
             self._ev_loss.record(main)
             self.loss, self.lo.loss = out, out.data_ptr()
-            with torch.cuda.stream(self._side), _ffi.known_stream(self._side):
-                self._side.wait_event(self._ev_loss)
-                self.engine.forward_head(0)
-                if not getattr(extras, "persistent", False):
-                    for t in extras.values():
-                        if torch.is_tensor(t) and t.is_cuda:
-                            t.record_stream(self._side)
-                self.set_loss_inputs(extras)
-                self.engine.loss_backward_raw(self.kind_id, self.li, self.lo, self.objective, self._terms_ptr)
-                self._exchange_and_finalize(False, None)
-                self._ev_param.record(self._side)
-                self._ev_tail[slot].record(self._side)
+            issue(0)
             return out
         self.wait_update()              # (a deferred tail may still be reading the activations this forward is about to overwrite)
         self._loss_slot(None)

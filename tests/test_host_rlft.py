@@ -497,6 +497,8 @@ def test_rlft_train_updates_only_pi_head_and_checkpoints(policy, tmp_path):
     assert any(k.startswith("planning_decoder.pi_head") for k in changed)
     assert len(buf) == 0 and not buf.buffer_full
     assert pol.current_epoch == 1 and pol.checkpoint == ck[0].as_posix()
+    assert set(fit["timing"]) == {"load_checkpoint_s", "trainer_s", "arena_s", "preprocess_s", "epochs_s", "write_checkpoint_s", "reload_s",
+                                  "reset_buffer_s"}        # (bench.py and tools/e2e_profile.py print these)
     # the next update decays the base lr: lr * 0.9 ** current_epoch (rlft_pluto.py:212)
     pol.set_buffer(_filled_buffer(48, with_ref=policy == 'grpo_pluto'))
     fit2 = pol.train(8)
@@ -547,15 +549,18 @@ def test_deferred_top1_decision_writes_the_checkpoint_of_the_per_epoch_decision(
 
 
 @pytest.mark.gpu
-def test_failed_update_keeps_the_rollout_buffer(tmp_path, monkeypatch):
+@pytest.mark.parametrize("checkpoint_every_improvement", [False, True])
+def test_failed_update_keeps_the_rollout_buffer(tmp_path, monkeypatch, checkpoint_every_improvement):
     """Round-5 advisor: the deferred top-1 path resets the buffer in the device's shadow, BEFORE the update's one host read, the finiteness
     check and the checkpoint write.  The reset is reversible now (CBVRolloutBuffer.reset_buffer_reversibly): an update that raises at any
     of those points leaves the buffer as it found it -- full, same rows, host mirror usable -- as the reference does (its reset follows a
-    successful fit, rlft_pluto.py:244-250); the next, successful update trains on that data and only then empties the buffer."""
+    successful fit, rlft_pluto.py:244-250); the next, successful update trains on that data and only then empties the buffer.  Likewise the
+    per-epoch path (`checkpoint_every_improvement`), which raises at an epoch's end and resets only behind the reload."""
     from rift_amd.planning import CBV_POLICY_LIST
     torch.cuda.set_device(0)
     cfg = {'num_scenario': 1, 'ROOT_DIR': str(tmp_path), 'model_path': 'ckpt', 'device': 'cuda:0', 'compute_precision': 'fp32',
-           'rlft': {'epochs': 2, 'warmup_epochs': 1, 'train_batch_size': 16, 'val_batch_size': 16, 'lr': 1e-3}}
+           'rlft': {'epochs': 2, 'warmup_epochs': 1, 'train_batch_size': 16, 'val_batch_size': 16, 'lr': 1e-3,
+                    'checkpoint_every_improvement': checkpoint_every_improvement}}
     torch.manual_seed(0)
     pol = CBV_POLICY_LIST['rift_pluto'](cfg, None)
     pol.load_model(resume=True)
@@ -585,6 +590,43 @@ def test_failed_update_keeps_the_rollout_buffer(tmp_path, monkeypatch):
     fit = pol.train(3)                     # the same data, now committed
     assert len(fit["history"]) == 2 and buf.buffer_pos == 0 and not buf.buffer_full
     assert len(list((tmp_path / 'ckpt').rglob("*.ckpt"))) == 1
+
+
+@pytest.mark.gpu
+def test_update_from_the_device_snapshot_equals_the_update_from_the_checkpoint_file(tmp_path):
+    """The second update of a policy finds its training weights on the device (the frozen trunk in place, the moving tensors in the snapshot
+    kept with the checkpoint its first update wrote) and refreshes the inference model in place; a policy that lost both bindings reads the
+    file and reloads the inference model from it.  Same checkpoint (name, every tensor bit for bit), same history, same inference model --
+    fp32 mode, both policies seeded alike, identically built buffers (48 scenes: minibatches of 16 + 16 + 11, one 5-scene validation batch)."""
+    from rift_amd.planning import CBV_POLICY_LIST
+    torch.cuda.set_device(0)
+    out = {}
+    for mode in ("warm", "cold"):
+        cfg = {'num_scenario': 1, 'ROOT_DIR': str(tmp_path / mode), 'model_path': 'ckpt', 'device': 'cuda:0', 'compute_precision': 'fp32',
+               'rlft': {'epochs': 2, 'warmup_epochs': 1, 'train_batch_size': 16, 'val_batch_size': 16, 'lr': 3e-3}}
+        torch.manual_seed(0)            # ahead of the constructor: the Conv1d biases keep their default (random) initialisation
+        pol = CBV_POLICY_LIST['rift_pluto'](cfg, None)
+        torch.manual_seed(0)
+        with torch.no_grad():
+            for p in pol.pluto_model.parameters():
+                if p.dim() > 1:
+                    p.normal_(0, 0.05)
+        pol.load_model(resume=True)
+        pol.set_mode('train')
+        pol.set_buffer(_filled_buffer(48, with_ref=False))
+        assert pol.train(5)["loaded_from"] == "inference model"
+        if mode == "cold":
+            pol._mem_ckpt = None
+            pol._infer_bound = None
+        pol.set_buffer(_filled_buffer(48, with_ref=False))
+        fit = pol.train(6)
+        assert fit["loaded_from"] == {"warm": "device snapshot", "cold": "file"}[mode]
+        out[mode] = (fit, torch.load(fit["checkpoint"], weights_only=False)["state_dict"],
+                     {k: v.detach().cpu().clone() for k, v in pol.pluto_model.state_dict().items()})
+    (fw, sw, iw), (fc, sc, ic) = out["warm"], out["cold"]
+    assert os.path.basename(fw["checkpoint"]) == os.path.basename(fc["checkpoint"]) and fw["history"] == fc["history"]
+    assert sw.keys() == sc.keys() and all(torch.equal(sw[k], sc[k]) for k in sw)
+    assert iw.keys() == ic.keys() and all(torch.equal(iw[k], ic[k]) for k in iw)
 
 
 @pytest.mark.gpu
@@ -1195,3 +1237,57 @@ def test_sft_family_train_updates_the_configured_layers(policy, tmp_path):
     if policy == 'rtr_pluto':
         assert "value_net.net.0.weight" in changed
     assert len(buf) == 0 and pol.current_epoch == 1
+
+
+def test_minibatch_shards_tile_every_kept_minibatch_and_drop_only_a_short_tail():
+    """minibatch_shards: every rank keeps the same minibatches, the ranks' [lo, hi) tile [0, m) with at least one scene each, and what a pass
+    loses is at most world - 1 scenes of its LAST minibatch -- for bs >= world; a batch size below the rank count loses everything (which
+    RLFTPluto.train refuses at the door: check_batch_covers_ranks)."""
+    from rift_amd.planning.fine_tuner.rlft.rlft_pluto import minibatch_shards
+    for count in range(0, 41):
+        for bs in (1, 5, 16):
+            for world in (1, 2, 3, 8):
+                ranks = [list(minibatch_shards(count, bs, r, world)) for r in range(world)]
+                kept = [(s, m) for s, m, _, _ in ranks[0]]
+                assert all([(s, m) for s, m, _, _ in got] == kept for got in ranks), (count, bs, world)
+                for j, (s, m) in enumerate(kept):
+                    cuts = [got[j][2:] for got in ranks]
+                    assert cuts[0][0] == 0 and cuts[-1][1] == m and all(a[1] == b[0] for a, b in zip(cuts, cuts[1:])), (count, bs, world, cuts)
+                    assert all(lo < hi for lo, hi in cuts), (count, bs, world, cuts)
+                every = [(s, min(bs, count - s)) for s in range(0, count, bs)]
+                if world == 1:
+                    assert kept == every and all(got[2:] == (0, got[1]) for got in ranks[0])
+                if bs < world:
+                    assert kept == [], (count, bs, world)
+                else:
+                    assert kept == every[:len(kept)] and len(every) - len(kept) <= 1, (count, bs, world)      # only the last one may go
+                    assert count - sum(m for _, m in kept) <= world - 1, (count, bs, world)
+
+
+def test_pass_draw_is_the_seeded_split_then_one_permutation_per_epoch():
+    """draw_passes against the draw restated: ONE generator seeded with e_i + 1234, the 90/10 split of its first permutation, then one
+    permutation of the training indices per epoch; the validation indices last.  Every rank draws for itself: two draws are identical."""
+    from rift_amd.planning.fine_tuner.rlft.rlft_pluto import draw_passes
+    n, e_i, cfg = 10, 3, {"epochs": 2, "train_ratio": 0.9, "shuffle": True}
+    g = torch.Generator().manual_seed(e_i + 1234)
+    perm = torch.randperm(n, generator=g)
+    train, val = perm[:9], perm[9:]
+    want = [train[torch.randperm(9, generator=g)] for _ in range(2)] + [val]
+    passes = draw_passes(n, e_i, cfg)
+    assert len(passes) == 3 and all(torch.equal(a, b) for a, b in zip(passes, want))
+    for p in passes[:2]:
+        assert sorted(torch.cat([p, passes[2]]).tolist()) == list(range(n))
+    again = draw_passes(n, e_i, cfg)
+    assert len(again) == 3 and all(torch.equal(a, b) for a, b in zip(passes, again))
+    plain = draw_passes(n, e_i, dict(cfg, shuffle=False))
+    assert len(plain) == 3 and torch.equal(plain[0], train) and torch.equal(plain[1], train) and torch.equal(plain[2], val)
+
+
+def test_a_train_batch_smaller_than_the_rank_count_is_refused():
+    """RLFTPluto.train's check ahead of everything else (no trainer, no device work, the buffer untouched): with train_batch_size < world
+    every minibatch of every pass would be dropped on all ranks and the update would checkpoint untouched weights."""
+    from rift_amd.planning.fine_tuner.rlft.rlft_pluto import check_batch_covers_ranks
+    with pytest.raises(ValueError, match=r"train_batch_size = 1 .* 2 data-parallel ranks"):
+        check_batch_covers_ranks(1, 2)
+    for bs, world in ((2, 2), (1, 1), (256, 8)):
+        check_batch_covers_ranks(bs, world)

@@ -16,7 +16,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from rift_amd import _abi, _abi_drivable
+from rift_amd import _abi, _abi_drivable, tick_pack
 from rift_amd._abi import (EXPORTS, RiftControlCBV, RiftCritic, RiftDp, RiftEvalParams, RiftFeatureBatch, RiftLossIn,  # noqa: F401
                            RiftLossOut, RiftObjectiveParams, RiftOutputs, RiftReplayArena, RiftRolloutIO, RiftTensorDesc, RiftTickCBV)
 from rift_amd._abi_drivable import RiftDrivableInfo      # the drivable-area-map extension (include/rift_drivable.h)
@@ -270,9 +270,6 @@ class Engine:
 
     def stage_many(self, tensors):
         """[CPU tensor] -> [device tensor], the arena-sized ones through one span of the pinned arena and one asynchronous copy (see stage())."""
-        if self._stage_host is None:
-            self._stage_host = torch.empty(self._STAGE_BYTES, dtype=torch.uint8).pin_memory()
-            self._stage_dev = torch.empty(self._STAGE_BYTES, dtype=torch.uint8, device=self.device)
         plan, total = [], 0
         for t in tensors:
             if t.is_cuda or t.dtype not in self._NP_OF or t.numel() == 0 or t.numel() * t.element_size() > self._STAGE_BYTES // 4:
@@ -283,10 +280,7 @@ class Engine:
             total = (total + a.nbytes + 255) & ~255
         if total > self._STAGE_BYTES // 2:               # (an unusually large batch: leaf by leaf, each with its own wrap check)
             return [self.stage(t, t.dtype) if p is not None else (t if t.is_cuda else t.to(self.device)) for t, p in zip(tensors, plan)]
-        off = (self._stage_off + 255) & ~255
-        if off + total > self._STAGE_BYTES:
-            torch.cuda.synchronize(self.device)          # (see stage(): every consumer of the slots about to be rewritten is done)
-            off = 0
+        off = self._arena_span(total)
         host = self._stage_host.numpy()
         for p in plan:
             if p is not None:
@@ -294,7 +288,6 @@ class Engine:
                 host[off + o:off + o + a.nbytes] = a.reshape(-1).view(np.uint8)
         if total:
             self._stage_dev[off:off + total].copy_(self._stage_host[off:off + total], non_blocking=True)
-        self._stage_off = off + total
         out = []
         for t, p in zip(tensors, plan):
             if p is None:
@@ -303,6 +296,20 @@ class Engine:
                 a, o = p
                 out.append(self._stage_dev[off + o:off + o + a.nbytes].view(t.dtype).view(a.shape))
         return out
+
+    def _arena_span(self, nbytes: int) -> int:
+        """The offset of the next `nbytes` of the pinned arena and its device twin (allocated at the first call): 256-byte aligned, behind
+        the span before it; a span that would run past the end starts at 0 again, behind a synchronisation."""
+        if self._stage_host is None:
+            self._stage_host = torch.empty(self._STAGE_BYTES, dtype=torch.uint8).pin_memory()
+            self._stage_dev = torch.empty(self._STAGE_BYTES, dtype=torch.uint8, device=self.device)
+        off = (self._stage_off + 255) & ~255
+        if off + nbytes > self._STAGE_BYTES:
+            torch.cuda.synchronize(self.device)      # every consumer of the slots about to be rewritten is done -- on ANY stream (a staged batch may
+                                                     # have been handed to a hook that reads it elsewhere); once per 8 MiB of uploads
+            off = 0
+        self._stage_off = off + nbytes
+        return off
 
     def stage(self, a, dtype: torch.dtype) -> torch.Tensor:
         """Host array / CPU tensor -> device tensor of `dtype` through a pinned arena and an ASYNCHRONOUS copy on the current stream.
@@ -319,18 +326,10 @@ class Engine:
         n = a.nbytes
         if n == 0 or n > self._STAGE_BYTES // 4:
             return torch.from_numpy(a).to(self.device)
-        if self._stage_host is None:
-            self._stage_host = torch.empty(self._STAGE_BYTES, dtype=torch.uint8).pin_memory()
-            self._stage_dev = torch.empty(self._STAGE_BYTES, dtype=torch.uint8, device=self.device)
-        off = (self._stage_off + 255) & ~255
-        if off + n > self._STAGE_BYTES:
-            torch.cuda.synchronize(self.device)      # every consumer of the slots about to be rewritten is done -- on ANY stream (a staged batch may
-                                                     # have been handed to a hook that reads it elsewhere); once per 8 MiB of uploads
-            off = 0
+        off = self._arena_span(n)
         self._stage_host.numpy()[off:off + n] = a.reshape(-1).view(np.uint8)
         d = self._stage_dev[off:off + n]
         d.copy_(self._stage_host[off:off + n], non_blocking=True)
-        self._stage_off = off + n
         return d.view(dtype).view(a.shape)
 
     def close(self):
@@ -684,15 +683,10 @@ class Engine:
         assert Cc == 6
         Pmax = max(p.shape[0] for p in ref_pos_list)
         if all(not (torch.is_tensor(p) and p.is_cuda) for p in ref_pos_list):
-            # host-side lines (the rollout tick: straight from the observation): padded on the host, ONE upload -- [x, y, angle] planes + lengths
-            host = np.zeros((R, Pmax, 3), dtype=np.float32)
-            for r in range(R):
-                n = ref_pos_list[r].shape[0]
-                host[r, :n, :2] = np.asarray(ref_pos_list[r], dtype=np.float32)
-                host[r, :n, 2] = np.asarray(ref_angle_list[r], dtype=np.float32)
-            hp = np.concatenate([host[..., :2].reshape(-1), host[..., 2].reshape(-1)])      # [positions (R, Pmax, 2) | angles (R, Pmax)]
-            up = self.stage(hp, torch.float32)
-            rp, ra = up[:R * Pmax * 2].view(R, Pmax, 2), up[R * Pmax * 2:].view(R, Pmax)
+            # host-side lines (the rollout tick: straight from the observation): padded on the host, ONE upload -- [positions | angles] + lengths
+            hp, ha, _ = tick_pack.pad_ref_lines(ref_pos_list, ref_angle_list)
+            up = self.stage(np.concatenate([hp.reshape(-1), ha.reshape(-1)]), torch.float32)
+            rp, ra = up[:hp.size].view(R, Pmax, 2), up[hp.size:].view(R, Pmax)
         else:
             rp = torch.zeros(R, Pmax, 2, device=dev)
             ra = torch.zeros(R, Pmax, device=dev)
@@ -744,15 +738,12 @@ class Engine:
                               near_lane_change: bool = True, bbox_inflation_ratio: float = 1.1):
         """get_other_vehicle_rollout on the device: per-actor arrays (see rift_hip.h) -> (N, T, 4, 2) float64 device tensor."""
         dev = self.device
-        f64 = lambda a: np.asarray(a.cpu() if torch.is_tensor(a) else a, dtype=np.float64)    # noqa: E731
-        act_h = np.stack([f64(steer), f64(throttle), f64(brake)], -1)
-        N = act_h.shape[0]
+        N, block = tick_pack.actor_block({"steer": steer, "throttle": throttle, "brake": brake, "speed": speed, "location": location,
+                                          "yaw_deg": yaw_deg, "extent": extent})
         out = torch.empty(N, num_future_frames, 4, 2, dtype=torch.float64, device=dev)
         if N:
             # the five per-actor arrays in ONE upload: [controls (N,3) | speed (N) | location (N,3) | yaw (N) | extent (N,2)] as blocks of one buffer
-            blocks = [act_h.reshape(-1), f64(speed).reshape(-1), f64(location).reshape(-1), f64(yaw_deg).reshape(-1), f64(extent).reshape(-1)]
-            assert [b.size for b in blocks] == [3 * N, N, 3 * N, N, 2 * N], "per-actor arrays of different lengths"
-            up = self.stage(np.concatenate(blocks), torch.float64)
+            up = self.stage(block, torch.float64)
             act, sp, loc, yaw, ext = up[:3 * N], up[3 * N:4 * N], up[4 * N:7 * N], up[7 * N:8 * N], up[8 * N:]
             self._check(self.lib.rift_other_vehicle_rollout(self.ctx, _ptr(act), _ptr(sp), _ptr(loc), _ptr(yaw), _ptr(ext), N, num_future_frames,
                                                             1 if near_lane_change else 0, float(bbox_inflation_ratio), _ptr(out), _stream()),
@@ -767,9 +758,7 @@ class Engine:
     def group_advantage_tick(self, trajectory, cbvs, pid_state, gamma: float = 0.98, *, params: Optional[RiftEvalParams] = None,
                              want_returns: bool = False, want_terms: bool = False):
         """The group advantages of one tick's CBVs in one C-ABI call (rift_group_advantage_tick): `trajectory` (bs, Rb, 12, Tfull, 6) the tick's
-        model output (device), `cbvs` a list of dicts in tick order --
-            batch_index, center_state (6), ref_pos / ref_angle (lists of the valid lines' valid points, host), actors (None or the dict of
-            nearby-actor readings of other_vehicle_rollout), off_road (None or (mask (H, W) uint8, (x, y, heading)))
+        model output (device), `cbvs` a list of dicts in tick order -- the entries rift_amd/tick_pack.py describes, key by key
         -- whose valid reference lines are a prefix of their rows.  Everything host-side goes up in ONE staged copy.  Returns the (K, Rb, 12) f64
         device tensor; rows r >= R of a CBV are zero.
         `params` (eval_params; its gamma replaces the argument's) sends the call through rift_group_advantage_tick_ex: reward model, gamma,
@@ -777,102 +766,38 @@ class Engine:
         result is a dict: "advantage" (K, Rb, 12), "returns" (K, Rb, 12), "terms" (K, Rb, 12, 8) -- the ones asked for, views of the ONE device
         tensor "packed" (K * Rb * 12 * 10 doubles, zero where nothing is written), so that a tick reads all of it back in one copy.  With
         params None and nothing wanted the call is rift_group_advantage_tick, as ever.
-        An entry without off_road that carries "raster": (H, W) and "pose": (x, y, heading) takes its off-road flags from the loaded
-        drivable-area map (load_drivable_map): the call is riftdm_group_advantage_tick (params None: eval_params(gamma=gamma)); a tick
-        may mix such entries with mask entries and with entries that have neither."""
+        A tick with an entry that takes its off-road flags from the loaded drivable-area map ("raster" + "pose", load_drivable_map) goes
+        through riftdm_group_advantage_tick (params None: eval_params(gamma=gamma))."""
         dev = self.device
         traj = _dev(trajectory, torch.float32, dev)
         bs, Rb, M, Tfull, Cc = traj.shape
         assert M == 12 and Cc == 6
-        K = len(cbvs)
-        # one blob: float64 block | float32 block | int32 block | uint8 block, offsets in BYTES from the blob's start
-        plan = []
-        o64 = o32 = oi = o8 = 0
-        b64, b32, bi, b8 = [], [], [], []
-        for v in cbvs:
-            R = len(v["ref_pos"])
-            Pmax = max(int(p.shape[0]) for p in v["ref_pos"])
-            rp = np.zeros((R, Pmax, 2), dtype=np.float32); ra = np.zeros((R, Pmax), dtype=np.float32)
-            for r in range(R):
-                n = v["ref_pos"][r].shape[0]
-                rp[r, :n] = np.asarray(v["ref_pos"][r], dtype=np.float32); ra[r, :n] = np.asarray(v["ref_angle"][r], dtype=np.float32)
-            rl = np.array([p.shape[0] for p in v["ref_pos"]], dtype=np.int32)
-            cs = np.asarray(v["center_state"], dtype=np.float32).reshape(6)
-            e = {"R": R, "Pmax": Pmax, "cs": o32, "rp": o32 + 6, "ra": o32 + 6 + rp.size, "rl": oi, "N": 0, "act": None, "mask": None}
-            b32 += [cs, rp.reshape(-1), ra.reshape(-1)]; o32 += 6 + rp.size + ra.size
-            pad = (-o32) % 4                     # keep every float32 piece 16-byte aligned
-            if pad: b32.append(np.zeros(pad, dtype=np.float32)); o32 += pad
-            bi.append(rl); oi += R
-            a = v.get("actors")
-            if a is not None:
-                g = lambda x: np.asarray(x.cpu() if torch.is_tensor(x) else x, dtype=np.float64)      # noqa: E731
-                act = np.stack([g(a["steer"]), g(a["throttle"]), g(a["brake"])], -1)
-                N = act.shape[0]
-                blocks = [act.reshape(-1), g(a["speed"]).reshape(-1), g(a["location"]).reshape(-1), g(a["yaw_deg"]).reshape(-1), g(a["extent"]).reshape(-1)]
-                assert [b.size for b in blocks] == [3 * N, N, 3 * N, N, 2 * N], "per-actor arrays of different lengths"
-                if N:
-                    e["N"], e["act"] = N, o64
-                    b64 += blocks; o64 += 10 * N
-            m = v.get("off_road")
-            if m is not None:
-                mask = np.ascontiguousarray(m[0], dtype=np.uint8)
-                e["mask"], e["H"], e["W"], e["pose"] = o8, mask.shape[0], mask.shape[1], [float(m[1][0]), float(m[1][1]), float(m[1][2])]
-                b8.append(mask.reshape(-1)); o8 += mask.size
-                pad = (-o8) % 16
-                if pad: b8.append(np.zeros(pad, dtype=np.uint8)); o8 += pad
-            elif v.get("raster") is not None:        # no mask: the flags come from the loaded drivable-area map (riftdm_group_advantage_tick)
-                if v.get("pose") is None:
-                    raise ValueError("group_advantage_tick: an entry with 'raster' needs 'pose' (x, y, heading of the footprint centre)")
-                e["map"], e["H"], e["W"], e["pose"] = True, int(v["raster"][0]), int(v["raster"][1]), [float(x) for x in v["pose"]]
-            plan.append(e)
-        n64 = o64 * 8
-        n32 = o32 * 4
-        ni = oi * 4
-        ni_pad = (-(n64 + n32 + ni)) % 16
-        blob = np.concatenate([np.concatenate(b64).view(np.uint8) if b64 else np.zeros(0, np.uint8),
-                               np.concatenate(b32).view(np.uint8), np.concatenate(bi).view(np.uint8), np.zeros(ni_pad, np.uint8)] + b8)
-        up = self.stage(blob, torch.uint8)
-        base = up.data_ptr()
-        base32, basei, base8 = base + n64, base + n64 + n32, base + n64 + n32 + ni + ni_pad
-        arr = (RiftTickCBV * K)()
-        for k, (v, e) in enumerate(zip(cbvs, plan)):
-            t = arr[k]
-            t.batch_index, t.R, t.Pmax, t.n_actors = int(v["batch_index"]), e["R"], e["Pmax"], e["N"]
-            t.center_state, t.ref_pos, t.ref_angle, t.ref_len = base32 + 4 * e["cs"], base32 + 4 * e["rp"], base32 + 4 * e["ra"], basei + 4 * e["rl"]
-            t.actors = (base + 8 * e["act"]) if e["act"] is not None else None
-            if e["mask"] is not None:
-                t.off_road_mask, t.H, t.W = base8 + e["mask"], e["H"], e["W"]
-                t.pose[0], t.pose[1], t.pose[2] = e["pose"]
-            elif e.get("map"):
-                t.H, t.W = e["H"], e["W"]
-                t.pose[0], t.pose[1], t.pose[2] = e["pose"]
-        use_map = any(e.get("map") for e in plan)
-        Gmax = 12 * max(e["R"] for e in plan)
-        for k in ("turn_buf", "turn_ptr", "turn_len", "speed_buf", "speed_ptr", "speed_len"):
-            assert pid_state[k].shape[0] >= Gmax
-        pid = [_ptr(pid_state[k]) for k in ("turn_buf", "turn_ptr", "turn_len", "speed_buf", "speed_ptr", "speed_len")]
-        if params is None and not want_returns and not want_terms and not use_map:
-            out = torch.zeros(K, Rb, 12, dtype=torch.float64, device=dev)
-            self._check(self.lib.rift_group_advantage_tick(self.ctx, _ptr(traj), Rb, Tfull, arr, K, *pid, float(gamma), _ptr(out), _stream()),
-                        "rift_group_advantage_tick")
-            self._keep_tick = (traj, up)
-            return out
-        if params is None:
-            params = eval_params(gamma=gamma)
-        n = K * Rb * 12
-        packed = torch.zeros(n * 10, dtype=torch.float64, device=dev)
-        res = {"packed": packed, "advantage": packed[:n].view(K, Rb, 12), "returns": packed[n:2 * n].view(K, Rb, 12),
-               "terms": packed[2 * n:].view(K, Rb, 12, 8)}
-        fn, name = (self.lib.riftdm_group_advantage_tick, "riftdm_group_advantage_tick") if use_map else \
-                   (self.lib.rift_group_advantage_tick_ex, "rift_group_advantage_tick_ex")
-        self._check(fn(self.ctx, _ptr(traj), Rb, Tfull, arr, K, *pid, C.byref(params), _ptr(res["advantage"]),
-                       _ptr(res["returns"]) if want_returns else None, _ptr(res["terms"]) if want_terms else None, _stream()), name)
+        blob, layout = tick_pack.pack_tick(cbvs)                                  # 1. pack: host arithmetic only
+        up = self.stage(blob, torch.uint8)                                        # 2. stage once
+        arr = tick_pack.fill_tick_cbvs(layout, up.data_ptr())                     # 3. fill
+        K, pid_keys = len(layout), ("turn_buf", "turn_ptr", "turn_len", "speed_buf", "speed_ptr", "speed_len")
+        Gmax = 12 * max(c.R for c in layout)
+        assert all(pid_state[k].shape[0] >= Gmax for k in pid_keys)
+        use_map = any(c.from_map for c in layout)
+        plain = params is None and not want_returns and not want_terms and not use_map
+        if plain:                                                                 # 4. the C entry: plain | _ex | riftdm_
+            res = {"advantage": torch.zeros(K, Rb, 12, dtype=torch.float64, device=dev)}
+            name, tail = "rift_group_advantage_tick", (float(gamma), _ptr(res["advantage"]))
+        else:
+            n = K * Rb * 12
+            packed = torch.zeros(n * 10, dtype=torch.float64, device=dev)
+            res = {"packed": packed, "advantage": packed[:n].view(K, Rb, 12)}
+            if want_returns:
+                res["returns"] = packed[n:2 * n].view(K, Rb, 12)
+            if want_terms:
+                res["terms"] = packed[2 * n:].view(K, Rb, 12, 8)
+            name = "riftdm_group_advantage_tick" if use_map else "rift_group_advantage_tick_ex"
+            tail = (C.byref(eval_params(gamma=gamma) if params is None else params), _ptr(res["advantage"]), _ptr(res.get("returns")),
+                    _ptr(res.get("terms")))
+        self._check(getattr(self.lib, name)(self.ctx, _ptr(traj), Rb, Tfull, arr, K, *(_ptr(pid_state[k]) for k in pid_keys), *tail, _stream()),
+                    name)
         self._keep_tick = (traj, up)
-        if not want_returns and not want_terms:
-            return res["advantage"]
-        if not want_returns: del res["returns"]
-        if not want_terms: del res["terms"]
-        return res
+        return res if want_returns or want_terms else res["advantage"]
 
     def control_state(self, n_slots: int = 0) -> torch.Tensor:
         """The (n_slots, CONTROL_STATE) f64 controller state of control_tick, owned by the engine and grow-only (a zero row = a fresh PIDController);

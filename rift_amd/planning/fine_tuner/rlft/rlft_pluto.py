@@ -15,7 +15,7 @@ import re
 import threading
 import time
 from pathlib import Path
-from typing import Any, Dict, List, Optional
+from typing import Any, Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -492,6 +492,21 @@ class RLFTPluto(PLUTO):
         self._infer_bound = (self.checkpoint, self.pluto_model._tensor_version())
 
 
+class _TickCBV(NamedTuple):      # one CBV of a train-mode tick: what the engine is handed, and what stays with the policy
+    entry: dict               # the CBV's entry of Engine.group_advantage_tick (rift_amd/tick_pack.py names its keys)
+    lines: np.ndarray         # its valid reference lines, as rows of its observation
+    column: dict              # its 'CBVs_group_advantage' column; "advantage" is filled in by _finish_columns
+
+
+class _TickRead(NamedTuple):
+    """One device tensor of a tick that _finish_columns reads back: (K, Rb, 12) advantages -- or, with `breakdown` = (K, Rb), the packed
+    advantage (K, Rb, 12) | returns (K, Rb, 12) | terms (K, Rb, 12, 8) of Engine.group_advantage_tick for the K CBVs `ids`."""
+    tensor: torch.Tensor
+    columns: list             # [(column, k, R)]: the column takes rows [:R] of tensor[k]
+    breakdown: Optional[tuple] = None
+    ids: Optional[list] = None
+
+
 class _GroupRelativePluto(RLFTPluto):
     """Shared rollout side of RIFT and GRPO (rift_pluto.py:74-161): in train mode every tick also yields, per CBV, the raw logits of
     its valid reference lines (the "old policy" of the coming update) and the group-relative advantage of all R x 12 candidates."""
@@ -512,9 +527,10 @@ class _GroupRelativePluto(RLFTPluto):
         # call is the one made before these could vary.
         self._eval = self._read_traj_eval(config.get('traj_eval'))
         self.last_tick_breakdown = {}            # breakdown: True -> {cbv_id: {'returns': (R, 12), 'terms': (R, 12, 8)}} of the last train-mode tick
-        self._breakdown_reads = []
         self._fused_tick = bool(config.get('fused_tick', True))       # False: the per-CBV evaluator chain (the two are bit-identical, tested)
-        self._tick_columns, self._tick_reads = {}, []
+        self._tick_columns, self._tick_reads = {}, []                 # cbv_id -> column; [_TickRead] of the tick under way
+        # 'off_road': 'map' -- (id(engine), the source's key) of the town on the device, what its load returned, how many loads there were
+        self._drivable_loaded, self.drivable_map_info, self.drivable_map_loads = None, None, 0
 
     @classmethod
     def _read_objective(cls, section):
@@ -580,24 +596,23 @@ class _GroupRelativePluto(RLFTPluto):
                                "(key, polygons) of the environment's town")
         key, polygons = area
         eng = self.traj_evaluator.engine
-        if getattr(self, "_drivable_loaded", None) != (id(eng), key):
+        if self._drivable_loaded != (id(eng), key):
             self.drivable_map_info = eng.load_drivable_map(polygons, cell=self._eval['map_cell'], margin=self._eval['map_margin'])
             self._drivable_loaded = (id(eng), key)
-            self.drivable_map_loads = getattr(self, "drivable_map_loads", 0) + 1
+            self.drivable_map_loads += 1
 
     def _get_action(self, CBVs_obs_list, infos, deterministic=False):
-        self._tick_reads, self._breakdown_reads = [], []       # (a tick that raised half-way must not leave its read-backs to the next one)
+        self._tick_reads = []                    # (a tick that raised half-way must not leave its read-backs to the next one)
         self.last_tick_breakdown = {}
         return super()._get_action(CBVs_obs_list, infos, deterministic)
 
     def _begin_env(self, env_id, CBVs_obs, data, out, states):
         """Train mode: the group advantages of the environment's CBVs are ISSUED here, ahead of the per-CBV decisions, so that the device
         evaluates them (0.3 ms per CBV, serial through the shared PID state) while the host trims candidates and runs the PIDs of the loop
-        behind it.  The model outputs that loop needs are read back first -- a read-back behind the evaluation would wait for it.  In tick
-        order (the evaluator's PID state is shared and never reset, as the reference's): one fused call (rift_group_advantage_tick: one C-ABI
-        call, one staged upload) when every CBV's valid reference lines are a prefix of its rows (they are: PlutoFeature pads behind them),
-        else -- or with config['fused_tick'] = False -- the per-CBV chain of TrajEvaluator.get_grpo_advantage.  The results stay on the
-        device until _finish_columns reads the tick back."""
+        behind it.  The model outputs that loop needs are read back first -- a read-back behind the evaluation would wait for it.  Then, in
+        tick order (the evaluator's PID state is shared and never reset, as the reference's): one fused call when every CBV's valid reference
+        lines are a prefix of its rows (they are: PlutoFeature pads behind them), else -- or with config['fused_tick'] = False -- the
+        per-CBV chain.  The results stay on the device until _finish_columns reads the tick back."""
         self._tick_columns = {}
         if self.mode != 'train':
             return
@@ -605,11 +620,18 @@ class _GroupRelativePluto(RLFTPluto):
         for key in host_keys + (("output_prediction",) if self._render and self._use_prediction else ()):
             if key in out:
                 self._host(out, key)
-        src = self.state_source
-        pending = []
+        if self._eval is not None and self._eval['off_road'] == 'map':
+            self._load_drivable_map(self.state_source, env_id)
+        cbvs, ids = self._tick_entries(env_id, CBVs_obs, states), list(CBVs_obs.keys())
+        if self._fused_tick and all(len(c.lines) and int(c.lines[-1]) == len(c.lines) - 1 for c in cbvs):
+            self._issue_fused(out["trajectory"], cbvs, ids)
+        else:
+            self._issue_chain(out["trajectory"], cbvs, ids)
+
+    def _tick_entries(self, env_id, CBVs_obs, states) -> List[_TickCBV]:
+        """The tick's readings, host only: one _TickCBV per CBV, in tick order, and its column in _tick_columns."""
+        src, cbvs = self.state_source, []
         use_map = self._eval is not None and self._eval['off_road'] == 'map'
-        if use_map:
-            self._load_drivable_map(src, env_id)
         for index, (cbv_id, obs) in enumerate(CBVs_obs.items()):
             # the CBV's reference lines come from its own observation (host memory: the rows the collated batch was built from), so the
             # ragged valid points of every valid line are cut on the host -- the device-side boolean indexing of the collated batch was a
@@ -633,51 +655,55 @@ class _GroupRelativePluto(RLFTPluto):
                 raise RuntimeError(f"{type(src).__name__}.off_road_raster returned None: return (mask, pose) or NoFlagSource.ALL_CLEAR")
             column = {"advantage": None, "valid_mask": np.ones((int(keep.sum()), 12), dtype=np.bool_)}
             self._tick_columns[cbv_id] = column
-            pending.append({
-                "batch_index": index, "center_state": states[cbv_id].rollout_tuple(), "lines": lines,
-                "ref_pos": [pos[r][valid[r]] for r in lines], "ref_angle": [ang[r][valid[r]] for r in lines],     # ragged: only the valid points of each valid line
-                "actors": None if (actors is None or actors is NoFlagSource.ALL_CLEAR) else actors,
-                "off_road": None if raster is NoFlagSource.ALL_CLEAR else raster, "column": column,
-                "raster": self._eval['raster_size'] if use_map else None, "pose": map_pose})
-        ev = self.traj_evaluator
-        prefix = all(len(v["lines"]) and int(v["lines"][-1]) == len(v["lines"]) - 1 for v in pending)
-        cfg = self._eval
+            entry = {"batch_index": index, "center_state": states[cbv_id].rollout_tuple(),
+                     "ref_pos": [pos[r][valid[r]] for r in lines], "ref_angle": [ang[r][valid[r]] for r in lines],     # ragged: only the valid points of each valid line
+                     "actors": None if (actors is None or actors is NoFlagSource.ALL_CLEAR) else actors,
+                     "off_road": None if raster is NoFlagSource.ALL_CLEAR else raster, "raster": self._eval['raster_size'] if use_map else None, "pose": map_pose}
+            cbvs.append(_TickCBV(entry, lines, column))
+        return cbvs
+
+    def _issue_fused(self, trajectory, cbvs, ids):
+        """rift_group_advantage_tick: one C-ABI call, one staged upload and one read-back for the environment's CBVs."""
+        ev, cfg = self.traj_evaluator, self._eval
+        cols = [(c.column, k, len(c.lines)) for k, c in enumerate(cbvs)]
+        if cfg is None:                          # (the call made before the evaluator had settings)
+            res = ev.engine.group_advantage_tick(trajectory, [c.entry for c in cbvs], ev.pid_state)
+        else:
+            res = ev.engine.group_advantage_tick(trajectory, [c.entry for c in cbvs], ev.pid_state, cfg['gamma'], params=cfg['params'],
+                                                 want_returns=cfg['breakdown'], want_terms=cfg['breakdown'])
+        if isinstance(res, dict):                # breakdown: advantage | returns | terms are slices of one tensor, still one read-back
+            self._tick_reads.append(_TickRead(res["packed"], cols, tuple(res["advantage"].shape[:2]), ids))
+        else:
+            self._tick_reads.append(_TickRead(res, cols))
+
+    def _issue_chain(self, trajectory, cbvs, ids):
+        """The per-CBV chain of TrajEvaluator.get_grpo_advantage, in tick order: one read-back per CBV."""
+        ev, cfg = self.traj_evaluator, self._eval
         breakdown = cfg is not None and cfg['breakdown']
-        if self._fused_tick and prefix:
-            cols = [(v["column"], k, len(v["lines"])) for k, v in enumerate(pending)]
-            if cfg is None:
-                self._tick_reads.append((ev.engine.group_advantage_tick(out["trajectory"], pending, ev.pid_state), cols))
-                return
-            res = ev.engine.group_advantage_tick(out["trajectory"], pending, ev.pid_state, cfg['gamma'], params=cfg['params'],
-                                                 want_returns=breakdown, want_terms=breakdown)
-            if not breakdown:
-                self._tick_reads.append((res, cols))
-                return
-            # advantage | returns | terms are slices of one tensor: still one read-back per environment of the tick
-            self._tick_reads.append((res["packed"], cols, tuple(res["advantage"].shape[:2]), list(CBVs_obs.keys())))
-            return
-        for cbv_id, v in zip(CBVs_obs.keys(), pending):
+        for cbv_id, c in zip(ids, cbvs):
+            v, R = c.entry, len(c.lines)
             kw = {} if cfg is None else {"near_lane_change": cfg['near_lane_change'], "return_terms": breakdown}
-            G = len(v["lines"]) * 12
-            if use_map:
+            if v["raster"] is not None:          # the flags of the drivable-area map
                 kw["drivable_map"], kw["center_pose"], kw["raster_size"] = True, v["pose"], v["raster"]
             elif v["off_road"] is None:
-                kw["off_road_matrix"] = np.zeros((G, 80), dtype=np.bool_)
+                kw["off_road_matrix"] = np.zeros((12 * R, 80), dtype=np.bool_)
             else:
                 kw["off_road_mask"], kw["center_pose"] = v["off_road"]
                 if cfg is not None:              # the pixel offset comes from the CBV's own raster, as in the fused call
-                    ev.map_height, ev.map_width = np.asarray(kw["off_road_mask"]).shape
+                    kw["raster_size"] = np.asarray(kw["off_road_mask"]).shape
             if v["actors"] is None:
-                kw["collision_matrix"] = np.zeros((G, 40), dtype=np.bool_)
+                kw["collision_matrix"] = np.zeros((12 * R, 40), dtype=np.bool_)
             else:
                 kw["nearby_actor_states"] = v["actors"]
-            traj = out["trajectory"][v["batch_index"]]
-            if len(v["lines"]) != traj.shape[0] or not prefix:
-                traj = traj[v["lines"].tolist()]
+            traj = trajectory[v["batch_index"]]
+            if R != traj.shape[0]:
+                traj = traj[c.lines.tolist()]
             got = ev.get_grpo_advantage(v["center_state"], traj, v["ref_pos"], v["ref_angle"], to_host=False, **kw)
-            v["column"]["advantage"] = got["advantage"]
-            if breakdown:
-                self._breakdown_reads.append((cbv_id, got["returns"], got["terms"]))
+            if breakdown:                        # packed like the fused call's, for K = 1
+                packed = torch.cat([got[k].reshape(-1) for k in ("advantage", "returns", "terms")])
+                self._tick_reads.append(_TickRead(packed, [(c.column, 0, R)], (1, R), [cbv_id]))
+            else:
+                self._tick_reads.append(_TickRead(got["advantage"].view(1, R, 12), [(c.column, 0, R)]))
 
     def _group_columns(self, env_id, cbv_id, obs, data, out, index, state, decision) -> Dict[str, Any]:
         """The old-policy logits of the CBV's valid lines; its group advantage was issued in _begin_env."""
@@ -686,20 +712,17 @@ class _GroupRelativePluto(RLFTPluto):
                 'CBVs_group_advantage': self._tick_columns[cbv_id]}
 
     def _finish_columns(self, result):
-        for adv, cols, *packed in self._tick_reads:  # one read-back per environment of the tick
-            host = adv.cpu().numpy()
-            if packed:                               # breakdown: advantage (K, Rb, 12) | returns (K, Rb, 12) | terms (K, Rb, 12, 8)
-                (K, Rb), ids = packed
+        for read in self._tick_reads:            # one read-back per environment of the tick (the chain: per CBV)
+            host = read.tensor.cpu().numpy()
+            if read.breakdown:
+                K, Rb = read.breakdown
                 n = K * Rb * 12
                 host, ret, terms = host[:n].reshape(K, Rb, 12), host[n:2 * n].reshape(K, Rb, 12), host[2 * n:].reshape(K, Rb, 12, 8)
-                for cbv_id, (_, k, R) in zip(ids, cols):
+                for cbv_id, (_, k, R) in zip(read.ids, read.columns):
                     self.last_tick_breakdown[cbv_id] = {'returns': ret[k, :R].copy(), 'terms': terms[k, :R].copy()}
-            for column, k, R in cols:
+            for column, k, R in read.columns:
                 column["advantage"] = host[k, :R].copy()
         self._tick_reads = []
-        for cbv_id, ret, terms in self._breakdown_reads:      # (the per-CBV chain)
-            self.last_tick_breakdown[cbv_id] = {'returns': ret.cpu().numpy(), 'terms': terms.cpu().numpy()}
-        self._breakdown_reads = []
         super()._finish_columns(result)
 
     @staticmethod

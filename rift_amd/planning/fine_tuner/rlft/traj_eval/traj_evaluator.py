@@ -44,8 +44,9 @@ class TrajEvaluator:
         centre, get_off_road_matrix's origin / angle) to have them computed on the device from this call's rollout; OR, instead of
         other_vehicle_vertices, nearby_actor_states = dict(steer, throttle, brake, speed, location (N,3), yaw_deg, extent (N,2)) read
         off the CARLA actors, forecast on the device (get_other_vehicle_rollout, with near_lane_change and the constructor's
-        bbox_inflation_ratio).  drivable_map=True with center_pose (and raster_size (H, W); None: the constructor's map_height, map_width):
-        the off-road matrix comes from the engine's loaded drivable-area map (Engine.load_drivable_map) -- no mask is drawn or uploaded.
+        bbox_inflation_ratio).  drivable_map=True with center_pose: the off-road matrix comes from the engine's loaded drivable-area map
+        (Engine.load_drivable_map) -- no mask is drawn or uploaded.  raster_size (H, W), for the mask and for the map: the raster the pixel
+        offset (H / 2, W / 2) is taken from; None: the constructor's map_height, map_width.
         gamma None: the constructor's.  return_terms: also "returns" (R, M) and "terms" (R, M, 8), the seven
         discounted reward-term sums and the steps counted of every candidate."""
         eng = self.engine
@@ -64,17 +65,17 @@ class TrajEvaluator:
             if other_vehicle_vertices is None:
                 raise ValueError("pass collision_matrix, other_vehicle_vertices or nearby_actor_states")
             collision_matrix = eng.collision_matrix(ro["vertices"], other_vehicle_vertices, Ts=T)
+        size = (self.map_height, self.map_width) if raster_size is None else tuple(raster_size)
         if off_road_matrix is None and drivable_map:
             if center_pose is None:
                 raise ValueError("drivable_map=True needs center_pose")
-            size = (self.map_height, self.map_width) if raster_size is None else tuple(raster_size)
             off_road_matrix = eng.off_road_matrix_map(ro["center"], center_pose, size, eng.eval_params(resolution=self.resolution))
         if off_road_matrix is None:
             if off_road_mask is None or center_pose is None:
                 raise ValueError("pass off_road_matrix or off_road_mask + center_pose")
             res = float(np.float32(self.resolution))                       # resolution_hw is a float32 array in the reference (:102)
             off_road_matrix = eng.off_road_matrix(ro["center"], off_road_mask, center_pose[:2], float(center_pose[2]), resolution_hw=(res, -res),
-                                                  offset=(self.map_height / 2, self.map_width / 2))
+                                                  offset=(size[0] / 2, size[1] / 2))
         kw = {}
         if self.reward_model is not None or return_terms:               # (neither: the call made before the reward model could vary)
             kw = {"reward_model": self.reward_model, "terms": return_terms}

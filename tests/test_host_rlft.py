@@ -941,6 +941,43 @@ def test_staging_arena_wraps_and_large_inputs_take_the_ordinary_path():
 
 
 @pytest.mark.gpu
+def test_a_4_kib_arena_wraps_and_stage_many_mixes_its_leaves():
+    """Engine._arena_span behind stage and stage_many, on an engine whose arena is 4 KiB: twelve 1000-byte stage calls cross the wrap
+    twice; one stage_many (wrapping once more) mixes arena-sized leaves (float32, int64, bool) with a leaf above a quarter of the arena, an empty one and
+    one that is on the device already; a stage_many above half the arena goes leaf by leaf.  Every value reads back equal, dtypes and
+    shapes are kept, every span starts on a multiple of 256 and ends inside the arena."""
+    from rift_amd import _ffi
+    torch.cuda.set_device(0)
+    eng = _ffi.Engine("cuda:0")
+    eng._STAGE_BYTES = 4096
+    spans, span_of = [], eng._arena_span
+    eng._arena_span = lambda n: spans.append((span_of(n), n)) or spans[-1][0]
+    g = np.random.default_rng(11)
+    for k in range(12):
+        a = g.normal(size=250).astype(np.float32)
+        assert np.array_equal(eng.stage(a, torch.float32).cpu().numpy(), a), k
+    assert [off for off, _ in spans] == [0, 1024, 2048, 3072] * 3
+    on_device = torch.arange(6, device="cuda:0", dtype=torch.float32)
+    leaves = [torch.from_numpy(g.normal(size=(20, 5)).astype(np.float32)), torch.from_numpy(g.normal(size=300).astype(np.float32)),
+              torch.zeros(0, 3), on_device, torch.from_numpy(g.integers(-9, 9, size=10)), torch.from_numpy(g.random(33) < 0.5)]
+    n_before = len(spans)
+    out = eng.stage_many(leaves)
+    assert len(spans) == n_before + 1 and spans[-1] == (0, 1024)                   # 400 -> 512, + 80 -> 768, + 33 -> 1024: one span for the three, past the end: wrapped
+    assert out[3].data_ptr() == on_device.data_ptr()
+    arena = eng._stage_dev.data_ptr()
+    for k, (t, d) in enumerate(zip(leaves, out)):
+        assert d.is_cuda and d.dtype == t.dtype and d.shape == t.shape and torch.equal(d.cpu(), t.cpu()), k
+        assert (arena <= d.data_ptr() < arena + 4096) == (k in (0, 4, 5)) and (k not in (0, 4, 5) or (d.data_ptr() - arena) % 256 == 0), k
+    big = [torch.from_numpy(g.normal(size=250).astype(np.float32)) for _ in range(3)]      # 3 x 1024 > half the arena: leaf by leaf
+    n_before = len(spans)
+    for t, d in zip(big, eng.stage_many(big)):
+        assert torch.equal(d.cpu(), t)
+    assert [n for _, n in spans[n_before:]] == [1000] * 3
+    assert all(off % 256 == 0 and off + n <= 4096 for off, n in spans)
+    eng.close()
+
+
+@pytest.mark.gpu
 def test_tick_with_a_gap_in_the_valid_lines_falls_back_to_the_chain(tmp_path):
     """The fused tick call takes CBVs whose valid reference lines are a prefix of their rows (what PlutoFeature produces).  A CBV with an
     all-invalid line BETWEEN valid ones sends the whole environment through the per-CBV chain, in tick order; both policies agree bit for

@@ -16,10 +16,11 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from rift_amd import _abi, _abi_drivable, tick_pack
+from rift_amd import _abi, _abi_advantage, _abi_drivable, tick_pack
 from rift_amd._abi import (EXPORTS, RiftControlCBV, RiftCritic, RiftDp, RiftEvalParams, RiftFeatureBatch, RiftLossIn,  # noqa: F401
                            RiftLossOut, RiftObjectiveParams, RiftOutputs, RiftReplayArena, RiftRolloutIO, RiftTensorDesc, RiftTickCBV)
 from rift_amd._abi_drivable import RiftDrivableInfo      # the drivable-area-map extension (include/rift_drivable.h)
+from rift_amd._abi_advantage import RiftAdvantageParams  # the arena-advantage extension (include/rift_advantage.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librift_hip.so")
@@ -96,6 +97,26 @@ def objective_params(kind: str, **settings) -> RiftObjectiveParams:
     return p
 
 
+ADVANTAGE_BASELINES = {"mean": _abi_advantage.RIFTGA_BASELINE_MEAN, "leave_one_out": _abi_advantage.RIFTGA_BASELINE_LEAVE_ONE_OUT,
+                       "none": _abi_advantage.RIFTGA_BASELINE_NONE}
+ADVANTAGE_SCALES = {"group_std": _abi_advantage.RIFTGA_SCALE_GROUP_STD, "batch_rms": _abi_advantage.RIFTGA_SCALE_BATCH_RMS,
+                    "none": _abi_advantage.RIFTGA_SCALE_NONE}
+ADVANTAGE_KEYS = ("baseline", "scale", "clip", "eps")
+
+
+def advantage_params(baseline: str = "mean", scale: str = "group_std", clip: float = 0.0, eps: float = 1e-5) -> RiftAdvantageParams:
+    """RiftAdvantageParams of Engine.arena_advantage (include/rift_advantage.h states the rule): the baseline and the scale by name; the
+    defaults are the reference's z-score.  An unknown name raises ValueError; what a value may be (clip >= 0, ...) is the library's
+    refusal, at the call that takes the struct."""
+    if baseline not in ADVANTAGE_BASELINES:
+        raise ValueError(f"advantage: baseline = {baseline!r}; known: {list(ADVANTAGE_BASELINES)}")
+    if scale not in ADVANTAGE_SCALES:
+        raise ValueError(f"advantage: scale = {scale!r}; known: {list(ADVANTAGE_SCALES)}")
+    p = RiftAdvantageParams()
+    p.baseline, p.scale, p.eps, p.clip = ADVANTAGE_BASELINES[baseline], ADVANTAGE_SCALES[scale], float(eps), float(clip)
+    return p
+
+
 PI_KEYS = ("mlp.0.weight", "mlp.0.bias", "mlp.1.weight", "mlp.1.bias", "mlp.3.weight", "mlp.3.bias")       # flat order of PI_NPARAM
 PI_SIZES = (128 * 128, 128, 128, 128, 128, 1)
 CRITIC_SIZES = (256 * 128, 256, 256 * 256, 256, 256, 1, 128, 128, 1, 1)                                       # flat order of CRITIC_NPARAM
@@ -118,7 +139,7 @@ def load_library(variant: str = "") -> C.CDLL:
         raise RuntimeError(
             f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). rift_amd has no CPU fallback.")
-    _libs[variant] = lib = _abi_drivable.bind(_abi.bind(C.CDLL(path)))
+    _libs[variant] = lib = _abi_advantage.bind(_abi_drivable.bind(_abi.bind(C.CDLL(path))))
     return lib
 
 
@@ -1032,6 +1053,32 @@ class Engine:
         out = torch.empty_like(r)
         self._check(self.lib.rift_group_advantage(self.ctx, _ptr(r), ng, G, _ptr(out), _stream()), "rift_group_advantage")
         return out
+
+    def arena_advantage(self, returns, r_count=None, valid_mask=None, params: Optional[RiftAdvantageParams] = None, out=None,
+                        want_stats: bool = False):
+        """The advantage of every candidate of an arena from its stored returns (riftga_arena_advantage; include/rift_advantage.h states the
+        rule), on the current stream: `returns` (n, Rcap, 12) f64, `r_count` (n) i32 or None (every scene has Rcap lines), `valid_mask`
+        (n, Rcap, 12) bool / u8 or None (all valid), `params` advantage_params(...) (None: the defaults, the reference's z-score), `out` the
+        (n, Rcap, 12) f64 device tensor to write (None: a new one; never `returns` itself).  Returns the advantage, or with want_stats
+        (advantage, stats): the eight f64 of the header, on the device."""
+        dev = self.device
+        r = _dev(returns, torch.float64, dev)
+        if r.dim() != 3 or r.shape[2] != 12:
+            raise ValueError(f"arena_advantage: returns (n, Rcap, 12), got {tuple(r.shape)}")
+        n, Rcap = int(r.shape[0]), int(r.shape[1])
+        rc = None if r_count is None else _dev(r_count, torch.int32, dev)
+        vm = None if valid_mask is None else _dev(valid_mask.view(torch.uint8) if valid_mask.dtype == torch.bool else valid_mask, torch.uint8, dev)
+        if (rc is not None and rc.numel() != n) or (vm is not None and tuple(vm.shape) != tuple(r.shape)):
+            raise ValueError("arena_advantage: r_count (n) and valid_mask (n, Rcap, 12) go with returns (n, Rcap, 12)")
+        if out is None:
+            out = torch.empty_like(r)
+        elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == tuple(r.shape)):
+            raise ValueError("arena_advantage: out must be a contiguous f64 device tensor of the shape of returns")
+        stats = torch.empty(8, dtype=torch.float64, device=dev) if want_stats else None
+        p = advantage_params() if params is None else params
+        self._check(self.lib.riftga_arena_advantage(self.ctx, _ptr(r), _ptr(rc), _ptr(vm), n, Rcap, C.byref(p), _ptr(out), _ptr(stats), _stream()),
+                    "riftga_arena_advantage")
+        return (out, stats) if want_stats else out
 
     def rollout_return(self, delta_dis, delta_angle, speed, acc, ang_vel, ang_acc, collision, off_road, gamma=0.98, *, reward_model=None,
                        terms: bool = False):

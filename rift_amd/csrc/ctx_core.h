@@ -45,6 +45,7 @@ struct RiftCtxCore {
   // riftdm_load: the town's drivable polygons and their grid (drivable_grid.h).  `grid` keeps the host-side numbers only (its vectors
   // are emptied after the upload); used_on: the stream of the last launch that read the images -- waited for before they are released
   struct DMap { bool loaded = false; DrivableGrid grid; DrivableImages img; hipStream_t used_on = nullptr; bool used = false; } dmap;
+  DevBuf<double> ga_scratch;        // riftga_arena_advantage: per-scene partials and the arena's totals (adv_params.h), handed from launch to launch
 };
 
 // The C handle of include/rift_hip.h.  It adds nothing: a build's context derives from it and its entries cast down once at the top.

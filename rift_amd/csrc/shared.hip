@@ -14,10 +14,12 @@
 
 #include "launch.h"
 #include "../../include/rift_drivable.h"
+#include "../../include/rift_advantage.h"
 #include "lanes.h"
 #include "loss.h"
 #include "critic.h"
 #include "adv.h"
+#include "adv_params.h"
 #include "rollout.h"
 #include "drivable_map.h"
 #include "tick_multi.h"
@@ -686,6 +688,44 @@ int riftdm_group_advantage_tick(RiftCtx* c, const float* trajectory, int Rb, int
                               advantage, returns, terms, stream, true);
 }
 
+// ---- the advantage of the update from stored returns (include/rift_advantage.h; adv_params.h) ----------------------
+int riftga_params_default(RiftAdvantageParams* out) {
+  if (!out) return RIFT_ERR_ARG;
+  riftga_params_set_default(out);
+  return RIFT_OK;
+}
+
+int riftga_arena_advantage(RiftCtx* c, const double* returns, const int32_t* r_count, const uint8_t* valid_mask, int n, int Rcap,
+                           const RiftAdvantageParams* params, double* advantage, double* stats, void* stream) {
+  if (!c) return RIFT_ERR_ARG;
+  c->err.clear();
+  if (const char* why = riftga_refusal(returns, n, Rcap, params, advantage)) { c->err = std::string("riftga_arena_advantage: ") + why; return RIFT_ERR_ARG; }
+  if (n == 0) return RIFT_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->stream = (hipStream_t)stream; c->dry = false;
+  const bool batch = params->scale == RIFTGA_SCALE_BATCH_RMS;
+  ArenaAdvP p; memset(&p, 0, sizeof(p));
+  p.ret = returns; p.r_count = r_count; p.mask = valid_mask; p.n = n; p.Rcap = Rcap;
+  p.baseline = params->baseline; p.scale = params->scale; p.eps = params->eps; p.clip = params->clip;
+  p.adv = advantage; p.stats = stats;
+  if (batch || stats) {                                        // the partials travel from launch to launch in the context's scratch
+    const size_t need = riftga_scratch_doubles(n);
+    if (need > c->ga_scratch.cap() && c->ga_scratch.get()) HIPCHK(c, hipDeviceSynchronize());      // (grown behind a device-wide wait, as ro_raw)
+    DEVCHK(c, c->ga_scratch.reserve(need, need * 2));
+    p.part = c->ga_scratch.get(); p.tot = p.part + (size_t)n * RIFTGA_NPART;
+  }
+  launch(c, "arena_adv_scene_kernel", arena_adv_scene_kernel, dim3(cdiv(n, 4)), dim3(256), 0, p);
+  if (p.part) launch(c, "arena_adv_reduce_kernel", arena_adv_reduce_kernel, dim3(1), dim3(RIFTGA_REDUCE_THREADS), 0, p);
+  if (batch) {
+    const size_t total = (size_t)n * Rcap * 12;
+    const int count = (stats && params->clip > 0.0) ? 1 : 0;
+    launch(c, "arena_adv_scale_kernel", arena_adv_scale_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, RIFTGA_SCALE_BLOCKS)), dim3(256), 0, p, total, count);
+    if (count) launch(c, "arena_adv_clamped_kernel", arena_adv_clamped_kernel, dim3(1), dim3(64), 0, (const double*)p.tot, stats);
+  }
+  HIPCHK(c, hipGetLastError());
+  return RIFT_OK;
+}
+
 // One rollout tick's decisions (rift_hip.h): every refusal is decided here, on the host, before anything is launched; then one wave per CBV
 // (control.h), RIFT_CTL_CHUNK descriptors per launch.  The logits of a row are held MAXPL per lane: dispatched as loss_kernel<MAXPL> is.
 int rift_control_tick(RiftCtx* c, const float* trajectory, const float* probability, const float* ref_free_trajectory, int Rb, int Tfull,
@@ -805,5 +845,17 @@ int riftdm_group_advantage_tick(RiftCtx* ctx, const float* trajectory, int Rb, i
                                 const RiftEvalParams* params, double* advantage, double* returns, double* terms, void* stream) {
   return rift::abi::riftdm_group_advantage_tick(ctx, trajectory, Rb, Tfull, cbvs, K, turn_buf, turn_ptr, turn_len, speed_buf, speed_ptr, speed_len,
                                                 params, advantage, returns, terms, stream);
+}
+}  // extern "C"
+
+// The arena-advantage extension (include/rift_advantage.h), layered the same way: two exported symbols, defined once per library.
+#define RIFT_GA_FN(name) static_assert(std::is_same<decltype(&::name), decltype(&rift::abi::name)>::value, #name);
+RIFT_GA_FN(riftga_params_default) RIFT_GA_FN(riftga_arena_advantage)
+#undef RIFT_GA_FN
+extern "C" {
+int riftga_params_default(RiftAdvantageParams* out) { return rift::abi::riftga_params_default(out); }
+int riftga_arena_advantage(RiftCtx* ctx, const double* returns, const int32_t* r_count, const uint8_t* valid_mask, int n, int Rcap,
+                           const RiftAdvantageParams* params, double* advantage, double* stats, void* stream) {
+  return rift::abi::riftga_arena_advantage(ctx, returns, r_count, valid_mask, n, Rcap, params, advantage, stats, stream);
 }
 }  // extern "C"

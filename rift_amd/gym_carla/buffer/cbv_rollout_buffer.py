@@ -123,6 +123,8 @@ class CBVRolloutBuffer:
             a, o, r = row.get('CBVs_group_advantage'), row.get('CBVs_actions_old_group_logits'), row.get('CBVs_actions_ref_group_logits')
             if isinstance(a, dict):
                 ex["group_advantage"], ex["group_advantage_mask"] = np.asarray(a['advantage']), np.asarray(a['valid_mask'])
+                if a.get('returns') is not None:        # config['advantage']: the returns travel with the transition
+                    ex["group_return"] = np.asarray(a['returns'])
             if isinstance(o, dict):
                 ex["old_group_logits"] = np.asarray(o['logits'])
             if isinstance(r, dict):

@@ -49,6 +49,8 @@ def buffer_to_scenes(buffer: CBVRolloutBuffer) -> List[Dict]:
             a = buffer.buffer_data['CBVs_group_advantage'][i]
             ex["group_advantage"] = torch.as_tensor(np.asarray(a['advantage']), dtype=torch.float64)
             ex["group_advantage_mask"] = torch.as_tensor(np.asarray(a['valid_mask']), dtype=torch.bool)
+            if a.get('returns') is not None:        # config['advantage']: the returns travel with the transition
+                ex["group_return"] = torch.as_tensor(np.asarray(a['returns']), dtype=torch.float64)
         if has('CBVs_actions_old_group_logits'):
             o = buffer.buffer_data['CBVs_actions_old_group_logits'][i]
             ex["old_group_logits"] = torch.as_tensor(np.asarray(o['logits']), dtype=torch.float32)
@@ -243,6 +245,7 @@ class RLFTPluto(PLUTO):
     EXTRA_COLUMNS = ('CBVs_actions_old_log_prob', 'CBVs_actions_mode')      # rlft_pluto.py:131-135
     clip_epsilon, lambda_entropy = 0.2, 0.01       # (PPO's; ppo_pluto.yaml sets them)
     _objective = None                              # run-time settings of the group objective (_GroupRelativePluto)
+    _advantage_stats = None                        # config['advantage']: the device tensor of the last arena_advantage call's eight statistics
 
     def __init__(self, config, logger):
         super().__init__(config, logger)
@@ -434,6 +437,9 @@ class RLFTPluto(PLUTO):
         if process_group is not None:
             torch.distributed.barrier(group=process_group)         # the checkpoint of rank 0 is on disk before anyone reloads
         self.last_fit = {"history": history, "best_val_loss": best, "checkpoint": best_path.as_posix(), "lr": lr}
+        if self._advantage_stats is not None:      # (read here, behind the epochs: no host wait at the head of the update)
+            self.last_fit["advantage_stats"] = self._advantage_stats.cpu().tolist()
+            self._advantage_stats = None
         self.update_training_ckpt()
         # the snapshot pairs with the file THIS update wrote and with this very training model (set_mode / load_model drop it; a
         # checkpoint directory in which update_training_ckpt resolves to another file never takes the fast path)
@@ -505,6 +511,8 @@ class _TickRead(NamedTuple):
     columns: list             # [(column, k, R)]: the column takes rows [:R] of tensor[k]
     breakdown: Optional[tuple] = None
     ids: Optional[list] = None
+    terms: bool = True        # the packed tensor holds the terms (False: advantage | returns only, config['advantage'] without `breakdown`)
+    returns: bool = False     # config['advantage']: the returns also go into the column, as 'returns'
 
 
 class _GroupRelativePluto(RLFTPluto):
@@ -514,6 +522,7 @@ class _GroupRelativePluto(RLFTPluto):
     TRAJ_EVAL_KEYS = ('gamma', 'reward_model', 'reward_params', 'bbox_inflation_ratio', 'resolution', 'near_lane_change', 'breakdown',
                       'off_road', 'raster_size', 'map_cell', 'map_margin')      # the last three are read with 'off_road': 'map' only
     OBJECTIVE_KEYS = ('clip_low', 'clip_high', 'dual_clip', 'kl_beta', 'entropy_coef')      # the fields of RiftObjectiveParams
+    ADVANTAGE_KEYS = ('baseline', 'scale', 'clip', 'eps')                                   # the arguments of _ffi.advantage_params
     GROUP_OBJECTIVE = True
 
     def __init__(self, config, logger):
@@ -526,6 +535,11 @@ class _GroupRelativePluto(RLFTPluto):
         # DenseRewardModel.params and passes to TrajEvaluator(...) / get_rollout_return / get_other_vehicle_rollout.  Without the key every
         # call is the one made before these could vary.
         self._eval = self._read_traj_eval(config.get('traj_eval'))
+        # config['advantage']: baseline, scale and clip of the group advantage at run time -- what the reference spells as the literal z-score
+        # of get_grpo_advantage.  With the key the ticks keep every candidate's return with the transition ('returns' beside 'advantage' in
+        # the CBVs_group_advantage column) and each update forms the advantage again from them, over the whole replay arena
+        # (preprocess_buffer); without it nothing is kept and nothing is recomputed.
+        self._advantage = self._read_advantage(config.get('advantage'))
         self.last_tick_breakdown = {}            # breakdown: True -> {cbv_id: {'returns': (R, 12), 'terms': (R, 12, 8)}} of the last train-mode tick
         self._fused_tick = bool(config.get('fused_tick', True))       # False: the per-CBV evaluator chain (the two are bit-identical, tested)
         self._tick_columns, self._tick_reads = {}, []                 # cbv_id -> column; [_TickRead] of the tick under way
@@ -545,6 +559,20 @@ class _GroupRelativePluto(RLFTPluto):
             raise ValueError("config['objective']['kl_beta'] > 0 on rift_pluto: its buffer records no reference logits.  grpo_pluto records "
                              "them; with 'dual_clip': 3.0 it trains that objective (RIFT's dual clip plus the KL term)")
         return ob
+
+    @classmethod
+    def _read_advantage(cls, section):
+        """None without the section; else the settings with the z-score's defaults filled in and the RiftAdvantageParams of the update's call."""
+        if section is None:
+            return None
+        from rift_amd import _ffi
+        unknown = sorted(set(section) - set(cls.ADVANTAGE_KEYS))
+        if unknown:
+            raise ValueError(f"config['advantage']: unknown key(s) {unknown}; known: {list(cls.ADVANTAGE_KEYS)}")
+        ad = {'baseline': section.get('baseline', 'mean'), 'scale': section.get('scale', 'group_std'), 'clip': float(section.get('clip', 0.0)),
+              'eps': float(section.get('eps', 1e-5))}
+        ad['params'] = _ffi.advantage_params(**ad)
+        return ad
 
     @classmethod
     def _read_traj_eval(cls, section):
@@ -666,13 +694,21 @@ class _GroupRelativePluto(RLFTPluto):
         """rift_group_advantage_tick: one C-ABI call, one staged upload and one read-back for the environment's CBVs."""
         ev, cfg = self.traj_evaluator, self._eval
         cols = [(c.column, k, len(c.lines)) for k, c in enumerate(cbvs)]
-        if cfg is None:                          # (the call made before the evaluator had settings)
+        keep = self._advantage is not None       # config['advantage']: the returns are asked for and kept with the transition
+        if cfg is None and not keep:             # (the call made before the evaluator had settings)
             res = ev.engine.group_advantage_tick(trajectory, [c.entry for c in cbvs], ev.pid_state)
+        elif cfg is None:                        # (the _ex entry under the default parameters: the plain entry's bits, and the returns)
+            from rift_amd import _ffi
+            res = ev.engine.group_advantage_tick(trajectory, [c.entry for c in cbvs], ev.pid_state, 0.98, params=_ffi.eval_params(),
+                                                 want_returns=True, want_terms=False)
         else:
             res = ev.engine.group_advantage_tick(trajectory, [c.entry for c in cbvs], ev.pid_state, cfg['gamma'], params=cfg['params'],
-                                                 want_returns=cfg['breakdown'], want_terms=cfg['breakdown'])
-        if isinstance(res, dict):                # breakdown: advantage | returns | terms are slices of one tensor, still one read-back
-            self._tick_reads.append(_TickRead(res["packed"], cols, tuple(res["advantage"].shape[:2]), ids))
+                                                 want_returns=cfg['breakdown'] or keep, want_terms=cfg['breakdown'])
+        if isinstance(res, dict):                # advantage | returns | terms are slices of one tensor, still one read-back
+            K, Rb = res["advantage"].shape[:2]
+            terms = "terms" in res
+            packed = res["packed"] if terms else res["packed"][:2 * K * Rb * 12]      # (no terms: only advantage | returns come back)
+            self._tick_reads.append(_TickRead(packed, cols, (K, Rb), ids, terms=terms, returns=keep))
         else:
             self._tick_reads.append(_TickRead(res, cols))
 
@@ -680,9 +716,12 @@ class _GroupRelativePluto(RLFTPluto):
         """The per-CBV chain of TrajEvaluator.get_grpo_advantage, in tick order: one read-back per CBV."""
         ev, cfg = self.traj_evaluator, self._eval
         breakdown = cfg is not None and cfg['breakdown']
+        keep = self._advantage is not None       # config['advantage']: the returns are asked for and kept with the transition
         for cbv_id, c in zip(ids, cbvs):
             v, R = c.entry, len(c.lines)
             kw = {} if cfg is None else {"near_lane_change": cfg['near_lane_change'], "return_terms": breakdown}
+            if keep:
+                kw["return_returns"] = True
             if v["raster"] is not None:          # the flags of the drivable-area map
                 kw["drivable_map"], kw["center_pose"], kw["raster_size"] = True, v["pose"], v["raster"]
             elif v["off_road"] is None:
@@ -701,7 +740,10 @@ class _GroupRelativePluto(RLFTPluto):
             got = ev.get_grpo_advantage(v["center_state"], traj, v["ref_pos"], v["ref_angle"], to_host=False, **kw)
             if breakdown:                        # packed like the fused call's, for K = 1
                 packed = torch.cat([got[k].reshape(-1) for k in ("advantage", "returns", "terms")])
-                self._tick_reads.append(_TickRead(packed, [(c.column, 0, R)], (1, R), [cbv_id]))
+                self._tick_reads.append(_TickRead(packed, [(c.column, 0, R)], (1, R), [cbv_id], returns=keep))
+            elif keep:                           # packed like the fused call's without terms
+                packed = torch.cat([got[k].reshape(-1) for k in ("advantage", "returns")])
+                self._tick_reads.append(_TickRead(packed, [(c.column, 0, R)], (1, R), [cbv_id], terms=False, returns=True))
             else:
                 self._tick_reads.append(_TickRead(got["advantage"].view(1, R, 12), [(c.column, 0, R)]))
 
@@ -717,13 +759,31 @@ class _GroupRelativePluto(RLFTPluto):
             if read.breakdown:
                 K, Rb = read.breakdown
                 n = K * Rb * 12
-                host, ret, terms = host[:n].reshape(K, Rb, 12), host[n:2 * n].reshape(K, Rb, 12), host[2 * n:].reshape(K, Rb, 12, 8)
-                for cbv_id, (_, k, R) in zip(read.ids, read.columns):
-                    self.last_tick_breakdown[cbv_id] = {'returns': ret[k, :R].copy(), 'terms': terms[k, :R].copy()}
+                host, ret, terms = host[:n].reshape(K, Rb, 12), host[n:2 * n].reshape(K, Rb, 12), host[2 * n:].reshape(K, Rb, 12, 8) if read.terms else None
+                for cbv_id, (column, k, R) in zip(read.ids, read.columns):
+                    if terms is not None:
+                        self.last_tick_breakdown[cbv_id] = {'returns': ret[k, :R].copy(), 'terms': terms[k, :R].copy()}
+                    if read.returns:
+                        column["returns"] = ret[k, :R].copy()
             for column, k, R in read.columns:
                 column["advantage"] = host[k, :R].copy()
         self._tick_reads = []
         super()._finish_columns(result)
+
+    def preprocess_buffer(self, trainer: RLFTTrainer, replay: DeviceReplay) -> Dict[str, torch.Tensor]:
+        """Without config['advantage']: no-op, the arena's group_advantage is the z-score the ticks stored.  With it: ONE
+        Engine.arena_advantage call over the uploaded arena (train and validation split alike) writes group_advantage anew from the stored
+        returns.  The call goes onto the current stream, the one DeviceReplay.upload queued the arena's copies on, so it runs behind them;
+        the prefetch stream's gathers are ordered behind it by the event _Minibatches records on this same stream right after (`up`, which
+        every gather waits for: RLFTTrainer.gather(ready=...)) -- the event that already orders them behind the upload."""
+        if self._advantage is None:
+            return {}
+        if "group_return" not in replay.t:
+            raise ValueError("config['advantage'] forms the advantage from the returns stored with every transition ('group_return'), and this "
+                             "replay has none: it was collected without config['advantage']")
+        _, self._advantage_stats = trainer.engine.arena_advantage(replay.t["group_return"], replay.r_count, replay.t["group_valid_mask"],
+                                                                  params=self._advantage["params"], out=replay.t["group_advantage"], want_stats=True)
+        return {}
 
     @staticmethod
     def _host_line_mask(obs, out) -> np.ndarray:

@@ -36,7 +36,8 @@ class TrajEvaluator:
     def get_grpo_advantage(self, center_state, trajectories: torch.Tensor, ref_line_pos: List[torch.Tensor],
                            ref_line_angle: List[torch.Tensor], collision_matrix=None, off_road_matrix=None, gamma: Optional[float] = None,
                            other_vehicle_vertices=None, off_road_mask=None, center_pose=None, nearby_actor_states=None, to_host: bool = True,
-                           near_lane_change: bool = True, return_terms: bool = False, drivable_map: bool = False, raster_size=None):
+                           near_lane_change: bool = True, return_terms: bool = False, drivable_map: bool = False, raster_size=None,
+                           return_returns: bool = False):
         """center_state: (x, y, heading, speed, width, length) of the CBV rear axle / footprint.
         trajectories: (R, M, 80, 6) raw model output of the valid reference lines.
         collision_matrix (G, >=40) / off_road_matrix (G, >=40): bool flags per candidate and frame, OR
@@ -48,7 +49,7 @@ class TrajEvaluator:
         (Engine.load_drivable_map) -- no mask is drawn or uploaded.  raster_size (H, W), for the mask and for the map: the raster the pixel
         offset (H / 2, W / 2) is taken from; None: the constructor's map_height, map_width.
         gamma None: the constructor's.  return_terms: also "returns" (R, M) and "terms" (R, M, 8), the seven
-        discounted reward-term sums and the steps counted of every candidate."""
+        discounted reward-term sums and the steps counted of every candidate.  return_returns: "returns" alone (the same calls as without)."""
         eng = self.engine
         gamma = self.gamma if gamma is None else gamma
         R, M = trajectories.shape[:2]
@@ -89,4 +90,6 @@ class TrajEvaluator:
         out = {"advantage": host(adv), "valid_mask": np.ones((R, M), dtype=np.bool_)}
         if return_terms:
             out["returns"], out["terms"] = host(ret.view(R, M)), host(terms.view(R, M, 8))
+        elif return_returns:
+            out["returns"] = host(ret.view(R, M))
         return out

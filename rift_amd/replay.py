@@ -87,6 +87,7 @@ class HostReplay:
         self.r_count = torch.zeros(self.capacity, dtype=torch.int32)
         self._rc = self.r_count.numpy()
         self.has_ref_logits = False
+        self._has_return = np.zeros(self.capacity, dtype=np.bool_)      # per slot: the scene last put there brought 'group_return'
         self.version = 0                        # bumped by every write: DeviceReplay.upload skips an arena it already holds
         self.grown = 0
 
@@ -111,7 +112,7 @@ class HostReplay:
     def _dim_of(name: str) -> Optional[str]:
         if name in _GROUP_OF:
             return _DIM_OF[_GROUP_OF[name]]
-        return "R" if name in ("old_group_logits", "group_advantage", "group_valid_mask", "ref_group_logits") else None
+        return "R" if name in ("old_group_logits", "group_advantage", "group_valid_mask", "ref_group_logits", "group_return") else None
 
     def _put(self, i: int, name: str, a: np.ndarray, dtype, dim: Optional[str]):
         if dim is None:
@@ -158,7 +159,25 @@ class HostReplay:
         if ref is not None:
             self.has_ref_logits = True
             self._put(i, "ref_group_logits", _np(ref), _F32, "R")
+        # the returns the advantage was formed from (config['advantage']: the update forms it again, Engine.arena_advantage); the field is
+        # allocated when a scene brings it, as ref_group_logits is
+        ret = ex.get("group_return")
+        self._has_return[i] = ret is not None
+        if ret is not None:
+            self._put(i, "group_return", _np(ret), torch.float64, "R")
+        elif "group_return" in self.v:
+            self.v["group_return"][i] = 0
         self.version += 1
+
+    def has_group_return(self, n: Optional[int] = None) -> bool:
+        """Whether the first `n` slots all carry 'group_return'; none of them: False; some of them: ValueError naming the first without."""
+        have = self._has_return[:self.capacity if n is None else n]
+        if not have.any():
+            return False
+        if not have.all():
+            raise ValueError(f"the replay is mixed: row {int(np.argmin(have))} carries no 'group_return' while {int(have.sum())} of {have.size} rows do "
+                             "(rows committed with and without config['advantage'])")
+        return True
 
     def reset(self):
         """New replay generation: the slots are overwritten (each put() clears its own padding), the batch dimensions start over."""
@@ -210,6 +229,11 @@ class DeviceReplay:
         self.t["group_valid_mask"] = _pad_stack([e["group_advantage_mask"] for e in ex], self.Rcap, _U8).to(self.device)
         if "ref_group_logits" in ex[0]:
             self.t["ref_group_logits"] = _pad_stack([e["ref_group_logits"] for e in ex], self.Rcap, _F32).to(self.device)
+        have = [e.get("group_return") is not None for e in ex]
+        if any(have):
+            if not all(have):
+                raise ValueError(f"the replay is mixed: scene {have.index(False)} carries no 'group_return' while {sum(have)} of {n} scenes do")
+            self.t["group_return"] = _pad_stack([e["group_return"] for e in ex], self.Rcap, torch.float64).to(self.device)
         self.r_count = self.r_count_cpu.to(self.device)
         self._describe(self.A, self.Mp, self.Rcap, self.S)
 
@@ -249,11 +273,14 @@ class DeviceReplay:
         if self._host_version == (id(host), host.version, n):
             return
         caps, dims = host.caps, host.dims
-        geom = (n, caps["A"], caps["Mp"], caps["R"], caps["S"], host.T, host.cs_ld, host.has_ref_logits, dims["S"] > 0)
+        has_return = host.has_group_return(n)
+        geom = (n, caps["A"], caps["Mp"], caps["R"], caps["S"], host.T, host.cs_ld, host.has_ref_logits, dims["S"] > 0, has_return)
         if getattr(self, "_geom", None) != geom:
             self.t = {}
             for name, src in host.t.items():
                 if name == "ref_group_logits" and not host.has_ref_logits:
+                    continue
+                if name == "group_return" and not has_return:
                     continue
                 if _GROUP_OF.get(name) == "static_objects" and dims["S"] == 0:
                     continue

@@ -1,5 +1,5 @@
 """Achieved time / algorithmic GB/s of the HBM- and latency-bound kernels of the path (GAE scan, discounted return,
-buffer z-score, group z-score, rollout return, replay collate), by torch.cuda events on the launch stream.
+buffer z-score, group z-score, arena advantage, rollout return, replay collate), by torch.cuda events on the launch stream.
 Run on the GPU box: python tools/adv_bench.py > gpurun_out/adv_bench.json"""
 import json
 import os
@@ -50,6 +50,19 @@ def main():
         ret = torch.randn(ng, G, generator=g, dtype=torch.float64).to(dev)
         rec(f"group_advantage groups={ng} G={G}", timeit(lambda: eng.group_advantage(ret)), ng * G * 16,
             "group z-score (ddof 0, +1e-5), traj_evaluator.py:115-158")
+    # the arena advantage of one policy update (include/rift_advantage.h): the 4096-scene, Rcap 6 replay, two to three lines a scene
+    n, Rcap = 4096, 6
+    ret = torch.randn(n, Rcap, 12, generator=g, dtype=torch.float64).to(dev)
+    rcount = torch.randint(1, Rcap + 1, (n,), generator=g).to(torch.int32).to(dev)
+    vmask = torch.ones(n, Rcap, 12, dtype=torch.bool, device=dev)
+    adv_out = torch.empty_like(ret)
+    for scale, launches in (("group_std", 1), ("batch_rms", 3)):
+        for stats in (False, True):
+            p = _ffi.advantage_params("mean", scale, clip=1.5)
+            extra = 0 if not stats else (1 if scale == "group_std" else 2)
+            rec(f"arena_advantage n={n} Rcap={Rcap} {scale}{' +stats' if stats else ''}",
+                timeit(lambda: eng.arena_advantage(ret, rcount, vmask, params=p, out=adv_out, want_stats=stats)),
+                n * Rcap * 12 * (8 + 8 + 1) * (2 if scale == "batch_rms" else 1), f"{launches + extra} launches; the time includes the host's enqueue")
     for G in (48, 192, 4096 * 72):
         Ts = 40
         f = [torch.randn(G, Ts, generator=g).to(dev) for _ in range(6)]
@@ -73,6 +86,7 @@ def main():
     per_scene = replay.nbytes() / 512
     rec("collate 256 scenes", timeit(lambda: replay.collate(eng, idx)), 2 * 256 * per_scene, "replay gather: read + write of the padded scene tensors")
     print(json.dumps(out, indent=1))
+    eng.close()
 
 
 if __name__ == "__main__":

@@ -16,11 +16,12 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from rift_amd import _abi, _abi_advantage, _abi_drivable, tick_pack
+from rift_amd import _abi, _abi_advantage, _abi_drivable, _abi_select, tick_pack
 from rift_amd._abi import (EXPORTS, RiftControlCBV, RiftCritic, RiftDp, RiftEvalParams, RiftFeatureBatch, RiftLossIn,  # noqa: F401
                            RiftLossOut, RiftObjectiveParams, RiftOutputs, RiftReplayArena, RiftRolloutIO, RiftTensorDesc, RiftTickCBV)
 from rift_amd._abi_drivable import RiftDrivableInfo      # the drivable-area-map extension (include/rift_drivable.h)
 from rift_amd._abi_advantage import RiftAdvantageParams  # the arena-advantage extension (include/rift_advantage.h)
+from rift_amd._abi_select import RiftSelectParams        # the candidate-selection extension (include/rift_select.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librift_hip.so")
@@ -117,6 +118,21 @@ def advantage_params(baseline: str = "mean", scale: str = "group_std", clip: flo
     return p
 
 
+SELECT_MODES = {"greedy": _abi_select.RIFTCS_GREEDY, "sample": _abi_select.RIFTCS_SAMPLE}
+SELECT_KEYS = ("mode", "temperature")
+
+
+def select_params(mode: str = "greedy", temperature: float = 1.0) -> RiftSelectParams:
+    """RiftSelectParams of Engine.control_tick(select=...) (include/rift_select.h states the rule): the mode by name; the default is the
+    greedy choice of rift_control_tick.  An unknown name raises ValueError; what the temperature may be (finite, > 0) is the library's
+    refusal, at the call that takes the struct."""
+    if mode not in SELECT_MODES:
+        raise ValueError(f"select: mode = {mode!r}; known: {list(SELECT_MODES)}")
+    p = RiftSelectParams()
+    p.mode, p.reserved, p.temperature = SELECT_MODES[mode], 0, float(temperature)
+    return p
+
+
 PI_KEYS = ("mlp.0.weight", "mlp.0.bias", "mlp.1.weight", "mlp.1.bias", "mlp.3.weight", "mlp.3.bias")       # flat order of PI_NPARAM
 PI_SIZES = (128 * 128, 128, 128, 128, 128, 1)
 CRITIC_SIZES = (256 * 128, 256, 256 * 256, 256, 256, 1, 128, 128, 1, 1)                                       # flat order of CRITIC_NPARAM
@@ -139,7 +155,7 @@ def load_library(variant: str = "") -> C.CDLL:
         raise RuntimeError(
             f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). rift_amd has no CPU fallback.")
-    _libs[variant] = lib = _abi_advantage.bind(_abi_drivable.bind(_abi.bind(C.CDLL(path))))
+    _libs[variant] = lib = _abi_select.bind(_abi_advantage.bind(_abi_drivable.bind(_abi.bind(C.CDLL(path)))))
     return lib
 
 
@@ -847,11 +863,14 @@ class Engine:
                 if 0 <= int(s) < self._ctl_state.shape[0]:
                     self._ctl_state[int(s)].zero_()          # (a memset per slot: an index list would be a blocking upload)
 
-    def control_tick(self, trajectory, probability, ref_free_trajectory, cbvs, topk: int = 10, sample_interval: int = 10):
+    def control_tick(self, trajectory, probability, ref_free_trajectory, cbvs, topk: int = 10, sample_interval: int = 10, select=None, u=None):
         """The decisions of one tick's CBVs in one C-ABI call (rift_control_tick): `trajectory` (bs, Rb, 12, Tfull, 6), `probability`
         (bs, Rb, 12) and `ref_free_trajectory` ((bs, Tfull, 4) or None) are the raw outputs of the tick's forward; `cbvs` is a list of
         (batch_index, slot, x, y, heading, speed).  Returns the (K, 8) f64 device tensor of rift_hip.h: throttle, steer, brake, flat
-        index (-1: ref-free), kept position, score, desired_speed, delta_angle.  Enqueued on the current stream; no synchronisation."""
+        index (-1: ref-free), kept position, score, desired_speed, delta_angle.  Enqueued on the current stream; no synchronisation.
+        `select` (a RiftSelectParams, or {'mode': 'greedy' | 'sample', 'temperature': float}) makes the call riftcs_control_tick
+        (include/rift_select.h states the rule): in 'sample' mode `u` holds one number in [0, 1) per CBV, a host sequence, and elements 3 to 5
+        describe the drawn candidate (its flat index, its kept position, the probability it was drawn with)."""
         dev = self.device
         traj = _dev(trajectory, torch.float32, dev)
         prob = _dev(probability, torch.float32, dev)
@@ -866,8 +885,25 @@ class Engine:
             t.batch_index, t.slot, t.x, t.y, t.heading, t.speed = int(b), int(slot), float(x), float(y), float(heading), float(speed)
         state = self.control_state(max([int(v[1]) + 1 for v in cbvs if int(v[1]) >= 0], default=0))
         out = torch.empty(K, 8, dtype=torch.float64, device=dev)
-        self._check(self.lib.rift_control_tick(self.ctx, _ptr(traj), _ptr(prob), _ptr(rf), Rb, Tfull, arr, K, int(topk), int(sample_interval),
-                                               _ptr(state), state.shape[0], _ptr(out), _stream()), "rift_control_tick")
+        if select is None:
+            if u is not None:
+                raise ValueError("control_tick: `u` is read with select={'mode': 'sample', ...} only")
+            self._check(self.lib.rift_control_tick(self.ctx, _ptr(traj), _ptr(prob), _ptr(rf), Rb, Tfull, arr, K, int(topk), int(sample_interval),
+                                                   _ptr(state), state.shape[0], _ptr(out), _stream()), "rift_control_tick")
+        else:
+            if not isinstance(select, RiftSelectParams):
+                unknown = sorted(set(select) - set(SELECT_KEYS))
+                if unknown:
+                    raise ValueError(f"select: unknown key(s) {unknown}; known: {list(SELECT_KEYS)}")
+                select = select_params(**select)
+            draws = None
+            if u is not None:
+                draws = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+                if draws.size != K:
+                    raise ValueError(f"control_tick: {draws.size} numbers in `u` for {K} CBVs")
+            self._check(self.lib.riftcs_control_tick(self.ctx, _ptr(traj), _ptr(prob), _ptr(rf), Rb, Tfull, arr, K, int(topk), int(sample_interval),
+                                                     _ptr(state), state.shape[0], C.byref(select), None if draws is None else C.c_void_p(draws.ctypes.data),
+                                                     _ptr(out), _stream()), "riftcs_control_tick")
         self._keep_ctl = (traj, prob, rf)
         return out
 

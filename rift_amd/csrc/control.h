@@ -9,6 +9,9 @@
 // re-anchor on the rear axle, rotate back): the two frames cancel only to rounding, and the host result is the statement of the interface.
 // One sum is not numpy's tree: the segment lengths behind the target speed are added in path order, which is what np.mean does below eight
 // segments (the default: 80 frames, interval 10, seven segments); from eight segments on numpy sums pairwise and the two agree to rounding.
+// Which candidate is executed is a stage selected at compile time: the largest logit (rift_control_tick, and GREEDY of riftcs_control_tick),
+// or a draw from the softmax over the kept logits at a temperature (SAMPLE; include/rift_select.h states the rule).  Path, PID and decision
+// row are shared.
 #pragma once
 #include "../../include/rift_hip.h"
 #include "lanes.h"
@@ -27,8 +30,9 @@ struct CtlK {                                    // one CBV
   double* state;                                 // (44) this CBV's pid_state row
   double* dec;                                   // (8) this CBV's decision row
   double ox, oy, ch, sh, speed;                  // rear axle, cos / sin of the heading, speed
+  double u;                                      // this CBV's uniform number in [0, 1) (the SAMPLE stage only)
 };
-struct CtlArr { CtlK d[RIFT_CTL_CHUNK]; int K, G, Tfull, topk, interval; };
+struct CtlArr { CtlK d[RIFT_CTL_CHUNK]; int K, G, Tfull, topk, interval; float inv_t; };      // inv_t: (float)(1 / temperature), formed on the host (SAMPLE)
 
 __device__ __forceinline__ int wave_min_i(int v) {
 #pragma unroll
@@ -61,7 +65,52 @@ __device__ inline double ctl_pid_step(double* ring, double* head_last, double kp
   return out;
 }
 
+// The SAMPLE stage (include/rift_select.h states the rule; sample_candidate of planning/pluto/inference.py is its host statement): on what the
+// wave holds after the top-k rounds -- z[MAXPL] per lane, candidate g = lane + 64 i, the kept candidates in `taken`.  Plane i holds the flat
+// indices [64 i, 64 i + 64) in lane order, so the prefix sums in flat order are an inclusive 64-lane scan per plane (fp64, six shuffle steps)
+// plus the running total of the planes before it; a plane without a drawable candidate is skipped (wave-uniform).  No LDS, no atomics.
+// Whatever the logits hold, `chosen` leaves as a flat index in [0, G): a kept candidate or the greedy top.
 template <int MAXPL>
+__device__ __forceinline__ void ctl_sample(const float (&z)[MAXPL], unsigned taken, float ztop, int top, float inv_t, double u, int lane,
+                                           int& chosen, int& pos, double& prob) {
+#pragma clang fp contract(off)
+  float w[MAXPL];
+  double c[MAXPL];
+  double carry = 0.0;
+#pragma unroll
+  for (int i = 0; i < MAXPL; ++i) {
+    w[i] = ((taken >> i) & 1u) ? expf((z[i] - ztop) * inv_t) : 0.f;
+    const bool live = w[i] > 0.f;                                      // (false for a NaN)
+    double s = live ? (double)w[i] : 0.0;
+    if (__ballot(live) != 0ull) {
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) { const double t = __shfl_up(s, o, 64); if (lane >= o) s += t; }
+      c[i] = carry + s;
+      carry += __shfl(s, 63, 64);
+    } else {
+      c[i] = carry;
+    }
+  }
+  const double W = carry, thr = u * W;
+  int hit = 0x7fffffff, last = -1;                                     // per lane: the first drawable candidate past u * W, the last drawable one
+#pragma unroll
+  for (int i = 0; i < MAXPL; ++i)
+    if (w[i] > 0.f) { const int g = lane + i * 64; if (hit == 0x7fffffff && thr < c[i]) hit = g; last = g; }
+  int sel = wave_min_i(hit);
+  if (sel == 0x7fffffff) { last = -wave_min_i(-last); sel = last >= 0 ? last : top; }
+  float zc = 0.f, wc = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXPL; ++i) if (i == (sel >> 6)) { zc = z[i]; wc = w[i]; }
+  zc = __shfl(zc, sel & 63, 64); wc = __shfl(wc, sel & 63, 64);
+  int before = 0;                                                      // kept candidates ahead of it by descending logit, ties to the lower index
+#pragma unroll
+  for (int i = 0; i < MAXPL; ++i)
+    if ((taken >> i) & 1u) { const int g = lane + i * 64; if (z[i] > zc || (z[i] == zc && g < sel)) ++before; }
+  chosen = sel; pos = (int)wave_sum((float)before); prob = (double)wc / W;
+}
+
+// SAMPLE = false is the choice of rift_control_tick (the largest logit); SAMPLE = true adds the stage above between the score and the path.
+template <int MAXPL, bool SAMPLE>
 __global__ __launch_bounds__(64) void control_tick_kernel(const CtlArr a) {
 #pragma clang fp contract(off)
   if ((int)blockIdx.x >= a.K) return;
@@ -93,9 +142,15 @@ __global__ __launch_bounds__(64) void control_tick_kernel(const CtlArr a) {
   for (int i = 0; i < MAXPL; ++i) if ((taken >> i) & 1u) e += expf(z[i] - ztop);
   const float score = 1.0f / wave_sum(e);
   const bool ref_free = d.rf != nullptr && 0.25f > score;              // first maximum: a learned candidate wins a tie with 0.25
+  int chosen = top, pos = 0;                                           // (read in the SAMPLE instantiation only: the greedy one keeps its own expressions)
+  double prob = 0.0;
+  if constexpr (SAMPLE) {
+    prob = (double)score;
+    if (!ref_free) ctl_sample<MAXPL>(z, taken, ztop, top, a.inv_t, d.u, lane, chosen, pos, prob);
+  }
 
   // ---- the chosen path in the vehicle frame: point 0 and the thinned points path[k-1::k], lane j transforms thinned point j
-  const float* path = ref_free ? d.rf : d.traj + (size_t)top * Tfull * 6;
+  const float* path = ref_free ? d.rf : d.traj + (size_t)(SAMPLE ? chosen : top) * Tfull * 6;
   const int stride = ref_free ? 4 : 6;
   const double ox = d.ox, oy = d.oy, ch = d.ch, sh = d.sh, v = d.speed;
   const double x0 = (double)path[0], y0 = (double)path[1];
@@ -138,7 +193,11 @@ __global__ __launch_bounds__(64) void control_tick_kernel(const CtlArr a) {
   const double steer = fmin(fmax(ctl_pid_step(st, st + 40, 1.25, 0.75, 0.3, bearing), -1.0), 1.0);
   double* o = d.dec;
   o[0] = throttle; o[1] = steer; o[2] = brake ? 1.0 : 0.0;
-  o[3] = ref_free ? -1.0 : (double)top; o[4] = ref_free ? (double)a.topk : 0.0; o[5] = ref_free ? 0.25 : (double)score;
+  if constexpr (SAMPLE) {
+    o[3] = ref_free ? -1.0 : (double)chosen; o[4] = ref_free ? (double)a.topk : (double)pos; o[5] = ref_free ? 0.25 : prob;
+  } else {
+    o[3] = ref_free ? -1.0 : (double)top; o[4] = ref_free ? (double)a.topk : 0.0; o[5] = ref_free ? 0.25 : (double)score;
+  }
   o[6] = target; o[7] = bearing;
 }
 

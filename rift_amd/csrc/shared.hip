@@ -15,6 +15,7 @@
 #include "launch.h"
 #include "../../include/rift_drivable.h"
 #include "../../include/rift_advantage.h"
+#include "../../include/rift_select.h"
 #include "lanes.h"
 #include "loss.h"
 #include "critic.h"
@@ -24,6 +25,7 @@
 #include "drivable_map.h"
 #include "tick_multi.h"
 #include "control.h"
+#include "select_params.h"
 #include "eval_params.h"
 #include "objective_params.h"
 
@@ -728,11 +730,19 @@ int riftga_arena_advantage(RiftCtx* c, const double* returns, const int32_t* r_c
 
 // One rollout tick's decisions (rift_hip.h): every refusal is decided here, on the host, before anything is launched; then one wave per CBV
 // (control.h), RIFT_CTL_CHUNK descriptors per launch.  The logits of a row are held MAXPL per lane: dispatched as loss_kernel<MAXPL> is.
-int rift_control_tick(RiftCtx* c, const float* trajectory, const float* probability, const float* ref_free_trajectory, int Rb, int Tfull,
-                      const RiftControlCBV* cbvs, int K, int topk, int sample_interval, double* pid_state, int n_slots, double* decision,
-                      void* stream) {
-  if (!c) return RIFT_ERR_ARG;
-  auto refuse = [&](const char* why) { c->err = std::string("rift_control_tick: ") + why; return (int)RIFT_ERR_ARG; };
+// The checks and the descriptor fill are shared by rift_control_tick and riftcs_control_tick (include/rift_select.h): `who` is the entry's
+// name in the message; with `sel` in SAMPLE mode the launches are the <MAXPL, true> instantiations and u[k] rides in CBV k's descriptor.
+template <bool SAMPLE>
+static void control_tick_launch(const CtlArr& a, hipStream_t st) {
+  if (a.G <= 64 * 2) hipLaunchKernelGGL((control_tick_kernel<2, SAMPLE>), dim3(a.K), dim3(64), 0, st, a);
+  else if (a.G <= 64 * 4) hipLaunchKernelGGL((control_tick_kernel<4, SAMPLE>), dim3(a.K), dim3(64), 0, st, a);
+  else hipLaunchKernelGGL((control_tick_kernel<16, SAMPLE>), dim3(a.K), dim3(64), 0, st, a);
+}
+
+static int control_tick(RiftCtx* c, const char* who, const float* trajectory, const float* probability, const float* ref_free_trajectory, int Rb,
+                        int Tfull, const RiftControlCBV* cbvs, int K, int topk, int sample_interval, double* pid_state, int n_slots,
+                        const RiftSelectParams* sel, const double* u, double* decision, void* stream) {
+  auto refuse = [&](const char* why) { c->err = std::string(who) + ": " + why; return (int)RIFT_ERR_ARG; };
   if (K < 0) return refuse("K < 0");
   if (Rb < 1) return refuse("Rb < 1");
   const long long G = (long long)Rb * 12;
@@ -754,9 +764,11 @@ int rift_control_tick(RiftCtx* c, const float* trajectory, const float* probabil
   if (K == 0) return RIFT_OK;
   HIPCHK(c, hipSetDevice(c->device));
   const hipStream_t st = (hipStream_t)stream;
+  const bool sample = sel && sel->mode == RIFTCS_SAMPLE;
   for (int k0 = 0; k0 < K; k0 += RIFT_CTL_CHUNK) {
     CtlArr a; memset(&a, 0, sizeof(a));
     a.K = std::min(RIFT_CTL_CHUNK, K - k0); a.G = (int)G; a.Tfull = Tfull; a.topk = topk; a.interval = sample_interval;
+    if (sample) a.inv_t = riftcs_inv_temperature(sel);
     for (int j = 0; j < a.K; ++j) {
       const RiftControlCBV& v = cbvs[k0 + j];
       CtlK& d = a.d[j];
@@ -766,13 +778,37 @@ int rift_control_tick(RiftCtx* c, const float* trajectory, const float* probabil
       d.state = pid_state + (size_t)v.slot * RIFT_CONTROL_STATE;
       d.dec = decision + (size_t)(k0 + j) * 8;
       d.ox = v.x; d.oy = v.y; d.ch = std::cos(v.heading); d.sh = std::sin(v.heading); d.speed = v.speed;
+      if (sample) d.u = u[k0 + j];
     }
-    if (G <= 64 * 2) hipLaunchKernelGGL(control_tick_kernel<2>, dim3(a.K), dim3(64), 0, st, a);
-    else if (G <= 64 * 4) hipLaunchKernelGGL(control_tick_kernel<4>, dim3(a.K), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(control_tick_kernel<16>, dim3(a.K), dim3(64), 0, st, a);
+    if (sample) control_tick_launch<true>(a, st);
+    else control_tick_launch<false>(a, st);
     HIPCHK(c, hipGetLastError());
   }
   return RIFT_OK;
+}
+
+int rift_control_tick(RiftCtx* c, const float* trajectory, const float* probability, const float* ref_free_trajectory, int Rb, int Tfull,
+                      const RiftControlCBV* cbvs, int K, int topk, int sample_interval, double* pid_state, int n_slots, double* decision,
+                      void* stream) {
+  if (!c) return RIFT_ERR_ARG;
+  return control_tick(c, "rift_control_tick", trajectory, probability, ref_free_trajectory, Rb, Tfull, cbvs, K, topk, sample_interval, pid_state,
+                      n_slots, nullptr, nullptr, decision, stream);
+}
+
+// ---- the choice of the executed candidate at run time (include/rift_select.h; select_params.h, control.h) ----------------------
+int riftcs_params_default(RiftSelectParams* out) {
+  if (!out) return RIFT_ERR_ARG;
+  riftcs_params_set_default(out);
+  return RIFT_OK;
+}
+
+int riftcs_control_tick(RiftCtx* c, const float* trajectory, const float* probability, const float* ref_free_trajectory, int Rb, int Tfull,
+                        const RiftControlCBV* cbvs, int K, int topk, int sample_interval, double* pid_state, int n_slots,
+                        const RiftSelectParams* params, const double* u, double* decision, void* stream) {
+  if (!c) return RIFT_ERR_ARG;
+  if (const char* why = riftcs_refusal(params, u, K)) { c->err = std::string("riftcs_control_tick: ") + why; return RIFT_ERR_ARG; }
+  return control_tick(c, "riftcs_control_tick", trajectory, probability, ref_free_trajectory, Rb, Tfull, cbvs, K, topk, sample_interval,
+                      pid_state, n_slots, params, u, decision, stream);
 }
 
 int rift_collate(RiftCtx* c, const RiftReplayArena* ar, const int32_t* scene_idx, int bs, int R_out,
@@ -857,5 +893,19 @@ int riftga_params_default(RiftAdvantageParams* out) { return rift::abi::riftga_p
 int riftga_arena_advantage(RiftCtx* ctx, const double* returns, const int32_t* r_count, const uint8_t* valid_mask, int n, int Rcap,
                            const RiftAdvantageParams* params, double* advantage, double* stats, void* stream) {
   return rift::abi::riftga_arena_advantage(ctx, returns, r_count, valid_mask, n, Rcap, params, advantage, stats, stream);
+}
+}  // extern "C"
+
+// The candidate-selection extension (include/rift_select.h), layered the same way: two exported symbols, defined once per library.
+#define RIFT_CS_FN(name) static_assert(std::is_same<decltype(&::name), decltype(&rift::abi::name)>::value, #name);
+RIFT_CS_FN(riftcs_params_default) RIFT_CS_FN(riftcs_control_tick)
+#undef RIFT_CS_FN
+extern "C" {
+int riftcs_params_default(RiftSelectParams* out) { return rift::abi::riftcs_params_default(out); }
+int riftcs_control_tick(RiftCtx* ctx, const float* trajectory, const float* probability, const float* ref_free_trajectory, int Rb, int Tfull,
+                        const RiftControlCBV* cbvs, int K, int topk, int sample_interval, double* pid_state, int n_slots,
+                        const RiftSelectParams* params, const double* u, double* decision, void* stream) {
+  return rift::abi::riftcs_control_tick(ctx, trajectory, probability, ref_free_trajectory, Rb, Tfull, cbvs, K, topk, sample_interval, pid_state,
+                                        n_slots, params, u, decision, stream);
 }
 }  // extern "C"

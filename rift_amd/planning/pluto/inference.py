@@ -34,6 +34,40 @@ def trim_candidates(candidate_trajectories: np.ndarray, probability: np.ndarray,
     return traj, score, orig, n_ref, n_mode
 
 
+def candidate_distribution(flat_logits: np.ndarray, topk: int, temperature: float):
+    """The distribution sample_candidate draws from (include/rift_select.h: kept set, weights, prefix sums):
+    -> (order, kept, w, c): `order` the `topk` largest logits by descending logit, ties to the lower flat index; `kept` the same flat
+    indices in ascending order; `w` (fp32) their weights expf((z - z_top) * r), r the fp32 reciprocal of the temperature; `c` (fp64) the
+    inclusive prefix sums of `w` in `kept` order, c[-1] = W."""
+    z = np.asarray(flat_logits, dtype=np.float32).reshape(-1)
+    order = np.argsort(-z, kind="stable")[:int(topk)]
+    kept = np.sort(order)
+    inv_t = np.float32(min(1.0 / float(temperature), float(np.finfo(np.float32).max)))
+    with np.errstate(under="ignore", invalid="ignore"):
+        w = np.exp(((z[kept] - z[order[0]]) * inv_t).astype(np.float32)).astype(np.float32)
+    return order, kept, w, np.cumsum(w.astype(np.float64))
+
+
+def sample_candidate(flat_logits: np.ndarray, topk: int, temperature: float, u: float) -> Tuple[int, int, float]:
+    """The host statement of the sampled choice (include/rift_select.h states the rule; the SAMPLE stage of control_tick_kernel is tested
+    against this function): among the `topk` largest of the flat logits, draw with weights expf((z - z_top) / T) in fp32 and prefix sums in
+    fp64 over ascending flat index -- the first kept candidate with a positive weight and u * W < c, the last such candidate if rounding
+    leaves none.  -> (flat index, position in the kept list by descending logit, probability w / W).
+    The ref-free rule is the caller's and comes first (PLUTO._decide): this function is asked only when a learned candidate is executed.
+    The ordering is a STABLE descending sort (exact ties to the lower flat index, as the device keeps them).  trim_candidates sorts with
+    numpy's default kind, which promises no order among equal logits: the two can differ in which of several equal logits at the edge of
+    the kept set is kept, and in the positions of equal logits inside it."""
+    order, kept, w, c = candidate_distribution(flat_logits, topk, temperature)
+    live = w > 0
+    hit = np.nonzero(live & (float(u) * c[-1] < c))[0]
+    drawable = np.nonzero(live)[0]
+    if hit.size == 0 and drawable.size == 0:           # (non-finite logits, outside the contract: the greedy top)
+        return int(order[0]), 0, float("nan")
+    j = int(hit[0]) if hit.size else int(drawable[-1])
+    flat = int(kept[j])
+    return flat, int(np.nonzero(order == flat)[0][0]), float(np.float64(w[j]) / c[-1])
+
+
 def global_to_local(global_trajectory: np.ndarray, origin: np.ndarray, angle: float) -> np.ndarray:
     """pluto.py:262-279: re-anchor the first point on the rear axle, rotate into the vehicle frame."""
     delta = origin - global_trajectory[0, :2]

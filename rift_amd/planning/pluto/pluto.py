@@ -18,7 +18,7 @@ import torch
 
 from rift_amd.planning.pluto.controller.pid_controller import PIDController
 from rift_amd.planning.pluto.feature_builder.pluto_feature import PlutoFeature
-from rift_amd.planning.pluto.inference import ControlSlots, global_to_local, trim_candidates
+from rift_amd.planning.pluto.inference import ControlSlots, global_to_local, sample_candidate, trim_candidates
 from rift_amd.planning.pluto.model.pluto_model import PlanningModel
 
 
@@ -265,6 +265,8 @@ class PLUTO(CBVBasePolicy):
     name = 'pluto'
     type = 'il'
     GROUP_OBJECTIVE = False      # True on the policies whose update is the RIFT / GRPO group objective: they read config['objective']
+    ACTION_SELECTION_KEYS = ('mode', 'temperature', 'seed')
+    ACTION_SELECTION_MODES = ('greedy', 'sample')
 
     def __init__(self, config, logger):
         if config.get('objective') is not None and not self.GROUP_OBJECTIVE:
@@ -296,9 +298,41 @@ class PLUTO(CBVBasePolicy):
         self._control_slots = ControlSlots()
         self._control_engine = None                            # the engine whose control_state() the slots index
         self._control_pinned = None                            # (K, 8) f64 pinned: the tick's one read-back
+        # config['action_selection']: which candidate a CBV executes, at run time -- what the reference spells as the arg-max of the learned
+        # score (rlft_pluto.py:169).  {'mode': 'sample'} draws it from the softmax over the kept logits at a temperature (include/rift_select.h
+        # states the rule) in train mode, unless get_action is asked to be deterministic; the policy owns the stream of uniform numbers, one
+        # per CBV and tick, so the host path and the device path make the same choices.  Without the key nothing is drawn.
+        self._selection = self._read_action_selection(config.get('action_selection'), config.get('seed', 0))
+        self._select_rng = np.random.default_rng(self._selection['seed']) if self._selection and self._selection['mode'] == 'sample' else None
         self.mode = 'eval'
         if self._render:
             self.reset_render_data()
+
+    @classmethod
+    def _read_action_selection(cls, section, default_seed):
+        """None without the section; else {'mode', 'temperature', 'seed'} with the defaults filled in (greedy, 1.0, the config's seed)."""
+        if section is None:
+            return None
+        unknown = sorted(set(section) - set(cls.ACTION_SELECTION_KEYS))
+        if unknown:
+            raise ValueError(f"config['action_selection']: unknown key(s) {unknown}; known: {list(cls.ACTION_SELECTION_KEYS)}")
+        mode = section.get('mode', 'greedy')
+        if mode not in cls.ACTION_SELECTION_MODES:
+            raise ValueError(f"config['action_selection']['mode'] = {mode!r}; known: {list(cls.ACTION_SELECTION_MODES)}")
+        temperature = float(section.get('temperature', 1.0))
+        if not np.isfinite(temperature) or temperature <= 0.0:
+            raise ValueError(f"config['action_selection']['temperature'] = {temperature!r}: a finite number above 0")
+        seed = section.get('seed', default_seed)
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0:
+            raise ValueError(f"config['action_selection']['seed'] = {seed!r}: an integer >= 0")
+        return {'mode': mode, 'temperature': temperature, 'seed': int(seed)}
+
+    def _draws(self, n: int, deterministic: bool) -> Optional[np.ndarray]:
+        """The uniform numbers of one environment's CBVs for this tick, in the tick's CBV order -- one per CBV, whether or not the ref-free
+        rule will fire -- or None when the choice is greedy: no 'sample' mode, not train mode, or a deterministic call."""
+        if self._select_rng is None or self.mode != 'train' or deterministic:
+            return None
+        return self._select_rng.random(n)
 
     # ---- state source ---------------------------------------------------------------------------------------------------
     @property
@@ -368,28 +402,40 @@ class PLUTO(CBVBasePolicy):
             cache[key] = out[key].cpu().numpy()
         return cache[key]
 
-    def _decide(self, out: Dict[str, torch.Tensor], index: int, env_id, cbv_id, state: CenterState) -> Candidates:
-        """pluto.py:142-194: trim, choose by learned score, PID control."""
+    def _decide(self, out: Dict[str, torch.Tensor], index: int, env_id, cbv_id, state: CenterState, u: Optional[float] = None) -> Candidates:
+        """pluto.py:142-194: trim, choose by learned score, PID control.  With `u` (config['action_selection'], _draws) a learned choice is
+        drawn instead (sample_candidate); the ref-free fallback comes first and is the greedy path's."""
         cand = self._host(out, "candidate_trajectories")[index].astype(np.float64)
         prob = self._host(out, "probability")[index]
         rf = self._host(out, "output_ref_free_trajectory")[index].astype(np.float64) if "output_ref_free_trajectory" in out else None
         origin = np.array([state.x, state.y], dtype=np.float64)
         kept, score, flat, _, n_mode = trim_candidates(cand, prob, origin, float(state.heading), rf, self._topk)
         best = int(score.argmax())
-        trajectory = kept[best, 1:]
+        chosen_flat, chosen_score, trajectory = int(flat[best]), score[best], kept[best, 1:]
+        if u is not None and chosen_flat != -1:
+            chosen_flat, _, chosen_score = sample_candidate(prob, self._topk, self._selection['temperature'], u)
+            if chosen_flat not in flat:
+                # equal logits at the edge of the kept set, and trim_candidates (no stable order) kept another of them: the drawn one joins the
+                # kept set behind the others, through the same transform, so that kept[best] is the executed path for the renderer too
+                r, m = divmod(chosen_flat, n_mode)
+                one = trim_candidates(cand[r:r + 1, m:m + 1], prob[r:r + 1, m:m + 1], origin, float(state.heading), None, 1)[0]
+                kept, score, flat = np.concatenate([kept, one]), np.append(score, chosen_score), np.append(flat, chosen_flat)
+            best = int(np.nonzero(flat == chosen_flat)[0][0])
+            trajectory = kept[best, 1:]
         local = global_to_local(trajectory, origin, float(state.heading))
         control = self.controllers[env_id][cbv_id].control_pid(local[:, :2], state.pid_speed())      # centre speed, pluto.py:252
-        return Candidates(control, trajectory, kept, score, flat, best, n_mode, prob, int(flat[best]), score[best])
+        return Candidates(control, trajectory, kept, score, flat, best, n_mode, prob, chosen_flat, chosen_score)
 
     # ---- the device path of _decide (config['device_control']) ----------------------------------------------------------------
     @property
     def device_control(self) -> bool:
         return self._device_control and not self._render
 
-    def _issue_control(self, env_id, CBVs_obs, out, states):
+    def _issue_control(self, env_id, CBVs_obs, out, states, draws=None):
         """One rift_control_tick for the environment's CBVs on the current stream, behind its forward, and the asynchronous copy of the
         (K, 8) decision buffer into pinned memory; returns the event behind that copy.  Slots released since the last tick are zeroed
-        first, on the same stream, and only then handed out again."""
+        first, on the same stream, and only then handed out again.  With `draws` (config['action_selection'], _draws) the call is
+        riftcs_control_tick in SAMPLE mode."""
         eng = self.pluto_model._engine
         if self._control_engine is not eng:                    # the model re-bound (precision / device change): the controller state moves along
             if self._control_engine is not None:
@@ -403,8 +449,9 @@ class PLUTO(CBVBasePolicy):
         for index, cbv_id in enumerate(CBVs_obs):
             st = states[cbv_id]
             cbvs.append((index, slots.slot((env_id, cbv_id)), st.x, st.y, st.heading, st.pid_speed()))
+        select = {} if draws is None else {'select': {'mode': 'sample', 'temperature': self._selection['temperature']}, 'u': draws}
         decision = eng.control_tick(out["trajectory"], out["probability"], out.get("ref_free_trajectory"), cbvs, topk=self._topk,
-                                    sample_interval=self._frame_rate)
+                                    sample_interval=self._frame_rate, **select)
         K = len(cbvs)
         if self._control_pinned is None or self._control_pinned.shape[0] < K:
             self._control_pinned = torch.empty(max(K, 16), 8, dtype=torch.float64).pin_memory()
@@ -462,12 +509,14 @@ class PLUTO(CBVBasePolicy):
             states = {cbv_id: self.state_source.center_state(env_id, cbv_id) for cbv_id in CBVs_obs}
             # device path: the decisions are issued AHEAD of a variant's own device work (_begin_env: the group advantages, same stream) and
             # read behind it, so the controls do not wait for the advantages
-            issued = self._issue_control(env_id, CBVs_obs, out, states) if self.device_control else None
+            draws = self._draws(len(CBVs_obs), deterministic)
+            issued = self._issue_control(env_id, CBVs_obs, out, states, draws) if self.device_control else None
             self._begin_env(env_id, CBVs_obs, data, out, states)
             decisions = self._read_control(issued, out) if issued is not None else None
             for index, (cbv_id, obs) in enumerate(CBVs_obs.items()):
                 state = states[cbv_id]
-                decision = decisions[index] if decisions is not None else self._decide(out, index, env_id, cbv_id, state)
+                decision = decisions[index] if decisions is not None else \
+                    self._decide(out, index, env_id, cbv_id, state, None if draws is None else float(draws[index]))
                 result['CBVs_actions'][env_id][cbv_id] = decision.control
                 for key, value in self._per_cbv(env_id, cbv_id, obs, data, out, index, state, decision).items():
                     result[key][env_id][cbv_id] = value

@@ -2,10 +2,13 @@
 -> PID) and of RIFTPluto in train mode (that + the device-side group advantage of every CBV: rollout, neighbour forecast, collision and
 off-road flags, return, z-score) for K CBVs of one environment at the CARLA shapes (49 agent slots, 60 polygon slots, 1..6 reference
 lines): host wall time per tick (the caller waits for the controls), median / p90 of N ticks.
-    python tools/tick_latency.py [--ticks 60] [--cbvs 1,2,4,8] [--profile rift_pluto/4] [--device-control] [--traj-eval '{"breakdown": true}']
+    python tools/tick_latency.py [--ticks 60] [--cbvs 1,2,4,8] [--profile rift_pluto/4] [--device-control] [--sample] [--traj-eval '{"breakdown": true}']
 --traj-eval: the policies' config['traj_eval'] section as JSON (reward model and evaluator settings at run time, the per-term breakdown).
 --device-control: the A/B of config['device_control'] (candidate choice + waypoint PID in one device call, rift_control_tick) in ONE process:
 the host leg, the device leg, the host leg again (its run-to-run spread is the yardstick of the difference).
+--sample: config['action_selection'] = {'mode': 'sample'} on every leg (the executed candidate is drawn, include/rift_select.h); it shows on
+the policies that tick in train mode (rift_pluto), since eval-mode ticks stay greedy: run with and without it for the cost of the stage.
+--policies: a comma-separated subset of pluto,rift_pluto; it selects the policies of the --device-control legs as well as of the plain run.
 --drivable-map: the A/B of config['traj_eval']['off_road'] on rift_pluto in train mode, in ONE process: the raster leg (a mask per CBV goes up
 every tick), the map leg (a seeded town of --map-polygons lane polygons on the device, poses go up), the raster leg again; then the one-time
 cost of loading that map.  The raster leg's mask is drawn once, ahead of the ticks: the host draw the map removes is in neither leg."""
@@ -75,7 +78,7 @@ def _ticks(n, ids):
 
 
 def run(ticks=40, cbvs=(1, 8), precision="fp16", policies=(("pluto", "eval"), ("rift_pluto", "train")), profile="", verbose=False,
-        device_control=False, traj_eval=None, polygons=None):
+        device_control=False, traj_eval=None, polygons=None, sample=False):
     """{"<policy>/<mode>/K=<k>": {"median_ms", "p90_ms", "min_ms"}}"""
     from rift_amd.planning import CBV_POLICY_LIST
     from rift_amd.planning.pluto.model.pluto_model import PlanningModel
@@ -90,6 +93,8 @@ def run(ticks=40, cbvs=(1, 8), precision="fp16", policies=(("pluto", "eval"), ("
                    'compute_precision': precision, 'device_control': bool(device_control)}
             if traj_eval is not None:
                 cfg['traj_eval'] = traj_eval
+            if sample:
+                cfg['action_selection'] = {'mode': 'sample', 'temperature': 1.0, 'seed': 0}
             pol = CBV_POLICY_LIST[name](cfg, None)
             pol.pluto_model.load_state_dict(sd)
             pol.set_mode(mode)
@@ -129,6 +134,7 @@ def main():
     ap.add_argument("--precision", default="fp16")
     ap.add_argument("--profile", default="", help="policy/K to run under cProfile instead, e.g. rift_pluto/4")
     ap.add_argument("--device-control", action="store_true", help="A/B of config['device_control']: host, device, host again, in this process")
+    ap.add_argument("--sample", action="store_true", help="config['action_selection'] = {'mode': 'sample'}: train-mode ticks draw the executed candidate")
     ap.add_argument("--traj-eval", default="", help="config['traj_eval'] as JSON, e.g. '{\"breakdown\": true}'")
     ap.add_argument("--policies", default="", help="comma-separated subset of pluto,rift_pluto")
     ap.add_argument("--drivable-map", action="store_true", help="A/B of config['traj_eval']['off_road']: raster, map, raster again, in this process")
@@ -155,16 +161,18 @@ def main():
         legs["map_load"] = {"ms": [round(x, 3) for x in loads], "info": info}
         print(json.dumps(legs))
         return
+    policies = tuple(p for p in (("pluto", "eval"), ("rift_pluto", "train")) if not args.policies or p[0] in args.policies.split(","))
     if args.device_control:
         legs = {}
         for leg, on in (("host", False), ("device", True), ("host_again", False)):
             print(f"-- {leg} leg (device_control={on})", flush=True)
-            legs[leg] = run(args.ticks, [int(k) for k in args.cbvs.split(",")], args.precision, profile=args.profile, verbose=True, device_control=on, traj_eval=traj_eval)
+            legs[leg] = run(args.ticks, [int(k) for k in args.cbvs.split(",")], args.precision, policies=policies, profile=args.profile, verbose=True,
+                            device_control=on, traj_eval=traj_eval, sample=args.sample)
         if not args.profile:
             print(json.dumps(legs))
         return
-    policies = tuple(p for p in (("pluto", "eval"), ("rift_pluto", "train")) if not args.policies or p[0] in args.policies.split(","))
-    out = run(args.ticks, [int(k) for k in args.cbvs.split(",")], args.precision, policies=policies, profile=args.profile, verbose=True, traj_eval=traj_eval)
+    out = run(args.ticks, [int(k) for k in args.cbvs.split(",")], args.precision, policies=policies, profile=args.profile, verbose=True, traj_eval=traj_eval,
+              sample=args.sample)
     if out:
         print(json.dumps(out))
 

@@ -13,6 +13,8 @@
  *   - all work is enqueued on the hipStream_t passed by the caller (void*; NULL = the
  *     default stream); no hidden synchronisation unless stated.
  *   - return value: 0 = ok, <0 = error; message via rift_last_error().
+ *     A refused call leaves a message that names the entry called; an accepted call leaves
+ *     an empty one.
  *   - one context per (process, device); not thread-safe.
  */
 #ifndef RIFT_HIP_H

@@ -1,5 +1,5 @@
-// Launch bookkeeping and error macros on the format-free core of a context (ctx_core.h), for the units that launch kernels: the engine
-// builds and shared.hip.
+// Launch bookkeeping, error macros and the call protocol of an entry on the format-free core of a context (ctx_core.h), for the units
+// that launch kernels: the engine builds and shared.hip.
 #pragma once
 #include "ctx_core.h"
 
@@ -27,6 +27,18 @@ namespace {
 const std::string NOT_LOADED = ": no model is loaded (rift_model_load is missing, or the last one failed)";
 
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// The call protocol of an entry that launches, allocates or copies (every one of shared.hip): `if (!c) return RIFT_ERR_ARG;`, the message
+// cleared, its refusals (host only, each with a message that names the entry called), call_open, its work, call_close -- in that order.  So a
+// refused call leaves its own message, an accepted one an empty message, and every launch is on the context's device and the call's stream.
+// (c->stream is the call's alone: no entry of the library launches on a value an earlier call left there -- profiles/NOTES_r28.md has the list.)
+inline int refuse(RiftCtxCore* c, const char* entry, const std::string& why, int code = RIFT_ERR_ARG) { c->err = std::string(entry) + ": " + why; return code; }
+inline int call_open(RiftCtxCore* c, void* stream) {
+  c->err.clear(); c->stream = (hipStream_t)stream; c->dry = false;
+  HIPCHK(c, hipSetDevice(c->device));
+  return RIFT_OK;
+}
+inline int call_close(RiftCtxCore* c) { HIPCHK(c, hipGetLastError()); return RIFT_OK; }
 
 inline void prof_events(RiftCtxCore* c, hipEvent_t* e0, hipEvent_t* e1) {
   while (c->prof_pool.size() < c->prof_used + 2) { hipEvent_t e; (void)hipEventCreate(&e); c->prof_pool.push_back(e); }
@@ -57,7 +69,7 @@ inline void delay_behind(RiftCtxCore* c, const char* label) {
   if (c->dg.delay_ticks > 0 && c->dg.delay_label == label) hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(1), 0, c->stream, c->dg.delay_ticks);
 }
 
-// the bookkeeping around one launch (the callable): LDS poison ahead of it, profiling events around it, the diagnostic delay behind it
+// the bookkeeping around one launch (the callable) on c->stream: LDS poison ahead of it, profiling events around it, the diagnostic delay behind it
 template <class F>
 void launch_call(RiftCtxCore* c, const char* label, F&& f) {
   if (c->dry) return;
@@ -79,8 +91,10 @@ void launch_call(RiftCtxCore* c, const char* label, F&& f) {
   delay_behind(c, label);
 }
 
+// every kernel launch of shared.hip and the single-kernel launches of the engine; `label` is the kernel's name, one per kernel whatever the
+// instantiation.  (arguments by reference: the ticks' descriptor arrays are a few KB)
 template <class... KArgs, class... Args>
-void launch(RiftCtxCore* c, const char* label, void (*kern)(KArgs...), dim3 grid, dim3 block, size_t shmem, Args... args) {
+void launch(RiftCtxCore* c, const char* label, void (*kern)(KArgs...), dim3 grid, dim3 block, size_t shmem, const Args&... args) {
   if (grid.x == 0 || grid.y == 0) return;
   launch_call(c, label, [&] { hipLaunchKernelGGL(kern, grid, block, shmem, c->stream, static_cast<KArgs>(args)...); });
 }

@@ -32,6 +32,7 @@ struct DropStats {
   float* scale;                 // [RIFT_DS_SITES + RIFT_DS_DEC_SITES] keep multiplier 1 / (1 - p) as the kernel used it
   unsigned long long* elem;     // [RIFT_DS_DEC_SITES][2] kept, drawn
   int nmax;
+  unsigned int* skip;           // [8] half-blocks the DropPath grouping skipped: (tile, block, branch) of NAT level 1, then (workgroup round, block, branch) of level 2
 };
 
 #if RIFT_DROP_STATS
@@ -43,8 +44,12 @@ __device__ __forceinline__ void ds_sample(const DropStats& d, int site, int samp
   atomicAnd(&d.all[i], mult != 0.f ? 0xffffffffu : 0u);
   if (mult != 0.f) d.scale[site] = mult;
 }
+__device__ __forceinline__ void ds_skip(const DropStats& d, int slot, bool on) {
+  if (d.skip && on) atomicAdd(&d.skip[slot], 1u);
+}
 #else
 __device__ __forceinline__ void ds_sample(const DropStats&, int, int, float) {}
+__device__ __forceinline__ void ds_skip(const DropStats&, int, bool) {}
 #endif
 
 }  // namespace RIFT_NS

@@ -547,6 +547,9 @@ int dp_mask_and_drop_counters(Fwd& f) {
     }
     tap(c, "drop_cnt", (float*)f.ds.cnt, (int64_t)n); tap(c, "drop_any", (float*)f.ds.any, (int64_t)n); tap(c, "drop_all", (float*)f.ds.all, (int64_t)n);
     tap(c, "drop_scale", f.ds.scale, RIFT_DS_SITES + RIFT_DS_DEC_SITES); tap(c, "drop_elem", (float*)f.ds.elem, 4 * RIFT_DS_DEC_SITES);
+    f.ds.skip = A_alloc<unsigned int>(c, 8);      // half-blocks the DropPath grouping of NAT levels 1 and 2 skipped
+    if (!c->dry) HIPCHK(c, hipMemsetAsync(f.ds.skip, 0, 8 * 4, c->stream));
+    tap(c, "nat_skip", (float*)f.ds.skip, 8);
   }
 #endif
   if (f.kp.nat_compact) { tap(c, "nat_aidx", (float*)f.nat_aidx, nA); tap(c, "nat_cnt", (float*)f.nat_cnt, 3); }      // (int32 words read back through the float tap)
@@ -569,6 +572,12 @@ void history_encoder(Fwd& f) {
   if (f.kp.hist_wave) {
     // one launch per level: [ConvTokenizer ->] 2 NAT blocks -> {FPN LayerNorm of the last 3 steps, downsample conv + LN}
     float* Xin[3] = {nullptr, A_alloc<float>(c, (size_t)nA * 10 * 64), A_alloc<float>(c, (size_t)nA * 5 * 128)};
+    // DropPath grouping: the two lists block 0 of level 0's launch makes for levels 1 and 2 (nat_l0w.h: nat_group_body), -1 = no sequence
+    const bool group = f.kp.nat_group;
+    const int cap1 = 4 * cdiv(nA + 2, 4), cap2 = 3 * cdiv(nA, 3);
+    int* perm1 = group ? A_alloc<int>(c, cap1) : nullptr;
+    int* perm2 = group ? A_alloc<int>(c, cap2) : nullptr;
+    if (group) { tap(c, "nat_perm1", (float*)perm1, cap1); tap(c, "nat_perm2", (float*)perm2, cap2); }      // (int32 words read back through the float tap)
     for (int lv = 0; lv < 3; ++lv) {
       const int C = NAT_C[lv], ksz = Kl[lv], L = NAT_L[lv], rows = nA * L;
       if (lv == 0) {   // level 0 as wave-private, register-resident tiles (no workgroup barriers): nat_l0w.h
@@ -578,13 +587,18 @@ void history_encoder(Fwd& f) {
         { if (c->sw.nat_ts == 1) { q.ts = A_alloc<long long>(c, 64); tap(c, "nat_ts", (float*)q.ts, 128); } }
         q.droppath[0] = f.drop ? NAT_DPR[0] : 0.f; q.droppath[1] = f.drop ? NAT_DPR[1] : 0.f; q.seed = f.seed; q.stream = f.next_stream(); f.stream_id += 4;
         q.ds = f.ds;
+        if (group) {      // (levels 1 and 2 take the next two stream numbers: four each)
+          q.perm1 = perm1; q.perm2 = perm2; q.cap1 = cap1; q.cap2 = cap2; q.gstream[0] = q.stream + 5; q.gstream[1] = q.stream + 10;
+          for (int i = 0; i < 4; ++i) q.gdpr[i] = NAT_DPR[2 + i];
+        }
         c->prof_flops = 2.0 * rows * (20.0 * C * C + 4.0 * ksz * C) + 2.0 * rows * 27 * 32 + (rows / 2) * 2.0 * 3 * C * 2 * C;
-        { const int g0 = std::min(cdiv(cdiv(nA, 4), L0W_NWV), c->sw.nat_grid); launch_call(c, "nat_l0w_kernel", [&] { l0w_launch(q, g0, c->stream); }); }
+        // (grouped: one block more, the lists', inside the same bound on the launch's workgroups)
+        { const int g0 = std::min(cdiv(cdiv(nA, 4), L0W_NWV), std::max(c->sw.nat_grid - (group ? 1 : 0), 1)) + (group ? 1 : 0); launch_call(c, "nat_l0w_kernel", [&] { l0w_launch(q, g0, c->stream); }); }
         continue;
       }
       if (lv == 1) {   // level 1 likewise (weights swapped through LDS between the two layers): nat_l1w.h
         NatL1WP q; memset(&q, 0, sizeof(q));
-        q.cnt = f.nat_cnt;
+        q.cnt = f.nat_cnt; q.perm = perm1;
         q.X = Xin[1]; q.nseq = nA; q.img = c->img.l1w_img.get(); q.par = c->img.l1w_par.get(); q.Oc = Oc[1]; q.Ocb = Ocb[1]; q.Xnext = Xin[2];
         q.droppath[0] = f.drop ? NAT_DPR[2] : 0.f; q.droppath[1] = f.drop ? NAT_DPR[3] : 0.f; q.seed = f.seed; q.stream = f.next_stream(); f.stream_id += 4;
         q.ds = f.ds;
@@ -594,7 +608,7 @@ void history_encoder(Fwd& f) {
       }
       {   // level 2: wave-private tiles of 3 agents, the two layers' weights streamed through LDS (nat_l2w.h)
         NatL2WP q; memset(&q, 0, sizeof(q));
-        q.cnt = f.nat_cnt;
+        q.cnt = f.nat_cnt; q.perm = perm2;
         q.X = Xin[2]; q.nseq = nA; q.img = c->img.l2w_img.get(); q.par = c->img.l2w_par.get(); q.Oc = Oc[2]; q.Ocb = Ocb[2];
         q.droppath[0] = f.drop ? NAT_DPR[4] : 0.f; q.droppath[1] = f.drop ? NAT_DPR[5] : 0.f; q.seed = f.seed; q.stream = f.next_stream(); f.stream_id += 4;
         q.ds = f.ds;
@@ -906,7 +920,7 @@ KernelIn kernel_in(const Ctx* c, const RiftFeatureBatch* B, const RiftOutputs* o
   in.nat_fused = sw.nat_fused; in.dec_fused = sw.dec_fused; in.enc_fused = sw.enc_fused; in.pe_fused = sw.pe_fused; in.fo_fused = sw.fo_fused;
   in.fpn_fused = sw.fpn_fused; in.ego_fused = sw.ego_fused; in.heads_fused = sw.heads_fused; in.pi_fused = sw.pi_fused;
   in.fo_w = sw.fo_w; in.pe_w = sw.pe_w; in.nat_compact = sw.nat_compact; in.pe_live = sw.pe_live; in.pe_pack = sw.pe_pack;
-  in.rank_in_prep = sw.rank_in_prep; in.enc112 = sw.enc112;
+  in.rank_in_prep = sw.rank_in_prep; in.enc112 = sw.enc112; in.nat_group = sw.nat_group; in.no_skip = sw.no_skip;
   in.dec_defer_max = sw.dec_defer_max; in.dec_split = sw.dec_split; in.dec_layers = sw.dec_layers; in.dec_ts = sw.dec_ts != 0;
   in.fp32 = (flags & RIFT_F_FP32) != 0; in.train = (flags & RIFT_F_TRAIN) != 0; in.drop = in.train && !(flags & RIFT_F_NO_DROP);
   in.need_traj = (flags & RIFT_F_NEED_TRAJ) != 0; in.want_traj = out->trajectory != nullptr;
@@ -1014,6 +1028,7 @@ static void read_switches(Ctx* c) {
   env_flag("RIFT_PE_PACK", &c->sw.pe_pack);                  // 0: reference lines of pass B in two-line rounds instead of packed valid-prefix tiles
   env_flag("RIFT_RANK_IN_PREP", &c->sw.rank_in_prep);        // 0: the ranking as its own launch behind the preparation (nat_rank_kernel)
   env_flag("RIFT_NO_SKIP", &c->sw.no_skip);                  // 1: compute, then discard (dropped encoder branches, padded reference lines of the decoder)
+  env_flag("RIFT_NAT_GROUP", &c->sw.nat_group);              // 0: NAT levels 1 and 2 in rank order, no DropPath grouping
   env_flag("RIFT_ENC112", &c->sw.enc112);                    // 0: scenes of 97 .. 112 token slots on enc_w_kernel
   env_flag("RIFT_RANK_FAULT", &c->sw.rank_fault);            // 1 (diagnostic): the first scene block of the in-launch ranking never publishes
   env_int("RIFT_SIDE_GATE", &c->sw.side_gate);               // 1: both front chains behind the caller's queue (fwd_plan.h)

@@ -62,6 +62,7 @@ struct Ctx : RiftCtx {
     bool no_skip = false;                  // RIFT_NO_SKIP=1: the scene encoder computes the branches DropPath drops and the decoder the padded reference lines' discarded
                                            // sub-blocks, as until round 7 (the reference of tests/test_gpu_skip_discarded.py and the "before" leg of the A/B in one binary)
     bool enc112 = true;                    // RIFT_ENC112=0: scenes of 97 .. 112 token slots on enc_w_kernel (rounds 3 - 5) instead of the fused kernel's 112-row layout
+    bool nat_group = true;                 // RIFT_NAT_GROUP=0: NAT levels 1 and 2 in rank order, every half-block computed (the path RIFT_NO_SKIP=1 also takes)
     bool rank_in_prep = true;              // RIFT_RANK_IN_PREP=0: the ranking as its own launch behind the preparation (nat_rank_kernel, rounds 3 - 5)
     // the per-call diagnostic switches: RIFT_{PE,PEW,NAT,ENC,DEC}_TS, RIFT_{PEW,DEC}_DBG, RIFT_POISON_ARENA
     int pe_ts = -1, pew_dbg = 0, pew_ts = 0, nat_ts = 0, enc_ts = 0, dec_ts = 0, dec_dbg = 0, poison_arena = -1;

@@ -22,6 +22,8 @@ struct KernelIn {
   bool forked;                 // StreamPlan::forked of the launch pass (fwd_plan.h)
   int bs, A, Mp, S, R;         // the batch shape; token slots N = A + Mp + S
   int enc_nw;                  // build constant: the waves of enc_fused_kernel (ENC_NW); only the eight-wave build emits the decoder's operands
+  // RIFT_NAT_GROUP (0: off) and RIFT_NO_SKIP (1: nothing a DropPath drop would skip is skipped): the history encoder's DropPath grouping
+  bool nat_group = true, no_skip = false;
 };
 
 enum PePath { PE_LAYERWISE = 0, PE_PAIR_MID, PE_PAIR_W };            // one encoder after the other; the pair with pe_mid_kernel / pe_w_kernel as pass B
@@ -37,6 +39,7 @@ struct KernelPlan {
   bool fpn_fused;              // fpn_tail_kernel, and with it the levels' Oc rows as 16-bit operand words
   bool nat_compact;            // the history chain on the compacted valid sequences
   bool rank_in_prep;           // ... ranked by the first blocks of prep_kernel instead of nat_rank_kernel
+  bool nat_group;              // levels 1 and 2 take their sequences grouped by DropPath pattern and skip what a whole tile / round drops (nat_l0w.h: nat_group_body)
   bool ego_fused;
   // map chain
   PePath pe;
@@ -73,6 +76,9 @@ inline KernelPlan plan_kernels(const KernelIn& in) {
   p.fpn_fused = p.hist_wave && in.fpn_fused;
   p.nat_compact = p.fpn_fused && in.nat_compact;
   p.rank_in_prep = p.nat_compact && in.rank_in_prep && in.A <= 256;
+  // a train-mode forward with drops on the compacted wave-private chain (the lists are made from the class counts); else the levels get no
+  // list: rank order and every half-block computed
+  p.nat_group = p.nat_compact && in.drop && in.nat_group && !in.no_skip;
   p.ego_fused = bf && in.ego_fused;
   // ---- PointsEncoders
   p.pe = !(bf && in.pe_fused) ? PE_LAYERWISE : (in.pe_w ? PE_PAIR_W : PE_PAIR_MID);

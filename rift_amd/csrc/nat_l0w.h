@@ -146,6 +146,10 @@ struct NatL0WP {
   // (agent_encoder.py:77-80 runs it on agent_feature[valid_agent_mask]; the ego row is replaced at :87), ranked per residue class of the
   // agent slot (common.h: SeqCount) -- rank r is sequence r of this and the next levels' buffers and reads the features of slot aidx[r]
   const int* aidx; const int* cnt;
+  // DropPath grouping of levels 1 and 2 (fwd_kernels.h: nat_group; nat_group_body below): if perm1 is set, block 0 of this launch does no
+  // tile -- it lists the live ranks for nat_l1w_kernel (perm1) and nat_l2w_kernel (perm2), the other blocks are the level's workgroups
+  int* perm1; int* perm2; int cap1, cap2;  // cap: the ints of each list (a multiple of 4 / of 3)
+  float gdpr[4]; uint32_t gstream[2];      // the DropPath rates of level 1's and level 2's two blocks, the levels' stream numbers
   DropStats ds;                            // diagnostic build only (dropstats.h)
 };
 
@@ -190,10 +194,60 @@ __device__ __forceinline__ void l0w_layer_norm(const f32x4 (&x)[5][2], h16x8 (&x
   }
 }
 
+// A level's DropPath pattern of a sequence as its sort key.  Pattern bits: block 0 attention, block 0 MLP, block 1 attention, block 1 MLP
+// (the decisions nat_l1w_kernel / nat_l2w_kernel take: uniform01(seed, stream + 2 bi (+ 1), seq) < rate); the key is the pattern's place
+// in the Gray sequence i ^ (i >> 1), so that neighbouring buckets differ in ONE branch.
+__device__ __forceinline__ int nat_gray_key(uint32_t seed, uint32_t stream, const float* dpr, uint32_t seq) {
+  int pat = 0;
+#pragma unroll
+  for (int bi = 0; bi < 2; ++bi) {
+    if (dpr[bi] > 0.f) {
+      pat |= (uniform01(seed, stream + 2 * bi, seq) < dpr[bi]) ? (1 << (2 * bi)) : 0;
+      pat |= (uniform01(seed, stream + 2 * bi + 1, seq) < dpr[bi]) ? (2 << (2 * bi)) : 0;
+    }
+  }
+  pat ^= pat >> 1; pat ^= pat >> 2;
+  return pat;
+}
+// The two lists of the DropPath grouping, by ONE workgroup: a counting sort of the live ranks by (position class, key).  A sequence keeps
+// its lane rows: list entry k of perm1 belongs to class k % 4 = seq % 4 (level 1's four agent rows), of perm2 to class k % 3 = seq % 3
+// (level 2's three; common.h: SeqCount says why the position matters there); tile t takes the t-th entry of every class.  Order inside a
+// bucket is whatever the LDS atomics make it -- nothing a result depends on.  Entries behind a class's live ranks are holes (-1).
+__device__ __forceinline__ void nat_group_body(const NatL0WP& p, int* sh) {
+  int* hist = sh; int* base = sh + 112; int* count = sh + 224;      // bins: 4 classes x 16 keys of perm1, then 3 x 16 of perm2
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  RIFT_SEQ_COUNT(p.cnt, p.nseq);
+  for (int i = tid; i < 232; i += nthr) sh[i] = 0;
+  __syncthreads();
+  for (int r = tid; r < sq_n; r += nthr) {
+    if (!RIFT_SEQ_LIVE(r)) continue;
+    atomicAdd(&hist[(r & 3) * 16 + nat_gray_key(p.seed, p.gstream[0], p.gdpr, (uint32_t)r)], 1);
+    atomicAdd(&hist[64 + (r % 3) * 16 + nat_gray_key(p.seed, p.gstream[1], p.gdpr + 2, (uint32_t)r)], 1);
+  }
+  __syncthreads();
+  if (tid < 7) {
+    int acc = 0;
+    for (int k = 0; k < 16; ++k) { base[tid * 16 + k] = acc; acc += hist[tid * 16 + k]; }
+    count[tid] = acc;
+  }
+  __syncthreads();
+  for (int r = tid; r < sq_n; r += nthr) {
+    if (!RIFT_SEQ_LIVE(r)) continue;
+    const int i1 = atomicAdd(&base[(r & 3) * 16 + nat_gray_key(p.seed, p.gstream[0], p.gdpr, (uint32_t)r)], 1);
+    const int i2 = atomicAdd(&base[64 + (r % 3) * 16 + nat_gray_key(p.seed, p.gstream[1], p.gdpr + 2, (uint32_t)r)], 1);
+    p.perm1[i1 * 4 + (r & 3)] = r;
+    p.perm2[i2 * 3 + r % 3] = r;
+  }
+  for (int k = tid; k < p.cap1; k += nthr) if ((k >> 2) >= count[k & 3]) p.perm1[k] = -1;
+  for (int k = tid; k < p.cap2; k += nthr) if (k / 3 >= count[4 + k % 3]) p.perm2[k] = -1;
+}
+
 __global__ __launch_bounds__(64 * L0W_NWV) void nat_l0w_kernel(NatL0WP p) {
   constexpr int NTHR = 64 * L0W_NWV;
   constexpr int L = 20;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  if (p.perm1 && blockIdx.x == 0) { nat_group_body(p, reinterpret_cast<int*>(smem_raw)); return; }
+  const int wb = (int)blockIdx.x - (p.perm1 ? 1 : 0), nwb = (int)gridDim.x - (p.perm1 ? 1 : 0);      // this workgroup among those that run tiles
   unsigned short* wl = reinterpret_cast<unsigned short*>(smem_raw);            // [54][64][8] weight fragments
   float* par = reinterpret_cast<float*>(wl + L0W_NFRAG * 512);
   unsigned short* stg = reinterpret_cast<unsigned short*>(par + L0W_NPAR);
@@ -210,10 +264,10 @@ __global__ __launch_bounds__(64 * L0W_NWV) void nat_l0w_kernel(NatL0WP p) {
   const int a = l15 >> 2, s = l15 & 3;
   const int ntiles = (sq_n + 3) >> 2;
   int tsn = 0;
-#define L0TS() do { if (p.ts && blockIdx.x == 0 && tid == 0 && tsn < 60) p.ts[tsn++] = clock64(); } while (0)
+#define L0TS() do { if (p.ts && wb == 0 && tid == 0 && tsn < 60) p.ts[tsn++] = clock64(); } while (0)
   L0TS();
 
-  for (int tile = blockIdx.x * L0W_NWV + wave; tile < ntiles; tile += gridDim.x * L0W_NWV) {
+  for (int tile = wb * L0W_NWV + wave; tile < ntiles; tile += nwb * L0W_NWV) {
     const int seq = tile * 4 + a;
     const bool seq_ok = RIFT_SEQ_LIVE(seq);
     f32x4 x[5][2];

@@ -111,6 +111,7 @@ struct NatL1WP {
   float* Xnext;                            // (nseq * 5, 128) downsample conv + LayerNorm
   float droppath[2]; uint32_t seed, stream;
   const int* cnt;                          // if set: the three class counts of the compacted launch (nat_l0w.h; common.h: SeqCount); nseq is the bound
+  const int* perm;                         // if set: the DropPath grouping's list (nat_l0w.h: nat_group_body) -- lane row a of tile t works on sequence perm[4 t + a], -1 = none
   DropStats ds;                            // diagnostic build only (dropstats.h)
 };
 
@@ -179,8 +180,10 @@ __global__ __launch_bounds__(64 * L1W_NWV) void nat_l1w_kernel(NatL1WP p) {
 
   for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
     const int tile = grp * L1W_NWV + wave;
-    const int seq = tile * 4 + a;
-    const bool seq_ok = RIFT_SEQ_LIVE(seq);
+    // grouped: the tile's sequences come from the list (the same lane rows seq % 4, tiles of one DropPath pattern), every buffer stays
+    // indexed by seq; a half-block that DropPath drops for all four takes the wave-uniform branch around it below
+    const int seq = !p.perm ? tile * 4 + a : tile < ntiles ? p.perm[tile * 4 + a] : -1;
+    const bool seq_ok = p.perm ? seq >= 0 : RIFT_SEQ_LIVE(seq);
     f32x4 x[3][4];
 #pragma unroll
     for (int mt = 0; mt < 3; ++mt) {
@@ -198,11 +201,21 @@ __global__ __launch_bounds__(64 * L1W_NWV) void nat_l1w_kernel(NatL1WP p) {
       load_weights(bi * L1W_BLK_FRAGS, L1W_BLK_FRAGS);
       const float* pb = par + L1W_P_BLK(bi);
       h16x8 xn[3][2];
+      float dps = 1.f, dp2 = 1.f;
+      if (p.droppath[bi] > 0.f) {
+        dps = (uniform01(p.seed, p.stream + 2 * bi, (uint32_t)seq) < p.droppath[bi]) ? 0.f : 1.0f / (1.0f - p.droppath[bi]);
+        dp2 = (uniform01(p.seed, p.stream + 2 * bi + 1, (uint32_t)seq) < p.droppath[bi]) ? 0.f : 1.0f / (1.0f - p.droppath[bi]);
+        ds_sample(p.ds, RIFT_DS_NAT(1, bi, 0), seq_ok ? seq : -1, dps);
+        ds_sample(p.ds, RIFT_DS_NAT(1, bi, 1), seq_ok ? seq : -1, dp2);
+      }
+      // a half-block dropped for every sequence of the tile (a hole counts as dropped) leaves x as it is: x + 0 * branch
+      const bool skip_att = p.perm && __builtin_amdgcn_ballot_w64(seq_ok && dps != 0.f) == 0ull;
+      const bool skip_mlp = p.perm && __builtin_amdgcn_ballot_w64(seq_ok && dp2 != 0.f) == 0ull;
+      ds_skip(p.ds, bi * 2, skip_att && tile < ntiles && lane == 0);
+      ds_skip(p.ds, bi * 2 + 1, skip_mlp && tile < ntiles && lane == 0);
       // ================= attention half =================
+      if (!skip_att) {
       l1w_layer_norm(x, xn);
-      float dps = 1.f;
-      if (p.droppath[bi] > 0.f) dps = (uniform01(p.seed, p.stream + 2 * bi, (uint32_t)seq) < p.droppath[bi]) ? 0.f : 1.0f / (1.0f - p.droppath[bi]);
-      if (p.droppath[bi] > 0.f) ds_sample(p.ds, RIFT_DS_NAT(1, bi, 0), seq_ok ? seq : -1, dps);
       // neighbourhood attention on the matrix pipe (nat_l0w.h describes the scheme): 4 heads x 3 row tiles, K = 16 MFMAs
       const int trow = (l4 == a) ? s : 4;
 #pragma unroll 1
@@ -257,9 +270,10 @@ __global__ __launch_bounds__(64 * L1W_NWV) void nat_l1w_kernel(NatL1WP p) {
 #pragma unroll
         for (int mt = 0; mt < 3; ++mt) x[mt][nt] += (f32x4){b4.x, b4.y, b4.z, b4.w} * dps;
       }
+      }
       // ================= MLP half: fc1 (64 -> 192) -> GELU -> fc2 (192 -> 64), 32 hidden channels (one fc2 k-step) at a time =================
-      l1w_layer_norm(x, xn);
-      {
+      if (!skip_mlp) {
+        l1w_layer_norm(x, xn);
         f32x4 acc2[3][4];
 #pragma unroll
         for (int mt = 0; mt < 3; ++mt)
@@ -284,9 +298,6 @@ __global__ __launch_bounds__(64 * L1W_NWV) void nat_l1w_kernel(NatL1WP p) {
             for (int nt = 0; nt < 4; ++nt) acc2[mt][nt] = mfma_hid(u[nt], hop, acc2[mt][nt]);
           }
         }
-        float dp2 = 1.f;
-        if (p.droppath[bi] > 0.f) dp2 = (uniform01(p.seed, p.stream + 2 * bi + 1, (uint32_t)seq) < p.droppath[bi]) ? 0.f : 1.0f / (1.0f - p.droppath[bi]);
-        if (p.droppath[bi] > 0.f) ds_sample(p.ds, RIFT_DS_NAT(1, bi, 1), seq_ok ? seq : -1, dp2);
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
           const float4 b4 = *reinterpret_cast<const float4*>(pb + L1W_PB_B2 + nt * 16 + l4 * 4);
@@ -374,8 +385,10 @@ __global__ __launch_bounds__(64 * L1W_NWV) void nat_l1w_kernel(NatL1WP p) {
         }
         const float r = rsqrtf(rows_sum(qs) * (1.0f / 128.0f) + 1e-5f);
         const int m = mt * 16 + l15, oa = m / 5;
-        if (m < 20 && RIFT_SEQ_LIVE(tile * 4 + oa)) {
-          float* dst = p.Xnext + ((size_t)tile * 20 + m) * 128;
+        // output rows (oa, m - 5 oa) of the sequence in lane row oa: rank order tile * 4 + oa, or the list's
+        const int so = m >= 20 ? -1 : !p.perm ? (RIFT_SEQ_LIVE(tile * 4 + oa) ? tile * 4 + oa : -1) : tile < ntiles ? p.perm[tile * 4 + oa] : -1;
+        if (so >= 0) {
+          float* dst = p.Xnext + ((size_t)so * 5 + (m - oa * 5)) * 128;
 #pragma unroll
           for (int nt = 0; nt < 8; ++nt) {
             const float4 gg = *reinterpret_cast<const float4*>(g + nt * 16 + l4 * 4), bb = *reinterpret_cast<const float4*>(g + 128 + nt * 16 + l4 * 4);

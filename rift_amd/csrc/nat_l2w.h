@@ -43,6 +43,7 @@ struct NatL2WP {
   float droppath[2]; uint32_t seed, stream;
   long long* ts;                           // optional: clock of wave 0 of workgroup 0 at every group boundary (diagnostic)
   const int* cnt;                          // if set: the three class counts of the compacted launch (nat_l0w.h; common.h: SeqCount); nseq is the bound
+  const int* perm;                         // if set: the DropPath grouping's list (nat_l0w.h: nat_group_body) -- lane row qa of tile t works on sequence perm[3 t + qa], -1 = none
   DropStats ds;                            // diagnostic build only (dropstats.h)
 };
 

@@ -144,14 +144,38 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     const int last_idx = wv * G + (int)blockIdx.x;
     const int tile = rr < full ? (rr * G + (int)blockIdx.x) * 8 + wv : full * 8 * G + last_idx;
+    // grouped: which of the round's four half-blocks DropPath drops for ALL its sequences (bit 2 bi + branch).  The operand stream keeps the
+    // eight waves in lock step, so only a round-wide drop can be skipped, and the branch must be workgroup-uniform: every wave restates the
+    // decisions of the whole round -- lane l < 24 takes lane row l % 3 of wave l / 3's tile, a hole or a wave without a tile counts as
+    // dropped -- instead of exchanging per-wave masks through LDS ahead of a boundary (four hashes and four ballots per round, no LDS slot,
+    // and the parent's instruction order around the boundaries stays as it is).
+    int skipm = 0;
+    if (p.perm) {
+      const int w = lane / 3, a3 = lane - 3 * w, li = w * G + (int)blockIdx.x;
+      const int t = rr < full ? (rr * G + (int)blockIdx.x) * 8 + w : li < trem ? full * 8 * G + li : ntiles;
+      const int sq = (lane < 24 && t < ntiles) ? p.perm[t * 3 + a3] : -1;
+      int keep = 0;
+      if (sq >= 0) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const float rate = p.droppath[b >> 1];
+          keep |= (rate > 0.f && uniform01(p.seed, p.stream + b, (uint32_t)sq) < rate) ? 0 : (1 << b);
+        }
+      }
+#pragma unroll
+      for (int b = 0; b < 4; ++b) skipm |= __builtin_amdgcn_ballot_w64((keep >> b) & 1) == 0ull ? (1 << b) : 0;
+      skipm = __builtin_amdgcn_readfirstlane(skipm);
+    }
     if (__builtin_amdgcn_readfirstlane((int)(rr >= full && last_idx >= trem))) {      // a wave without a tile in the last round: the stream's protocol only
 #pragma unroll 1
       for (int g = 0; g < 20; ++g) { boundary(s); ++s; }
       continue;
     }
     const int qa = l15 / L, qt = l15 - qa * L;           // this lane row: agent qa (3 = the idle row 15), step qt
-    const int seq = tile * 3 + qa;
-    const bool row_ok = qa < 3 && RIFT_SEQ_LIVE(seq);
+    // grouped (nat_l0w.h: nat_group_body): the tile's sequences come from the list -- the same lane rows seq % 3, rounds of one DropPath
+    // pattern --, every buffer stays indexed by seq
+    const int seq = !p.perm ? tile * 3 + qa : (qa < 3 && tile < ntiles) ? p.perm[tile * 3 + qa] : -1;
+    const bool row_ok = qa < 3 && (p.perm ? seq >= 0 : RIFT_SEQ_LIVE(seq));
     f32x4 res[8];
     {
       const float* src = p.X + ((size_t)(row_ok ? seq : 0) * L + (row_ok ? qt : 0)) * 128 + l4 * 4;
@@ -182,6 +206,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         ds_sample(p.ds, RIFT_DS_NAT(2, bi, 0), row_ok ? seq : -1, dps);
         ds_sample(p.ds, RIFT_DS_NAT(2, bi, 1), row_ok ? seq : -1, dp2);
       }
+      const bool skip_att = (skipm >> (2 * bi)) & 1, skip_mlp = (skipm >> (2 * bi + 1)) & 1;
+      ds_skip(p.ds, 4 + 2 * bi, skip_att && tid == 0);
+      ds_skip(p.ds, 5 + 2 * bi, skip_mlp && tid == 0);
+      if (skip_att) {      // dropped for the whole round: res + 0 * branch = res; the stream's four boundaries only
+#pragma unroll 1
+        for (int g = 0; g < 4; ++g) { boundary(s); ++s; }
+      } else {
       // ---- group 0: q
       layer_norm(res, xb);
       init8(acc, pb + L2W_PB_BQKV);
@@ -227,6 +258,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       boundary(s); gemm(slot_off(s), ao, acc); ++s;
 #pragma unroll
       for (int nt = 0; nt < 8; ++nt) res[nt] += acc[nt] * dps;
+      }
+      if (skip_mlp) {      // likewise the MLP half's six
+#pragma unroll 1
+        for (int g = 0; g < 6; ++g) { boundary(s); ++s; }
+        continue;
+      }
       // ---- groups 4..9: fc1 chunk -> GELU -> fc2 partial
       layer_norm(res, xb);
       f32x4 acc2[8];

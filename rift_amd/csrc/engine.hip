@@ -722,9 +722,11 @@ int map_and_embeddings(Fwd& f) {
     } else
     launch(c, "fourier_fused_kernel", fourier_fused_kernel, dim3(q3.nblk[0] + q3.nblk[1] + q3.nblk[2]), dim3(256), (size_t)FO_LDS, q3);
     f.PEtok = q3.e[0].Y; f.speed_emb = q3.e[1].Y;
+    tap(c, "fo_pos", f.PEtok, (int64_t)nT * 128);
   } else {
     f.speed_emb = fourier(f, B->map_polygon_speed_limit, 1, nP, c->m.map.speed_limit_emb, -1);
   }
+  tap(c, "fo_speed", f.speed_emb, (int64_t)nP * 128);
   if (f.kp.q0_early) TRY(build_q0(f));      // ahead of the join
   return RIFT_OK;
 }
@@ -745,6 +747,7 @@ void assemble_tokens(Fwd& f) {
   launch(c, "token_kernel", token_kernel, dim3(q.nblk_a + cdiv((long long)nP * 32, 256)), dim3(256), 0, q);
   if (S > 0) {
     float* semb = fourier(f, B->static_shape, 2, bs * S, c->m.stat.obj_encoder, -1);
+    tap(c, "fo_static", semb, (int64_t)bs * S * 128);
     launch(c, "static_token_kernel", static_token_kernel, dim3(cdiv((long long)bs * S * 128, 256)), dim3(256), 0, (const float*)semb, B->static_category,
            B->static_valid_mask, c->m.stat.type_emb, bs, A, Mp, S, N, f.X);
   }

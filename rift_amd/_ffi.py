@@ -16,12 +16,13 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from rift_amd import _abi, _abi_advantage, _abi_drivable, _abi_select, tick_pack
+from rift_amd import _abi, _abi_advantage, _abi_drivable, _abi_footprint, _abi_select, tick_pack
 from rift_amd._abi import (EXPORTS, RiftControlCBV, RiftCritic, RiftDp, RiftEvalParams, RiftFeatureBatch, RiftLossIn,  # noqa: F401
                            RiftLossOut, RiftObjectiveParams, RiftOutputs, RiftReplayArena, RiftRolloutIO, RiftTensorDesc, RiftTickCBV)
 from rift_amd._abi_drivable import RiftDrivableInfo      # the drivable-area-map extension (include/rift_drivable.h)
 from rift_amd._abi_advantage import RiftAdvantageParams  # the arena-advantage extension (include/rift_advantage.h)
 from rift_amd._abi_select import RiftSelectParams        # the candidate-selection extension (include/rift_select.h)
+from rift_amd._abi_footprint import RiftCollisionParams  # the collision-test extension (include/rift_footprint.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librift_hip.so")
@@ -133,7 +134,20 @@ def select_params(mode: str = "greedy", temperature: float = 1.0) -> RiftSelectP
     return p
 
 
-PI_KEYS = ("mlp.0.weight", "mlp.0.bias", "mlp.1.weight", "mlp.1.bias", "mlp.3.weight", "mlp.3.bias")       # flat order of PI_NPARAM
+COLLISION_MODES = {"envelope": _abi_footprint.RIFTFP_ENVELOPE, "footprint": _abi_footprint.RIFTFP_FOOTPRINT}
+
+
+def collision_params(mode: str = "envelope") -> RiftCollisionParams:
+    """RiftCollisionParams of Engine.collision_matrix(mode=...) / Engine.group_advantage_tick(collision=...) (include/rift_footprint.h states
+    the rule): the mode by name; the default is the envelope test of rift_collision_matrix.  An unknown name raises ValueError."""
+    if mode not in COLLISION_MODES:
+        raise ValueError(f"collision: mode = {mode!r}; known: {list(COLLISION_MODES)}")
+    p = RiftCollisionParams()
+    p.mode, p.reserved = COLLISION_MODES[mode], 0
+    return p
+
+
+PI_KEYS = ("mlp.0.weight","mlp.0.bias", "mlp.1.weight", "mlp.1.bias", "mlp.3.weight", "mlp.3.bias")       # flat order of PI_NPARAM
 PI_SIZES = (128 * 128, 128, 128, 128, 128, 1)
 CRITIC_SIZES = (256 * 128, 256, 256 * 256, 256, 256, 1, 128, 128, 1, 1)                                       # flat order of CRITIC_NPARAM
 CRITIC_KEYS = ("net.0.weight", "net.0.bias", "net.2.weight", "net.2.bias", "net.4.weight", "net.4.bias",
@@ -155,7 +169,7 @@ def load_library(variant: str = "") -> C.CDLL:
         raise RuntimeError(
             f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). rift_amd has no CPU fallback.")
-    _libs[variant] = lib = _abi_select.bind(_abi_advantage.bind(_abi_drivable.bind(_abi.bind(C.CDLL(path)))))
+    _libs[variant] = lib = _abi_footprint.bind(_abi_select.bind(_abi_advantage.bind(_abi_drivable.bind(_abi.bind(C.CDLL(path))))))
     return lib
 
 
@@ -793,7 +807,7 @@ class Engine:
         return eval_params(reward_model, gamma, bbox_inflation_ratio, resolution, near_lane_change)
 
     def group_advantage_tick(self, trajectory, cbvs, pid_state, gamma: float = 0.98, *, params: Optional[RiftEvalParams] = None,
-                             want_returns: bool = False, want_terms: bool = False):
+                             want_returns: bool = False, want_terms: bool = False, collision=None):
         """The group advantages of one tick's CBVs in one C-ABI call (rift_group_advantage_tick): `trajectory` (bs, Rb, 12, Tfull, 6) the tick's
         model output (device), `cbvs` a list of dicts in tick order -- the entries rift_amd/tick_pack.py describes, key by key
         -- whose valid reference lines are a prefix of their rows.  Everything host-side goes up in ONE staged copy.  Returns the (K, Rb, 12) f64
@@ -804,8 +818,13 @@ class Engine:
         tensor "packed" (K * Rb * 12 * 10 doubles, zero where nothing is written), so that a tick reads all of it back in one copy.  With
         params None and nothing wanted the call is rift_group_advantage_tick, as ever.
         A tick with an entry that takes its off-road flags from the loaded drivable-area map ("raster" + "pose", load_drivable_map) goes
-        through riftdm_group_advantage_tick (params None: eval_params(gamma=gamma))."""
+        through riftdm_group_advantage_tick (params None: eval_params(gamma=gamma)).
+        `collision` ('envelope' | 'footprint', or a ready RiftCollisionParams; include/rift_footprint.h states the rule) sends the tick through
+        riftfp_group_advantage_tick, with or without the map: 'envelope' gives the bits of the call made without it, 'footprint' takes the
+        collision flags from the footprints themselves.  None: the entry choice above."""
         dev = self.device
+        if collision is not None and not isinstance(collision, RiftCollisionParams):
+            collision = collision_params(collision)
         traj = _dev(trajectory, torch.float32, dev)
         bs, Rb, M, Tfull, Cc = traj.shape
         assert M == 12 and Cc == 6
@@ -816,8 +835,8 @@ class Engine:
         Gmax = 12 * max(c.R for c in layout)
         assert all(pid_state[k].shape[0] >= Gmax for k in pid_keys)
         use_map = any(c.from_map for c in layout)
-        plain = params is None and not want_returns and not want_terms and not use_map
-        if plain:                                                                 # 4. the C entry: plain | _ex | riftdm_
+        plain = params is None and not want_returns and not want_terms and not use_map and collision is None
+        if plain:                                                                 # 4. the C entry: plain | _ex | riftdm_ | riftfp_
             res = {"advantage": torch.zeros(K, Rb, 12, dtype=torch.float64, device=dev)}
             name, tail = "rift_group_advantage_tick", (float(gamma), _ptr(res["advantage"]))
         else:
@@ -831,6 +850,8 @@ class Engine:
             name = "riftdm_group_advantage_tick" if use_map else "rift_group_advantage_tick_ex"
             tail = (C.byref(eval_params(gamma=gamma) if params is None else params), _ptr(res["advantage"]), _ptr(res.get("returns")),
                     _ptr(res.get("terms")))
+            if collision is not None:                                             # (the map entry's semantics per CBV, the collision params behind `params`)
+                name, tail = "riftfp_group_advantage_tick", tail[:1] + (C.byref(collision),) + tail[1:]
         self._check(getattr(self.lib, name)(self.ctx, _ptr(traj), Rb, Tfull, arr, K, *(_ptr(pid_state[k]) for k in pid_keys), *tail, _stream()),
                     name)
         self._keep_tick = (traj, up)
@@ -919,8 +940,11 @@ class Engine:
                     "rift_sft_teacher_mode")
         return out
 
-    def collision_matrix(self, center_vertices, other_vertices, Ts: int = 40):
-        """get_collision_matrix: envelope overlap of candidate footprints (G,Tc,4,2) with forecast neighbours (N,Ts,4,2) -> (G,Ts) bool."""
+    def collision_matrix(self, center_vertices, other_vertices, Ts: int = 40, mode=None, want_first: bool = False):
+        """get_collision_matrix: envelope overlap of candidate footprints (G,Tc,4,2) with forecast neighbours (N,Ts,4,2) -> (G,Ts) bool.
+        `mode` ('envelope' | 'footprint', or a ready RiftCollisionParams) or want_first make the call riftfp_collision_matrix
+        (include/rift_footprint.h states the rule); with want_first the result is (flags, first_actor (G,Ts) int32: the lowest colliding
+        neighbour, or -1).  mode None and no want_first: rift_collision_matrix, as ever."""
         dev = self.device
         cv = _dev(center_vertices, torch.float32, dev)
         G, Tc = cv.shape[:2]
@@ -930,9 +954,15 @@ class Engine:
         if N and ov.shape[1] != Ts:
             ov = ov[:, :Ts].contiguous()
         out = torch.empty(G, Ts, dtype=torch.uint8, device=dev)
-        self._check(self.lib.rift_collision_matrix(self.ctx, _ptr(cv), G, Tc, _ptr(ov) if N else None, N, Ts, _ptr(out), _stream()),
-                    "rift_collision_matrix")
-        return out.bool()
+        if mode is None and not want_first:
+            self._check(self.lib.rift_collision_matrix(self.ctx, _ptr(cv), G, Tc, _ptr(ov) if N else None, N, Ts, _ptr(out), _stream()),
+                        "rift_collision_matrix")
+            return out.bool()
+        p = mode if isinstance(mode, RiftCollisionParams) else collision_params("envelope" if mode is None else mode)
+        first = torch.empty(G, Ts, dtype=torch.int32, device=dev) if want_first else None
+        self._check(self.lib.riftfp_collision_matrix(self.ctx, _ptr(cv), G, Tc, _ptr(ov) if N else None, N, Ts, C.byref(p), _ptr(out), _ptr(first),
+                                                     _stream()), "riftfp_collision_matrix")
+        return (out.bool(), first) if want_first else out.bool()
 
     def off_road_matrix(self, rollout_center, off_road_mask, origin, heading: float, resolution_hw=(0.5, -0.5), offset=(200.0, 200.0)):
         """get_off_road_matrix lookup: rollout_center (G,T,2), off_road_mask (H,W) uint8 with 1 = not drivable -> (G,T) bool."""

@@ -1,6 +1,6 @@
 // The entries of include/rift_hip.h that do not depend on the MFMA operand format: the objective and its backward, AdamW and clipping,
 // the PPO critic, the advantage scans, the candidate rollout, the group-advantage tick, the control tick and collate -- and the entries of
-// the three extension headers (rift_drivable.h, rift_advantage.h, rift_select.h), defined here with C linkage under their declarations.  They
+// the four extension headers (rift_drivable.h, rift_advantage.h, rift_select.h, rift_footprint.h), defined here with C linkage under their declarations.  They
 // use no MFMA and no operand conversion and touch the format-free half of a context only (ctx_core.h), so they are compiled ONCE per
 // library and serve contexts of both engine builds; the exported trampolines (abi.cpp) call the rift_* ones directly.
 // Every entry follows one protocol (launch.h): the message cleared, its refusals on the host (refuse: "<entry called>: <why>"), call_open,
@@ -19,6 +19,7 @@
 #include "../../include/rift_drivable.h"
 #include "../../include/rift_advantage.h"
 #include "../../include/rift_select.h"
+#include "../../include/rift_footprint.h"
 #include "lanes.h"
 #include "loss.h"
 #include "critic.h"
@@ -29,6 +30,7 @@
 #include "tick_multi.h"
 #include "control.h"
 #include "select_params.h"
+#include "collision_params.h"
 #include "eval_params.h"
 #include "objective_params.h"
 
@@ -178,15 +180,27 @@ int rift_other_vehicle_rollout(RiftCtx* c, const double* actions, const double* 
   return call_close(c);
 }
 
+// rift_collision_matrix (sel == nullptr) and riftfp_collision_matrix (include/rift_footprint.h; sel: its accepted params): `who` is the
+// entry's name in the message.  The envelope test without first_actor is collision_matrix_kernel's, whichever entry asks for it.
+static int collision_matrix(RiftCtx* c, const char* who, const float* center_vertices, int G, int Tc, const double* other_vertices, int N, int Ts,
+                            const RiftCollisionParams* sel, uint8_t* collision, int32_t* first_actor, void* stream) {
+  if (G <= 0 || Ts <= 0 || Tc < Ts || N < 0 || !center_vertices || !collision || (N > 0 && !other_vertices)) return refuse(c, who, "G <= 0, Ts <= 0, Tc < Ts, N < 0 or a null pointer");
+  TRY(call_open(c, stream));
+  const int mode = sel ? sel->mode : RIFTFP_ENVELOPE;
+  if (mode == RIFTFP_ENVELOPE && !first_actor)
+    launch(c, "collision_matrix_kernel", collision_matrix_kernel, dim3(cdiv((long long)G * Ts, 256)), dim3(256), 0, center_vertices, G, Tc,
+           other_vertices, N, Ts, collision);
+  else
+    launch(c, "footprint_collision_kernel", footprint_collision_kernel, dim3(cdiv((long long)G * Ts, 256)), dim3(256), 0, center_vertices, G, Tc,
+           other_vertices, N, Ts, mode, collision, first_actor);
+  return call_close(c);
+}
+
 int rift_collision_matrix(RiftCtx* c, const float* center_vertices, int G, int Tc, const double* other_vertices, int N, int Ts,
                           uint8_t* collision, void* stream) {
   if (!c) return RIFT_ERR_ARG;
   c->err.clear();
-  if (G <= 0 || Ts <= 0 || Tc < Ts || N < 0 || !center_vertices || !collision || (N > 0 && !other_vertices)) return refuse(c, "rift_collision_matrix", "G <= 0, Ts <= 0, Tc < Ts, N < 0 or a null pointer");
-  TRY(call_open(c, stream));
-  launch(c, "collision_matrix_kernel", collision_matrix_kernel, dim3(cdiv((long long)G * Ts, 256)), dim3(256), 0, center_vertices, G, Tc,
-         other_vertices, N, Ts, collision);
-  return call_close(c);
+  return collision_matrix(c, "rift_collision_matrix", center_vertices, G, Tc, other_vertices, N, Ts, nullptr, collision, nullptr, stream);
 }
 
 int rift_off_road_matrix(RiftCtx* c, const float* rollout_center, int n_points, const uint8_t* off_road_mask, int H, int W,
@@ -617,11 +631,13 @@ extern "C" int riftdm_raster(RiftCtx* c, int H, int W, double ox, double oy, dou
 // them (tick_multi.h) -- reference-line deviations and neighbour forecasts first, then the rollouts CBV by CBV in list order (the shared PID
 // state), then kinematics, flags, returns and z-scores: K + 7 launches instead of 9 K.  Three entries share it; TickCall is what they pass on.
 // (own_offset: the pixel offset of a CBV comes from its own raster -- the _ex entries; else 200, 200 whatever the raster.  use_map: a CBV
-// with a NULL mask and H, W > 0 takes its off-road flags from the drivable-area map -- riftdm_group_advantage_tick)
+// with a NULL mask and H, W > 0 takes its off-road flags from the drivable-area map -- riftdm_group_advantage_tick.  footprint: the
+// collision flags come from the footprints themselves, stage 8 in place of stage 3 -- riftfp_group_advantage_tick in FOOTPRINT mode)
 struct TickCall {
   const char* who; const float* trajectory; int Rb, Tfull; const RiftTickCBV* cbvs; int K;
   float* turn_buf; int32_t *turn_ptr, *turn_len; float* speed_buf; int32_t *speed_ptr, *speed_len;
   RiftEvalParams ev; bool own_offset, use_map; double *advantage, *returns, *terms;
+  bool footprint = false;
 };
 constexpr int TICK_M = 12, TICK_TS = 40, TICK_TR = RIFT_RO_LEN;
 
@@ -694,16 +710,18 @@ static void tick_fill(RiftCtx* c, const TickCall& t, const TickLayout& l, const 
 template <int STAGE>
 static void tick_stage(RiftCtx* c, const TickArr& a, int blocks, int block) {
   static const char* const label[] = {"tick_multi_kernel_0", "tick_multi_kernel_1", "tick_multi_kernel_2", "tick_multi_kernel_3",
-                                      "tick_multi_kernel_4", "tick_multi_kernel_5", "tick_multi_kernel_6", "tick_multi_kernel_7"};
+                                      "tick_multi_kernel_4", "tick_multi_kernel_5", "tick_multi_kernel_6", "tick_multi_kernel_7",
+                                      "tick_multi_kernel_8"};
   launch(c, label[STAGE], tick_multi_kernel<STAGE>, dim3(blocks, a.K), dim3(block), 0, a);
 }
-static void tick_launch(RiftCtx* c, const TickChunk& ch) {
+static void tick_launch(RiftCtx* c, const TickChunk& ch, bool footprint) {
   const TickArr& a = ch.a;
   tick_stage<0>(c, a, cdiv(ch.gmax * TICK_TS, 128), 128);
   if (ch.nmax > 0) tick_stage<1>(c, a, cdiv(ch.nmax, 64), 64);
   for (int j = 0; j < a.K; ++j) launch_rollout(c, a.d[j].ro);
   tick_stage<2>(c, a, cdiv(ch.gmax * TICK_TR, 256), 256);
-  tick_stage<3>(c, a, cdiv(ch.gmax * TICK_TS, 256), 256);
+  if (footprint) tick_stage<8>(c, a, cdiv(ch.gmax * TICK_TS, 256), 256);     // (in place of stage 3: the footprints themselves, include/rift_footprint.h)
+  else tick_stage<3>(c, a, cdiv(ch.gmax * TICK_TS, 256), 256);
   if (ch.map) tick_stage<7>(c, a, cdiv(ch.gmax * TICK_TR, 256), 256);      // (in place of stage 4: masks, the map and "no flags" in one launch)
   else tick_stage<4>(c, a, cdiv(ch.gmax * TICK_TR, 256), 256);
   tick_stage<5>(c, a, cdiv(ch.gmax, 4), 256);
@@ -723,7 +741,7 @@ static int group_advantage_tick(RiftCtx* c, const TickCall& t, void* stream) {
   for (int k0 = 0; k0 < t.K; k0 += RIFT_TICK_CHUNK) {
     TickChunk ch;
     tick_fill(c, t, l, dmap, any_map, k0, &ch);
-    tick_launch(c, ch);
+    tick_launch(c, ch, t.footprint);
     TRY(call_close(c));
   }
   return RIFT_OK;
@@ -759,6 +777,35 @@ extern "C" int riftdm_group_advantage_tick(RiftCtx* c, const float* trajectory, 
   if (const char* why = rift_eval_params_refusal(params)) return refuse(c, "riftdm_group_advantage_tick", why);
   return group_advantage_tick(c, TickCall{"riftdm_group_advantage_tick", trajectory, Rb, Tfull, cbvs, K, turn_buf, turn_ptr, turn_len, speed_buf,
                                           speed_ptr, speed_len, *params, true, true, advantage, returns, terms}, stream);
+}
+
+// ---- collision flags from the footprints themselves (include/rift_footprint.h; collision_params.h, footprint.h) ----------------------
+extern "C" int riftfp_params_default(RiftCollisionParams* out) {
+  if (!out) return RIFT_ERR_ARG;
+  riftfp_params_set_default(out);
+  return RIFT_OK;
+}
+
+extern "C" int riftfp_collision_matrix(RiftCtx* c, const float* center_vertices, int G, int Tc, const double* other_vertices, int N, int Ts,
+                                       const RiftCollisionParams* params, uint8_t* collision, int32_t* first_actor, void* stream) {
+  if (!c) return RIFT_ERR_ARG;
+  c->err.clear();
+  if (const char* why = riftfp_refusal(params)) return refuse(c, "riftfp_collision_matrix", why);
+  return collision_matrix(c, "riftfp_collision_matrix", center_vertices, G, Tc, other_vertices, N, Ts, params, collision, first_actor, stream);
+}
+
+extern "C" int riftfp_group_advantage_tick(RiftCtx* c, const float* trajectory, int Rb, int Tfull, const RiftTickCBV* cbvs, int K,
+                                           float* turn_buf, int32_t* turn_ptr, int32_t* turn_len, float* speed_buf, int32_t* speed_ptr, int32_t* speed_len,
+                                           const RiftEvalParams* params, const RiftCollisionParams* collision, double* advantage, double* returns,
+                                           double* terms, void* stream) {
+  if (!c) return RIFT_ERR_ARG;
+  c->err.clear();
+  if (const char* why = riftfp_refusal(collision)) return refuse(c, "riftfp_group_advantage_tick", why);
+  if (const char* why = rift_eval_params_refusal(params)) return refuse(c, "riftfp_group_advantage_tick", why);
+  TickCall t{"riftfp_group_advantage_tick", trajectory, Rb, Tfull, cbvs, K, turn_buf, turn_ptr, turn_len, speed_buf,
+             speed_ptr, speed_len, *params, true, true, advantage, returns, terms};
+  t.footprint = collision->mode == RIFTFP_FOOTPRINT;
+  return group_advantage_tick(c, t, stream);
 }
 
 // ---- the advantage of the update from stored returns (include/rift_advantage.h; adv_params.h) ----------------------

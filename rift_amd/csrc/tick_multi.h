@@ -6,6 +6,7 @@
 #pragma once
 #include "adv.h"
 #include "drivable_map.h"
+#include "footprint.h"
 #include "rollout.h"
 
 namespace rift {
@@ -41,6 +42,7 @@ __device__ __forceinline__ void tick_return(const TickK& d, double gamma, const 
 // STAGE 0: reference-line deviations (block 128)   1: neighbour forecast (block 64)   2: kinematics + corners (block 256)
 //       3: collision flags (256)   4: off-road flags (256)   5: returns (256)   6: z-score (256)
 //       7: off-road flags of a chunk with CBVs that use the drivable-area map (256): launched IN PLACE of stage 4 (riftdm_group_advantage_tick)
+//       8: collision flags from the footprints themselves (256; footprint.h): launched IN PLACE of stage 3 (riftfp_group_advantage_tick, FOOTPRINT)
 template <int STAGE>
 __global__ void tick_multi_kernel(const TickArr a) {
   if ((int)blockIdx.y >= a.K) return;
@@ -50,6 +52,7 @@ __global__ void tick_multi_kernel(const TickArr a) {
   if (STAGE == 1) { if (d.N > 0) { const double* p = d.actors; const size_t N = (size_t)d.N; other_vehicle_rollout_body(p, p + 3 * N, p + 4 * N, p + 7 * N, p + 8 * N, d.N, Ts, a.near_lane_change, a.inflation, d.ov); } }
   if (STAGE == 2) rollout_kinematics_body(d.ro);
   if (STAGE == 3) collision_matrix_body(d.ro.vertices, d.G, TR, d.ov, d.N, Ts, d.col);          // (no neighbours: the loop over them is empty, every flag 0)
+  if (STAGE == 8) footprint_collision_body(d.ro.vertices, d.G, TR, d.ov, d.N, Ts, RIFTFP_FOOTPRINT, d.col, (int32_t*)nullptr);
   if (STAGE == 4) {
     if (d.mask) off_road_body(d.ro.center, d.G * TR, d.mask, d.H, d.W, d.ox, d.oy, d.ch, d.sh, a.res, -a.res, d.off_x, d.off_y, d.offr);
     else { const int i = blockIdx.x * 256 + threadIdx.x; if (i < d.G * TR) d.offr[i] = 0; }

@@ -520,7 +520,8 @@ class _GroupRelativePluto(RLFTPluto):
     its valid reference lines (the "old policy" of the coming update) and the group-relative advantage of all R x 12 candidates."""
     EXTRA_COLUMNS = ('CBVs_actions_old_group_logits', 'CBVs_group_advantage')
     TRAJ_EVAL_KEYS = ('gamma', 'reward_model', 'reward_params', 'bbox_inflation_ratio', 'resolution', 'near_lane_change', 'breakdown',
-                      'off_road', 'raster_size', 'map_cell', 'map_margin')      # the last three are read with 'off_road': 'map' only
+                      'off_road', 'raster_size', 'map_cell', 'map_margin',      # these last three are read with 'off_road': 'map' only
+                      'collision')                                              # 'envelope' | 'footprint' (include/rift_footprint.h)
     OBJECTIVE_KEYS = ('clip_low', 'clip_high', 'dual_clip', 'kl_beta', 'entropy_coef')      # the fields of RiftObjectiveParams
     ADVANTAGE_KEYS = ('baseline', 'scale', 'clip', 'eps')                                   # the arguments of _ffi.advantage_params
     GROUP_OBJECTIVE = True
@@ -601,6 +602,11 @@ class _GroupRelativePluto(RLFTPluto):
             H, W = section.get('raster_size', (400, 400))
             ev['raster_size'] = (int(H), int(W))
             ev['map_cell'], ev['map_margin'] = float(section.get('map_cell', 16.0)), float(section.get('map_margin', 1.0))
+        # 'collision': 'envelope' (the reference's test of axis-aligned envelopes) | 'footprint' (the oriented footprints themselves).  None
+        # without the key: the calls made before the test could vary; 'envelope' given explicitly goes through the new entry and gives their bits
+        ev['collision'] = section.get('collision')
+        if ev['collision'] is not None and ev['collision'] not in ('envelope', 'footprint'):
+            raise ValueError(f"config['traj_eval']['collision'] = {ev['collision']!r}; known: ['envelope', 'footprint']")
         return ev
 
     @property
@@ -608,6 +614,8 @@ class _GroupRelativePluto(RLFTPluto):
         if self._traj_evaluator is None:
             from rift_amd.planning.fine_tuner.rlft.traj_eval.traj_evaluator import TrajEvaluator
             kw = {} if self._eval is None else {k: self._eval[k] for k in ('bbox_inflation_ratio', 'resolution', 'reward_model', 'gamma')}
+            if self._eval is not None and self._eval['collision'] is not None:
+                kw['collision'] = self._eval['collision']
             self._traj_evaluator = TrajEvaluator(self.pluto_model.engine(), dt=self._step_interval, **kw)
         eng = self.pluto_model._engine
         if eng is not None and self._traj_evaluator.engine is not eng:      # the model re-bound (precision / device change): the PID state is torch's, it carries over
@@ -702,8 +710,9 @@ class _GroupRelativePluto(RLFTPluto):
             res = ev.engine.group_advantage_tick(trajectory, [c.entry for c in cbvs], ev.pid_state, 0.98, params=_ffi.eval_params(),
                                                  want_returns=True, want_terms=False)
         else:
+            kw = {} if cfg['collision'] is None else {'collision': cfg['collision']}      # (without the key: the call made before the test could vary)
             res = ev.engine.group_advantage_tick(trajectory, [c.entry for c in cbvs], ev.pid_state, cfg['gamma'], params=cfg['params'],
-                                                 want_returns=cfg['breakdown'] or keep, want_terms=cfg['breakdown'])
+                                                 want_returns=cfg['breakdown'] or keep, want_terms=cfg['breakdown'], **kw)
         if isinstance(res, dict):                # advantage | returns | terms are slices of one tensor, still one read-back
             K, Rb = res["advantage"].shape[:2]
             terms = "terms" in res

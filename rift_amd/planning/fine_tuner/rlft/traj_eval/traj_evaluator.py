@@ -15,7 +15,8 @@ through rift_off_road_matrix.
 The constructor takes the reference's arguments (traj_evaluator.py:83-103): bbox_inflation_ratio (the neighbours' footprints),
 map_width / map_height / resolution (the raster lookup: pixel = coord / (res, -res) + (map_height / 2, map_width / 2) -- the height goes
 to x, as in the reference), and the reward model (rift_amd.gym_carla.reward.reward_model; None = DenseRewardModel's defaults) and gamma
-of the return.  With all of them at their defaults every call is the one made without them.
+of the return, and `collision`: 'envelope' (the reference's test) | 'footprint' (the oriented footprints themselves, include/rift_footprint.h)
+for the device-computed collision matrix.  With all of them at their defaults every call is the one made without them.
 """
 from typing import Dict, List, Optional
 
@@ -25,8 +26,12 @@ import torch
 
 class TrajEvaluator:
     def __init__(self, engine, dt: float = 0.1, num_frames: int = 40, pid_capacity: int = 256, *, bbox_inflation_ratio: float = 1.1,
-                 map_width: int = 400, map_height: int = 400, resolution: float = 0.5, reward_model=None, gamma: float = 0.98):
+                 map_width: int = 400, map_height: int = 400, resolution: float = 0.5, reward_model=None, gamma: float = 0.98,
+                 collision: str = "envelope"):
         assert abs(dt - 0.1) < 1e-9 and num_frames == 40, "kernels are built for dt = 0.1 s, 40 evaluated frames"
+        if collision not in ("envelope", "footprint"):
+            raise ValueError(f"TrajEvaluator: collision = {collision!r}; known: ['envelope', 'footprint']")
+        self.collision = collision                              # the test behind the device-computed collision matrix (include/rift_footprint.h)
         self.engine, self.dt, self.num_frames = engine, dt, num_frames
         self.bbox_inflation_ratio, self.map_width, self.map_height, self.resolution = bbox_inflation_ratio, map_width, map_height, resolution
         self.reward_model, self.gamma = reward_model, gamma
@@ -65,7 +70,9 @@ class TrajEvaluator:
                                                                    bbox_inflation_ratio=self.bbox_inflation_ratio, **nearby_actor_states)
             if other_vehicle_vertices is None:
                 raise ValueError("pass collision_matrix, other_vehicle_vertices or nearby_actor_states")
-            collision_matrix = eng.collision_matrix(ro["vertices"], other_vehicle_vertices, Ts=T)
+            # ('envelope': the call made before the test could vary; a caller's own collision_matrix is used as it is)
+            kw_col = {} if self.collision == "envelope" else {"mode": self.collision}
+            collision_matrix = eng.collision_matrix(ro["vertices"], other_vehicle_vertices, Ts=T, **kw_col)
         size = (self.map_height, self.map_width) if raster_size is None else tuple(raster_size)
         if off_road_matrix is None and drivable_map:
             if center_pose is None:

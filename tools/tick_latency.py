@@ -8,6 +8,8 @@ lines): host wall time per tick (the caller waits for the controls), median / p9
 the host leg, the device leg, the host leg again (its run-to-run spread is the yardstick of the difference).
 --sample: config['action_selection'] = {'mode': 'sample'} on every leg (the executed candidate is drawn, include/rift_select.h); it shows on
 the policies that tick in train mode (rift_pluto), since eval-mode ticks stay greedy: run with and without it for the cost of the stage.
+--collision envelope|footprint: config['traj_eval']['collision'] on every leg: the collision flags of the train-mode ticks from the envelopes
+(through the new entry; the launches of the run without the switch) or from the footprints themselves (stage 8 in place of stage 3).
 --policies: a comma-separated subset of pluto,rift_pluto; it selects the policies of the --device-control legs as well as of the plain run.
 --drivable-map: the A/B of config['traj_eval']['off_road'] on rift_pluto in train mode, in ONE process: the raster leg (a mask per CBV goes up
 every tick), the map leg (a seeded town of --map-polygons lane polygons on the device, poses go up), the raster leg again; then the one-time
@@ -141,8 +143,12 @@ def main():
     ap.add_argument("--map-seed", type=int, default=1)
     ap.add_argument("--map-polygons", type=int, default=5000, help="lane polygons of the seeded town (--drivable-map)")
     ap.add_argument("--map-span", type=float, default=1500.0, help="side of the town's square in metres (--drivable-map)")
+    ap.add_argument("--collision", default="", choices=("", "envelope", "footprint"),
+                    help="config['traj_eval']['collision']: the collision test of the train-mode ticks (include/rift_footprint.h); without it the key is not set")
     args = ap.parse_args()
     traj_eval = json.loads(args.traj_eval) if args.traj_eval else None
+    if args.collision:
+        traj_eval = dict(traj_eval or {}, collision=args.collision)
     if args.drivable_map:
         polygons = _lane_polygons(args.map_seed, args.map_polygons, args.map_span)
         legs = {}

@@ -16,13 +16,14 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from rift_amd import _abi, _abi_advantage, _abi_drivable, _abi_footprint, _abi_select, tick_pack
+from rift_amd import _abi, _abi_advantage, _abi_drivable, _abi_footprint, _abi_offroad, _abi_select, tick_pack
 from rift_amd._abi import (EXPORTS, RiftControlCBV, RiftCritic, RiftDp, RiftEvalParams, RiftFeatureBatch, RiftLossIn,  # noqa: F401
                            RiftLossOut, RiftObjectiveParams, RiftOutputs, RiftReplayArena, RiftRolloutIO, RiftTensorDesc, RiftTickCBV)
 from rift_amd._abi_drivable import RiftDrivableInfo      # the drivable-area-map extension (include/rift_drivable.h)
 from rift_amd._abi_advantage import RiftAdvantageParams  # the arena-advantage extension (include/rift_advantage.h)
 from rift_amd._abi_select import RiftSelectParams        # the candidate-selection extension (include/rift_select.h)
 from rift_amd._abi_footprint import RiftCollisionParams  # the collision-test extension (include/rift_footprint.h)
+from rift_amd._abi_offroad import RiftOffRoadParams      # the off-road-extent extension (include/rift_offroad.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librift_hip.so")
@@ -147,6 +148,20 @@ def collision_params(mode: str = "envelope") -> RiftCollisionParams:
     return p
 
 
+OFFROAD_EXTENTS = {"center": _abi_offroad.RIFTOF_CENTER, "footprint": _abi_offroad.RIFTOF_FOOTPRINT}
+
+
+def offroad_params(extent: str = "center") -> RiftOffRoadParams:
+    """RiftOffRoadParams of Engine.off_road_matrix(extent=...) / Engine.off_road_matrix_map(extent=...) / Engine.group_advantage_tick(
+    off_road_extent=...) (include/rift_offroad.h states the rule): the extent by name; the default is the footprint centre alone, the flag of
+    rift_off_road_matrix.  An unknown name raises ValueError."""
+    if extent not in OFFROAD_EXTENTS:
+        raise ValueError(f"off_road: extent = {extent!r}; known: {list(OFFROAD_EXTENTS)}")
+    p = RiftOffRoadParams()
+    p.extent, p.reserved = OFFROAD_EXTENTS[extent], 0
+    return p
+
+
 PI_KEYS = ("mlp.0.weight","mlp.0.bias", "mlp.1.weight", "mlp.1.bias", "mlp.3.weight", "mlp.3.bias")       # flat order of PI_NPARAM
 PI_SIZES = (128 * 128, 128, 128, 128, 128, 1)
 CRITIC_SIZES = (256 * 128, 256, 256 * 256, 256, 256, 1, 128, 128, 1, 1)                                       # flat order of CRITIC_NPARAM
@@ -169,7 +184,7 @@ def load_library(variant: str = "") -> C.CDLL:
         raise RuntimeError(
             f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). rift_amd has no CPU fallback.")
-    _libs[variant] = lib = _abi_footprint.bind(_abi_select.bind(_abi_advantage.bind(_abi_drivable.bind(_abi.bind(C.CDLL(path))))))
+    _libs[variant] = lib = _abi_offroad.bind(_abi_footprint.bind(_abi_select.bind(_abi_advantage.bind(_abi_drivable.bind(_abi.bind(C.CDLL(path)))))))
     return lib
 
 
@@ -807,7 +822,7 @@ class Engine:
         return eval_params(reward_model, gamma, bbox_inflation_ratio, resolution, near_lane_change)
 
     def group_advantage_tick(self, trajectory, cbvs, pid_state, gamma: float = 0.98, *, params: Optional[RiftEvalParams] = None,
-                             want_returns: bool = False, want_terms: bool = False, collision=None):
+                             want_returns: bool = False, want_terms: bool = False, collision=None, off_road_extent=None):
         """The group advantages of one tick's CBVs in one C-ABI call (rift_group_advantage_tick): `trajectory` (bs, Rb, 12, Tfull, 6) the tick's
         model output (device), `cbvs` a list of dicts in tick order -- the entries rift_amd/tick_pack.py describes, key by key
         -- whose valid reference lines are a prefix of their rows.  Everything host-side goes up in ONE staged copy.  Returns the (K, Rb, 12) f64
@@ -821,10 +836,19 @@ class Engine:
         through riftdm_group_advantage_tick (params None: eval_params(gamma=gamma)).
         `collision` ('envelope' | 'footprint', or a ready RiftCollisionParams; include/rift_footprint.h states the rule) sends the tick through
         riftfp_group_advantage_tick, with or without the map: 'envelope' gives the bits of the call made without it, 'footprint' takes the
-        collision flags from the footprints themselves.  None: the entry choice above."""
+        collision flags from the footprints themselves.  None: the entry choice above.
+        `off_road_extent` ('center' | 'footprint', or a ready RiftOffRoadParams; include/rift_offroad.h states the rule): 'footprint' sends the
+        tick through riftof_group_advantage_tick (collision None: the envelope test), which takes the off-road flags from the centre and the
+        four corners of every rollout step, against mask or map.  None or 'center': the entry choice above, the call made without it."""
         dev = self.device
         if collision is not None and not isinstance(collision, RiftCollisionParams):
             collision = collision_params(collision)
+        if off_road_extent is not None and not isinstance(off_road_extent, RiftOffRoadParams):
+            off_road_extent = offroad_params(off_road_extent)
+        if off_road_extent is not None and off_road_extent.extent == _abi_offroad.RIFTOF_CENTER and off_road_extent.reserved == 0:
+            off_road_extent = None                                                # (the centre alone: the entries of before)
+        if off_road_extent is not None and collision is None:
+            collision = collision_params("envelope")
         traj = _dev(trajectory, torch.float32, dev)
         bs, Rb, M, Tfull, Cc = traj.shape
         assert M == 12 and Cc == 6
@@ -852,6 +876,8 @@ class Engine:
                     _ptr(res.get("terms")))
             if collision is not None:                                             # (the map entry's semantics per CBV, the collision params behind `params`)
                 name, tail = "riftfp_group_advantage_tick", tail[:1] + (C.byref(collision),) + tail[1:]
+            if off_road_extent is not None:                                       # (the off-road params behind the collision params)
+                name, tail = "riftof_group_advantage_tick", tail[:2] + (C.byref(off_road_extent),) + tail[2:]
         self._check(getattr(self.lib, name)(self.ctx, _ptr(traj), Rb, Tfull, arr, K, *(_ptr(pid_state[k]) for k in pid_keys), *tail, _stream()),
                     name)
         self._keep_tick = (traj, up)
@@ -964,13 +990,37 @@ class Engine:
                                                      _stream()), "riftfp_collision_matrix")
         return (out.bool(), first) if want_first else out.bool()
 
-    def off_road_matrix(self, rollout_center, off_road_mask, origin, heading: float, resolution_hw=(0.5, -0.5), offset=(200.0, 200.0)):
-        """get_off_road_matrix lookup: rollout_center (G,T,2), off_road_mask (H,W) uint8 with 1 = not drivable -> (G,T) bool."""
+    def _off_road_extent(self, rc, vertices, extent, which, mask, H, W, pose, params):
+        """riftof_off_road_matrix for off_road_matrix / off_road_matrix_map: rc (G, T, 2) on the device, mask a device tensor or None (the map)
+        -> (G, T) bool, or (flags, which (G, T) uint8: bit k = point k of the rule is off road)."""
+        G, T = rc.shape[:2]
+        p = extent if isinstance(extent, RiftOffRoadParams) else offroad_params(extent)
+        vt = None if vertices is None else _dev(vertices, torch.float32, self.device)
+        assert vt is None or tuple(vt.shape) == (G, T, 4, 2)
+        out = torch.empty(G, T, dtype=torch.uint8, device=self.device)
+        wh = torch.empty(G, T, dtype=torch.uint8, device=self.device) if which else None
+        self._check(self.lib.riftof_off_road_matrix(self.ctx, _ptr(rc), _ptr(vt), G * T, _ptr(mask), int(H), int(W), float(pose[0]), float(pose[1]),
+                                                    float(pose[2]), C.byref(params), C.byref(p), _ptr(out), _ptr(wh), _stream()), "riftof_off_road_matrix")
+        return (out.bool(), wh) if which else out.bool()
+
+    def off_road_matrix(self, rollout_center, off_road_mask, origin, heading: float, resolution_hw=(0.5, -0.5), offset=(200.0, 200.0), vertices=None,
+                        extent="center", which: bool = False):
+        """get_off_road_matrix lookup: rollout_center (G,T,2), off_road_mask (H,W) uint8 with 1 = not drivable -> (G,T) bool.
+        `vertices` (G,T,4,2), `extent` ('center' | 'footprint', or a ready RiftOffRoadParams) and `which` make the call riftof_off_road_matrix
+        (include/rift_offroad.h states the rule): 'footprint' flags a step whose centre or one of whose four corners is off road; with `which`
+        the result is (flags, which (G,T) uint8: bit k = point k is off road).  That entry takes the resolution as (r, -r) and the offset as
+        (H / 2, W / 2) only.  With the defaults: rift_off_road_matrix, as ever."""
         dev = self.device
         rc = _dev(rollout_center, torch.float32, dev)
         G, T = rc.shape[:2]
         m = self.stage(off_road_mask, torch.uint8)
         H, W = m.shape
+        if vertices is not None or which or isinstance(extent, RiftOffRoadParams) or extent != "center":
+            res = float(resolution_hw[0])
+            if float(resolution_hw[1]) != -res or res <= 0 or (float(offset[0]), float(offset[1])) != (float(np.float32(H / 2)), float(np.float32(W / 2))):
+                raise ValueError(f"off_road_matrix: with vertices, extent or which the resolution is (r, -r) and the offset (H / 2, W / 2) = "
+                                 f"{(H / 2, W / 2)}; got {tuple(resolution_hw)}, {tuple(offset)}")
+            return self._off_road_extent(rc, vertices, extent, which, m, H, W, (origin[0], origin[1], heading), eval_params(resolution=res))
         out = torch.empty(G, T, dtype=torch.uint8, device=dev)
         self._check(self.lib.rift_off_road_matrix(self.ctx, _ptr(rc), G * T, _ptr(m), H, W, float(origin[0]), float(origin[1]), float(heading),
                                                   float(resolution_hw[0]), float(resolution_hw[1]), float(offset[0]), float(offset[1]),
@@ -1002,13 +1052,17 @@ class Engine:
         self._check(rc, "riftdm_info")
         return {k: getattr(info, k) for k, _ in RiftDrivableInfo._fields_ if k != "reserved"}
 
-    def off_road_matrix_map(self, rollout_center, pose, raster_size=(400, 400), params: Optional[RiftEvalParams] = None):
+    def off_road_matrix_map(self, rollout_center, pose, raster_size=(400, 400), params: Optional[RiftEvalParams] = None, vertices=None,
+                            extent="center", which: bool = False):
         """get_off_road_matrix from the loaded map: rollout_center (G, T, 2), pose (x, y, heading) of the footprint centre, raster_size (H, W) of
-        the raster the rule speaks of, params (eval_params: its resolution is read) -> (G, T) bool."""
+        the raster the rule speaks of, params (eval_params: its resolution is read) -> (G, T) bool.  `vertices`, `extent` and `which` as in
+        off_road_matrix (riftof_off_road_matrix with a NULL mask); with the defaults: riftdm_off_road_matrix, as ever."""
         dev = self.device
         rc = _dev(rollout_center, torch.float32, dev)
         G, T = rc.shape[:2]
         params = eval_params() if params is None else params
+        if vertices is not None or which or isinstance(extent, RiftOffRoadParams) or extent != "center":
+            return self._off_road_extent(rc, vertices, extent, which, None, raster_size[0], raster_size[1], pose, params)
         out = torch.empty(G, T, dtype=torch.uint8, device=dev)
         self._check(self.lib.riftdm_off_road_matrix(self.ctx, _ptr(rc), G * T, int(raster_size[0]), int(raster_size[1]), float(pose[0]), float(pose[1]),
                                                       float(pose[2]), C.byref(params), _ptr(out), _stream()), "riftdm_off_road_matrix")

@@ -44,7 +44,7 @@ def hipcc() -> str:
 
 def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.cpp"))
-                  + [os.path.join(os.path.dirname(HERE), "include", h) for h in ("rift_hip.h", "rift_drivable.h", "rift_advantage.h", "rift_select.h", "rift_footprint.h")] + [os.path.abspath(__file__)])
+                  + [os.path.join(os.path.dirname(HERE), "include", h) for h in ("rift_hip.h", "rift_drivable.h", "rift_advantage.h", "rift_select.h", "rift_footprint.h", "rift_offroad.h")] + [os.path.abspath(__file__)])
 
 
 def compile_commands(extra=(), stats=False, variant=None):

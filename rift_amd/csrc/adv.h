@@ -288,18 +288,28 @@ __global__ __launch_bounds__(256) void collision_matrix_kernel(const float* __re
 
 // get_off_road_matrix, lookup part (traj_evaluator.py:299-318): pixel = round(((p - origin) . rot) / resolution_hw + offset) in fp64
 // (np.round = half to even = rint), inside the raster and mask == 1 -> off road.  rot = [[c, -s], [s, c]] of the centre heading.
+// The two halves are shared with the lookups of the other sources and extents (drivable_map.h, offroad_extent.h): the pixel of a point ...
+__device__ __forceinline__ void off_road_pixel(double x, double y, double ox, double oy, double c, double s, double res_x, double res_y,
+                                               double off_x, double off_y, double& px, double& py) {
+  const double dx = x - ox, dy = y - oy;
+  const double lx = __dadd_rn(__dmul_rn(dx, c), __dmul_rn(dy, s));        // (d . rot)[0] = dx*c + dy*s   (no fused multiply-add, as numpy)
+  const double ly = __dadd_rn(__dmul_rn(dx, -s), __dmul_rn(dy, c));       // (d . rot)[1] = -dx*s + dy*c
+  px = rint(lx / res_x + off_x); py = rint(ly / res_y + off_y);
+}
+// ... and the raster's decision on it: a pixel outside the raster is not off road
+__device__ __forceinline__ uint8_t off_road_mask_flag(double px, double py, const uint8_t* __restrict__ mask, int H, int W) {
+  uint8_t off = 0;
+  if (px >= 0.0 && px < (double)W && py >= 0.0 && py < (double)H) off = mask[(size_t)(int)py * W + (int)px] == 1;
+  return off;
+}
 __device__ __forceinline__ void off_road_body(const float* __restrict__ pts /*(n,2)*/, int n, const uint8_t* __restrict__ mask, int H,
                                                        int W, double ox, double oy, double c, double s, double res_x, double res_y,
                                                        double off_x, double off_y, uint8_t* __restrict__ out) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const double dx = (double)pts[2 * i] - ox, dy = (double)pts[2 * i + 1] - oy;
-  const double lx = __dadd_rn(__dmul_rn(dx, c), __dmul_rn(dy, s));        // (d . rot)[0] = dx*c + dy*s   (no fused multiply-add, as numpy)
-  const double ly = __dadd_rn(__dmul_rn(dx, -s), __dmul_rn(dy, c));       // (d . rot)[1] = -dx*s + dy*c
-  const double px = rint(lx / res_x + off_x), py = rint(ly / res_y + off_y);
-  uint8_t off = 0;
-  if (px >= 0.0 && px < (double)W && py >= 0.0 && py < (double)H) off = mask[(size_t)(int)py * W + (int)px] == 1;
-  out[i] = off;
+  double px, py;
+  off_road_pixel((double)pts[2 * i], (double)pts[2 * i + 1], ox, oy, c, s, res_x, res_y, off_x, off_y, px, py);
+  out[i] = off_road_mask_flag(px, py, mask, H, W);
 }
 __global__ __launch_bounds__(256) void off_road_kernel(const float* __restrict__ pts, int n, const uint8_t* __restrict__ mask, int H, int W, double ox, double oy, double c, double s,
                                                        double res_x, double res_y, double off_x, double off_y, uint8_t* __restrict__ out) {

@@ -10,6 +10,7 @@
 // This is NOT cv2.fillPoly bit for bit: a scanline rasteriser also sets the 8-connected outline it draws along every edge, whose pixels lie
 // up to half a pixel outside the mathematical polygon ("Unpinned").  Hence opt-in.
 #pragma once
+#include "adv.h"
 #include "drivable_grid.h"
 
 namespace rift {
@@ -76,18 +77,21 @@ __device__ __forceinline__ bool pixel_drivable(const DrivableMapDev& m, const Ra
   return false;
 }
 
-// one thread per rollout point: the pixel is off_road_body's, bit for bit; off road = inside the raster and not drivable
+// the map's decision on the pixel of a rollout point (off_road_pixel, adv.h): off road = inside the raster and not drivable
+__device__ __forceinline__ uint8_t off_road_map_flag(double px, double py, const DrivableMapDev& m, const RasterPose& q, int H, int W) {
+  uint8_t off = 0;
+  if (px >= 0.0 && px < (double)W && py >= 0.0 && py < (double)H) off = pixel_drivable(m, q, (int)px, (int)py) ? 0 : 1;
+  return off;
+}
+
+// one thread per rollout point: the pixel is off_road_body's, bit for bit
 __device__ __forceinline__ void off_road_map_body(const float* __restrict__ pts /*(n,2)*/, int n, const DrivableMapDev& m, const RasterPose& q, int H, int W,
                                                   uint8_t* __restrict__ out) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const double dx = (double)pts[2 * i] - q.ox, dy = (double)pts[2 * i + 1] - q.oy;
-  const double lx = __dadd_rn(__dmul_rn(dx, q.c), __dmul_rn(dy, q.s));
-  const double ly = __dadd_rn(__dmul_rn(dx, -q.s), __dmul_rn(dy, q.c));
-  const double px = rint(lx / q.res + q.off_x), py = rint(ly / -q.res + q.off_y);
-  uint8_t off = 0;
-  if (px >= 0.0 && px < (double)W && py >= 0.0 && py < (double)H) off = pixel_drivable(m, q, (int)px, (int)py) ? 0 : 1;
-  out[i] = off;
+  double px, py;
+  off_road_pixel((double)pts[2 * i], (double)pts[2 * i + 1], q.ox, q.oy, q.c, q.s, q.res, -q.res, q.off_x, q.off_y, px, py);
+  out[i] = off_road_map_flag(px, py, m, q, H, W);
 }
 __global__ __launch_bounds__(256) void off_road_map_kernel(const float* __restrict__ pts, int n, const DrivableMapDev m, const RasterPose q, int H, int W,
                                                            uint8_t* __restrict__ out) {

@@ -1,6 +1,6 @@
 // The entries of include/rift_hip.h that do not depend on the MFMA operand format: the objective and its backward, AdamW and clipping,
 // the PPO critic, the advantage scans, the candidate rollout, the group-advantage tick, the control tick and collate -- and the entries of
-// the four extension headers (rift_drivable.h, rift_advantage.h, rift_select.h, rift_footprint.h), defined here with C linkage under their declarations.  They
+// the five extension headers (rift_drivable.h, rift_advantage.h, rift_select.h, rift_footprint.h, rift_offroad.h), defined here with C linkage under their declarations.  They
 // use no MFMA and no operand conversion and touch the format-free half of a context only (ctx_core.h), so they are compiled ONCE per
 // library and serve contexts of both engine builds; the exported trampolines (abi.cpp) call the rift_* ones directly.
 // Every entry follows one protocol (launch.h): the message cleared, its refusals on the host (refuse: "<entry called>: <why>"), call_open,
@@ -20,6 +20,7 @@
 #include "../../include/rift_advantage.h"
 #include "../../include/rift_select.h"
 #include "../../include/rift_footprint.h"
+#include "../../include/rift_offroad.h"
 #include "lanes.h"
 #include "loss.h"
 #include "critic.h"
@@ -31,6 +32,7 @@
 #include "control.h"
 #include "select_params.h"
 #include "collision_params.h"
+#include "offroad_params.h"
 #include "eval_params.h"
 #include "objective_params.h"
 
@@ -632,12 +634,14 @@ extern "C" int riftdm_raster(RiftCtx* c, int H, int W, double ox, double oy, dou
 // state), then kinematics, flags, returns and z-scores: K + 7 launches instead of 9 K.  Three entries share it; TickCall is what they pass on.
 // (own_offset: the pixel offset of a CBV comes from its own raster -- the _ex entries; else 200, 200 whatever the raster.  use_map: a CBV
 // with a NULL mask and H, W > 0 takes its off-road flags from the drivable-area map -- riftdm_group_advantage_tick.  footprint: the
-// collision flags come from the footprints themselves, stage 8 in place of stage 3 -- riftfp_group_advantage_tick in FOOTPRINT mode)
+// collision flags come from the footprints themselves, stage 8 in place of stage 3 -- riftfp_group_advantage_tick in FOOTPRINT mode.
+// offroad_footprint: the off-road flags come from the centre and the four corners, stage 9 in place of stage 4 / 7 --
+// riftof_group_advantage_tick with the FOOTPRINT extent)
 struct TickCall {
   const char* who; const float* trajectory; int Rb, Tfull; const RiftTickCBV* cbvs; int K;
   float* turn_buf; int32_t *turn_ptr, *turn_len; float* speed_buf; int32_t *speed_ptr, *speed_len;
   RiftEvalParams ev; bool own_offset, use_map; double *advantage, *returns, *terms;
-  bool footprint = false;
+  bool footprint = false, offroad_footprint = false;
 };
 constexpr int TICK_M = 12, TICK_TS = 40, TICK_TR = RIFT_RO_LEN;
 
@@ -711,10 +715,10 @@ template <int STAGE>
 static void tick_stage(RiftCtx* c, const TickArr& a, int blocks, int block) {
   static const char* const label[] = {"tick_multi_kernel_0", "tick_multi_kernel_1", "tick_multi_kernel_2", "tick_multi_kernel_3",
                                       "tick_multi_kernel_4", "tick_multi_kernel_5", "tick_multi_kernel_6", "tick_multi_kernel_7",
-                                      "tick_multi_kernel_8"};
+                                      "tick_multi_kernel_8", "tick_multi_kernel_9"};
   launch(c, label[STAGE], tick_multi_kernel<STAGE>, dim3(blocks, a.K), dim3(block), 0, a);
 }
-static void tick_launch(RiftCtx* c, const TickChunk& ch, bool footprint) {
+static void tick_launch(RiftCtx* c, const TickChunk& ch, bool footprint, bool offroad_footprint) {
   const TickArr& a = ch.a;
   tick_stage<0>(c, a, cdiv(ch.gmax * TICK_TS, 128), 128);
   if (ch.nmax > 0) tick_stage<1>(c, a, cdiv(ch.nmax, 64), 64);
@@ -722,7 +726,8 @@ static void tick_launch(RiftCtx* c, const TickChunk& ch, bool footprint) {
   tick_stage<2>(c, a, cdiv(ch.gmax * TICK_TR, 256), 256);
   if (footprint) tick_stage<8>(c, a, cdiv(ch.gmax * TICK_TS, 256), 256);     // (in place of stage 3: the footprints themselves, include/rift_footprint.h)
   else tick_stage<3>(c, a, cdiv(ch.gmax * TICK_TS, 256), 256);
-  if (ch.map) tick_stage<7>(c, a, cdiv(ch.gmax * TICK_TR, 256), 256);      // (in place of stage 4: masks, the map and "no flags" in one launch)
+  if (offroad_footprint) tick_stage<9>(c, a, cdiv(ch.gmax * TICK_TR * 8, 256), 256);      // (in place of stage 4 / 7: 8 lanes per step, include/rift_offroad.h)
+  else if (ch.map) tick_stage<7>(c, a, cdiv(ch.gmax * TICK_TR, 256), 256);      // (in place of stage 4: masks, the map and "no flags" in one launch)
   else tick_stage<4>(c, a, cdiv(ch.gmax * TICK_TR, 256), 256);
   tick_stage<5>(c, a, cdiv(ch.gmax, 4), 256);
   tick_stage<6>(c, a, 1, 256);
@@ -741,7 +746,7 @@ static int group_advantage_tick(RiftCtx* c, const TickCall& t, void* stream) {
   for (int k0 = 0; k0 < t.K; k0 += RIFT_TICK_CHUNK) {
     TickChunk ch;
     tick_fill(c, t, l, dmap, any_map, k0, &ch);
-    tick_launch(c, ch, t.footprint);
+    tick_launch(c, ch, t.footprint, t.offroad_footprint);
     TRY(call_close(c));
   }
   return RIFT_OK;
@@ -805,6 +810,57 @@ extern "C" int riftfp_group_advantage_tick(RiftCtx* c, const float* trajectory, 
   TickCall t{"riftfp_group_advantage_tick", trajectory, Rb, Tfull, cbvs, K, turn_buf, turn_ptr, turn_len, speed_buf,
              speed_ptr, speed_len, *params, true, true, advantage, returns, terms};
   t.footprint = collision->mode == RIFTFP_FOOTPRINT;
+  return group_advantage_tick(c, t, stream);
+}
+
+// ---- off-road flags for the whole footprint (include/rift_offroad.h; offroad_params.h, offroad_extent.h) -----------------------------
+extern "C" int riftof_params_default(RiftOffRoadParams* out) {
+  if (!out) return RIFT_ERR_ARG;
+  riftof_params_set_default(out);
+  return RIFT_OK;
+}
+
+extern "C" int riftof_off_road_matrix(RiftCtx* c, const float* center, const float* vertices, int n, const uint8_t* mask, int H, int W, double ox,
+                                      double oy, double heading, const RiftEvalParams* params, const RiftOffRoadParams* offroad,
+                                      uint8_t* off_road, uint8_t* which, void* stream) {
+  if (!c) return RIFT_ERR_ARG;
+  c->err.clear();
+  const char* who = "riftof_off_road_matrix";
+  if (const char* why = riftof_matrix_refusal(offroad, vertices, which)) return refuse(c, who, why);
+  if (n <= 0 || !center || !off_road) return refuse(c, who, "n <= 0 or a null pointer");
+  DrivableMapDev m; RasterPose q;
+  memset(&m, 0, sizeof(m));
+  if (mask) {                                      // the raster source: rift_off_road_matrix's refusals, the pose as riftdm_off_road_matrix forms it
+    if (const char* why = rift_eval_params_refusal(params)) return refuse(c, who, why);
+    if (H <= 0 || W <= 0) return refuse(c, who, "H or W <= 0");
+    const double res = (double)(float)params->resolution;
+    q = RasterPose{ox, oy, std::cos(heading), std::sin(heading), res, (double)(float)(H / 2.0), (double)(float)(W / 2.0), drivable_inv_res(res)};
+  }
+  else TRY(drivable_call(c, who, H, W, ox, oy, heading, params, stream, &m, &q));
+  TRY(call_open(c, stream));
+  if (offroad->extent == RIFTOF_CENTER && !which) {      // the kernels and the labels of before
+    if (mask) launch(c, "off_road_kernel", off_road_kernel, dim3(cdiv(n, 256)), dim3(256), 0, center, n, mask, H, W, q.ox, q.oy, q.c, q.s, q.res, -q.res,
+                     q.off_x, q.off_y, off_road);
+    else launch(c, "off_road_map_kernel", off_road_map_kernel, dim3(cdiv(n, 256)), dim3(256), 0, center, n, m, q, H, W, off_road);
+  }
+  else launch(c, "footprint_off_road_kernel", footprint_off_road_kernel, dim3(cdiv((long long)n * 8, 256)), dim3(256), 0, center, vertices, n, mask, m, q,
+              H, W, (int)offroad->extent, off_road, which);
+  return call_close(c);
+}
+
+extern "C" int riftof_group_advantage_tick(RiftCtx* c, const float* trajectory, int Rb, int Tfull, const RiftTickCBV* cbvs, int K,
+                                           float* turn_buf, int32_t* turn_ptr, int32_t* turn_len, float* speed_buf, int32_t* speed_ptr, int32_t* speed_len,
+                                           const RiftEvalParams* params, const RiftCollisionParams* collision, const RiftOffRoadParams* offroad,
+                                           double* advantage, double* returns, double* terms, void* stream) {
+  if (!c) return RIFT_ERR_ARG;
+  c->err.clear();
+  if (const char* why = riftof_refusal(offroad)) return refuse(c, "riftof_group_advantage_tick", why);
+  if (const char* why = riftfp_refusal(collision)) return refuse(c, "riftof_group_advantage_tick", why);
+  if (const char* why = rift_eval_params_refusal(params)) return refuse(c, "riftof_group_advantage_tick", why);
+  TickCall t{"riftof_group_advantage_tick", trajectory, Rb, Tfull, cbvs, K, turn_buf, turn_ptr, turn_len, speed_buf,
+             speed_ptr, speed_len, *params, true, true, advantage, returns, terms};
+  t.footprint = collision->mode == RIFTFP_FOOTPRINT;
+  t.offroad_footprint = offroad->extent == RIFTOF_FOOTPRINT;
   return group_advantage_tick(c, t, stream);
 }
 

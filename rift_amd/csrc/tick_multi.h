@@ -7,6 +7,7 @@
 #include "adv.h"
 #include "drivable_map.h"
 #include "footprint.h"
+#include "offroad_extent.h"
 #include "rollout.h"
 
 namespace rift {
@@ -43,6 +44,8 @@ __device__ __forceinline__ void tick_return(const TickK& d, double gamma, const 
 //       3: collision flags (256)   4: off-road flags (256)   5: returns (256)   6: z-score (256)
 //       7: off-road flags of a chunk with CBVs that use the drivable-area map (256): launched IN PLACE of stage 4 (riftdm_group_advantage_tick)
 //       8: collision flags from the footprints themselves (256; footprint.h): launched IN PLACE of stage 3 (riftfp_group_advantage_tick, FOOTPRINT)
+//       9: off-road flags from the centre and the four corners stage 2 wrote (256; offroad_extent.h), masks, the map and "no flags" in one launch
+//          as in stage 7: launched IN PLACE of stage 4 / 7 (riftof_group_advantage_tick, FOOTPRINT) on eight times their blocks -- 8 lanes per step
 template <int STAGE>
 __global__ void tick_multi_kernel(const TickArr a) {
   if ((int)blockIdx.y >= a.K) return;
@@ -62,6 +65,8 @@ __global__ void tick_multi_kernel(const TickArr a) {
     else if (d.H > 0) off_road_map_body(d.ro.center, d.G * TR, a.map, RasterPose{d.ox, d.oy, d.ch, d.sh, a.res, d.off_x, d.off_y, a.map_inv_res}, d.H, d.W, d.offr);
     else { const int i = blockIdx.x * 256 + threadIdx.x; if (i < d.G * TR) d.offr[i] = 0; }
   }
+  if (STAGE == 9) footprint_off_road_body(d.ro.center, d.ro.vertices, d.G * TR, d.mask, a.map, RasterPose{d.ox, d.oy, d.ch, d.sh, a.res, d.off_x, d.off_y, a.map_inv_res},
+                                          d.H, d.W, RIFTOF_FOOTPRINT, d.offr, (uint8_t*)nullptr);
   if (STAGE == 5) {                                // (wave-uniform branches: nothing of the breakdown runs without `terms`)
     if (a.reward_default) tick_return(d, a.gamma, RewardDefaults());
     else tick_return(d, a.gamma, a.reward);

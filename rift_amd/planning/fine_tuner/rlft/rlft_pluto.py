@@ -521,6 +521,7 @@ class _GroupRelativePluto(RLFTPluto):
     EXTRA_COLUMNS = ('CBVs_actions_old_group_logits', 'CBVs_group_advantage')
     TRAJ_EVAL_KEYS = ('gamma', 'reward_model', 'reward_params', 'bbox_inflation_ratio', 'resolution', 'near_lane_change', 'breakdown',
                       'off_road', 'raster_size', 'map_cell', 'map_margin',      # these last three are read with 'off_road': 'map' only
+                      'off_road_extent',                                        # 'center' | 'footprint' (include/rift_offroad.h)
                       'collision')                                              # 'envelope' | 'footprint' (include/rift_footprint.h)
     OBJECTIVE_KEYS = ('clip_low', 'clip_high', 'dual_clip', 'kl_beta', 'entropy_coef')      # the fields of RiftObjectiveParams
     ADVANTAGE_KEYS = ('baseline', 'scale', 'clip', 'eps')                                   # the arguments of _ffi.advantage_params
@@ -607,6 +608,11 @@ class _GroupRelativePluto(RLFTPluto):
         ev['collision'] = section.get('collision')
         if ev['collision'] is not None and ev['collision'] not in ('envelope', 'footprint'):
             raise ValueError(f"config['traj_eval']['collision'] = {ev['collision']!r}; known: ['envelope', 'footprint']")
+        # 'off_road_extent': 'center' (the reference's flag: the footprint centre alone) | 'footprint' (the centre and the four corners of the
+        # footprint, against mask or map).  None without the key; 'center' given explicitly makes the calls of the run without it as well
+        ev['off_road_extent'] = section.get('off_road_extent')
+        if ev['off_road_extent'] is not None and ev['off_road_extent'] not in ('center', 'footprint'):
+            raise ValueError(f"config['traj_eval']['off_road_extent'] = {ev['off_road_extent']!r}; known: ['center', 'footprint']")
         return ev
 
     @property
@@ -616,6 +622,8 @@ class _GroupRelativePluto(RLFTPluto):
             kw = {} if self._eval is None else {k: self._eval[k] for k in ('bbox_inflation_ratio', 'resolution', 'reward_model', 'gamma')}
             if self._eval is not None and self._eval['collision'] is not None:
                 kw['collision'] = self._eval['collision']
+            if self._eval is not None and self._eval['off_road_extent'] is not None:
+                kw['off_road_extent'] = self._eval['off_road_extent']
             self._traj_evaluator = TrajEvaluator(self.pluto_model.engine(), dt=self._step_interval, **kw)
         eng = self.pluto_model._engine
         if eng is not None and self._traj_evaluator.engine is not eng:      # the model re-bound (precision / device change): the PID state is torch's, it carries over
@@ -711,6 +719,8 @@ class _GroupRelativePluto(RLFTPluto):
                                                  want_returns=True, want_terms=False)
         else:
             kw = {} if cfg['collision'] is None else {'collision': cfg['collision']}      # (without the key: the call made before the test could vary)
+            if cfg['off_road_extent'] is not None:                                        # (likewise; 'center' makes that call as well, inside the engine)
+                kw['off_road_extent'] = cfg['off_road_extent']
             res = ev.engine.group_advantage_tick(trajectory, [c.entry for c in cbvs], ev.pid_state, cfg['gamma'], params=cfg['params'],
                                                  want_returns=cfg['breakdown'] or keep, want_terms=cfg['breakdown'], **kw)
         if isinstance(res, dict):                # advantage | returns | terms are slices of one tensor, still one read-back

@@ -274,6 +274,9 @@ class PLUTO(CBVBasePolicy):
         if 'off_road' in (config.get('traj_eval') or {}) and not self.GROUP_OBJECTIVE:
             raise ValueError(f"config['traj_eval']['off_road'] selects the off-road source of the group advantage (rift_pluto, grpo_pluto); "
                              f"{self.name} evaluates no group advantage")
+        if 'off_road_extent' in (config.get('traj_eval') or {}) and not self.GROUP_OBJECTIVE:
+            raise ValueError(f"config['traj_eval']['off_road_extent'] selects the points behind the off-road flag of the group advantage (rift_pluto, "
+                             f"grpo_pluto); {self.name} evaluates no group advantage")
         super().__init__(config, logger)
         self.logger = logger
         self.radius = config.get('obs', {}).get('radius', config.get('radius', 120))

@@ -10,6 +10,8 @@ the host leg, the device leg, the host leg again (its run-to-run spread is the y
 the policies that tick in train mode (rift_pluto), since eval-mode ticks stay greedy: run with and without it for the cost of the stage.
 --collision envelope|footprint: config['traj_eval']['collision'] on every leg: the collision flags of the train-mode ticks from the envelopes
 (through the new entry; the launches of the run without the switch) or from the footprints themselves (stage 8 in place of stage 3).
+--off-road-extent center|footprint: config['traj_eval']['off_road_extent'] on every leg: the off-road flags of the train-mode ticks from the
+footprint centre alone (the launches of the run without the switch) or from the centre and the four corners (stage 9 in place of stage 4 / 7).
 --policies: a comma-separated subset of pluto,rift_pluto; it selects the policies of the --device-control legs as well as of the plain run.
 --drivable-map: the A/B of config['traj_eval']['off_road'] on rift_pluto in train mode, in ONE process: the raster leg (a mask per CBV goes up
 every tick), the map leg (a seeded town of --map-polygons lane polygons on the device, poses go up), the raster leg again; then the one-time
@@ -145,8 +147,12 @@ def main():
     ap.add_argument("--map-span", type=float, default=1500.0, help="side of the town's square in metres (--drivable-map)")
     ap.add_argument("--collision", default="", choices=("", "envelope", "footprint"),
                     help="config['traj_eval']['collision']: the collision test of the train-mode ticks (include/rift_footprint.h); without it the key is not set")
+    ap.add_argument("--off-road-extent", default="", choices=("", "center", "footprint"),
+                    help="config['traj_eval']['off_road_extent']: the points behind the off-road flag of the train-mode ticks (include/rift_offroad.h); without it the key is not set")
     args = ap.parse_args()
     traj_eval = json.loads(args.traj_eval) if args.traj_eval else None
+    if args.off_road_extent:
+        traj_eval = dict(traj_eval or {}, off_road_extent=args.off_road_extent)
     if args.collision:
         traj_eval = dict(traj_eval or {}, collision=args.collision)
     if args.drivable_map:
